@@ -1,9 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the GenPC geometric hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the headline line (contract fields,
+`ranks_seen`, `config`); nothing else runs in it.  `--full` adds everything else listed below: the
+per-step spread, the roofline figures (a pass of their own through the filter kernel's events), the
+oracle check of the timed step's output, `extra` and `cpu_baseline` (`--no-extra` / `--no-cpu-baseline`
+drop those two).  `--dump-outputs DIR` writes what the last timed step computed, the arrays a caller of
+`chamfer_3DDist.forward` receives (dist1, dist2, idx1, idx2; the gathered scan table for --workload), as
+DIR/<name>.npy (see dump_outputs); the inputs are seeded, so two builds compare output for output.
 
 Workload (BASELINE.json metric "Chamfer Gpair-dist/sec", SURVEY.md section 8d headline):
 one STEP = one `chamfer_3DDist.forward` (both directions, i.e. 2*N*M pair
@@ -20,7 +28,7 @@ workloads of BASELINE configs 3 / 4 / 5 instead of the pair benchmark (13 bundle
 CAR crops registered against a complete car; 64 synthetic scans registered + scored -- strong scaling:
 the scans are dealt round-robin over the ranks, metric completed scans/s, every rank's own time in `per_rank`).
 
-One JSON line on stdout (rank 0).  Besides the contract fields:
+One JSON line on stdout (rank 0).  Besides the contract fields, with --full:
   roofline      the dominant kernel (nn_f16_kernel, the MFMA filter that evaluates every
                 pair) against the dense f16 MFMA roofline, 2500 TFLOP/s: one K = 16
                 product per pair = 32 flop/pair of matrix work (DESIGN.md section 4.1);
@@ -75,6 +83,28 @@ def time_events(fn, reps, stream):
     e1.record(stream)
     e1.synchronize()
     return e0.elapsed_time(e1) / reps
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(where, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array as where/<name>.npy, float32 / float16 as float32, everything else (the int32
+    indices included, exactly) as float64.  Above `limit` bytes in all, every array keeps the same fixed, seeded
+    sample of its flat positions, in order, so that two runs or two builds still compare element for element."""
+    os.makedirs(where, exist_ok=True)
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        out[name] = a.astype(np.float32 if a.dtype in (np.float32, np.float16) else np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > limit:
+        budget = limit - 4096 * len(out)          # (room for the .npy headers)
+        for name, a in out.items():
+            keep = a.size * budget // total
+            out[name] = a.reshape(-1)[np.sort(np.random.default_rng(SEED).choice(a.size, keep, replace=False))]
+    for name, a in out.items():
+        np.save(os.path.join(where, name + ".npy"), a)
 
 
 ROUND_TAG = "r06"          # the profiles/ tag this bench's PMC-derived numbers must come from
@@ -723,6 +753,8 @@ def run_scan_workload(args, rank, world, dev):
                                             world, rank, world)
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"scan_metrics": table.cpu().numpy()})
     what = {"c3": "CD-L1 / CD-L2 / EMD metric of the 13 bundled scans (partial vs GT), no registration",
             "c4": "diff_obj_pose registration (4 starts x 201 Adam steps, mask + 3 cd + ortho) of a complete car to each Waymo CAR "
                   "crop + CD/EMD of the posed car against the crop",
@@ -749,13 +781,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--points", type=int, default=N_PTS)
     ap.add_argument("--workload", choices=("pairs", "c3", "c4", "c5"), default="pairs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-step spread, rooflines, the oracle check, extra and cpu_baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: no extra")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 200 if args.workload == "pairs" else 2
     if args.warmup is None:
         args.warmup = 20 if args.workload == "pairs" else 1
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     maybe_spawn(args)
 
     from genpc_amd import sharding
@@ -785,7 +822,6 @@ def main():
         return
 
     from genpc_amd import _lib, chamfer_3D
-    from genpc_amd.loss_functions import chamfer_3DDist, emdModule
 
     n = args.points
     A, B, a_np, b_np = make_pair(n, SEED + rank, dev)
@@ -812,6 +848,8 @@ def main():
     sharding.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    # what the last timed step computed, copied on the launch stream before any later step (--full) overwrites it
+    last = {"dist1": dist1.clone(), "dist2": dist2.clone(), "idx1": idx1.clone(), "idx2": idx2.clone()} if args.dump_outputs else None
     elapsed = sharding.max_over_ranks(elapsed, device=dev if world > 1 else "cpu")
     ranks_seen = sharding.all_ranks(dev if world > 1 else "cpu")
 
@@ -820,6 +858,25 @@ def main():
 
     out = None
     if rank == 0:
+        out = {
+            "metric": "chamfer_nn_pair_dist_throughput",
+            "value": round(value, 3),
+            "unit": "Gpair-dist/s",
+            "n_gpus": n_gpus,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 5),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic",
+            "ranks_seen": ranks_seen,
+            "config": {"workload": "chamfer_3DDist.forward B=1 N=M=%d (both directions), one pair per rank" % n,
+                       "points": n, "batch": 1, "arith": "fma" if _lib.lib.genpc_get_arith() else "strict",
+                       "sharding": "independent scans per rank, no data-path collective"},
+        }
+    if rank == 0 and args.full:
         # ---- per-step spread and the dominant kernel's own duration: HIP events on the launch stream, taken right
         # after the timed region (before any host-side checker work disturbs the launch thread)
         reps = max(20, min(args.steps, 200))
@@ -855,27 +912,11 @@ def main():
             raise RuntimeError("bench.py: the timed step's output differs from the oracle")
         tflops = MFMA_FLOP_PER_PAIR * pairs_per_step / (kernel_ms * 1e-3) / 1e12
         alg_bytes = 20.0 * (n + n)        # 12 B read + 8 B written per point, both clouds
-        out = {
-            "metric": "chamfer_nn_pair_dist_throughput",
-            "value": round(value, 3),
-            "unit": "Gpair-dist/s",
-            "n_gpus": n_gpus,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 5),
+        out.update({
             "ms_per_step_spread": {"min": round(per_step[0], 5), "median": round(per_step[len(per_step) // 2], 5),
                                    "max": round(per_step[-1], 5), "steps": len(per_step),
                                    "how": "HIP events between consecutive steps, a second pass right after the timed region"},
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "ranks_seen": ranks_seen,
             "output_checked": "first and last 256 queries of both directions (512 of 16384 each) bit-exact vs the oracle inside this run; every distance and index of the same input: tests/test_gpu_chamfer_parity.py::test_bench_input_elementwise (-m gpu)",
-            "config": {"workload": "chamfer_3DDist.forward B=1 N=M=%d (both directions), one pair per rank" % n,
-                       "points": n, "batch": 1, "arith": "fma" if _lib.lib.genpc_get_arith() else "strict",
-                       "sharding": "independent scans per rank, no data-path collective"},
             "roofline": {"bound": "mfma", "achieved": round(tflops, 3), "peak": PEAK_F16_MFMA_TFLOPS,
                          "unit": "TFLOP/s", "frac": round(tflops / PEAK_F16_MFMA_TFLOPS, 4), "traffic": None,
                          "kernel": kernel_name, "ms_per_launch": round(kernel_ms, 5),
@@ -889,7 +930,7 @@ def main():
                              "peak": PEAK_HBM_GBS, "unit": "GB/s",
                              "frac": round(alg_bytes / (ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 6), "traffic": None,
                              "algorithmic_bytes": alg_bytes},
-        }
+        })
         out["roofline"]["traffic"], out["roofline"]["traffic_source"] = pmc_traffic(n)
     # the last collective: the other ranks leave here; rank 0's secondary measurements and the CPU baseline run
     # AFTER it (nobody waits in RCCL for them)
@@ -897,18 +938,20 @@ def main():
     sharding.shutdown()
     if rank == 0:
         # (the headline above is measured and complete: nothing below may keep the line from being printed)
-        if not args.no_extra:
+        if args.full and not args.no_extra:
             try:
                 out["extra"] = extras(A, B, n, dev, stream)
             except Exception as e:
                 out["extra"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(a_np, b_np)
             except Exception as e:
                 out["cpu_baseline"] = {"value": None, "error": "%s: %s" % (type(e).__name__, e)}
             if isinstance(out.get("extra"), dict) and "error" not in out["extra"]:
                 out["extra"]["cpu_context_16384x16384"] = cpu_context(a_np, b_np)
+        if last is not None:
+            dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in last.items()})
         print(json.dumps(out), flush=True)
 
 

@@ -11,7 +11,7 @@ rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 K="timeout -s KILL 240"
 SQ="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES"
-$K rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o bench -- python3 bench.py --steps 50 --warmup 5 --no-extra --no-cpu-baseline > $OUT/bench_trace.log 2>&1
+$K rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o bench -- python3 bench.py --steps 50 --warmup 5 --full --no-extra --no-cpu-baseline > $OUT/bench_trace.log 2>&1
 family() {   # family <name> <script> [args...]
     local name=$1; shift
     $K rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$name/trace -o t -- python3 "$@" > $OUT/$name.trace.log 2>&1

@@ -1,5 +1,5 @@
-"""DESIGN.md = tools/DESIGN.template.md with the <...> tokens replaced by the numbers of a bench.py line:
-    python tools/fill_design.py gpurun_out/bench_r05.json"""
+"""DESIGN.md = tools/DESIGN.template.md with the <...> tokens replaced by the numbers of a `bench.py --full` line:
+    python tools/fill_design.py <file holding the line>"""
 import json, sys, os
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
