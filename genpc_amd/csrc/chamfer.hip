@@ -566,12 +566,8 @@ __global__ __launch_bounds__(kBlock) void nn_mfma_kernel(NNArgs a)
 // Chamfer backward, both directions in one launch (chamfer3D.cu:155-195).
 // Thread j < B*N: direction 1 term of point j of cloud 1; B*N <= j < B*(N+M):
 // direction 2 term of point j-B*N of cloud 2.  Accumulates with fp32 atomics
-// into the caller-zeroed gradients, exactly like the reference.
-// PHASE 0: both halves with atomics in one launch (small calls: one launch is what a call costs).  PHASE 1 then PHASE 2 (two
-// launches, large calls): a point's OWN row first, as a plain read-modify-write (coalesced; nobody else touches the buffers
-// during that launch), then the scattered halves with atomics -- half the atomics, which are what bounds this kernel (six
-// per point at ~14 per clock chip-wide: 0.73 ms for 64 x 32768 x 2 points, 0.04 of the HBM roofline on its 56 B per point).
-template <int PHASE>
+// into the caller-zeroed gradients, exactly like the reference.  Small calls: one launch is what a call costs (large
+// calls take chamfer_grad_dir_kernel below: the atomics, six per point at ~14 per clock chip-wide, bound this kernel).
 __global__ __launch_bounds__(kBlock) void chamfer_grad_kernel(int b, int n, const float *__restrict__ xyz1, int m,
                                                               const float *__restrict__ xyz2,
                                                               const float *__restrict__ gd1, const int *__restrict__ idx1,
@@ -598,86 +594,18 @@ __global__ __launch_bounds__(kBlock) void chamfer_grad_kernel(int b, int n, cons
     const float x2 = P2[j2 * 3 + 0], y2 = P2[j2 * 3 + 1], z2 = P2[j2 * 3 + 2];
     const float g = __fmul_rn(G[t], 2.0f);
     const float vx = __fmul_rn(g, x1 - x2), vy = __fmul_rn(g, y1 - y2), vz = __fmul_rn(g, z1 - z2);
-    if (PHASE == 0) {
-        atomicAdd(&O1[t * 3 + 0], vx);
-        atomicAdd(&O1[t * 3 + 1], vy);
-        atomicAdd(&O1[t * 3 + 2], vz);
-    } else if (PHASE == 1) {
-        O1[t * 3 + 0] = __fadd_rn(O1[t * 3 + 0], vx);
-        O1[t * 3 + 1] = __fadd_rn(O1[t * 3 + 1], vy);
-        O1[t * 3 + 2] = __fadd_rn(O1[t * 3 + 2], vz);
-    }
-    if (PHASE != 1) {
-        atomicAdd(&O2[j2 * 3 + 0], -vx);
-        atomicAdd(&O2[j2 * 3 + 1], -vy);
-        atomicAdd(&O2[j2 * 3 + 2], -vz);
-    }
+    atomicAdd(&O1[t * 3 + 0], vx);
+    atomicAdd(&O1[t * 3 + 1], vy);
+    atomicAdd(&O1[t * 3 + 2], vz);
+    atomicAdd(&O2[j2 * 3 + 0], -vx);
+    atomicAdd(&O2[j2 * 3 + 1], -vy);
+    atomicAdd(&O2[j2 * 3 + 2], -vz);
 }
 
-// The scattered halves of large calls without global atomics (round 5).  The float atomics of PHASE 2 each cost a 64-byte
-// memory transaction (profiles/r05_streaming_64x32768.json: 790 MB of HBM traffic for 4 M points' 24-byte updates, 612 us).
-// Here a block OWNS a tile of kGradTile target rows of one cloud and direction: it walks the index array of the other cloud,
-// accumulates the terms that land in its tile in LDS (ds_add_f32), and adds the tile to the gradient with plain coalesced
-// read-modify-writes -- every output row has exactly one owner, and the own-row launch (PHASE 1) has finished before.
-// grid (tiles, b, 2).
-constexpr int kGradTile = 4096;
 constexpr int kGradBlock = 1024;      // (64 x 32768 both ways: 122 us; 512 threads 144, 256 threads 228 before the loads were batched; capped at 64 VGPRs for two blocks per CU 159)
-__global__ __launch_bounds__(kGradBlock) void chamfer_grad_scatter_tiled_kernel(int n, const float *__restrict__ xyz1, int m,
-                                                                            const float *__restrict__ xyz2,
-                                                                            const float *__restrict__ gd1, const int *__restrict__ idx1,
-                                                                            const float *__restrict__ gd2, const int *__restrict__ idx2,
-                                                                            float *__restrict__ gx1, float *__restrict__ gx2)
-{
-    __shared__ float acc[kGradTile * 3];
-    const int dir = blockIdx.z, e = blockIdx.y;
-    // direction 0: queries = cloud 1 (n points), targets = cloud 2 (m rows of gx2); direction 1 the converse
-    const int nq = dir ? m : n, nt = dir ? n : m;
-    const int t0 = blockIdx.x * kGradTile;
-    if (t0 >= nt) return;
-    const float *__restrict__ Q = (dir ? xyz2 : xyz1) + (size_t)e * nq * 3;
-    const float *__restrict__ T = (dir ? xyz1 : xyz2) + (size_t)e * nt * 3;
-    const float *__restrict__ G = (dir ? gd2 : gd1) + (size_t)e * nq;
-    const int *__restrict__ I = (dir ? idx2 : idx1) + (size_t)e * nq;
-    float *__restrict__ O = (dir ? gx1 : gx2) + (size_t)e * nt * 3;
-    const int rows = min(kGradTile, nt - t0);
-    for (int i = threadIdx.x; i < rows * 3; i += kGradBlock) acc[i] = 0.0f;
-    __syncthreads();
-    // Eight entries per thread and trip, every load of a trip issued before anything waits: the indices, then -- for all eight,
-    // hit or not, at clamped addresses -- the query row, its weight and the target row (L2 hits: a cloud is half a MiB), then
-    // the LDS adds of the hits.  (One entry in eight lands in the tile; fetched only for the hits, behind a branch per entry,
-    // the seven dependent loads of a hit were a round trip each, 128 times per thread: 228 us for 64 x 32768 both ways.)
-    for (int q0 = threadIdx.x; q0 < nq; q0 += 8 * kGradBlock) {
-        int kk[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            const int q = q0 + u * kGradBlock;
-            kk[u] = q < nq ? I[q] - t0 : -1;
-        }
-        float qx[8], qy[8], qz[8], gg[8], tx[8], ty[8], tz[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            const bool ok = (unsigned)kk[u] < (unsigned)rows;
-            const int q = ok ? q0 + u * kGradBlock : 0, k = ok ? kk[u] : 0;
-            qx[u] = Q[(size_t)q * 3 + 0]; qy[u] = Q[(size_t)q * 3 + 1]; qz[u] = Q[(size_t)q * 3 + 2];
-            gg[u] = G[q];
-            tx[u] = T[(size_t)(t0 + k) * 3 + 0]; ty[u] = T[(size_t)(t0 + k) * 3 + 1]; tz[u] = T[(size_t)(t0 + k) * 3 + 2];
-        }
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            const int k = kk[u];
-            if ((unsigned)k >= (unsigned)rows) continue;
-            const float g = __fmul_rn(gg[u], 2.0f);
-            atomicAdd(&acc[k * 3 + 0], -__fmul_rn(g, qx[u] - tx[u]));
-            atomicAdd(&acc[k * 3 + 1], -__fmul_rn(g, qy[u] - ty[u]));
-            atomicAdd(&acc[k * 3 + 2], -__fmul_rn(g, qz[u] - tz[u]));
-        }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < rows * 3; i += kGradBlock) O[(size_t)t0 * 3 + i] = __fadd_rn(O[(size_t)t0 * 3 + i], acc[i]);
-}
 
 // Large calls, round 6: ONE pass per direction computes every term once and puts it in both places (chamfer3D.cu:157-171) --
-// a block owns a tile of kGradTile target rows of one cloud; it walks the other cloud's index array, and for the entries that
+// a block owns a tile of TILE target rows of one cloud; it walks the other cloud's index array, and for the entries that
 // land in its tile (exactly one block per entry) it evaluates the term, adds it to the QUERY's own gradient row (a plain
 // read-modify-write: that row has no other writer in this launch) and accumulates its negative in the tile's LDS copy, which
 // is added to the gradient at the end (a plain coalesced read-modify-write: the tile has one owner).  Direction 0 and
@@ -1196,12 +1124,11 @@ GENPC_API int genpc_chamfer_backward(int b, int n, const float *xyz1, int m, con
     }
     static const int env_split = tune_env("GENPC_CHAMFER_GRAD_SPLIT", 262144, "chamfer backward: points (both clouds) from which the gradient is accumulated through LDS tiles that own their output rows instead of global atomics (0 = never)");
     if (env_split > 0 && (long long)b * ((long long)n + m) >= env_split) {
-        static const int env_tiled = tune_env("GENPC_CHAMFER_GRAD_TILED", 2, "chamfer backward, large calls: 2 = one pass per direction (own rows + tiles fused), 1 = own rows and tiles as two launches (round 5), 0 = global atomics");
         static const int env_tile = tune_env("GENPC_CHAMFER_GRAD_TILE", 4096, "chamfer backward, large calls: target rows a block owns (2048 | 4096 | 8192)");
         const int tile_rows = env_tile == 2048 || env_tile == 8192 ? env_tile : 4096;
         const int tiles_n = ceil_div(n, tile_rows), tiles_m = ceil_div(m, tile_rows);
-        const long long bb = (b & 7) == 0 ? b : b;      // (blocks per tile column: the batch; a multiple of eight is dealt XCD by XCD)
-        if (env_tiled == 2 && bb * (tiles_n > tiles_m ? tiles_n : tiles_m) <= 0x7fffffffLL) {
+        // (a grid of more than 2^31 blocks -- no call fits such clouds in memory -- takes the atomics below)
+        if ((long long)b * (tiles_n > tiles_m ? tiles_n : tiles_m) <= 0x7fffffffLL) {
             // direction 0: queries = cloud 1, tiles of cloud 2's gradient; direction 1 the converse
 #define GENPC_GRAD_DIR(TILE)                                                                                                          \
             do {                                                                                                                      \
@@ -1216,18 +1143,8 @@ GENPC_API int genpc_chamfer_backward(int b, int n, const float *xyz1, int m, con
 #undef GENPC_GRAD_DIR
             return check(hipGetLastError(), "chamfer_grad_dir_kernel launch") ? 1 : 0;
         }
-        hipLaunchKernelGGL(chamfer_grad_kernel<1>, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, b, n, xyz1, m,
-                           xyz2, graddist1, idx1, graddist2, idx2, gradxyz1, gradxyz2);
-        const int tiles = ceil_div(n > m ? n : m, kGradTile);
-        if (env_tiled && tiles <= 65535 && b <= 65535)
-            hipLaunchKernelGGL(chamfer_grad_scatter_tiled_kernel, dim3(tiles, b, 2), dim3(kGradBlock), 0, (hipStream_t)stream, n, xyz1, m, xyz2,
-                               graddist1, idx1, graddist2, idx2, gradxyz1, gradxyz2);
-        else
-            hipLaunchKernelGGL(chamfer_grad_kernel<2>, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, b, n, xyz1, m,
-                               xyz2, graddist1, idx1, graddist2, idx2, gradxyz1, gradxyz2);
-    } else {
-        hipLaunchKernelGGL(chamfer_grad_kernel<0>, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, b, n, xyz1, m,
-                           xyz2, graddist1, idx1, graddist2, idx2, gradxyz1, gradxyz2);
     }
+    hipLaunchKernelGGL(chamfer_grad_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, b, n, xyz1, m,
+                       xyz2, graddist1, idx1, graddist2, idx2, gradxyz1, gradxyz2);
     return check(hipGetLastError(), "chamfer_grad_kernel launch") ? 1 : 0;
 }

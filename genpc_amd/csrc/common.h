@@ -38,7 +38,7 @@ int arith_mode();
 // The per-thread modes of the library (each set through its own genpc_*_tune / genpc_set_arith_thread entry point); a host
 // thread that starts worker threads hands them over with genpc_thread_state_export / _import (the lanes of
 // pipeline.run_in_lanes started with the defaults whatever their caller had set).
-extern thread_local int t_arith, t_tune_path, t_tune_hooks, t_emd_grid, t_emd_hooks, t_pose_seeded, t_fps_legacy, t_render_blend;
+extern thread_local int t_arith, t_tune_path, t_tune_hooks, t_emd_grid, t_emd_hooks, t_pose_seeded, t_fps_multi_wg, t_render_blend;
 
 // Wave-wide sums on the DPP network (no LDS round trips: a __shfl_xor tree of a double is twelve ds_bpermute, ~0.25 us of
 // dependent latency per value -- 5 us of mask_sums_kernel's 12).  Call with the wave's lanes active; lanes that are not

@@ -142,7 +142,7 @@ void *workspace(int slot, size_t bytes, hipStream_t stream, bool *fresh, size_t 
 
 }  // namespace genpc
 
-GENPC_API int genpc_abi_version(void) { return 16; }
+GENPC_API int genpc_abi_version(void) { return 17; }
 
 GENPC_API const char *genpc_last_error(void)
 {
@@ -193,7 +193,7 @@ GENPC_API int genpc_thread_state_export(int out[8])
 {
     using namespace genpc;
     out[0] = t_arith; out[1] = t_tune_path; out[2] = t_tune_hooks; out[3] = t_emd_grid; out[4] = t_emd_hooks;
-    out[5] = t_pose_seeded; out[6] = t_fps_legacy; out[7] = t_render_blend;
+    out[5] = t_pose_seeded; out[6] = t_fps_multi_wg; out[7] = t_render_blend;
     return 8;
 }
 
@@ -201,7 +201,7 @@ GENPC_API int genpc_thread_state_import(const int in[8])
 {
     using namespace genpc;
     t_arith = in[0]; t_tune_path = in[1]; t_tune_hooks = in[2]; t_emd_grid = in[3]; t_emd_hooks = in[4];
-    t_pose_seeded = in[5]; t_fps_legacy = in[6]; t_render_blend = in[7];
+    t_pose_seeded = in[5]; t_fps_multi_wg = in[6]; t_render_blend = in[7];
     return 8;
 }
 

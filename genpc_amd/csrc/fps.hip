@@ -30,7 +30,6 @@
 #include "../../include/genpc_hip.h"
 #include <map>
 #include <mutex>
-#include <type_traits>
 #include <vector>
 
 namespace genpc {
@@ -62,8 +61,6 @@ struct FpsJobs {
     float *pdist[kFMaxJobs];     // the running minimum of every sample when it was drawn (fps_verify_kernel)
     int *verr[kFMaxJobs];        // != 0: the verification found a step whose sample is not the first arg-max
     int segoff[kFMaxJobs];       // first point of the job in the verification's per-(point, segment) minima
-    int legacy_pivot;            // test hook (genpc_fps_tune): the workers read the pivot as per-lane LDS broadcasts again -- the
-                                 // form that drew wrong samples next to f16 MFMAs on another stream (tests/test_gpu_concurrency.py)
 };
 
 template <int FMA>
@@ -208,12 +205,8 @@ __device__ __forceinline__ int wave_argbest(float v, int idx, float &m)
     return __ffsll((long long)__ballot(cand == best)) - 1;
 }
 
-// The body of the sampling.  HOOK = 1 compiles the bisection's variants (genpc_fps_tune bits, packed fp32 written out) into the
-// workers' update: that instantiation is inlined into fps_kernel_hook ONLY, the one kernel of the library that carries the
-// packed-fp32-ops target attribute and is launched when a test asks for a variant; the shipped fps_kernel has no such
-// attribute and no such code (the attribute used to sit on the shipped kernel, its update kept free of packed
-// instructions by opaque statements alone; tests/test_abi.py now exempts fps_kernel_hook by name and nothing else).
-template <int FMA, int R, int HOOK>
+// The body of the sampling.
+template <int FMA, int R>
 static __device__ __forceinline__ void fps_body(const FpsJobs &jobs, FpsSlot *slots, int *__restrict__ err)
 {
     __shared__ float s_c[kFWaves][kFT][5];     // per worker wave: dist, idx (bits), x, y, z of its kFT best
@@ -257,11 +250,7 @@ static __device__ __forceinline__ void fps_body(const FpsJobs &jobs, FpsSlot *sl
                 pr = prog_load(&s_prog);
                 if ((pr >> 16) != (round & 0xffffu)) { __builtin_amdgcn_s_sleep(1); continue; }
                 const unsigned avail = pr & kProgCount;
-                // (the bisection's variants -- genpc_fps_tune bits, a test hook -- are compiled into a second copy of the loop body: with
-                //  their tests inside the shipped loop a pick cost 0.55 us instead of 0.53)
-                auto apply_pivot = [&](auto hook_tag) {
-                    constexpr bool kHook = decltype(hook_tag)::value;
-                    const int hook_bits = kHook ? jobs.legacy_pivot : 0;
+                auto apply_pivot = [&]() {
                     // The pivot travels through SCALAR registers (first lane's copy).  As plain per-lane reads of the one LDS
                     // address (ds_read_b96 into VGPRs, consumed by packed fp32 ops right behind the wait) the lanes 48-63 of a
                     // worker wave were seen to use the PREVIOUS pivot now and then while another stream's kernel issued
@@ -271,124 +260,49 @@ static __device__ __forceinline__ void fps_body(const FpsJobs &jobs, FpsSlot *sl
                     // loads; all extra samples were points held by lanes 48-63).  The mechanism is not established (an isolated
                     // probe of broadcast reads + packed adds under the same load, tools/lds_probe.hip, shows nothing); with the
                     // value in SGPRs nine of nine stress runs are clean.  tests/test_gpu_concurrency.py keeps watch.
-                    float cx, cy, cz;
-                    if (hook_bits & 1) {   // the pre-fix form, kept reachable so that the trigger stays reproducible
-                        cx = s_piv[applied][0]; cy = s_piv[applied][1]; cz = s_piv[applied][2];
-                    } else {
-                        const unsigned want = (round & 0x3ffffffu) * 64u + applied + 1u;
-                        uint2 g0, g1, g2;
-                        int tries = 0;
-                        bool good;
-                        do {
-                            asm volatile("" ::: "memory");      // (re-read from LDS on every trip)
-                            const unsigned long long *gp = (const unsigned long long *)&s_pivt[applied][0];
-                            const unsigned long long w0 = __hip_atomic_load(gp + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                            const unsigned long long w1 = __hip_atomic_load(gp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                            const unsigned long long w2 = __hip_atomic_load(gp + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                            g0 = make_uint2((unsigned)w0, (unsigned)(w0 >> 32));
-                            g1 = make_uint2((unsigned)w1, (unsigned)(w1 >> 32));
-                            g2 = make_uint2((unsigned)w2, (unsigned)(w2 >> 32));
-                            good = g0.y == want && g1.y == want && g2.y == want;
-                        } while (!__all(good) && ++tries < 4096);
-                        // ... and the VALUE every lane uses is lane 0's copy, through scalar registers (tools/fps_reject_probe.py, round 5:
-                        // with six scans in flight 8 % of the samplings failed the device-side check, and every wrong sample -- 44 of 44 --
-                        // was a point held in REGISTER 0 by lanes 48-63 of a worker wave, its running minimum not lowered by one pivot:
-                        // the first arithmetic behind the wait used the previous occupant of the value register in the last sixteen
-                        // lanes although the tag registers of the same loads, compared later, were current)
-                        cx = __uint_as_float(__builtin_amdgcn_readfirstlane(g0.x));
-                        cy = __uint_as_float(__builtin_amdgcn_readfirstlane(g1.x));
-                        cz = __uint_as_float(__builtin_amdgcn_readfirstlane(g2.x));
-                    }
-                    // What the wrong samples were (round 5, tools/fps_reject_probe.py; six scans in flight): written plainly, the compiler
-                    // pairs registers r, r + 1 into PACKED fp32 instructions whose subtracts take ONE half of a source pair for both
-                    // lanes (v_pk_add_f32 ... op_sel_hi:[1,0] / op_sel:[0,1]), and beside other streams' kernels 8 % of the samplings
-                    // then failed the device-side check -- every first wrong sample, 55 of 55, a point held in the LOW lane of a pair
-                    // (register 0) by lanes 48-63 of a worker wave whose running minimum had missed one pivot.  The bits of
-                    // genpc_fps_tune select the variants of the bisection (DESIGN.md 6a has the table): the packed form WITH half
-                    // selection fails beside the f16 filter however the pivot arrives and however many wait states surround it (written
-                    // out, bits 2 | 32 | 128: every sampling), the same packed arithmetic on {c, c} pairs WITHOUT half selection never
-                    // (bits 2 | 32), and neither does anything alone on the GPU.  It reproduces in a plain HIP program: tools/opsel_probe.hip,
-                    // v_pk_add_f32 ... op_sel:[0,1] on known data beside tools/burn.hip's MFMA kernel on another stream -- 2.5e9 wrong
-                    // results in 5 s, all in lanes 48-63, all the low lane's, as if the selected half were 0 (op_sel_hi / plain: none).
-                    // Shipped: one register at a time (the opaque statements keep the compiler from pairing), and the whole
-                    // library is built without packed fp32 instructions (genpc_amd/build.py).
-                    if (hook_bits & 4) asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");
-                    if (hook_bits & 8) {
-                        asm volatile("v_mov_b32 %0, %0\n\tv_mov_b32 %1, %1\n\tv_mov_b32 %2, %2\n\ts_nop 4" : "+v"(cx), "+v"(cy), "+v"(cz));
-                    }
-                    if (hook_bits & 2) {       // the pre-fix form (test hook): registers r, r + 1 as two-element vectors -> v_pk_*_f32
-                        typedef float f32x2 __attribute__((ext_vector_type(2)));
-                        static_assert(R % 2 == 0, "pairs of registers");
+                    const unsigned want = (round & 0x3ffffffu) * 64u + applied + 1u;
+                    uint2 g0, g1, g2;
+                    int tries = 0;
+                    bool good;
+                    do {
+                        asm volatile("" ::: "memory");      // (re-read from LDS on every trip)
+                        const unsigned long long *gp = (const unsigned long long *)&s_pivt[applied][0];
+                        const unsigned long long w0 = __hip_atomic_load(gp + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        const unsigned long long w1 = __hip_atomic_load(gp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        const unsigned long long w2 = __hip_atomic_load(gp + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        g0 = make_uint2((unsigned)w0, (unsigned)(w0 >> 32));
+                        g1 = make_uint2((unsigned)w1, (unsigned)(w1 >> 32));
+                        g2 = make_uint2((unsigned)w2, (unsigned)(w2 >> 32));
+                        good = g0.y == want && g1.y == want && g2.y == want;
+                    } while (!__all(good) && ++tries < 4096);
+                    // ... and the VALUE every lane uses is lane 0's copy, through scalar registers (round 5: with six scans in flight
+                    // 8 % of the samplings failed the device-side check, and every wrong sample -- 44 of 44 -- was a point held in
+                    // REGISTER 0 by lanes 48-63 of a worker wave, its running minimum not lowered by one pivot: the first arithmetic
+                    // behind the wait used the previous occupant of the value register in the last sixteen lanes although the tag
+                    // registers of the same loads, compared later, were current)
+                    const float cx = __uint_as_float(__builtin_amdgcn_readfirstlane(g0.x));
+                    const float cy = __uint_as_float(__builtin_amdgcn_readfirstlane(g1.x));
+                    const float cz = __uint_as_float(__builtin_amdgcn_readfirstlane(g2.x));
+                    // What the wrong samples were (round 5; six scans in flight): written plainly, the compiler pairs registers
+                    // r, r + 1 into PACKED fp32 instructions whose subtracts take ONE half of a source pair for both lanes
+                    // (v_pk_add_f32 ... op_sel_hi:[1,0] / op_sel:[0,1]), and beside other streams' kernels 8 % of the samplings then
+                    // failed the device-side check -- every first wrong sample, 55 of 55, a point held in the LOW lane of a pair
+                    // (register 0) by lanes 48-63 of a worker wave whose running minimum had missed one pivot.  It reproduces in a
+                    // plain HIP program: tools/opsel_probe.hip, v_pk_add_f32 ... op_sel:[0,1] on known data beside tools/burn.hip's
+                    // MFMA kernel on another stream -- 2.5e9 wrong results in 5 s, all in lanes 48-63, all the low lane's, as if the
+                    // selected half were 0 (op_sel_hi / plain: none; tools/PACKED_FP32_OPSEL.md).  Hence one register at a time (the
+                    // opaque statements keep the compiler from pairing), and the whole library is built without packed fp32
+                    // instructions (genpc_amd/build.py).
 #pragma unroll
-                        for (int r = 0; r < R; r += 2) {
-                            const f32x2 dx = (f32x2){px[r], px[r + 1]} - cx, dy = (f32x2){py[r], py[r + 1]} - cy, dz = (f32x2){pz[r], pz[r + 1]} - cz;
-                            f32x2 dd;
-                            if (FMA && (hook_bits & 32)) {
-                                // (bisect: the same six packed instructions written out, four wait states behind each)
-                                const f32x2 pxx = {px[r], px[r + 1]}, pyy = {py[r], py[r + 1]}, pzz = {pz[r], pz[r + 1]};
-                                const f32x2 cxx = {cx, cx}, cyy = {cy, cy}, czz = {cz, cz};
-                                f32x2 ex, ey, ez;
-                                if (hook_bits & 128) {    // (... and with the operand forms the compiler chose where it failed: the pivot
-                                    // as pairs (x, y) and (y, z), a packed subtract taking ONE half of a pair for both of its lanes --
-                                    // op_sel_hi:[1,0] / op_sel:[0,1] --, four wait states behind each instruction)
-                                    const f32x2 cxy = {cx, cy}, cyz = {cy, cz};
-                                    asm volatile("s_nop 3\n\t"
-                                                 "v_pk_add_f32 %0, %4, %7 op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,1]\n\ts_nop 3\n\t"
-                                                 "v_pk_add_f32 %1, %5, %8 op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,1]\n\ts_nop 3\n\t"
-                                                 "v_pk_add_f32 %2, %6, %8 op_sel:[0,1] neg_lo:[0,1] neg_hi:[0,1]\n\ts_nop 3\n\t"
-                                                 "v_pk_mul_f32 %3, %1, %1\n\ts_nop 3\n\t"
-                                                 "v_pk_fma_f32 %3, %0, %0, %3\n\ts_nop 3\n\t"
-                                                 "v_pk_fma_f32 %3, %2, %2, %3\n\ts_nop 3"
-                                                 : "=&v"(ex), "=&v"(ey), "=&v"(ez), "=&v"(dd)
-                                                 : "v"(pxx), "v"(pyy), "v"(pzz), "v"(cxy), "v"(cyz));
-                                } else
-                                if (hook_bits & 64)       // (... and with ONE wait state behind each, what the compiler leaves between dependent ones)
-                                asm volatile("s_nop 0\n\t"
-                                             "v_pk_add_f32 %0, %4, %7 neg_lo:[0,1] neg_hi:[0,1]\n\ts_nop 0\n\t"
-                                             "v_pk_add_f32 %1, %5, %8 neg_lo:[0,1] neg_hi:[0,1]\n\ts_nop 0\n\t"
-                                             "v_pk_add_f32 %2, %6, %9 neg_lo:[0,1] neg_hi:[0,1]\n\ts_nop 0\n\t"
-                                             "v_pk_mul_f32 %3, %1, %1\n\ts_nop 0\n\t"
-                                             "v_pk_fma_f32 %3, %0, %0, %3\n\ts_nop 0\n\t"
-                                             "v_pk_fma_f32 %3, %2, %2, %3\n\ts_nop 0"
-                                             : "=&v"(ex), "=&v"(ey), "=&v"(ez), "=&v"(dd)
-                                             : "v"(pxx), "v"(pyy), "v"(pzz), "v"(cxx), "v"(cyy), "v"(czz));
-                                else
-                                asm volatile("s_nop 3\n\t"
-                                             "v_pk_add_f32 %0, %4, %7 neg_lo:[0,1] neg_hi:[0,1]\n\ts_nop 3\n\t"
-                                             "v_pk_add_f32 %1, %5, %8 neg_lo:[0,1] neg_hi:[0,1]\n\ts_nop 3\n\t"
-                                             "v_pk_add_f32 %2, %6, %9 neg_lo:[0,1] neg_hi:[0,1]\n\ts_nop 3\n\t"
-                                             "v_pk_mul_f32 %3, %1, %1\n\ts_nop 3\n\t"
-                                             "v_pk_fma_f32 %3, %0, %0, %3\n\ts_nop 3\n\t"
-                                             "v_pk_fma_f32 %3, %2, %2, %3\n\ts_nop 3"
-                                             : "=&v"(ex), "=&v"(ey), "=&v"(ez), "=&v"(dd)
-                                             : "v"(pxx), "v"(pyy), "v"(pzz), "v"(cxx), "v"(cyy), "v"(czz));
-                            } else if (FMA) dd = __builtin_elementwise_fma(dz, dz, __builtin_elementwise_fma(dx, dx, dy * dy));
-                            else dd = (dx * dx + dy * dy) + dz * dz;
-                            if (hook_bits & 16) {      // (bisect: the two results leave the pair through separate 32-bit registers)
-                                float e0 = dd.x, e1 = dd.y;
-                                asm volatile("" : "+v"(e0));
-                                asm volatile("" : "+v"(e1));
-                                d[r] = d[r] < e0 ? d[r] : e0;
-                                d[r + 1] = d[r + 1] < e1 ? d[r + 1] : e1;
-                                asm volatile("" : "+v"(d[r]));
-                                asm volatile("" : "+v"(d[r + 1]));
-                            } else {
-                                d[r] = d[r] < dd.x ? d[r] : dd.x;
-                                d[r + 1] = d[r + 1] < dd.y ? d[r + 1] : dd.y;
-                            }
-                        }
-                    } else {
-#pragma unroll
-                        for (int r = 0; r < R; r++) {
-                            float dx = px[r] - cx, dy = py[r] - cy, dz = pz[r] - cz;
-                            asm volatile("" : "+v"(dx), "+v"(dy), "+v"(dz));
-                            float dd = sqdist_f<FMA>(dx, dy, dz);
-                            asm volatile("" : "+v"(dd));
-                            d[r] = d[r] < dd ? d[r] : dd;       // padding slots stay at -1
-                        }
+                    for (int r = 0; r < R; r++) {
+                        float dx = px[r] - cx, dy = py[r] - cy, dz = pz[r] - cz;
+                        asm volatile("" : "+v"(dx), "+v"(dy), "+v"(dz));
+                        float dd = sqdist_f<FMA>(dx, dy, dz);
+                        asm volatile("" : "+v"(dd));
+                        d[r] = d[r] < dd ? d[r] : dd;       // padding slots stay at -1
                     }
-                                };
-                for (; applied < avail; applied++) apply_pivot(std::integral_constant<bool, HOOK != 0>{});
+                };
+                for (; applied < avail; applied++) apply_pivot();
                 if (pr & kProgDone) break;
             }
             if (pr & (kProgFinal | kProgAbort)) break;
@@ -578,13 +492,7 @@ static __device__ __forceinline__ void fps_body(const FpsJobs &jobs, FpsSlot *sl
 template <int FMA, int R>
 __global__ __launch_bounds__(kFBlock) void fps_kernel(FpsJobs jobs, FpsSlot *slots, int *__restrict__ err)
 {
-    fps_body<FMA, R, 0>(jobs, slots, err);
-}
-
-template <int FMA, int R>
-__global__ __launch_bounds__(kFBlock) __attribute__((target("packed-fp32-ops"))) void fps_kernel_hook(FpsJobs jobs, FpsSlot *slots, int *__restrict__ err)
-{
-    fps_body<FMA, R, 1>(jobs, slots, err);
+    fps_body<FMA, R>(jobs, slots, err);
 }
 
 // Verification of a sampling, on the device, against the DEFINITION (round 5).  The k steps of a sampling are sequential, but
@@ -709,17 +617,6 @@ __global__ void fps_count_kernel(FpsJobs jobs, int nj, int *__restrict__ violati
 template <int FMA>
 static void launch_fps(int R, dim3 grid, hipStream_t st, const FpsJobs &jobs, FpsSlot *slots, int *err)
 {
-    if (jobs.legacy_pivot != 0) {          // a test asked for one of the bisection's variants
-        switch (R) {
-        case 1: case 2: hipLaunchKernelGGL((fps_kernel_hook<FMA, 2>), grid, dim3(kFBlock), 0, st, jobs, slots, err); break;
-        case 3: case 4: hipLaunchKernelGGL((fps_kernel_hook<FMA, 4>), grid, dim3(kFBlock), 0, st, jobs, slots, err); break;
-        case 5: case 6: case 7: case 8: hipLaunchKernelGGL((fps_kernel_hook<FMA, 8>), grid, dim3(kFBlock), 0, st, jobs, slots, err); break;
-        case 9: case 10: case 11: case 12: hipLaunchKernelGGL((fps_kernel_hook<FMA, 12>), grid, dim3(kFBlock), 0, st, jobs, slots, err); break;
-        case 13: case 14: case 15: case 16: hipLaunchKernelGGL((fps_kernel_hook<FMA, 16>), grid, dim3(kFBlock), 0, st, jobs, slots, err); break;
-        default: hipLaunchKernelGGL((fps_kernel_hook<FMA, 24>), grid, dim3(kFBlock), 0, st, jobs, slots, err); break;
-        }
-        return;
-    }
     switch (R) {
     case 1: case 2: hipLaunchKernelGGL((fps_kernel<FMA, 2>), grid, dim3(kFBlock), 0, st, jobs, slots, err); break;
     case 3: case 4: hipLaunchKernelGGL((fps_kernel<FMA, 4>), grid, dim3(kFBlock), 0, st, jobs, slots, err); break;
@@ -747,37 +644,24 @@ static int fps_class(int R) { return R <= 2 ? 0 : (R <= 4 ? 1 : (R <= 8 ? 2 : (R
 template <int FMA>
 static int fps_blocks_per_cu(int cls)
 {
-    // (the hook kernel -- a test's variant of the update -- may need more registers than the shipped one: asked separately)
-    const int hook = (t_fps_legacy & 255) != 0 ? 1 : 0;
-    static int cache[2][6] = {{0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0}};
-    if (cache[hook][cls] > 0) return cache[hook][cls];
+    static int cache[6] = {0, 0, 0, 0, 0, 0};
+    if (cache[cls] > 0) return cache[cls];
     int nb = 0;
     hipError_t e = hipSuccess;
-    if (hook) {
-        switch (cls) {
-        case 0: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fps_kernel_hook<FMA, 2>, kFBlock, 0); break;
-        case 1: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fps_kernel_hook<FMA, 4>, kFBlock, 0); break;
-        case 2: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fps_kernel_hook<FMA, 8>, kFBlock, 0); break;
-        case 3: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fps_kernel_hook<FMA, 12>, kFBlock, 0); break;
-        case 4: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fps_kernel_hook<FMA, 16>, kFBlock, 0); break;
-        default: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fps_kernel_hook<FMA, 24>, kFBlock, 0); break;
-        }
-    } else {
-        switch (cls) {
-        case 0: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fps_kernel<FMA, 2>, kFBlock, 0); break;
-        case 1: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fps_kernel<FMA, 4>, kFBlock, 0); break;
-        case 2: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fps_kernel<FMA, 8>, kFBlock, 0); break;
-        case 3: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fps_kernel<FMA, 12>, kFBlock, 0); break;
-        case 4: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fps_kernel<FMA, 16>, kFBlock, 0); break;
-        default: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fps_kernel<FMA, 24>, kFBlock, 0); break;
-        }
+    switch (cls) {
+    case 0: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fps_kernel<FMA, 2>, kFBlock, 0); break;
+    case 1: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fps_kernel<FMA, 4>, kFBlock, 0); break;
+    case 2: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fps_kernel<FMA, 8>, kFBlock, 0); break;
+    case 3: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fps_kernel<FMA, 12>, kFBlock, 0); break;
+    case 4: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fps_kernel<FMA, 16>, kFBlock, 0); break;
+    default: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fps_kernel<FMA, 24>, kFBlock, 0); break;
     }
     if (e != hipSuccess || nb < 1) nb = 1;
-    cache[hook][cls] = nb;
+    cache[cls] = nb;
     return nb;
 }
 
-thread_local int t_fps_legacy = 0;
+thread_local int t_fps_multi_wg = 0;
 
 // Verification OFF the caller's critical path (round 6; genpc_fps_defer).  The check of a finished sequence reads the cloud, the
 // samples and their recorded minima: ~1 ms of chip-wide kernels behind a 4-5 ms sampling, twice per completed scan.  Deferred,
@@ -821,17 +705,16 @@ static FpsDeferred *fps_deferred_of(hipStream_t st, bool create)
 
 }  // namespace genpc
 
-/* Test hook (applies to the calling host thread; returns the previous setting): 1 = the sampling's workers read the
- * round's pivots as per-lane LDS broadcasts -- the round-4 form that silently drew a sample a step early while another
- * stream ran v_mfma_f32_32x32x16_f16 --, 0 = through scalar registers (the shipped form). */
-GENPC_API int genpc_fps_tune(int legacy_pivot)
+/* Test hook (applies to the calling host thread; returns the previous setting): 256 = every cloud takes the multi-workgroup
+ * kernel (never the one-workgroup kernel of fps_grid.hip), 0 = the default choice; any other value is refused (-1). */
+GENPC_API int genpc_fps_tune(int mode)
 {
-    const int prev = genpc::t_fps_legacy;
-    // bits (for bisecting the trigger, tools/fps_reject_probe.py): 1 pivots read as per-lane LDS broadcasts, 2 packed update,
-    // 4 sixteen wait states in front of the update, 8 the update's operands copied through fresh VGPRs first, 16 the packed results
-    // leave their pair through separate 32-bit registers, 32 (with 2) the packed instructions written out with four wait states behind
-    // each; 1 alone = 3, the pre-fix form
-    genpc::t_fps_legacy = legacy_pivot == 1 ? 3 : (legacy_pivot & 511);      // bit 256: never the one-workgroup kernel of fps_grid.hip
+    if (mode != 0 && mode != 256) {
+        genpc::set_error("genpc_fps_tune: the mode is 0 or 256");
+        return -1;
+    }
+    const int prev = genpc::t_fps_multi_wg;
+    genpc::t_fps_multi_wg = mode;
     return prev;
 }
 
@@ -868,9 +751,9 @@ GENPC_API int genpc_fps_multi(int c, const int *n, const int *k, const float *co
     };
     // Which kernel: clouds that fit one workgroup's LDS take the pruned sampling of fps_grid.hip (no hand-off, several samples
     // per round, updates confined to the ball a sample can change), the others the multi-workgroup kernel above.  Same
-    // sequences (tests/test_gpu_fps.py runs both on every case); genpc_fps_tune bit 256 / GENPC_FPS_GRID=0: never the former.
+    // sequences (tests/test_gpu_fps.py runs both on every case); genpc_fps_tune(256) / GENPC_FPS_GRID=0: never the former.
     static const int env_grid = tune_env("GENPC_FPS_GRID", 1, "farthest point sampling: 1 = clouds of up to 32768 points are sampled by one workgroup with spatial pruning (csrc/fps_grid.hip), 0 = always the multi-workgroup kernel");
-    const bool grid_on = env_grid != 0 && t_fps_legacy == 0;
+    const bool grid_on = env_grid != 0 && t_fps_multi_wg == 0;
     std::vector<int> small, big;
     for (int j = 0; j < c; j++) (grid_on && fps_grid_takes(n[j]) ? small : big).push_back(j);
     size_t total_slots = 0, total_k = 0, spt_pts = 0;
@@ -997,7 +880,6 @@ GENPC_API int genpc_fps_multi(int c, const int *n, const int *k, const float *co
         // a launch takes up to kFMaxJobs clouds; its grid is (largest W) x (clouds), all of it resident together
         FpsJobs jobs = {};
         jobs.stat0 = big[j0] < 32 ? big[j0] : 32;
-        jobs.legacy_pivot = t_fps_legacy & 255;
         int nj = 0, wmax = 0, rmax = 1;
         while (j0 + nj < cb && nj < kFMaxJobs) {
             const int j = big[j0 + nj];

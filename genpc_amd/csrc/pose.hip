@@ -513,8 +513,6 @@ __global__ __launch_bounds__(kQBlock) void pose_replicate_kernel(size_t count, i
 //   mask_grad_kernel     one thread per point: gathers the weights over the pixels it covers, chains
 //                        through (u, v, rho) to the point and on to (R, s, t): same 13 accumulators as
 //                        the Chamfer gradient
-//   mask_grad_tile_kernel  opt-in: the same gather per tile from LDS through the tile lists, per-(point, tile)
-//                        sums that mask_grad_kernel then adds
 constexpr int kMaskTile = 16;
 constexpr int kSplatBlock = 1024;  // 16 waves per tile: a wave per point leaves long dependent chains, four waves per SIMD hide them
 constexpr int kSplatPer = 16;      // points per thread and round of the splat (16384 points per round)
@@ -598,10 +596,10 @@ constexpr int kBinPoison = 1 << 30;      // set in a tile's counter by a disc th
 // Block-level binning of one point per thread (all threads of the block call it; `valid`: this thread has a point):
 // the tile counts of the block's points are first accumulated in LDS, ONE global atomic per (block, tile) reserves the
 // block's range in the tile's list, then the threads write their entries: point index * 4 + slot, slot = the position
-// of the tile among the point's tiles (where the tile pass of the mask gradient leaves the point's partial sums).
+// of the tile among the point's tiles (the splat reads the index alone).
 // (One global atomic per (point, tile) -- 144 k per launch of four starts, 640 on the counter of a crowded tile -- made
 // the 5 us projection kernel 50 us.)  A disc over more than kBinPer tiles is listed nowhere and poisons the counters of
-// its tiles: the splat draws those by the full scan, the mask gradient takes such a point by itself.
+// its tiles: the splat draws those by the full scan.
 __device__ __forceinline__ void bin_points_block(int *__restrict__ cnt, int *__restrict__ idx, int *s_cnt, int *s_base, int S, bool valid,
                                                  int j, float u, float v, float rho)
 {
@@ -986,7 +984,7 @@ template <int BLEND>
 __global__ __launch_bounds__(kSplatBlock, 8) void mask_splat_kernel(int n, const float4 *__restrict__ uvr,
                                                                  const float *__restrict__ col, int S,
                                                                  float *__restrict__ planes, double *__restrict__ accum,
-                                                                 int *__restrict__ bins, int keep_bins, int nb,
+                                                                 int *__restrict__ bins, int nb,
                                                                  const float *__restrict__ zex, int *__restrict__ clean = nullptr)
 {
     static_assert(kSplatBlock == 4 * kMaskTile * kMaskTile, "four threads per pixel of the tile");
@@ -1236,10 +1234,10 @@ __global__ __launch_bounds__(kSplatBlock, 8) void mask_splat_kernel(int n, const
             }
         }
     }
-    // the count is reset for the next launch by the last kernel that reads the lists: this one, or the mask gradient's tile pass
+    // the count is reset for the next launch by the last kernel that reads the lists: this one
     __syncthreads();
     GENPC_STL(4);
-    if (bins && !keep_bins && threadIdx.x == 0) bin_cnt[tile] = 0;
+    if (bins && threadIdx.x == 0) bin_cnt[tile] = 0;
     // (the full scan of a tile without a usable list is a function of its own, NOT inlined: its sixteen-points-per-thread
     // bookkeeping is what overflowed the 64 registers the two-blocks-per-CU launch allows -- 59 spilled VGPRs, ten scratch
     // instructions of them on the path of a tile that has its list; VERDICT r4 weak #8.  Here the spills stay in the callee.)
@@ -1632,151 +1630,6 @@ __global__ __launch_bounds__(kQBlock) void mask_w_kernel(int S, const float *__r
     if (blockIdx.x == 0 && threadIdx.x == 0) accum[15] += (double)mask_weight * mask_loss_value(accum, stats, P);
 }
 
-// grid (tiles, b), the tile pass of the mask gradient: a tile's W planes in LDS, one thread per entry of the tile's list
-// (bins), the entry's point gathers the weights of its pixels INSIDE the tile and leaves the three sums in its slot of
-// gpart[e, j, kBinPer]; mask_grad_kernel adds a point's slots in order and chains to the pose.  (A thread per point
-// gathering its whole box from global memory was bound by the scattered 16-byte reads: 8 scans in lock-step 150 us, 45 us
-// with the same instructions on coalesced addresses.)  A tile whose list overflowed walks all points of the image.
-// Resets the tile's counter (the splat kept it for this pass).
-// TB threads: 1024 with the entries sorted by piece size when few images are in flight (the crowded tiles are the critical
-// path), 256 unsorted when many are (a tile's list averages 125 entries: fourteen of sixteen waves of a 1024-thread block
-// idle while two blocks fill the CU -- 104 us at 32 images; eight small blocks per CU: see DESIGN 4.5)
-template <int TB, bool SORT, int BLEND>
-__global__ __launch_bounds__(TB) void mask_grad_tile_kernel(int n, const float4 *__restrict__ uvr, const float *__restrict__ col,
-                                                                       int S, const float *__restrict__ W1,
-                                                                       const float4 *__restrict__ W4, int *__restrict__ bins,
-                                                                       float4 *__restrict__ gpart, const float *__restrict__ zex)
-{
-    static_assert(TB >= kMaskTile * kMaskTile, "a thread per pixel for the load");
-    __shared__ float4 sW4[kMaskTile * kMaskTile];
-    __shared__ float sW1[kMaskTile * kMaskTile];
-    __shared__ int s_list[SORT ? kTileCap : 1];
-    __shared__ int s_ccnt[4];
-    static_assert(kTileCap % TB == 0, "whole entries per thread");
-    const int e = blockIdx.y, tile = blockIdx.x;
-    const int tiles_x = (S + kMaskTile - 1) / kMaskTile;
-    const int tx0 = (tile % tiles_x) * kMaskTile, ty0 = (tile / tiles_x) * kMaskTile;
-    const int tx1 = min(S, tx0 + kMaskTile) - 1, ty1 = min(S, ty0 + kMaskTile) - 1;
-    uvr += (size_t)e * n;
-    if (col) col += (size_t)e * n * 3;
-    if (BLEND) zex += (size_t)e * n;
-    W1 += (size_t)e * S * S;
-    W4 += (size_t)e * S * S;
-    gpart += (size_t)e * n * kBinPer;
-    int *bin_cnt = bins + (size_t)e * bins_tiles(S);
-    const int *bin_idx = bins + (size_t)gridDim.y * bins_tiles(S) + ((size_t)e * bins_tiles(S) + tile) * kTileCap;
-    if (threadIdx.x < kMaskTile * kMaskTile) {
-        const int px = tx0 + (threadIdx.x & (kMaskTile - 1)), py = ty0 + threadIdx.x / kMaskTile;
-        const bool in = px < S && py < S;
-        sW4[threadIdx.x] = in ? W4[(size_t)py * S + px] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        sW1[threadIdx.x] = in ? W1[(size_t)py * S + px] : 0.0f;
-    }
-    const int count = bin_cnt[tile] & (kBinPoison - 1);
-    __syncthreads();
-    // One thread per entry.  Once the weights come from LDS the gather is VALU-bound (40 instructions a pixel over a box of
-    // 81, and a wave runs the largest box of its lanes), so the walk is cut to the disc: rows whose chord is empty are
-    // skipped, a row is walked over its chord +- a pixel (the test on av below still decides), and 1 / (1 - av) is the
-    // hardware reciprocal (1 ulp; the oracle bar on the gradient is 2e-3).  Sixteen lanes per entry (a lane per row) was no
-    // faster (43.7 us against 44.7 for a thread per entry over the full box; this form 25.6).
-    auto gather = [&](int j, int slot, float4 q) {
-        const float u = q.x, v = q.y, rho = q.z, ir2 = q.w;
-        float cr = 1.0f, cg = 1.0f, cb = 1.0f;
-        if (col) { cr = col[(size_t)j * 3 + 0]; cg = col[(size_t)j * 3 + 1]; cb = col[(size_t)j * 3 + 2]; }
-        // the point's pixel box (mask_grad_kernel's), cut to the tile
-        const int c0 = max(max((int)floorf(u - rho - 0.5f), 0), tx0), c1 = min(min((int)ceilf(u + rho - 0.5f), S - 1), tx1);
-        const int r0 = max(max((int)floorf(v - rho - 0.5f), 0), ty0), r1 = min(min((int)ceilf(v + rho - 0.5f), S - 1), ty1);
-        const float rho2 = rho * rho;
-        float gu = 0.0f, gv = 0.0f, gr = 0.0f, gz = 0.0f;
-        const float ze = BLEND ? zex[j] : 0.0f;
-        for (int r = r0; r <= r1; r++) {
-            const float dy = (float)r + 0.5f - v;
-            const float h2 = rho2 - dy * dy;
-            if (h2 < -1e-5f * rho2) continue;
-            const float h = sqrtf(fmaxf(h2, 0.0f));
-            const int ca = max((int)floorf(u - h - 0.5f), c0), cz = min((int)ceilf(u + h - 0.5f), c1);
-            const float dy2 = dy * dy;
-            const float4 *rw4 = sW4 + (r - ty0) * kMaskTile - tx0;
-            const float *rw1 = sW1 + (r - ty0) * kMaskTile - tx0;
-            // (the loads behind the test: a branch-free form -- loads first, a selected 0 for pixels outside the disc, two
-            // pixels a trip -- was slower, 25.6 -> 30.9 us)
-            for (int cc = ca; cc <= cz; cc++) {
-                const float dx = (float)cc + 0.5f - u;
-                const float d2 = dx * dx + dy2;
-                const float av = 1.0f - d2 * ir2;
-                if (BLEND) {
-                    if (av <= 0.0f) continue;
-                    const float4 w4 = rw4[cc];
-                    const float w = ((cr * w4.x + cg * w4.y) + (cb * w4.z - w4.w)) * __expf(ze - rw1[cc]);
-                    gz += w * fminf(av, kMaskAmax);       // through the depth: also where the coverage is clamped
-                    if (av >= kMaskAmax) continue;
-                    gu += w * dx;
-                    gv += w * dy;
-                    gr += w * d2;
-                    continue;
-                }
-                if (av <= 0.0f || av >= kMaskAmax) continue;      // outside the disc / clamped: no gradient
-                const float4 w4 = rw4[cc];
-                const float w = rw1[cc] * __builtin_amdgcn_rcpf(1.0f - av) + ((cr * w4.x + cg * w4.y) + (cb * w4.z - w4.w));
-                gu += w * dx;
-                gv += w * dy;
-                gr += w * d2;
-            }
-        }
-        gpart[(size_t)j * kBinPer + slot] = make_float4(gu, gv, gr, gz);
-    };
-    if (count <= kTileCap && !SORT) {
-        for (int i = threadIdx.x; i < count; i += TB) {
-            const int ent = bin_idx[i];
-            gather(ent >> 2, ent & 3, uvr[ent >> 2]);
-        }
-    } else if (count <= kTileCap) {
-        // Entries in order of the size of their piece of the disc (four classes by the clipped box's area): a wave runs as
-        // long as its largest piece, and a tile's list mixes whole discs (81 pixels) with halves and corners of discs
-        // centred in the neighbouring tiles.  The order inside a class is arbitrary -- every entry writes its own slot.
-        constexpr int kPerThread = SORT ? kTileCap / TB : 1;
-        int my_c[kPerThread], my_pos[kPerThread], my_ent[kPerThread];
-        if (threadIdx.x < 4) s_ccnt[threadIdx.x] = 0;
-        __syncthreads();
-#pragma unroll
-        for (int t = 0; t < kPerThread; t++) {
-            const int i = threadIdx.x + t * TB;
-            my_c[t] = -1;
-            if (i < count) {
-                const int ent = bin_idx[i];
-                const float4 q = uvr[ent >> 2];
-                const int c0 = max(max((int)floorf(q.x - q.z - 0.5f), 0), tx0), c1 = min(min((int)ceilf(q.x + q.z - 0.5f), S - 1), tx1);
-                const int r0 = max(max((int)floorf(q.y - q.z - 0.5f), 0), ty0), r1 = min(min((int)ceilf(q.y + q.z - 0.5f), S - 1), ty1);
-                const int area = max(c1 - c0 + 1, 0) * max(r1 - r0 + 1, 0);
-                const int full = (2 * (int)q.z + 3) * (2 * (int)q.z + 3);      // about the unclipped box
-                const int c = 4 * area >= 3 * full ? 0 : (2 * area >= full ? 1 : (4 * area >= full ? 2 : 3));
-                my_ent[t] = ent;
-                my_c[t] = c;
-                my_pos[t] = atomicAdd(&s_ccnt[c], 1);
-            }
-        }
-        __syncthreads();
-        const int o1 = s_ccnt[0], o2 = o1 + s_ccnt[1], o3 = o2 + s_ccnt[2];
-#pragma unroll
-        for (int t = 0; t < kPerThread; t++)
-            if (my_c[t] >= 0) s_list[(my_c[t] == 0 ? 0 : (my_c[t] == 1 ? o1 : (my_c[t] == 2 ? o2 : o3))) + my_pos[t]] = my_ent[t];
-        __syncthreads();
-        for (int i = threadIdx.x; i < count; i += TB) {
-            const int ent = s_list[i];
-            gather(ent >> 2, ent & 3, uvr[ent >> 2]);
-        }
-    } else {
-        for (int j = threadIdx.x; j < n; j += TB) {
-            const float4 q = uvr[j];
-            if (!(q.z > 0.0f)) continue;
-            int slot;
-            const int total = tile_count(S, q.x, q.y, q.z, tile, slot);
-            if (slot >= 0 && total <= kBinPer) gather(j, slot, q);
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) bin_cnt[tile] = 0;
-}
-
 // 1-D grid of gx * nb blocks (xcd_block): gradient of the mask term with respect to (R, s, t), into accum[0..12].
 // FUSEW (round 6): the per-pixel weights are not read from W1 / W4 but evaluated where they are gathered, from the image's
 // planes and the reference mask with mask_w_kernel's own arithmetic (mask_w_pixel: same bits) -- the alignment loop's step is
@@ -1788,7 +1641,6 @@ __global__ __launch_bounds__(kQBlock) void mask_grad_kernel(int n, const float *
                                                             const float *__restrict__ params, int pstride, float radius,
                                                             int S, const float *__restrict__ W1,
                                                             const float4 *__restrict__ W4, double *__restrict__ accum,
-                                                            const float4 *__restrict__ gpart, const float4 *__restrict__ uvr,
                                                             int gx, int nb, const float *__restrict__ planes = nullptr,
                                                             const float *__restrict__ mref = nullptr,
                                                             const float *__restrict__ stats = nullptr, float mask_weight = 0.0f,
@@ -1804,7 +1656,6 @@ __global__ __launch_bounds__(kQBlock) void mask_grad_kernel(int n, const float *
     }
     const XcdBlock xb = xcd_block(gx, nb);
     const int e = xb.e;
-    if (uvr) uvr += (size_t)e * n;
     v += (size_t)e * n * 3;
     if (col) col += (size_t)e * n * 3;
     const int PP = S * S;
@@ -1812,7 +1663,6 @@ __global__ __launch_bounds__(kQBlock) void mask_grad_kernel(int n, const float *
         W1 += (size_t)e * PP;
         W4 += (size_t)e * PP;
     }
-    if (gpart) gpart += (size_t)e * n * kBinPer;
     center += (size_t)e * cstride;
     params += (size_t)e * pstride;
     accum += (size_t)e * kAcc;
@@ -1857,24 +1707,8 @@ __global__ __launch_bounds__(kQBlock) void mask_grad_kernel(int n, const float *
         const float ir2 = 1.0f / (q.rho * q.rho);
         float gu = 0.0f, gv = 0.0f, gr = 0.0f, gz = 0.0f;
         const float ze = pulsar_ze(q.zv);
-        // after the tile pass (gpart): the sums of a point over at most kBinPer tiles lie in its slots; a wider disc was
-        // left out there and gathers its box here
-        int ntile = kBinPer + 1;
-        if (kGradSub == 1 && gpart && ok) {
-            // (counted from the projection's OWN record of the point, which is what the lists were built from -- not from
-            // the values recomputed above, equal as they should be)
-            const float4 rec = uvr[j];
-            int none;
-            ntile = rec.z > 0.0f ? tile_count(S, rec.x, rec.y, rec.z, -1, none) : 0;
-            if (ntile <= kBinPer)
-                for (int k = 0; k < ntile; k++) {
-                    const float4 g = gpart[(size_t)j * kBinPer + k];
-                    gu += g.x; gv += g.y; gr += g.z; gz += g.w;
-                }
-        }
-        if (ok && ntile > kBinPer) {
-            // the walk of mask_grad_tile_kernel: rows with an empty chord skipped, a row over its chord +- a pixel, the
-            // hardware reciprocal for 1 / (1 - av)
+        if (ok) {
+            // rows with an empty chord skipped, a row over its chord +- a pixel, the hardware reciprocal for 1 / (1 - av)
             const float rho2 = q.rho * q.rho;
             for (int r = r0 + sub; r <= r1; r += kGradSub) {
                 const float dy = (float)r + 0.5f - q.v;
@@ -2030,12 +1864,7 @@ static int render_blend()
 }
 
 // scratch of the mask term for b scans of P pixels and up to nmax points (bytes, 256-aligned pieces)
-// GENPC_SPLAT_BINS=0: every tile by the full scan (A/B)
-static bool use_bins(int S)
-{
-    static const bool v = !(tune_env("GENPC_SPLAT_BINS", 1, "alignment loop: 0 = the colour splat scans every point per tile instead of reading per-tile lists") == 0);
-    return v && bins_tiles(S) <= (size_t)kBinTiles;
-}
+static bool use_bins(int S) { return bins_tiles(S) <= (size_t)kBinTiles; }
 
 struct MaskScratch {
     float *stats;      // [b, 8]
@@ -2046,7 +1875,6 @@ struct MaskScratch {
     float4 *uvr;       // [b, nmax]
     float *zex;        // [b, nmax] blend 1: the depth exponents of the projected points
     int *bins;         // [b, tiles] counts | [b, tiles, kTileCap] entries (bin_points_block)
-    float4 *gpart;     // [b, nmax, kBinPer] per-tile sums of the mask gradient (mask_grad_tile_kernel)
     int *clean;        // [b, tiles]: 1 = the tile's pixels hold the background in all five planes (mask_splat_kernel: an empty tile leaves at once)
     size_t clean_bytes;
     size_t bins_count_bytes;
@@ -2061,7 +1889,7 @@ struct MaskScratch {
     {
         return up((size_t)b * 8 * 4) + up((size_t)b * P * 4) + up((size_t)b * 5 * P * 4) + up((size_t)b * P * 4) +
                up((size_t)b * P * 16) + up((size_t)b * nmax * 16) + up((size_t)b * nmax * 4) + up(bins_bytes(b, P)) +
-               up((size_t)b * nmax * kBinPer * 16) + up((size_t)b * bins_tiles((int)side(P)) * sizeof(int));
+               up((size_t)b * bins_tiles((int)side(P)) * sizeof(int));
     }
     void carve(char *base, int b, size_t P, size_t nmax)
     {
@@ -2074,7 +1902,6 @@ struct MaskScratch {
         uvr = (float4 *)(base + off); off += up((size_t)b * nmax * 16);
         zex = (float *)(base + off); off += up((size_t)b * nmax * 4);
         bins = (int *)(base + off); off += up(bins_bytes(b, P));
-        gpart = (float4 *)(base + off); off += up((size_t)b * nmax * kBinPer * 16);
         clean = (int *)(base + off);
         clean_bytes = (size_t)b * bins_tiles((int)side(P)) * sizeof(int);
         bins_count_bytes = bins_bytes(b, P) ? (size_t)b * bins_tiles((int)side(P)) * sizeof(int) : 0;
@@ -2098,19 +1925,12 @@ static int mask_prepare_ref(int b, int np, const float *partial, const float *pa
                        (const float *)nullptr, 0, 0, radius, S, m.uvr, use_bins(S) ? m.bins : (int *)nullptr, blend ? m.zex : (float *)nullptr);
     if (blend)
         hipLaunchKernelGGL(mask_splat_kernel<1>, dim3(mask_tiles(S) * b), dim3(kSplatBlock), 0, st, np, (const float4 *)m.uvr, partial_col,
-                           S, m.planes, (double *)nullptr, use_bins(S) ? m.bins : (int *)nullptr, 0, b, (const float *)m.zex, m.clean);
+                           S, m.planes, (double *)nullptr, use_bins(S) ? m.bins : (int *)nullptr, b, (const float *)m.zex, m.clean);
     else
         hipLaunchKernelGGL(mask_splat_kernel<0>, dim3(mask_tiles(S) * b), dim3(kSplatBlock), 0, st, np, (const float4 *)m.uvr, partial_col,
-                           S, m.planes, (double *)nullptr, use_bins(S) ? m.bins : (int *)nullptr, 0, b, (const float *)nullptr, m.clean);
+                           S, m.planes, (double *)nullptr, use_bins(S) ? m.bins : (int *)nullptr, b, (const float *)nullptr, m.clean);
     hipLaunchKernelGGL(mask_ref_kernel, dim3(b), dim3(kMLThreads), 0, st, S, (const float *)m.planes, blend ? 2 : 0, m.mref, m.stats);
     return check(hipGetLastError(), "mask reference launch") ? 1 : 0;
-}
-
-// (the per-point silhouette gradient can carry pose_grad's blocks along; the per-tile form cannot)
-static bool mask_step_carries(int S)
-{
-    static const int env_tp = tune_env("GENPC_MASK_GRAD_TILES", -1, "alignment loop: 1 = the silhouette gradient through the per-tile lists (opt-in), 0 = per point");
-    return !(use_bins(S) && env_tp > 0);
 }
 
 // the launches of the mask term for the current parameters: accum[0..12] += gradient, accum[15] += loss
@@ -2120,17 +1940,6 @@ static int mask_step(int b, int nc, const float *complete, const float *complete
 {
     const float rad = 1.1f * radius;      // diff_obj_pose.py:385: the posed cloud is drawn with 1.1 x the radius
     const int gp = lin_grid((long long)S * S);
-    // The mask gradient per tile from LDS (mask_grad_tile_kernel + the per-point sum) or per point from global memory
-    // (mask_grad_kernel alone).  Measured at 16384 points per image, 224 x 224: 4 images (one scan's four starts, the W
-    // planes stay in L2) 25.6 + 8.2 us against 29.3; 32 images (8 scans in lock-step: 32 MB of W planes through every 4 MB
-    // L2, the scattered 16-byte reads cost 105 of the per-point kernel's 150 us) 107 + 21 against 150-168.
-    static const int env_tp = tune_env("GENPC_MASK_GRAD_TILES", -1, "alignment loop: 1 = the silhouette gradient through the per-tile lists (opt-in), 0 = per point");
-    // (8 x 4 images of 32768 points, 167 points per tile on average: 0.814 s per call with the tile pass, 0.789 without --
-    // crowded tiles take several rounds of the block; 16384 points, 84 per tile: 167 ms against 176)
-    // OPT-IN (GENPC_MASK_GRAD_TILES=1).  On a cloud that fills the image the tile pass wins 5 % with 32 images in flight, but
-    // on a small object (16384 points over ~18 tiles: tools/time_reg_small.py) a few blocks carry all the work and 8 scans
-    // take 328 ms against 191 with the per-point kernel -- which does not care where the points fall.
-    const bool tile_pass = use_bins(S) && env_tp > 0;
     (void)b;
     const int blend = render_blend(), mode = blend ? 2 : 0;
     const float *zex = blend ? m.zex : nullptr;
@@ -2139,63 +1948,46 @@ static int mask_step(int b, int nc, const float *complete, const float *complete
                            pstride, 1, rad, S, m.uvr, use_bins(S) ? m.bins : (int *)nullptr, blend ? m.zex : (float *)nullptr);
     if (blend)
         hipLaunchKernelGGL(mask_splat_kernel<1>, dim3(mask_tiles(S) * b), dim3(kSplatBlock), 0, st, nc, (const float4 *)m.uvr, complete_col,
-                           S, m.planes, accum, use_bins(S) ? m.bins : (int *)nullptr, tile_pass ? 1 : 0, b, zex, m.clean);
+                           S, m.planes, accum, use_bins(S) ? m.bins : (int *)nullptr, b, zex, m.clean);
     else
         hipLaunchKernelGGL(mask_splat_kernel<0>, dim3(mask_tiles(S) * b), dim3(kSplatBlock), 0, st, nc, (const float4 *)m.uvr, complete_col,
-                           S, m.planes, accum, use_bins(S) ? m.bins : (int *)nullptr, tile_pass ? 1 : 0, b, zex, m.clean);
+                           S, m.planes, accum, use_bins(S) ? m.bins : (int *)nullptr, b, zex, m.clean);
     // few blocks per image: every block ends in 22 double atomics on the image's accumulators, and 196 blocks x 22 on the
     // same addresses serialise in L2 (17.5 us for 0.2 M pixels; GENPC_MASK_SUMS_BLOCKS for A/B)
     static const int env_sb = tune_env("GENPC_MASK_SUMS_BLOCKS", 0, "alignment loop: blocks per image of mask_sums_kernel (0 = pick)");
     const int gs = std::min(gp, env_sb > 0 ? env_sb : 48);      // 196: 221 ms per 8-scan call, 48: 210, 24: 210, 12: 210 (single scan: 42.1 / 41.4 / 41.8 / 43.3)
     hipLaunchKernelGGL(mask_sums_kernel, dim3(gs, b), dim3(kQBlock), 0, st, S, (const float *)m.planes, mode, (const float *)m.mref,
                        (const float *)m.stats, accum);
-    // the weights per pixel as a launch of their own (the tile pass reads them from LDS tiles), or evaluated inside the gather
+    // the weights per pixel as a launch of their own, or evaluated inside the gather
     static const int env_fw = tune_env("GENPC_MASK_FUSE_W", 1, "alignment loop: 1 = the silhouette gradient evaluates the per-pixel weights where it gathers them (no mask_w launch), 0 = mask_w_kernel + gather");
     // (only where the gather touches fewer pixels than ~three and a half passes over the image (config 2: 4493 points): a point's disc covers ~pi rho^2 pixels, rho =
     //  S/2 * focal * radius / 3 at the camera's distance -- 2451 points: 0.4 of the image; 16384 points: 2.9 images' worth of
     //  weights, each 60 instructions where the launch of its own computes them once per pixel)
     const float rho_px = 0.5f * (float)S * kMaskFocal * rad / kMaskEyeZ;
-    const bool fuse_w = !tile_pass && env_fw != 0 && (double)nc * 3.1416 * rho_px * rho_px <= 3.5 * (double)S * S;
+    const bool fuse_w = env_fw != 0 && (double)nc * 3.1416 * rho_px * rho_px <= 3.5 * (double)S * S;
     if (!fuse_w)
         hipLaunchKernelGGL(mask_w_kernel, dim3(gp, b), dim3(kQBlock), 0, st, S, (const float *)m.planes, mode, (const float *)m.mref,
                            (const float *)m.stats, mask_weight, m.W1, m.W4, accum);
-    if (tile_pass) {
-#define GENPC_LAUNCH_TILE(TB, SORT, BL)                                                                                              \
-        hipLaunchKernelGGL((mask_grad_tile_kernel<TB, SORT, BL>), dim3(mask_tiles(S), b), dim3(TB), 0, st, nc, (const float4 *)m.uvr,   \
-                           complete_col, S, (const float *)m.W1, (const float4 *)m.W4, m.bins, m.gpart, zex)
-        if (b > 4) { if (blend) GENPC_LAUNCH_TILE(256, false, 1); else GENPC_LAUNCH_TILE(256, false, 0); }
-        else { if (blend) GENPC_LAUNCH_TILE(1024, true, 1); else GENPC_LAUNCH_TILE(1024, true, 0); }
-#undef GENPC_LAUNCH_TILE
-        if (blend)
-            hipLaunchKernelGGL((mask_grad_kernel<1, 1>), dim3(lin_grid(nc) * b), dim3(kQBlock), 0, st, nc, complete, complete_col, center,
-                               cstride, params, pstride, rad, S, (const float *)m.W1, (const float4 *)m.W4, accum,
-                               (const float4 *)m.gpart, (const float4 *)m.uvr, lin_grid(nc), b);
-        else
-            hipLaunchKernelGGL((mask_grad_kernel<1, 0>), dim3(lin_grid(nc) * b), dim3(kQBlock), 0, st, nc, complete, complete_col, center,
-                               cstride, params, pstride, rad, S, (const float *)m.W1, (const float4 *)m.W4, accum,
-                               (const float4 *)m.gpart, (const float4 *)m.uvr, lin_grid(nc), b);
-    } else {
-        // lanes per point: a thread per point walks its whole pixel box alone (a chain of ~35 dependent gathers at the loop's
-        // radius: 21 us for 4 x 2451 points), eight lanes share it row by row (12.9 us) -- until the points fill the chip by
-        // themselves (measured at 4 x 16384 points, the four starts in lock-step: <1> 35 us, <8> 42)
-        static const int env_sub = tune_env("GENPC_MASK_GRAD_SUB", 0, "alignment loop: lanes per point of the per-point silhouette gradient (0 = pick)");
-        const int sub = env_sub ? env_sub : ((long long)b * nc <= 24576 || b <= 2 ? 8 : 1);
-        const PoseGradArgs pgx = ride ? *ride : PoseGradArgs{};
+    // lanes per point: a thread per point walks its whole pixel box alone (a chain of ~35 dependent gathers at the loop's
+    // radius: 21 us for 4 x 2451 points), eight lanes share it row by row (12.9 us) -- until the points fill the chip by
+    // themselves (measured at 4 x 16384 points, the four starts in lock-step: <1> 35 us, <8> 42)
+    static const int env_sub = tune_env("GENPC_MASK_GRAD_SUB", 0, "alignment loop: lanes per point of the per-point silhouette gradient (0 = pick)");
+    const int sub = env_sub ? env_sub : ((long long)b * nc <= 24576 || b <= 2 ? 8 : 1);
+    const PoseGradArgs pgx = ride ? *ride : PoseGradArgs{};
 #define GENPC_LAUNCH_MASK_GRAD3(SUB, BL, FW)                                                                                         \
-        hipLaunchKernelGGL((mask_grad_kernel<SUB, BL, FW>), dim3(lin_grid((long long)nc * SUB) * b + pgx.gx * b), dim3(kQBlock), 0, st, nc, complete, \
-                           complete_col, center, cstride, params, pstride, rad, S, (const float *)m.W1, (const float4 *)m.W4, accum, \
-                           (const float4 *)nullptr, (const float4 *)nullptr, lin_grid((long long)nc * SUB), b, (const float *)m.planes, \
-                           (const float *)m.mref, (const float *)m.stats, mask_weight, pgx)
+    hipLaunchKernelGGL((mask_grad_kernel<SUB, BL, FW>), dim3(lin_grid((long long)nc * SUB) * b + pgx.gx * b), dim3(kQBlock), 0, st, nc, complete, \
+                       complete_col, center, cstride, params, pstride, rad, S, (const float *)m.W1, (const float4 *)m.W4, accum,     \
+                       lin_grid((long long)nc * SUB), b, (const float *)m.planes, (const float *)m.mref, (const float *)m.stats,      \
+                       mask_weight, pgx)
 #define GENPC_LAUNCH_MASK_GRAD2(SUB, BL) do { if (fuse_w) GENPC_LAUNCH_MASK_GRAD3(SUB, BL, 1); else GENPC_LAUNCH_MASK_GRAD3(SUB, BL, 0); } while (0)
 #define GENPC_LAUNCH_MASK_GRAD(SUB) do { if (blend) GENPC_LAUNCH_MASK_GRAD2(SUB, 1); else GENPC_LAUNCH_MASK_GRAD2(SUB, 0); } while (0)
-        if (sub == 8) GENPC_LAUNCH_MASK_GRAD(8);
-        else if (sub == 4) GENPC_LAUNCH_MASK_GRAD(4);
-        else if (sub == 2) GENPC_LAUNCH_MASK_GRAD(2);
-        else GENPC_LAUNCH_MASK_GRAD(1);
+    if (sub == 8) GENPC_LAUNCH_MASK_GRAD(8);
+    else if (sub == 4) GENPC_LAUNCH_MASK_GRAD(4);
+    else if (sub == 2) GENPC_LAUNCH_MASK_GRAD(2);
+    else GENPC_LAUNCH_MASK_GRAD(1);
 #undef GENPC_LAUNCH_MASK_GRAD3
 #undef GENPC_LAUNCH_MASK_GRAD2
 #undef GENPC_LAUNCH_MASK_GRAD
-    }
     return check(hipGetLastError(), "mask step launch") ? 1 : 0;
 }
 
@@ -2224,10 +2016,10 @@ GENPC_API int genpc_splat_image(int n, const float *pts, const float *col, float
                        (const float *)nullptr, 0, 0, radius, size, m.uvr, use_bins(size) ? m.bins : (int *)nullptr, blend ? m.zex : (float *)nullptr);
     if (blend)
         hipLaunchKernelGGL(mask_splat_kernel<1>, dim3(mask_tiles(size)), dim3(kSplatBlock), 0, st, n, (const float4 *)m.uvr, col, size,
-                           m.planes, (double *)nullptr, use_bins(size) ? m.bins : (int *)nullptr, 0, 1, (const float *)m.zex, m.clean);
+                           m.planes, (double *)nullptr, use_bins(size) ? m.bins : (int *)nullptr, 1, (const float *)m.zex, m.clean);
     else
         hipLaunchKernelGGL(mask_splat_kernel<0>, dim3(mask_tiles(size)), dim3(kSplatBlock), 0, st, n, (const float4 *)m.uvr, col, size,
-                           m.planes, (double *)nullptr, use_bins(size) ? m.bins : (int *)nullptr, 0, 1, (const float *)nullptr, m.clean);
+                           m.planes, (double *)nullptr, use_bins(size) ? m.bins : (int *)nullptr, 1, (const float *)nullptr, m.clean);
     hipLaunchKernelGGL(mask_image_kernel, dim3(ceil_div((int)P, 256)), dim3(256), 0, st, (int)P, (const float *)m.planes, img, blend ? 2 : 0);
     return check(hipGetLastError(), "splat_image launch") ? 1 : 0;
 }
@@ -2659,7 +2451,7 @@ GENPC_API int genpc_pose_optimize_batch(int b, int nc, const float *complete, co
             }
             // one stream and the full objective: pose_grad's blocks ride at the end of the silhouette gradient's launch
             static const int env_ride = tune_env("GENPC_POSE_GRAD_RIDES", 1, "alignment loop, one stream, full objective: 1 = pose_grad's blocks in mask_grad's launch, 0 = a launch of its own");
-            const bool ride = mask && !dual && env_ride != 0 && mask_step_carries(render_size);
+            const bool ride = mask && !dual && env_ride != 0;
             PoseGradArgs pga{};
             if (ride) {
                 pga.nc = nc; pga.cstride = 4; pga.pstride = kStateFloats; pga.np = np;

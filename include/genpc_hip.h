@@ -33,9 +33,9 @@ extern "C" {
 #define GENPC_ARITH_FMA 1
 
 /* Library / device ------------------------------------------------------- */
-int genpc_abi_version(void);              /* bumps when a signature or a documented behaviour changes (16: genpc_hpr_* asynchronous,
-                                           * counts -1 on an internal error; genpc_fps*: out_idx[0] -2 = failed the check;
-                                           * genpc_fps_tune takes bits) */
+int genpc_abi_version(void);              /* bumps when a signature or a documented behaviour changes (17: genpc_fps_tune takes 0 or
+                                           * 256 only; 16: genpc_hpr_* asynchronous, counts -1 on an internal error;
+                                           * genpc_fps*: out_idx[0] -2 = failed the check) */
 const char *genpc_last_error(void);       /* last HIP error string, "" if none */
 int genpc_set_arith(int mode);            /* process default; returns the previous one */
 int genpc_set_arith_thread(int mode);     /* calling thread only, < 0: follow the default; returns the previous override */
@@ -439,15 +439,10 @@ int genpc_fps_defer(int on);
  * streams of the process (csrc/pose.hip).  Optional; pipeline.run_in_lanes calls it before making its lanes.  Returns 1. */
 int genpc_streams_prepare(void *stream);
 int genpc_fps_deferred_check(void *stream);
-/* Test hook (calling host thread; returns the previous setting): 1 = the pre-fix form of the sampling's workers -- pivots read
- * as per-lane LDS broadcasts and running minima lowered with PACKED fp32 instructions on register pairs, which is what drew
- * wrong samples next to other streams' matrix instructions (csrc/fps.hip; kept reachable so that
- * tests/test_gpu_concurrency.py can show the trigger); 0 = one register at a time (shipped).  Bits, for bisecting the
- * trigger (tools/fps_reject_probe.py): 1 per-lane LDS pivot reads, 2 packed update, 4 sixteen wait states in front of it,
- * 8 its operands copied through fresh registers, 16 its results leave their pair through 32-bit registers, 32 (with 2) the
- * six packed instructions written out on {c, c} pairs, four wait states behind each (64: one), 128 (with 2 | 32) written out
- * with half selection (op_sel) on (x, y) / (y, z) pairs -- the form that fails beside other streams' kernels; 1 alone means 3. */
-int genpc_fps_tune(int legacy_pivot);
+/* Test hook (calling host thread; returns the previous setting): 256 = every cloud of genpc_fps* takes the multi-workgroup
+ * kernel, never the one-workgroup kernel with spatial pruning (tests compare the two); 0 = the default choice.  Any other
+ * value returns -1 and sets genpc_last_error. */
+int genpc_fps_tune(int mode);
 /* Diagnostics: rounds[j] (host, c <= 32) = inter-workgroup exchanges cloud j of the last
  * genpc_fps_multi call on this stream took (one exchange yields several samples).  Synchronises.  */
 int genpc_fps_stats(int c, int *rounds, void *stream);

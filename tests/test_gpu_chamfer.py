@@ -119,9 +119,10 @@ def test_backward_vs_oracle(gp, oracle):
 
 
 def test_backward_large_call_forms(gp, oracle):
-    """From 262144 points per call the backward is two launches: own rows by plain read-modify-write, then the scattered
-    halves through LDS tiles that own their output rows (csrc/chamfer.hip: chamfer_grad_scatter_tiled_kernel) -- against the
-    oracle, ragged sizes (a last tile of 904 rows, a cloud smaller than a tile), indices that pile up on few targets."""
+    """From 262144 points per call the backward is one pass per direction: each term goes to the query's own row by plain
+    read-modify-write and to the target's row through an LDS tile that owns its output rows (csrc/chamfer.hip:
+    chamfer_grad_dir_kernel) -- against the oracle, ragged sizes (a last tile of 904 rows, a cloud smaller than a tile),
+    indices that pile up on few targets."""
     torch = gp["torch"]
     rng = np.random.default_rng(77)
     bsz, n, m = 24, 9096, 3000            # 24 x (9096 + 3000) = 290 k points

@@ -5,7 +5,6 @@ ulp (device expf vs libm expf); pose gradient 1e-4 relative (fp64 reductions in 
 different order); the optimisation loop by outcome (same basin, transform within
 1e-2, loss history within 2 %)."""
 import math
-import os
 from types import SimpleNamespace
 
 import numpy as np
@@ -248,20 +247,12 @@ def test_splat_fuzz(gp, oracle, render_blend):
         _close_images(img, ref, render_blend)
 
 
-def test_mask_gradient_tile_pass_and_its_fallbacks(gp, oracle):
-    """The mask gradient is gathered per tile from the splat's lists (pose.hip mask_grad_tile_kernel) and summed per
-    point; a tile whose list overflowed walks all points, a disc over more than four tiles gathers its own box, an image
-    of more than 1024 tiles has no lists.  Each against the oracle's full loss and gradient."""
+def test_mask_gradient_on_crowded_wide_and_listless_images(gp, oracle):
+    """The loss and gradient of the mask term where the splat's tile lists are at their limits: a tile whose list overflowed
+    (drawn by the full scan), a long list, discs over more than four tiles (in no list), tiles of both widths, an image of
+    more than 1024 tiles (no lists), a single tile.  Each against the oracle's full loss and gradient, and again through the
+    same scratch (the lists are handed back empty)."""
     torch = gp["torch"]
-    if os.environ.get("GENPC_MASK_GRAD_TILES") != "1":
-        # the tile pass is opt-in and the library reads the switch once per process: this test and the full-objective
-        # test again in a process that turns it on
-        import subprocess
-        import sys
-        r = subprocess.run([sys.executable, "-m", "pytest", __file__, "-q", "-x", "-m", "gpu", "-k",
-                            "tile_pass_and_its_fallbacks or full_loss_and_gradient_vs_oracle or dark_points or batched_equals_singles"],
-                           env=dict(os.environ, GENPC_MASK_GRAD_TILES="1"), capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     rng = np.random.default_rng(5)
     complete, partial, _ = _shape(4, 2500)
     knot = (complete[:1] + 0.004 * rng.standard_normal((9000, 3))).astype(np.float32)      # more than a list holds (8192)

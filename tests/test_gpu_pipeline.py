@@ -185,10 +185,11 @@ def test_scans_in_flight_side_by_side_change_nothing(env, golden):
                 assert torch.equal(torch.as_tensor(ma), torch.as_tensor(mb))
 
 
-def test_lanes_inherit_the_callers_thread_modes(env):
+def test_lanes_carry_the_callers_thread_modes(env):
     """the library's per-call modes are thread-local and run_in_lanes / complete_scan's stage-1 thread are new
     threads: a caller in strict arithmetic got FMA bits from its lanes.  The caller's modes (and torch's grad mode) now
-    travel with the work."""
+    travel with the work: arithmetic, NN path, EMD implementation, pose mode and the sampling's kernel choice
+    (genpc_fps_tune(256): the multi-workgroup kernel, the one value besides 0 that it takes)."""
     import torch
     from genpc_amd import _lib, pipeline
     L = _lib.lib
@@ -203,14 +204,14 @@ def test_lanes_inherit_the_callers_thread_modes(env):
     prev_n = L.genpc_nn_tune(1, -1)
     prev_e = L.genpc_emd_tune(1, -1)
     prev_p = L.genpc_pose_tune(0)
-    prev_f = L.genpc_fps_tune(1)
+    prev_f = L.genpc_fps_tune(256)
     try:
         with torch.no_grad():
             got = pipeline.run_in_lanes(probe, range(3), 3, dev)
     finally:
         L.genpc_set_arith_thread(prev_a); L.genpc_emd_tune(prev_e, -1); L.genpc_pose_tune(prev_p); L.genpc_fps_tune(prev_f)
         _lib.apply_thread_state((tuple(_lib.thread_state()[0][:1]) + (-1,) + tuple(_lib.thread_state()[0][2:]), torch.is_grad_enabled()))
-    assert all(g == (0, 1, 1, 0, 3, False) for g in got), got          # (genpc_fps_tune(1) = bits 1 | 2: the pre-fix form)
+    assert all(g == (0, 1, 1, 0, 256, False) for g in got), got
     assert all(b[0] == L.genpc_get_arith() and b[5] for b in base), base
     # and a lane's strict-mode sampling is the caller's strict-mode sampling
     x = torch.rand(1, 5000, 3, device=dev)
