@@ -24,10 +24,9 @@ FLAGS = [
 ]
 # No packed fp32 instructions (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32) anywhere in the library: in the farthest-point
 # sampling they were what drew wrong samples beside other streams' matrix instructions (csrc/fps.hip; the low half
-# of a register pair, lanes 48-63); scalar fp32 instructions give the same bits.  GENPC_PACKED_FP32=1 builds with them (A/B).
+# of a register pair, lanes 48-63); scalar fp32 instructions give the same bits.
 # (The feature is the device compiler's: the host pass prints one "not a recognized feature" line per file, dropped below.)
-if os.environ.get("GENPC_PACKED_FP32", "0") != "1":
-    FLAGS += ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+FLAGS += ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 
 
 def sources():

@@ -605,7 +605,7 @@ __global__ __launch_bounds__(kBlock) void chamfer_grad_kernel(int b, int n, cons
 constexpr int kGradBlock = 1024;      // (64 x 32768 both ways: 122 us; 512 threads 144, 256 threads 228 before the loads were batched; capped at 64 VGPRs for two blocks per CU 159)
 
 // Large calls, round 6: ONE pass per direction computes every term once and puts it in both places (chamfer3D.cu:157-171) --
-// a block owns a tile of TILE target rows of one cloud; it walks the other cloud's index array, and for the entries that
+// a block owns a tile of kGradTile target rows of one cloud; it walks the other cloud's index array, and for the entries that
 // land in its tile (exactly one block per entry) it evaluates the term, adds it to the QUERY's own gradient row (a plain
 // read-modify-write: that row has no other writer in this launch) and accumulates its negative in the tile's LDS copy, which
 // is added to the gradient at the end (a plain coalesced read-modify-write: the tile has one owner).  Direction 0 and
@@ -615,13 +615,13 @@ constexpr int kGradBlock = 1024;      // (64 x 32768 both ways: 122 us; 512 thre
 // eight load instructions fetched nothing); the blocks of a batch element share an XCD, so the tiles' walks of the same index
 // array and the partial lines of the own rows meet in one L2.
 constexpr int kGradList = 128;     // compacted hits a wave keeps per trip (more: the hits are dense, the lanes take them in place)
-template <int TILE>
+constexpr int kGradTile = 4096;    // target rows a block owns
 __global__ __launch_bounds__(kGradBlock) void chamfer_grad_dir_kernel(int b, int tiles, int nq, const float *__restrict__ Qc, int nt,
                                                                       const float *__restrict__ Tc, const float *__restrict__ Gd,
                                                                       const int *__restrict__ Ix, float *__restrict__ Oq,
                                                                       float *__restrict__ Ot)
 {
-    __shared__ float acc[TILE * 3];
+    __shared__ float acc[kGradTile * 3];
     __shared__ unsigned long long lst[kGradBlock / kWave][kGradList];      // query << 32 | row of the tile
     int e, tile;
     {
@@ -630,14 +630,14 @@ __global__ __launch_bounds__(kGradBlock) void chamfer_grad_dir_kernel(int b, int
         else { e = lin / tiles; tile = lin % tiles; }
     }
     if (e >= b) return;
-    const int t0 = tile * TILE;
+    const int t0 = tile * kGradTile;
     const float *__restrict__ Q = Qc + (size_t)e * nq * 3;
     const float *__restrict__ T = Tc + (size_t)e * nt * 3;
     const float *__restrict__ G = Gd + (size_t)e * nq;
     const int *__restrict__ I = Ix + (size_t)e * nq;
     float *__restrict__ OQ = Oq + (size_t)e * nq * 3;
     float *__restrict__ OT = Ot + (size_t)e * nt * 3;
-    const int rows = min(TILE, nt - t0);
+    const int rows = min(kGradTile, nt - t0);
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
     for (int i = threadIdx.x; i < rows * 3; i += kGradBlock) acc[i] = 0.0f;
     __syncthreads();
@@ -764,7 +764,7 @@ static void launch_r(const NNArgs &a, int blocks, hipStream_t st)
 //     many re-dos switch the pre-pass on, a pre-pass that finds next to nothing switches it off again.  The words are
 //     read without any synchronisation -- a stale value delays the switch by a call; results do not depend on it (the
 //     masks only remove targets that can never be reported).
-// GENPC_NN_DEDUPE=0 / 1 forces it off / on (A/B; tests: hooks 2048 / 4096 of genpc_nn_tune).
+// Hooks 2048 / 4096 of genpc_nn_tune force it off / on (tests).
 struct DedupeHint {
     unsigned *host = nullptr;          // cumulative, written by the GPU: [0] exhaustive re-dos, [1] copies found, [2] pre-passes completed (hipHostMalloc, mapped)
     std::mutex mu;
@@ -945,8 +945,7 @@ int nn_forward(int b, int ndir, const float *q0, int n0, const float *t0, int m0
         // Single-round launches whose slice fits the kernel's 2048-target LDS tile: blocks of 8 waves / 1024 queries,
         // one per CU -- the same two waves per SIMD, but a slice is read, split into f16 pieces and staged once per
         // 1024 queries instead of once per 512 (the prologue was a third of a block's time: tools/nn_timeline.py).
-        static const bool no_wide = tune_env("GENPC_NN_NOWIDE", 0, "f16 filter: 1 = no 8-wave blocks for single-round launches") != 0;
-        if (f16 && q == 4 && !tight && !no_wide && len > 1024 && blocks_at(len) <= 2 * (long long)num_cus()) {
+        if (f16 && q == 4 && !tight && len > 1024 && blocks_at(len) <= 2 * (long long)num_cus()) {
             wide = true;
             for (int d = 0; d < nd; d++) a.dir[d].qblocks = ceil_div(a.dir[d].nq, 2 * qper);
         }
@@ -998,8 +997,7 @@ int nn_forward(int b, int ndir, const float *q0, int n0, const float *t0, int m0
     }
     if (path == 2) {
         // exact duplicates among the targets (policy above nn_forward)
-        static const int env_dd = tune_env("GENPC_NN_DEDUPE", -1, "f16 filter: exact-duplicate pre-pass 0 off / 1 on (-1: callers' masks + adaptive policy)");
-        const int force = (a.debug & 2048) ? 0 : ((a.debug & 4096) ? 1 : env_dd);
+        const int force = (a.debug & 2048) ? 0 : ((a.debug & 4096) ? 1 : -1);
         DedupeHint *H = dedupe_hint();
         bool own_masks = true;
         for (int d = 0; d < nd; d++) own_masks = own_masks && a.dir[d].dupmask != nullptr;
@@ -1122,25 +1120,17 @@ GENPC_API int genpc_chamfer_backward(int b, int n, const float *xyz1, int m, con
         set_error("chamfer backward: problem too large for one launch");
         return 0;
     }
-    static const int env_split = tune_env("GENPC_CHAMFER_GRAD_SPLIT", 262144, "chamfer backward: points (both clouds) from which the gradient is accumulated through LDS tiles that own their output rows instead of global atomics (0 = never)");
-    if (env_split > 0 && (long long)b * ((long long)n + m) >= env_split) {
-        static const int env_tile = tune_env("GENPC_CHAMFER_GRAD_TILE", 4096, "chamfer backward, large calls: target rows a block owns (2048 | 4096 | 8192)");
-        const int tile_rows = env_tile == 2048 || env_tile == 8192 ? env_tile : 4096;
-        const int tiles_n = ceil_div(n, tile_rows), tiles_m = ceil_div(m, tile_rows);
+    // from 262144 points (both clouds) the gradient is accumulated through LDS tiles that own their output rows instead of
+    // global atomics
+    if ((long long)b * ((long long)n + m) >= 262144) {
+        const int tiles_n = ceil_div(n, kGradTile), tiles_m = ceil_div(m, kGradTile);
         // (a grid of more than 2^31 blocks -- no call fits such clouds in memory -- takes the atomics below)
         if ((long long)b * (tiles_n > tiles_m ? tiles_n : tiles_m) <= 0x7fffffffLL) {
             // direction 0: queries = cloud 1, tiles of cloud 2's gradient; direction 1 the converse
-#define GENPC_GRAD_DIR(TILE)                                                                                                          \
-            do {                                                                                                                      \
-                hipLaunchKernelGGL(chamfer_grad_dir_kernel<TILE>, dim3((unsigned)(b * tiles_m)), dim3(kGradBlock), 0, (hipStream_t)stream, b, tiles_m, \
-                                   n, xyz1, m, xyz2, graddist1, idx1, gradxyz1, gradxyz2);                                            \
-                hipLaunchKernelGGL(chamfer_grad_dir_kernel<TILE>, dim3((unsigned)(b * tiles_n)), dim3(kGradBlock), 0, (hipStream_t)stream, b, tiles_n, \
-                                   m, xyz2, n, xyz1, graddist2, idx2, gradxyz2, gradxyz1);                                            \
-            } while (0)
-            if (tile_rows == 2048) GENPC_GRAD_DIR(2048);
-            else if (tile_rows == 8192) GENPC_GRAD_DIR(8192);
-            else GENPC_GRAD_DIR(4096);
-#undef GENPC_GRAD_DIR
+            hipLaunchKernelGGL(chamfer_grad_dir_kernel, dim3((unsigned)(b * tiles_m)), dim3(kGradBlock), 0, (hipStream_t)stream, b, tiles_m,
+                               n, xyz1, m, xyz2, graddist1, idx1, gradxyz1, gradxyz2);
+            hipLaunchKernelGGL(chamfer_grad_dir_kernel, dim3((unsigned)(b * tiles_n)), dim3(kGradBlock), 0, (hipStream_t)stream, b, tiles_n,
+                               m, xyz2, n, xyz1, graddist2, idx2, gradxyz2, gradxyz1);
             return check(hipGetLastError(), "chamfer_grad_dir_kernel launch") ? 1 : 0;
         }
     }

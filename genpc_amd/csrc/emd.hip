@@ -61,7 +61,7 @@ __global__ __launch_bounds__(kEBlock) void emd_init_kernel(int b, int n, int *__
     }
 }
 
-template <int FMA, int FILTER, int TILE, int AHEAD>
+template <int FMA, int TILE, int AHEAD>
 __global__ __launch_bounds__(kEBlock) void emd_bid_kernel(int n, const float *__restrict__ xyz1,
                                                           const float *__restrict__ xyz2,
                                                           const float *__restrict__ price, float eps,
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(kEBlock) void emd_bid_kernel(int n, const float *__
                                                           float *__restrict__ bid_increments,
                                                           float *__restrict__ max_increments, int force_p,
                                                           float4 *__restrict__ parts, int *__restrict__ arrive,
-                                                          int *__restrict__ second, int zmax,
+                                                          int *__restrict__ second,
                                                           unsigned long long *__restrict__ chain_head,
                                                           unsigned long long *__restrict__ chain_next, unsigned stamp, int G, int nb,
                                                           int *__restrict__ chain_cnt)
@@ -129,7 +129,7 @@ __global__ __launch_bounds__(kEBlock) void emd_bid_kernel(int n, const float *__
     if (P == 64 && parts != nullptr) {
         Z = G / NB;
         Z = Z > ntiles ? ntiles : Z;
-        Z = Z > zmax ? zmax : Z;
+        Z = Z > kZMax ? kZMax : Z;
         Z = Z < 1 ? 1 : Z;
         if ((long long)U > kSplitMaxBidders) Z = 1;     // parts[] holds kSplitMaxBidders bidders per batch
     }
@@ -177,7 +177,7 @@ __global__ __launch_bounds__(kEBlock) void emd_bid_kernel(int n, const float *__
         // of a lane's sequence (without it, late rounds with 64 lanes per bidder
         // evaluated every pair exactly).
         float seed = -1e9f;
-        if (FILTER && second != nullptr) {
+        if (second != nullptr) {
             const int sa = bid[(size_t)batch * n + j], sc = second[(size_t)batch * n + j];
             if (sc >= 0 && sa != sc && (unsigned)sa < (unsigned)n) {
                 const float da = bid_value<FMA>(x1, y1, z1, X2[(size_t)sa * 3 + 0], X2[(size_t)sa * 3 + 1],
@@ -210,7 +210,7 @@ __global__ __launch_bounds__(kEBlock) void emd_bid_kernel(int n, const float *__
             // no-op.  The exact path (double-precision expression of emd_cuda.cu:146)
             // runs for the whole wave when any lane passes; for lanes that did not pass
             // it is that same no-op.  Results are therefore bit-identical with and
-            // without the filter (GENPC_EMD_NOFILTER=1 disables it for A/B).
+            // without the filter.
             // Four CONSECUTIVE objects per lane and iteration (4*P divides every tile length: n % 256 == 0,
             // P <= 64), evaluated two per instruction (packed fp32: same operations, same roundings as
             // sqdist_e and filter_cb's test); a lane's verdicts stay in SGPRs (one ballot per object), so a
@@ -234,8 +234,8 @@ __global__ __launch_bounds__(kEBlock) void emd_bid_kernel(int n, const float *__
                     else sqv[h] = (dx * dx + dy * dy) + dz * dz;
                     const v2f tt = cbv - (h ? (v2f){W4.z, W4.w} : (v2f){W4.x, W4.y});
                     const v2f t2 = tt * tt;
-                    pass[2 * h] = __ballot(!FILTER || sqv[h].x < t2.x);
-                    pass[2 * h + 1] = __ballot(!FILTER || sqv[h].y < t2.y);
+                    pass[2 * h] = __ballot(sqv[h].x < t2.x);
+                    pass[2 * h + 1] = __ballot(sqv[h].y < t2.y);
                 }
                 if ((pass[0] | pass[1] | pass[2] | pass[3]) != 0ull) {
                     const float sq[4] = {sqv[0].x, sqv[0].y, sqv[1].x, sqv[1].y};
@@ -717,13 +717,11 @@ GENPC_API int genpc_emd_forward(int b, int n, int m, const float *xyz1, const fl
     }
     // all rounds in ONE launch whose threads own the points (emd_auction.hip): whenever the whole launch can be resident
     {
-        static const int env_auction = tune_env("GENPC_EMD_AUCTION", -1, "EMD: 1 all rounds in one launch (threads own the points) / 0 a launch per round step (-1 = pick)");
-        static const bool noseed_a = tune_env("GENPC_EMD_NOSEED", 0, "EMD: 1 = no seeds from the previous bid (tiled bid only; disables the culled bid)") != 0;
         // (default: from 8192 points per call on -- measured in one process against the launch-per-round path, 50 rounds:
         // 13 x 16384 2.50 -> 1.67 ms, 4 x 16384 1.30 -> 1.14, 64 x 2048 1.52 -> 1.33, 4 x 4096 0.88 -> 0.82, 1 x 16384 0.995 ->
         // 0.96, 1 x 8192 0.90 -> 0.89; a single small cloud loses: 1 x 2048 0.72 -> 0.77, 1 x 512 0.62 -> 0.66)
-        const bool want = t_emd_grid >= 0 ? t_emd_grid == 2 : (env_auction >= 0 ? env_auction != 0 : total >= 8192);
-        if (want && eps >= 0.0f && !noseed_a && !(t_emd_hooks & 1)) {
+        const bool want = t_emd_grid >= 0 ? t_emd_grid == 2 : total >= 8192;
+        if (want && eps >= 0.0f && !(t_emd_hooks & 1)) {
             const int rc = launch_emd_auction(b, n, xyz1, xyz2, dist, assignment, price, assignment_inv, bid, bid_increments, max_increments,
                                               max_idx, eps, iters, arith_mode() != 0 ? 1 : 0, st, t_emd_grid == 2);
             if (rc >= 0) return rc;
@@ -739,22 +737,19 @@ GENPC_API int genpc_emd_forward(int b, int n, int m, const float *xyz1, const fl
     const size_t parts_bytes = want_split ? (size_t)b * kSplitMaxBidders * kZMax * sizeof(float4) : 0;
     const size_t second_bytes = ((size_t)total * sizeof(int) + 255) / 256 * 256;
     // bidder chains per object (emd_settle_kernel): head word per object, link word per bidder
-    static const bool no_settle = tune_env("GENPC_EMD_SETTLE", 1, "EMD: 0 = GetMax and Assign as two launches instead of the one-launch settle") == 0;
-    const bool settle = !no_settle && eps >= 0.0f && n <= (1 << 24);
+    const bool settle = eps >= 0.0f && n <= (1 << 24);
     // chain_head | chain_next | whead | wnext (8-byte words per object / bidder), chain_cnt | arrived (ints per object)
     const size_t chain_bytes = settle ? (4 * (size_t)total * sizeof(unsigned long long) + 2 * (size_t)total * sizeof(int) + 255) / 256 * 256 : 0;
     // cell-sorted copy of the objects for the culled bid (emd_grid.hip): needs prices >= 0 (eps >= 0) and the seeds
-    static const int env_grid = tune_env("GENPC_EMD_GRID", -1, "EMD: 1 culled bid / 0 tiled bid whatever the size (-1 = pick)");
-    static const bool noseed_env = tune_env("GENPC_EMD_NOSEED", 0, "EMD: 1 = no seeds from the previous bid (tiled bid only; disables the culled bid)") != 0;
-    const bool grid = (t_emd_grid >= 0 ? t_emd_grid != 0 : (env_grid >= 0 ? env_grid != 0 : (n >= 4096 || (long long)b * n >= 65536))) && eps >= 0.0f && !noseed_env;
+    const bool grid = (t_emd_grid >= 0 ? t_emd_grid != 0 : (n >= 4096 || (long long)b * n >= 65536)) && eps >= 0.0f;
     auto al256 = [](size_t v) { return (v + 255) / 256 * 256; };
     const int cells_max = kEGMaxCells;
     const size_t g_hdr = grid ? al256((size_t)b * sizeof(EGridHdr)) : 0, g_start = grid ? al256((size_t)b * (cells_max + 1) * sizeof(int)) : 0;
     const size_t g_sorted = grid ? al256((size_t)total * sizeof(float4)) : 0, g_pos = grid ? al256((size_t)total * sizeof(int)) : 0;
     const size_t g_ps = grid ? al256((size_t)total * sizeof(float)) : 0;
-    // per-cell lower bounds of the prices (emd_grid.hip: the bid culls cell by cell with them), refreshed in front of a round's bid
-    static const int env_cc = tune_env("GENPC_EMD_CELLCULL", 2, "culled EMD bid: refresh the cells' smallest prices every this many rounds and cull cells by them (0 = rows are culled by distance only)");
-    const size_t g_pm = grid && env_cc > 0 ? al256((size_t)b * (cells_max + 1) * sizeof(float)) : 0;
+    // per-cell lower bounds of the prices (emd_grid.hip: the bid culls cell by cell with them), refreshed in front of every
+    // second round's bid
+    const size_t g_pm = grid ? al256((size_t)b * (cells_max + 1) * sizeof(float)) : 0;
     const size_t grid_off = arrive_bytes + list_bytes + second_bytes + parts_bytes + chain_bytes;
     char *ws = (char *)workspace(1, grid_off + g_hdr + g_start + g_sorted + g_pos + g_ps + g_pm, st, nullptr, arrive_bytes);
     if (!ws) return 0;
@@ -776,10 +771,7 @@ GENPC_API int genpc_emd_forward(int b, int n, int m, const float *xyz1, const fl
     int *second = (int *)(ws + arrive_bytes + list_bytes);
     float4 *parts = (float4 *)(ws + arrive_bytes + list_bytes + second_bytes);
     // second-best object of each point's last bid (-1: has not bid yet; set by emd_init_kernel)
-    static const bool noseed = tune_env("GENPC_EMD_NOSEED", 0, "EMD: 1 = no seeds from the previous bid (tiled bid only; disables the culled bid)") != 0;
-    if (noseed) second = nullptr;
-    static const bool nosplit = tune_env("GENPC_EMD_NOSPLIT", 0, "tiled EMD bid: 1 = no object slices in late rounds") != 0;
-    if (nosplit || !want_split) parts = nullptr;
+    if (!want_split) parts = nullptr;
     int *lists[2] = {unass_idx, list_b};
     int *cnts[2] = {unass_cnt, cnt_tmp};
     const bool fma = arith_mode() != 0;
@@ -792,14 +784,11 @@ GENPC_API int genpc_emd_forward(int b, int n, int m, const float *xyz1, const fl
     if (const volatile int *fb = emd_feedback_slot(b, n, false)) heavy = (long long)*fb * 100 > (long long)n * 35;
     if (grid) {
         // about two objects per cell if the cloud filled its box (surfaces fill far fewer cells, with more objects each)
-        static const int env_ppc = tune_env("GENPC_EMD_GRID_PPC_X10", 20, "culled EMD bid: target objects per cell x 10");
         // ... twice that where most points keep bidding (the feedback word of this shape's last call, emd_auction.hip: a partial scan
         // against its ground truth): the balls hold hundreds of objects there and a row of coarser cells is one run instead of
         // several (13 bundled scans 18.3 -> 17.4 ms; 80: 18.0, 10: 19.8)
-        static const int env_ppc_heavy = tune_env("GENPC_EMD_GRID_PPC_HEAVY_X10", 40, "culled EMD bid: target objects per cell x 10 for clouds whose last call kept more than a third of their points bidding");
-        int ppc = env_ppc > 0 ? env_ppc : 20;
-        if (heavy && env_ppc_heavy > 0) ppc = env_ppc_heavy;
-        int target = (int)((long long)n * 10 / ppc);
+        const int ppc_x10 = heavy ? 40 : 20;
+        int target = (int)((long long)n * 10 / ppc_x10);
         target = target < 8 ? 8 : (target > cells_max * 3 / 4 ? cells_max * 3 / 4 : target);
         if (!launch_emd_grid_build(b, n, xyz2, price, g_hdr_p, g_start_p, g_sorted_p, g_pos_p, g_of_p, target, cells_max, st)) return 0;
     }
@@ -815,8 +804,6 @@ GENPC_API int genpc_emd_forward(int b, int n, int m, const float *xyz1, const fl
     const int g_max = ceil_div(n * 64, kEBlock);
     if (G > g_max) G = g_max;
     if (G < 1) G = 1;
-    static const int env_g = tune_env("GENPC_EMD_G", 0, "EMD: bid blocks per cloud (0 = pick)");
-    if (env_g > 0) G = env_g;
     // rounds from which GetMax + Assign run as one single-block launch per cloud (few bidders left:
     // ~n/7 after four rounds).  The forced last round takes the same kernel: its bidders are that round's
     // unassigned points like any other round's (every one of them is assigned, none evicted) -- the numbers below
@@ -824,11 +811,10 @@ GENPC_API int genpc_emd_forward(int b, int n, int m, const float *xyz1, const fl
     // (measured, 50 rounds: 1 x 2048 0.75 -> 0.68 ms, 64 x 2048 2.18 -> 1.98, 13 x 16384 8.45 -> 8.19; but
     // 1 x 16384 1.61 -> 1.80: with ~1000-2000 bidders left per round one block walking the list is
     // slower than 64 -- so only for small clouds or many of them)
-    static const int env_rf = tune_env("GENPC_EMD_RESOLVE_FROM", -1, "EMD: round from which a single block per cloud resolves (-1 = pick)");
     // (the single block also where most points keep bidding -- a partial scan against its ground truth, thousands of bidders
     // per cloud in every round: measured in one process on the 13 bundled scans, 19.1 ms against 20.9 with the multi-block
     // settle, whose per-object tickets and chain walks cost more there than one block's two passes)
-    const int resolve_from = env_rf >= 0 ? env_rf : ((n <= 4096 || b >= 8) ? 4 : 0x7fffffff);
+    const int resolve_from = (n <= 4096 || b >= 8) ? 4 : 0x7fffffff;
     int GL = ceil_div(n, kEBlock);          // list-walking kernels
     if (GL > 64) GL = 64;
 
@@ -845,18 +831,15 @@ GENPC_API int genpc_emd_forward(int b, int n, int m, const float *xyz1, const fl
         if (grid) {
             EmdGridBid ga{};
             ga.n = n; ga.G = G; ga.nb = b; ga.cells_max = cells_max; ga.eps = eps; ga.stamp = stamp;
-            static const int env_lpb = tune_env("GENPC_EMD_LPB", 0, "culled EMD bid: lanes per bidder (8..64, 0 = pick)");
-            ga.force_lpb = env_lpb > 0 ? env_lpb : (heavy ? 16 : 0);      // (thousands of bidders per cloud in every round: sixteen lanes each -- 13 bundled scans 16.7 -> 16.0 ms; 8: 17.4)
+            ga.force_lpb = heavy ? 16 : 0;      // (thousands of bidders per cloud in every round: sixteen lanes each -- 13 bundled scans 16.7 -> 16.0 ms; 8: 17.4)
             ga.lpb_max = 0;
-            static const int env_xcd = tune_env("GENPC_EMD_XCD", 0, "culled EMD bid: 1 = a cloud's blocks on one XCD (the tiled bid's order), 0 = clouds interleaved");
-            ga.xcd_pin = env_xcd;
             ga.xyz1 = xyz1; ga.xyz2 = xyz2; ga.price = price; ga.orig_of = g_of_p;
             ga.list = lists[cur]; ga.cnt = cnts[cur]; ga.start = g_start_p; ga.cnt_next = cnts[nxt];
             ga.bid = bid; ga.second = second; ga.bid_increments = bid_increments; ga.max_increments = max_increments;
             ga.sorted = g_sorted_p; ga.hdr = g_hdr_p;
             // (round 0: every price is the caller's initial one -- zero in the reference's use --, nothing to cull by)
-            if (g_pm_p != nullptr && it >= 1) {
-                if ((it - 1) % env_cc == 0 && !launch_emd_cell_pmin(b, cells_max, g_hdr_p, g_start_p, g_sorted_p, n, g_pm_p, st)) return 0;
+            if (it >= 1) {
+                if ((it - 1) % 2 == 0 && !launch_emd_cell_pmin(b, cells_max, g_hdr_p, g_start_p, g_sorted_p, n, g_pm_p, st)) return 0;
                 ga.cell_pmin = g_pm_p;
             }
             ga.chain_head = use_chain ? chain_head : nullptr; ga.chain_next = chain_next; ga.chain_cnt = chain_cnt;
@@ -865,39 +848,29 @@ GENPC_API int genpc_emd_forward(int b, int n, int m, const float *xyz1, const fl
             launch_emd_bid_grid(ga, fma ? 1 : 0, st);
         } else {
             typedef void (*bid_fn)(int, const float *, const float *, const float *, float, const int *, const int *,
-                                   int *, int *, float *, float *, int, float4 *, int *, int *, int, unsigned long long *,
+                                   int *, int *, float *, float *, int, float4 *, int *, int *, unsigned long long *,
                                    unsigned long long *, unsigned, int, int, int *);
-            static const int zmax_env = tune_env("GENPC_EMD_ZMAX", kZMax, "tiled EMD bid: object slices per bidder group in late rounds (1..4)");
-            const int zmax = zmax_env < 1 ? 1 : (zmax_env > kZMax ? kZMax : zmax_env);
             // Lanes per bidder.  Round 0 has no filter seeds: the fewer lanes share a bidder, the sooner a
             // lane's own second-best makes the filter selective (16 lanes: 186 us, 64: 298 us at
             // n = 16384).  From round 1 on the seeds do that, and one bidder per wave (64 lanes)
             // keeps one bidder's rare exact evaluations from stalling another's lanes (round 1:
             // 95 us against 166 us at 32 lanes), even when that needs more units than blocks.  With
             // many clouds in flight (b >= 32) fewer bidders per staged tile cost more than that (+2 %).
-            static const int env_p = tune_env("GENPC_EMD_P", 0, "tiled EMD bid: lanes per bidder (0 = pick)");
-            static const int env_p0 = tune_env("GENPC_EMD_P0", 0, "tiled EMD bid: lanes per bidder in round 0 (0 = pick)");
-            const int force_p = env_p > 0 ? env_p : (it == 0 ? env_p0 : (second != nullptr && b < 32 ? 64 : 0));
-            static const bool nofilter = tune_env("GENPC_EMD_NOFILTER", 0, "tiled EMD bid: 1 = no squared-distance pre-filter (A/B)") != 0;
+            const int force_p = it > 0 && b < 32 ? 64 : 0;
             // 1024-object tiles (16 KiB of LDS; the default filter variant is 78 VGPRs = six waves per SIMD, the unfiltered one
             // 72 = eight: tools/kmeta.sh emd) wherever
             // the bid is throughput-bound; a single small cloud is latency-bound and pays for the extra barrier pairs
             // (in-run A/B: 13 x 16384 8.28 -> 7.65 ms, 64 x 2048 1.99 -> 1.80, 1 x 16384 =, 1 x 2048 0.69 -> 0.76;
             // 512-object tiles: 7.85 / 1.84 / 1.69 / 0.70)
-            static const int env_tile = tune_env("GENPC_EMD_TILE", 0, "tiled EMD bid: objects per LDS tile (1024 | 2048, 0 = pick)");
-            const bool small_tile = env_tile ? env_tile == 1024 : (long long)b * n > 8192;
+            const bool small_tile = (long long)b * n > 8192;
             // four tiles in flight from round 2 on for a single cloud (see the kernel)
-            static const int env_ahead = tune_env("GENPC_EMD_AHEAD", 0, "tiled EMD bid: object tiles in flight (1 | 4, 0 = pick)");
-            const bool deep = env_ahead ? env_ahead == 4 : (small_tile && it >= 2 && b == 1);      // in-run A/B: 1 x 8192 1.22 -> 1.07 ms, 1 x 16384 -2 %, 2 x 16384 +7 %, 4 x 16384 +15 %
-            bid_fn f = deep ? (fma ? (nofilter ? emd_bid_kernel<1, 0, 1024, 4> : emd_bid_kernel<1, 1, 1024, 4>)
-                                   : (nofilter ? emd_bid_kernel<0, 0, 1024, 4> : emd_bid_kernel<0, 1, 1024, 4>))
-                     : small_tile ? (fma ? (nofilter ? emd_bid_kernel<1, 0, 1024, 1> : emd_bid_kernel<1, 1, 1024, 1>)
-                                         : (nofilter ? emd_bid_kernel<0, 0, 1024, 1> : emd_bid_kernel<0, 1, 1024, 1>))
-                                  : (fma ? (nofilter ? emd_bid_kernel<1, 0, 2048, 1> : emd_bid_kernel<1, 1, 2048, 1>)
-                                         : (nofilter ? emd_bid_kernel<0, 0, 2048, 1> : emd_bid_kernel<0, 1, 2048, 1>));
+            const bool deep = small_tile && it >= 2 && b == 1;      // in-run A/B: 1 x 8192 1.22 -> 1.07 ms, 1 x 16384 -2 %, 2 x 16384 +7 %, 4 x 16384 +15 %
+            bid_fn f = deep ? (fma ? emd_bid_kernel<1, 1024, 4> : emd_bid_kernel<0, 1024, 4>)
+                     : small_tile ? (fma ? emd_bid_kernel<1, 1024, 1> : emd_bid_kernel<0, 1024, 1>)
+                                  : (fma ? emd_bid_kernel<1, 2048, 1> : emd_bid_kernel<0, 2048, 1>);
             hipLaunchKernelGGL(f, dim3(G * b), dim3(kEBlock), 0, st, n, xyz1, xyz2, (const float *)price, eps,
                                (const int *)lists[cur], (const int *)cnts[cur], cnts[nxt], bid, bid_increments,
-                               max_increments, force_p, parts, arrive, second, zmax, use_chain ? chain_head : (unsigned long long *)nullptr,
+                               max_increments, force_p, parts, arrive, second, use_chain ? chain_head : (unsigned long long *)nullptr,
                                chain_next, stamp, G, b, chain_cnt);
         }
         if (use_chain) {
@@ -933,7 +906,7 @@ GENPC_API int genpc_emd_forward(int b, int n, int m, const float *xyz1, const fl
 extern "C" __attribute__((visibility("default"))) int genpc_debug_emd_bid_occupancy(void)
 {
     int nb = -1;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, genpc::emd_bid_kernel<1, 1, 1024, 1>, genpc::kEBlock, 0);
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, genpc::emd_bid_kernel<1, 1024, 1>, genpc::kEBlock, 0);
     return nb;
 }
 

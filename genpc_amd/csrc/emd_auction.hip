@@ -91,7 +91,7 @@ __device__ __forceinline__ int acell1(float p, float lo, float inv, int g)
 }
 
 struct EmdAuction {
-    int n, nb, cells_max, iters, force_lpb, xcd_pin;
+    int n, nb, cells_max, iters;
     int K;                                  // lanes that own a point (a power of two <= 64): the cloud has n K / 256 workgroups
     int *feedback;                          // pinned host word (may be null): cloud 0's bidders left after round 2
     float eps;
@@ -106,8 +106,7 @@ struct EmdAuction {
     int *chain_cnt, *arrived;
     unsigned long long *ctrl;               // per cloud kCtrlWords words on 128-byte lines: see cloud_barrier
     int *status;                            // sticky: != 0 once a call gave up (genpc_emd_status)
-    unsigned spin_limit;
-    unsigned long long *timeline;           // debug (GENPC_EMD_TIMELINE=1): 100 MHz stamps of workgroup 0, 8 per round, 64 rounds
+    unsigned spin_limit;                    // polls of a barrier before the call is abandoned
 };
 
 __global__ __launch_bounds__(kABlock) void emd_auction_init_kernel(int b, int n, unsigned long long *__restrict__ ctrl,
@@ -168,21 +167,7 @@ __global__ __launch_bounds__(kABlock, 4) void emd_auction_kernel(EmdAuction a)
     __shared__ int s_out[kABlock][6];           // per owner thread: object, its position, second's position, increment, displaced record (2 words)
     __shared__ int s_flag;
     const int n = a.n, nb = a.nb, K = a.K, G = (int)(((long long)n * K) / kABlock);
-    int batch, bx;
-    {
-        const int lin = blockIdx.x, nb8 = nb & ~7;
-        if (a.xcd_pin && lin < G * nb8) {            // a cloud's workgroups on one XCD (blocks go to the XCDs round-robin): speed only
-            const int k = lin >> 3;
-            batch = 8 * (k / G) + (lin & 7);
-            bx = k % G;
-        } else if (a.xcd_pin) {
-            batch = nb8 + (lin - G * nb8) / G;
-            bx = (lin - G * nb8) % G;
-        } else {
-            batch = lin % nb;
-            bx = lin / nb;
-        }
-    }
+    const int batch = blockIdx.x % nb, bx = blockIdx.x / nb;
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
     const size_t base = (size_t)batch * n;
     const int j = (bx * kABlock + (int)threadIdx.x) / K;      // the point this thread owns (with its K - 1 neighbours: K lanes per point)
@@ -216,8 +201,6 @@ __global__ __launch_bounds__(kABlock, 4) void emd_auction_kernel(EmdAuction a)
             ok = cloud_barrier(bar, bx, G, ++nbar, a.spin_limit, &s_flag);
             if (!ok) break;
         }
-        const bool tl = a.timeline != nullptr && blockIdx.x == 0 && threadIdx.x == 0 && it < 64;
-        if (tl) a.timeline[it * 16 + 0] = wall_clock64();
         my_asg = ald(&a.assignment[base + j]);
         const int U = ald(ucnt);
         if (U <= 0) break;                                    // everybody is assigned: the remaining rounds are empty (uniform over the cloud)
@@ -235,10 +218,9 @@ __global__ __launch_bounds__(kABlock, 4) void emd_auction_kernel(EmdAuction a)
         if (bidder) s_list[w0 + __popcll(mask & ((1ull << lane) - 1ull))] = threadIdx.x;
         __syncthreads();
         const int nbid = T > wave ? (T - wave + kAWaves - 1) / kAWaves : 0;      // this wave serves bidders wave, wave + 4, ... of the pool
-        if (tl) { a.timeline[it * 16 + 1] = wall_clock64(); a.timeline[it * 16 + 6] = (unsigned long long)U; a.timeline[it * 16 + 7] = (unsigned long long)nbid; }
         if (nbid > 0) {
             // ---------------- Bid (emd_cuda.cu:95-179) ----------------
-            int LPB = a.force_lpb > 0 ? a.force_lpb : (nbid <= 1 ? 64 : (nbid == 2 ? 32 : (nbid <= 4 ? 16 : 8)));
+            int LPB = (nbid <= 1 ? 64 : (nbid == 2 ? 32 : (nbid <= 4 ? 16 : 8)));
             LPB = LPB < 8 ? 8 : (LPB > 64 ? 64 : LPB);
             const int per_wave = kWave / LPB;
             const int sub = lane & (LPB - 1), grp = lane / LPB;
@@ -267,7 +249,6 @@ __global__ __launch_bounds__(kABlock, 4) void emd_auction_kernel(EmdAuction a)
                     seed = fminf(da, dc);
                     seeded = true;
                 }
-                if (tl && k0 == 0) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); a.timeline[it * 16 + 8] = wall_clock64(); }
                 float cb = filter_cb(fmaxf(better, seed));
                 const float sx = H.slack[0] + kAU16 * fabsf(x1), sy = H.slack[1] + kAU16 * fabsf(y1), sz = H.slack[2] + kAU16 * fabsf(z1);
                 auto gap1 = [&](int c, int g, float lo, float q, float s) {
@@ -435,7 +416,6 @@ __global__ __launch_bounds__(kABlock, 4) void emd_auction_kernel(EmdAuction a)
                         set_box(cb);
                     }
                 }
-                if (tl && k0 == 0) a.timeline[it * 16 + 9] = wall_clock64();
                 auto sweep = [&]() {
                     const int wy = by1 - by0 + 1, nrows = wy * (bz1 - bz0 + 1);
                     for (int r0 = 0; r0 < nrows; r0 += LPB) {         // group-uniform trip count
@@ -468,14 +448,12 @@ __global__ __launch_bounds__(kABlock, 4) void emd_auction_kernel(EmdAuction a)
                 };
                 sweep();
                 flush();
-                if (tl && k0 == 0) a.timeline[it * 16 + 10] = wall_clock64();
                 for (int off = 1; off < LPB; off <<= 1) {
                     const float ob = __shfl_xor(best, off, kWave), obb = __shfl_xor(better, off, kWave);
                     const long long oi = __shfl_xor(best_p, off, kWave), obi = __shfl_xor(better_p, off, kWave);
                     merge_top2_64(best, better, best_p, better_p, ob, obb, oi, obi);
                 }
                 int best_i = best_p >= 0 ? (int)(best_p & 0xffffffffll) : -1;
-                if (tl && k0 == 0) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); a.timeline[it * 16 + 11] = wall_clock64(); }
                 const bool tie = active && (best == better);
                 if (__any(tie)) {
                     if (tie) {
@@ -509,13 +487,10 @@ __global__ __launch_bounds__(kABlock, 4) void emd_auction_kernel(EmdAuction a)
                     out[0] = best_i; out[1] = (int)(best_p >> 32); out[2] = (int)(better_p >> 32); out[3] = __float_as_int(inc);
                     out[4] = (int)(unsigned)(old & 0xffffffffull); out[5] = (int)(unsigned)(old >> 32);
                 }
-                if (tl && k0 == 0) a.timeline[it * 16 + 12] = wall_clock64();
             }
         }
-        if (tl) a.timeline[it * 16 + 2] = wall_clock64();
         ok = cloud_barrier(bar, bx, G, ++nbar, a.spin_limit, &s_flag);
         if (!ok) break;
-        if (tl) a.timeline[it * 16 + 3] = wall_clock64();
         // ---------------- GetMax + Assign (emd_cuda.cu:181-215) ----------------
         if (bidder) {
             auto live = [&](unsigned long long r) { return (unsigned)((r >> kAWhoBits) & kAStampPeriod) == stamp; };
@@ -594,11 +569,9 @@ __global__ __launch_bounds__(kABlock, 4) void emd_auction_kernel(EmdAuction a)
             }
             if (last) my_asg = bid_id;
         }
-        if (tl) a.timeline[it * 16 + 4] = wall_clock64();
         if (last) break;
         ok = cloud_barrier(bar, bx, G, ++nbar, a.spin_limit, &s_flag);
         if (!ok) break;
-        if (tl) a.timeline[it * 16 + 5] = wall_clock64();
     }
     // ---------------- CalcDist (emd_cuda.cu:217-226) ----------------
     if (!ok) {
@@ -742,21 +715,18 @@ int *emd_feedback_slot(int b, int n, bool device)
 int launch_emd_auction(int b, int n, const float *xyz1, const float *xyz2, float *dist, int *assignment, float *price, int *assignment_inv,
                        int *bid, float *bid_increments, float *max_increments, int *max_idx, float eps, int iters, int fma, hipStream_t st, bool forced)
 {
-    static const int env_cap = tune_env("GENPC_EMD_AUCTION_CAP", 0, "one-launch EMD: workgroups admitted at once (0 = 3.5 per CU)");
-    const int cap = env_cap > 0 ? env_cap : emd_auction_capacity();
+    const int cap = emd_auction_capacity();
     if (n > (1 << kAWhoBits) || n < kABlock || (long long)b * (n / kABlock) > cap) return -1;
     {
-        static const int env_heavy = tune_env("GENPC_EMD_AUCTION_HEAVY_PCT", 35, "one-launch EMD: bidders left after round 2 (percent of n, last call of the same shape) above which the launch-per-round path is taken (0 = never)");
+        // more than 35 % of n still bidding after round 2 (last call of the same shape): the launch-per-round path
         volatile int *fb = emd_feedback_slot(b, n, false);
-        if (!forced && env_heavy > 0 && fb && iters > 3 && (long long)*fb * 100 > (long long)n * env_heavy) return -1;
+        if (!forced && fb && iters > 3 && (long long)*fb * 100 > (long long)n * 35) return -1;
     }
     // lanes per point: as many as keep the launch within `fill` workgroups (the bidders of a round are served by the lanes
     // of their own workgroup: more lanes per point = fewer bidders per wave, and round 0 -- everybody bids -- on the whole chip)
-    static const int env_k = tune_env("GENPC_EMD_AUCTION_K", 0, "one-launch EMD: lanes that own a point (1..64, 0 = pick)");
-    static const int env_fill = tune_env("GENPC_EMD_AUCTION_FILL", 512, "one-launch EMD: workgroups up to which points get more lanes");
+    constexpr int fill = 512;
     int K = 1;
-    if (env_k > 0) { while (K < env_k && K < 64) K <<= 1; }
-    else { while (K < 64 && (long long)b * n * (2 * K) / kABlock <= env_fill) K <<= 1; }
+    while (K < 64 && (long long)b * n * (2 * K) / kABlock <= fill) K <<= 1;
     while (K > 1 && (long long)b * n * K / kABlock > cap) K >>= 1;
     const int G = (int)((long long)n * K / kABlock), wgs = b * G;
     auto al = [](size_t v) { return (v + 255) / 256 * 256; };
@@ -781,11 +751,10 @@ int launch_emd_auction(int b, int n, const float *xyz1, const float *xyz2, float
         const size_t items = total > (size_t)b * kCtrlWords ? total : (size_t)b * kCtrlWords;      // (a 256-point cloud has fewer points than control words)
         hipLaunchKernelGGL(emd_auction_init_kernel, dim3(ceil_div((int)items, kABlock)), dim3(kABlock), 0, st, b, n, ctrl, chain_head, chain_cnt, arrived);
     }
-    // (six objects per cell for the one-launch kernel since round 6 -- tools/emd_env_sweep.py, 1 x 16384 / 13 x 16384 uniform: 20 -> 1.04 /
+    // (six objects per cell for the one-launch kernel since round 6 -- 1 x 16384 / 13 x 16384 uniform: 20 -> 1.04 /
     //  1.70 ms, 40 -> 0.95 / 1.68, 60 -> 0.89 / 1.67, 80 -> 0.89 / 1.69, 120 -> 0.93 / 1.74: a bidder's ball is a handful of
     //  longer runs instead of dozens of short ones, each a dependent read of the cell table; the launch-per-round path keeps its own)
-    static const int env_ppc = tune_env("GENPC_EMD_AUCTION_PPC_X10", 60, "one-launch EMD: target objects per cell x 10 of the culled bid's grid");
-    int target = (int)((long long)n * 10 / (env_ppc > 0 ? env_ppc : 60));
+    int target = (int)((long long)n * 10 / 60);
     target = target < 8 ? 8 : (target > kEGMaxCells * 3 / 4 ? kEGMaxCells * 3 / 4 : target);
     if (!launch_emd_grid_build(b, n, xyz2, price, hdr, start, sorted, pos_of, orig_of, target, kEGMaxCells, st, price_s)) {
         persist_cancel(wgs, st);
@@ -794,19 +763,12 @@ int launch_emd_auction(int b, int n, const float *xyz1, const float *xyz2, float
     EmdAuction a{};
     a.n = n; a.nb = b; a.cells_max = kEGMaxCells; a.iters = iters; a.eps = eps; a.K = K;
     a.feedback = emd_feedback_slot(b, n, true);
-    static const int env_lpb = tune_env("GENPC_EMD_LPB", 0, "culled EMD bid: lanes per bidder (8..64, 0 = pick)");
-    a.force_lpb = env_lpb;
-    static const int env_xcd = tune_env("GENPC_EMD_AUCTION_XCD", 0, "one-launch EMD: 1 = a cloud's workgroups on one XCD");
-    a.xcd_pin = env_xcd;
     a.xyz1 = xyz1; a.xyz2 = xyz2; a.price = price; a.price_s = price_s; a.sorted = sorted; a.start = start; a.pos_of = pos_of; a.hdr = hdr;
     a.assignment = assignment; a.assignment_inv = assignment_inv; a.bid = bid; a.max_idx = max_idx;
     a.bid_increments = bid_increments; a.max_increments = max_increments; a.dist = dist;
     a.chain_head = chain_head; a.chain_next = chain_next; a.chain_cnt = chain_cnt; a.arrived = arrived;
     a.ctrl = ctrl; a.status = status;
-    static const int env_spin = tune_env("GENPC_EMD_AUCTION_SPIN", 1 << 21, "one-launch EMD: polls of a barrier before the call is abandoned");
-    a.spin_limit = (unsigned)env_spin;
-    static const int env_tl = tune_env("GENPC_EMD_TIMELINE", 0, "one-launch EMD: 1 = workgroup 0 stamps the phases of the first 64 rounds (genpc_debug_emd_timeline)");
-    a.timeline = env_tl ? (unsigned long long *)workspace(32, 64 * 16 * 8, nullptr, nullptr, 64 * 16 * 8) : nullptr;
+    a.spin_limit = 1u << 21;
     if (fma) hipLaunchKernelGGL((emd_auction_kernel<1>), dim3(wgs), dim3(kABlock), 0, st, a);
     else hipLaunchKernelGGL((emd_auction_kernel<0>), dim3(wgs), dim3(kABlock), 0, st, a);
     persist_commit(wgs, st);
@@ -836,13 +798,4 @@ GENPC_API int genpc_emd_status(int reset, void *stream)
     if (!check(hipMemcpy(&v, dev, sizeof v, hipMemcpyDeviceToHost), "genpc_emd_status copy")) return -1;
     if (reset && v && !check(hipMemset(dev, 0, sizeof v), "genpc_emd_status reset")) return -1;
     return v;
-}
-
-// Diagnostic (not part of the public header): the stamps of GENPC_EMD_TIMELINE=1, 64 rounds x 8 words.
-extern "C" __attribute__((visibility("default"))) int genpc_debug_emd_timeline(unsigned long long *out)
-{
-    using namespace genpc;
-    unsigned long long *dev = (unsigned long long *)workspace(32, 64 * 16 * 8, nullptr, nullptr, 64 * 16 * 8);
-    if (!dev || hipDeviceSynchronize() != hipSuccess) return 0;
-    return hipMemcpy(out, dev, 64 * 16 * 8, hipMemcpyDeviceToHost) == hipSuccess ? 1 : 0;
 }

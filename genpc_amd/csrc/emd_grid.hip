@@ -253,25 +253,11 @@ __global__ __launch_bounds__(kEBlock) __attribute__((amdgpu_waves_per_eu(4, 8)))
     __shared__ int s_pre[kEBlock / kWave][72], s_p0[kEBlock / kWave][72];      // per wave: (64 / LPB) groups x (LPB + 1) entries
     __shared__ int s_que[kEBlock / kWave][512];                                 // per wave: (64 / LPB) groups x 8 LPB queued entries
     const int n = a.n, G = a.G, nb = a.nb;
-    int batch, bx;
-    {
-        // Clouds interleaved over the block ids (and with them over the XCDs): the clouds of a call differ in work here --
-        // bidders left, sizes of their boxes; a mis-framed scan keeps ten times the work of its neighbours -- and
-        // emd_bid_kernel's "a cloud's blocks on one XCD" (its objects stay in that XCD's L2) made the launch as long as
-        // the heaviest cloud on an eighth of the chip.  GENPC_EMD_XCD=1 restores it for A/B.
-        const int lin = blockIdx.x, nb8 = nb & ~7;
-        if (a.xcd_pin && lin < G * nb8) {
-            const int k = lin >> 3;
-            batch = 8 * (k / G) + (lin & 7);
-            bx = k % G;
-        } else if (a.xcd_pin) {
-            batch = nb8 + (lin - G * nb8) / G;
-            bx = (lin - G * nb8) % G;
-        } else {
-            batch = lin % nb;
-            bx = lin / nb;
-        }
-    }
+    // Clouds interleaved over the block ids (and with them over the XCDs): the clouds of a call differ in work here --
+    // bidders left, sizes of their boxes; a mis-framed scan keeps ten times the work of its neighbours -- and
+    // emd_bid_kernel's "a cloud's blocks on one XCD" (its objects stay in that XCD's L2) made the launch as long as
+    // the heaviest cloud on an eighth of the chip.
+    const int batch = blockIdx.x % nb, bx = blockIdx.x / nb;
     const int U = a.cnt[batch];
     if (bx == 0 && threadIdx.x == 0) a.cnt_next[batch] = 0;   // filled by this round's settle / resolve
     if (a.feedback != nullptr && blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(a.feedback, U, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -658,9 +644,7 @@ int launch_emd_grid_build(int b, int n, const float *xyz2, const float *price, E
 {
     const size_t lds = ((size_t)cells_max + 2 * kEGWaves) * sizeof(int) + 6 * kEGWaves * sizeof(float);
     // pieces per cloud: enough blocks to spread a few clouds over the chip, one when there are many clouds anyway
-    static const int env_k = tune_env("GENPC_EMD_GRID_K", 0, "culled EMD bid: pieces per cloud of the grid build (0 = pick)");
-    int K = env_k > 0 ? env_k : (b >= 32 ? 1 : (b >= 8 ? 2 : (n >= 8192 ? 8 : 4)));
-    K = K > 64 ? 64 : K;
+    const int K = b >= 32 ? 1 : (b >= 8 ? 2 : (n >= 8192 ? 8 : 4));
     hipLaunchKernelGGL(emd_grid_build_kernel, dim3(b * K), dim3(kEGBlock), lds, st, n, xyz2, price, hdr, start, sorted, pos_of, orig_of,
                        cells_target, cells_max, K, price_sep);
     return check(hipGetLastError(), "emd_grid_build_kernel launch") ? 1 : 0;

@@ -751,21 +751,19 @@ GENPC_API int genpc_fps_multi(int c, const int *n, const int *k, const float *co
     };
     // Which kernel: clouds that fit one workgroup's LDS take the pruned sampling of fps_grid.hip (no hand-off, several samples
     // per round, updates confined to the ball a sample can change), the others the multi-workgroup kernel above.  Same
-    // sequences (tests/test_gpu_fps.py runs both on every case); genpc_fps_tune(256) / GENPC_FPS_GRID=0: never the former.
-    static const int env_grid = tune_env("GENPC_FPS_GRID", 1, "farthest point sampling: 1 = clouds of up to 32768 points are sampled by one workgroup with spatial pruning (csrc/fps_grid.hip), 0 = always the multi-workgroup kernel");
-    const bool grid_on = env_grid != 0 && t_fps_multi_wg == 0;
+    // sequences (tests/test_gpu_fps.py runs both on every case); genpc_fps_tune(256): never the former.
+    const bool grid_on = t_fps_multi_wg == 0;
     std::vector<int> small, big;
     for (int j = 0; j < c; j++) (grid_on && fps_grid_takes(n[j]) ? small : big).push_back(j);
     size_t total_slots = 0, total_k = 0, spt_pts = 0;
     for (int j : big) total_slots += 2 * (size_t)fps_workgroups(n[j]);
     for (int j : small) spt_pts += ((size_t)n[j] + 63) & ~(size_t)63;
     for (int j = 0; j < c; j++) total_k += ((size_t)k[j] + 63) / 64 * 64;
-    static const int env_verify = tune_env("GENPC_FPS_VERIFY", 1, "farthest point sampling: 1 = every sequence is checked on the device against the definition (a violation poisons out[0] = -1), 0 = no check");
     const size_t head = 256 + total_slots * sizeof(FpsSlot), verr_bytes = ((size_t)c * sizeof(int) + 255) / 256 * 256;
     size_t total_n = 0;
     for (int j = 0; j < c; j++) total_n += (size_t)n[j];
     const size_t pd_bytes = (total_k * sizeof(float) + 255) / 256 * 256;
-    const size_t seg_bytes = env_verify ? (total_n * kFVMaxSeg * sizeof(float) + 255) / 256 * 256 : 0;
+    const size_t seg_bytes = (total_n * kFVMaxSeg * sizeof(float) + 255) / 256 * 256;
     char *ws = (char *)workspace(7, head + verr_bytes + pd_bytes + seg_bytes + spt_pts * sizeof(float4), st);
     if (!ws) return 0;
     int *err = (int *)ws;
@@ -788,7 +786,6 @@ GENPC_API int genpc_fps_multi(int c, const int *n, const int *k, const float *co
     }
     // the verification of a group of clouds (fps_verify_kernel above), whichever kernel sampled them
     auto verify = [&](const FpsJobs &jobs, int nj, hipStream_t st, float *segmin, int *violations) {
-        if (!env_verify) return;
         int nmax = 1;
         for (int q = 0; q < nj; q++) nmax = jobs.n[q] > nmax ? jobs.n[q] : nmax;
         const int gxv = ceil_div(nmax, kFVBlock);
@@ -855,7 +852,7 @@ GENPC_API int genpc_fps_multi(int c, const int *n, const int *k, const float *co
         d->used[sl] = true;
         return true;
     };
-    FpsDeferred *defer = t_fps_defer && env_verify ? fps_deferred_of(st, true) : nullptr;
+    FpsDeferred *defer = t_fps_defer ? fps_deferred_of(st, true) : nullptr;
     if (!small.empty()) {
         if (fps_grid_run(fma, (int)small.size(), small.data(), n, k, xyz, out_idx, pd_of.data(), spt, err, st) != 1) return 0;
         for (size_t q0 = 0; q0 < small.size(); q0 += kFMaxJobs) {

@@ -1855,10 +1855,9 @@ static int hpr_run(int c, int n, const float *points, const double *eyes, double
     static const int no_cull = tune_env("GENPC_HPR_NOCULL", 0, "hidden-point removal: measurement mask (1 every tile, 8 no silhouette hand-off, 16 no early accept, 32 no verify, 64 no hand-off of much-cut polygons, 128 no decisions without the walk in the wave-per-point pass, 256 count those decisions on stderr, 512 two-kernel form WITH the first kernel's own verify phase)");      // measurement knob: 1 = every tile examined, 8 = no silhouette hand-off, 16 = no early accept, 32 = no verify phase, 64 = no hand-off of much-cut polygons (results unchanged)
     hipLaunchKernelGGL(hpr_flip_kernel, dim3(g256, c), dim3(256), 0, stream, n, points, (const int *)i1, eyes, radius, fl, (const unsigned char *)dup);
     hipLaunchKernelGGL(hpr_tile_kernel, dim3(ntiles, c), dim3(kHprThreads), 0, stream, n, (const double *)fl, tiles);
-    static const int env_clips = tune_env("GENPC_HPR_MAXCLIPS", 0, "hidden-point removal: clips after which a polygon goes to the wave-per-point pass (0 = pick)");
-    // (large clouds: 96 -- 2 x 165546 points 46 -> 40 ms; many views of a small cloud: the second pass fills up
+    // clips after which a polygon goes to the wave-per-point pass (large clouds: 96 -- 2 x 165546 points 46 -> 40 ms; many views of a small cloud: the second pass fills up
     //  instead -- 1024 x 10000 points 154 ms with 256, 168 with 128, 180 with 96)
-    const int max_clips = (no_cull & 64) ? 0x7fffffff : (env_clips > 0 ? env_clips : (ntiles >= kHprRimTiles ? 48 : 256));      // (large clouds: 96 -> 48 once the wave-per-point pass clipped by all lanes: 2 x 165546 24.9 -> 21.5 ms)
+    const int max_clips = (no_cull & 64) ? 0x7fffffff : (ntiles >= kHprRimTiles ? 48 : 256);      // (large clouds: 96 -> 48 once the wave-per-point pass clipped by all lanes: 2 x 165546 24.9 -> 21.5 ms)
     unsigned char *hard = (unsigned char *)(ws + o_hard);
     int *hardlist = (int *)(ws + o_hl), *hardcnt = (int *)(ws + o_hc);
     hipLaunchKernelGGL(hpr_accept_kernel, dim3(ntiles * c), dim3(kHprThreads), 0, stream, n, (const double *)fl, (const int *)i1,
@@ -1886,16 +1885,13 @@ static int hpr_run(int c, int n, const float *points, const double *eyes, double
     }
     int *work = (int *)(ws + o_work);          // line x: the first try's counter of segment x; lines 8 .. 11: the other passes'
     hipLaunchKernelGGL(hpr_segs_kernel, dim3(1), dim3(1024), 0, stream, c, (const int *)hardcnt, segs, (int)park_cap, work);
-    static const int env_sf = tune_env("GENPC_HPR_STRAGGLE_FROM", 4, "hidden-point removal: tile batches a block walks before the hand-over");
-    static const int env_sl = tune_env("GENPC_HPR_STRAGGLE_LANES", kHprThreads, "hidden-point removal: hand a block's points over when at most this many lanes are still undecided");
-    static const int env_st = tune_env("GENPC_HPR_STRAGGLE_TILES", 0, "hidden-point removal: clouds of at least this many tiles hand undecided points over early");
-    const int straggle_from = ntiles >= env_st ? env_sf : 0x7fffffff, straggle_lanes = env_sl;
+    // the first kernel hands a block's undecided points over after 4 tile batches, all of them (see the kernel)
+    const int straggle_from = 4, straggle_lanes = kHprThreads;
     // split form: home tiles (the point's own, the next, the previous) the first kernel takes before it tries to verify and
     // parks what is left; the wave-per-point pass decides most parked points from the polygon they bring and takes the
     // remaining home tiles only for the others
     static const int env_ht = tune_env("GENPC_HPR_HOME_TILES", 1, "hidden-point removal, two-kernel form: home tiles (1..3) the first kernel clips by before it parks a point");
-    static const int env_cw = tune_env("GENPC_HPR_CHUNK", 32, "hidden-point removal, first kernel: candidates marked at a time against the polygon as the previous ones left it (8, 16 or 32)");
-    const int chunk_w = env_cw == 8 || env_cw == 16 ? env_cw : 32;
+    const int chunk_w = 32;      // first kernel: candidates marked at a time against the polygon as the previous ones left it
     const int home_tiles = split ? (env_ht < 1 ? 1 : (env_ht > 3 ? 3 : env_ht)) : 3;
     static const int env_hc = tune_env("GENPC_HPR_HOME_CHUNKS", 2, "hidden-point removal, two-kernel form with one home tile: 32-candidate chunks of it (1..4) the first kernel clips by");
     const int home_chunks = split && home_tiles == 1 ? (env_hc < 1 ? 1 : (env_hc > 4 ? 4 : env_hc)) : 4;
@@ -1911,8 +1907,8 @@ static int hpr_run(int c, int n, const float *points, const double *eyes, double
     int *list3 = (int *)k1;          // (likewise: the points whose polygons outgrow the 1024-vertex tier)
     const int cus = num_cus();
     auto grid_of = [&](int per_cu) { return (int)std::min<size_t>(total, (size_t)per_cu * cus); };
-    static const int env_dw = tune_env("GENPC_HPR_DECIDE_WAVES", 64, "hidden-point removal: one-wave blocks per CU of the parked points' first try");
-    static const int env_ww = tune_env("GENPC_HPR_WALK_WAVES", 40, "hidden-point removal: one-wave blocks per CU of the wave-per-point pass (128-vertex tier)");
+    // one-wave blocks per CU: 64 for the parked points' first try, 40 for the wave-per-point pass (128-vertex tier)
+    const int decide_waves = 64, walk_waves = 40;
     // status words: [0] listed, [2] parked, [3] polygons over 128 vertices, [4] over kHprOverCap, [5] parked points the first try
     // left undecided, [32 .. 39] the segments' fills (the passes' work counters: `work`, a cache line each)
     if (split) {
@@ -1921,7 +1917,7 @@ static int hpr_run(int c, int n, const float *points, const double *eyes, double
         const int *count = nullptr;          // (null: the parked points by segment)
         if (env_dk && !(no_cull & (32 | 128))) {
             int *sl = i0;          // (the sort's index buffer is free by now; at most views x points entries)
-            const int gd = (grid_of(env_dw > 0 ? env_dw : 64) + 7) & ~7;          // block b -> segment b % 8
+            const int gd = (grid_of(decide_waves) + 7) & ~7;          // block b -> segment b % 8
             hipLaunchKernelGGL(hpr_decide_kernel, dim3(gd), dim3(kWave), 0, stream, n, (const double *)fl, (const HprTile *)tiles, visible,
                                counts, status, (const int *)i1, no_cull, (const unsigned char *)alive, (const int4 *)surv,
                                (const double2 *)surv_poly, sl, (const HprSegs *)segs, work);
@@ -1929,28 +1925,19 @@ static int hpr_run(int c, int n, const float *points, const double *eyes, double
             slots = sl;
             count = status + 5;
         }
-        hipLaunchKernelGGL(hpr_overflow_kernel<128>, dim3(grid_of(env_ww > 0 ? env_ww : 40)), dim3(kWave), 0, stream, n, (const double *)fl, (const HprTile *)tiles,
+        hipLaunchKernelGGL(hpr_overflow_kernel<128>, dim3(grid_of(walk_waves)), dim3(kWave), 0, stream, n, (const double *)fl, (const HprTile *)tiles,
                            visible, counts, status, (const int *)nullptr, (const int *)i1, (const int *)hardlist, (const int *)hardcnt,
                            no_cull, (const unsigned char *)alive, list2, (const int4 *)surv, (const double2 *)surv_poly, (double2 *)nullptr, 0, slots,
                            (const HprSegs *)segs, count, work + 8 * kHprWorkLine);
         if (!check(hipGetLastError(), "hpr continuation launch")) return 0;
     }
     {
-        static const bool one_tier = tune_env("GENPC_HPR_ONE_TIER", 0, "hidden-point removal: 1 = every listed point straight to the 1024-vertex tier") != 0;
-        if (!one_tier) {
-            hipLaunchKernelGGL(hpr_overflow_kernel<128>, dim3(grid_of(env_ww > 0 ? env_ww : 40)), dim3(kWave), 0, stream, n, (const double *)fl, (const HprTile *)tiles,
-                               visible, counts, status, (const int *)list, (const int *)i1, (const int *)hardlist, (const int *)hardcnt,
-                               no_cull, (const unsigned char *)alive, list2, (const int4 *)nullptr, (const double2 *)nullptr, (double2 *)nullptr, 0,
-                               (const int *)nullptr, (const HprSegs *)segs, (const int *)(status + 0), work + 9 * kHprWorkLine);
-            if (!check(hipGetLastError(), "hpr second pass launch")) return 0;
-        } else {
-            hipLaunchKernelGGL(hpr_overflow_kernel<kHprOverCap>, dim3(grid_of(5)), dim3(kWave), 0, stream, n, (const double *)fl,
-                               (const HprTile *)tiles, visible, counts, status, (const int *)list, (const int *)i1, (const int *)hardlist,
-                               (const int *)hardcnt, no_cull, (const unsigned char *)alive, list3, (const int4 *)nullptr,
-                               (const double2 *)nullptr, (double2 *)nullptr, 0, (const int *)nullptr, (const HprSegs *)segs,
-                               (const int *)(status + 0), work + 9 * kHprWorkLine);
-        }
-        // polygons over 128 vertices (from either launch above)
+        hipLaunchKernelGGL(hpr_overflow_kernel<128>, dim3(grid_of(walk_waves)), dim3(kWave), 0, stream, n, (const double *)fl, (const HprTile *)tiles,
+                           visible, counts, status, (const int *)list, (const int *)i1, (const int *)hardlist, (const int *)hardcnt,
+                           no_cull, (const unsigned char *)alive, list2, (const int4 *)nullptr, (const double2 *)nullptr, (double2 *)nullptr, 0,
+                           (const int *)nullptr, (const HprSegs *)segs, (const int *)(status + 0), work + 9 * kHprWorkLine);
+        if (!check(hipGetLastError(), "hpr second pass launch")) return 0;
+        // polygons over 128 vertices (from the two launches above)
         hipLaunchKernelGGL(hpr_overflow_kernel<kHprOverCap>, dim3(grid_of(5)), dim3(kWave), 0, stream, n, (const double *)fl,
                            (const HprTile *)tiles, visible, counts, status, (const int *)list2, (const int *)i1, (const int *)hardlist,
                            (const int *)hardcnt, no_cull, (const unsigned char *)alive, list3, (const int4 *)nullptr,
@@ -1960,10 +1947,10 @@ static int hpr_run(int c, int n, const float *points, const double *eyes, double
         // polygons over 1024 vertices (exactly co-spherical input, lattices seen from their centre): a third tier with the
         // polygon in global memory, n + 8 vertices per buffer -- it cannot overflow -- a pair of buffers per wave of the grid
         {
-            static const int env_gm = tune_env("GENPC_HPR_GLOBAL_MB", 256, "hidden-point removal: MiB of global-memory polygon buffers of the third tier (two buffers of n + 8 vertices per wave)");
             const int gcap = n + 8;
             const size_t per = (size_t)2 * gcap * sizeof(double2);
-            const int g3 = (int)std::min<size_t>(std::min<size_t>(total, 1024), std::max<size_t>(1, ((size_t)(env_gm > 0 ? env_gm : 1) << 20) / per));
+            // (256 MiB of buffers at most)
+            const int g3 = (int)std::min<size_t>(std::min<size_t>(total, 1024), std::max<size_t>(1, ((size_t)256 << 20) / per));
             double2 *gbuf = (double2 *)workspace(30, (size_t)g3 * per, stream);
             if (!gbuf) return 0;
             hipLaunchKernelGGL(hpr_overflow_kernel<0>, dim3(g3), dim3(kWave), 0, stream, n, (const double *)fl, (const HprTile *)tiles,
@@ -1974,8 +1961,7 @@ static int hpr_run(int c, int n, const float *points, const double *eyes, double
         }
         hipLaunchKernelGGL(hpr_finish_kernel, dim3(ceil_div(c, 256)), dim3(256), 0, stream, c, (const int *)status, counts);
         // the counters are fetched (the entry's only stream synchronisation) when somebody asks for them
-        const bool tiers = tune_env("GENPC_HPR_TIERS", 0, "hidden-point removal: 1 = report on stderr how many points took the wave-per-point tiers") != 0;
-        if (second_pass_points || tiers || (no_cull & 256)) {
+        if (second_pass_points || (no_cull & 256)) {
             int st[48] = {0};
             if (!check(hipMemcpyAsync(st, status, sizeof st, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(hpr status)")) return 0;
             if (!check(hipStreamSynchronize(stream), "hipStreamSynchronize(hpr)")) return 0;
@@ -1984,9 +1970,6 @@ static int hpr_run(int c, int n, const float *points, const double *eyes, double
                 set_error("genpc_hpr_visibility: internal error (a normal-cone polygon outgrew its buffer)");
                 return 0;
             }
-            if (tiers)
-                fprintf(stderr, "hpr: %d points parked, %d listed for the wave-per-point pass, %d polygons over 128 vertices, %d over %d (global-memory tier)\n",
-                        st[2], st[0], st[3], st[4], kHprOverCap);
             if (no_cull & 256)
                 fprintf(stderr, "hpr: parked points, first try: %d undecided, %d visible, %d hidden; after the home tiles: %d undecided, %d visible, %d hidden, %d died in the tiles\n",
                         st[8], st[9], st[10], st[12], st[13], st[14], st[15]);

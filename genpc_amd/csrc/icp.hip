@@ -683,29 +683,26 @@ GENPC_API int genpc_icp_batch(int k, int ns, const float *source, int nt, const 
     if (k <= 0 || ns <= 0 || nt <= 0 || max_iter < 0) return -1;
     hipStream_t st = (hipStream_t)stream;
     // the one-workgroup solve (one launch) when the target cloud and its grid fit a compute unit's LDS
-    static const int env_fused = tune_env("GENPC_ICP_FUSED", 1, "ICP: 1 = the whole solve of a candidate in one workgroup (target grid in LDS; clouds up to ~7000 target points), 0 = five launches per pass");
-    if (env_fused) {
-        int cells = 8192;
-        while (cells >= 1024 && icp_fused_lds(nt, cells) + 1024 > (size_t)160 * 1024) cells >>= 1;
-        if (cells >= 1024 && nt < 65536) {
-            const size_t lds = icp_fused_lds(nt, cells);
-            const int fma = arith_mode() != 0 ? 1 : 0;
-            static size_t set_bytes[2] = {0, 0};
-            if (lds > set_bytes[fma]) {
-                const hipError_t e = fma ? hipFuncSetAttribute((const void *)icp_fused_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                                         : hipFuncSetAttribute((const void *)icp_fused_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (!check(e, "hipFuncSetAttribute(icp_fused_kernel)")) return 0;
-                set_bytes[fma] = lds;
-            }
-            const float md2f = (float)(max_dist * max_dist);
-            if (fma)
-                hipLaunchKernelGGL((icp_fused_kernel<1>), dim3(k), dim3(kFT), lds, st, ns, source, nt, target, md2f, max_dist, init, max_iter,
-                                   rel_fitness, rel_rmse, cells, out_T, stats);
-            else
-                hipLaunchKernelGGL((icp_fused_kernel<0>), dim3(k), dim3(kFT), lds, st, ns, source, nt, target, md2f, max_dist, init, max_iter,
-                                   rel_fitness, rel_rmse, cells, out_T, stats);
-            return check(hipGetLastError(), "icp (one workgroup) launch") ? 1 : 0;
+    int cells = 8192;
+    while (cells >= 1024 && icp_fused_lds(nt, cells) + 1024 > (size_t)160 * 1024) cells >>= 1;
+    if (cells >= 1024 && nt < 65536) {
+        const size_t lds = icp_fused_lds(nt, cells);
+        const int fma = arith_mode() != 0 ? 1 : 0;
+        static size_t set_bytes[2] = {0, 0};
+        if (lds > set_bytes[fma]) {
+            const hipError_t e = fma ? hipFuncSetAttribute((const void *)icp_fused_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
+                                     : hipFuncSetAttribute((const void *)icp_fused_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (!check(e, "hipFuncSetAttribute(icp_fused_kernel)")) return 0;
+            set_bytes[fma] = lds;
         }
+        const float md2f = (float)(max_dist * max_dist);
+        if (fma)
+            hipLaunchKernelGGL((icp_fused_kernel<1>), dim3(k), dim3(kFT), lds, st, ns, source, nt, target, md2f, max_dist, init, max_iter,
+                               rel_fitness, rel_rmse, cells, out_T, stats);
+        else
+            hipLaunchKernelGGL((icp_fused_kernel<0>), dim3(k), dim3(kFT), lds, st, ns, source, nt, target, md2f, max_dist, init, max_iter,
+                               rel_fitness, rel_rmse, cells, out_T, stats);
+        return check(hipGetLastError(), "icp (one workgroup) launch") ? 1 : 0;
     }
     // scratch: accum[k,17] | state[k] | pts[k,ns,3] | target_rep[k,nt,3] | d[k,ns] | idx[k,ns]
     size_t off = 0;

@@ -300,8 +300,7 @@ __global__ __launch_bounds__(kKGBlock) void knn_grid_kernel(int n, const float4 
 template <int K>
 static bool launch_knn_grid(int n, const float *xyz, float *out, hipStream_t st)
 {
-    static const int env_grid = tune_env("GENPC_KNN_GRID", 1, "k-NN mean distance: 1 = through a uniform grid (shells of cells around the query), 0 = exhaustive");
-    if (!env_grid || n < 256) return false;
+    if (n < 256) return false;
     const size_t o_cend = ((size_t)n * sizeof(float4) + 255) / 256 * 256, o_g = o_cend + (size_t)kKGCells * sizeof(unsigned);
     char *ws = (char *)workspace(35, o_g + 256, st);
     if (!ws) return false;

@@ -86,7 +86,6 @@ struct GridArgs {
     int block_begin[2];
     int fma;
     float radius2;          // search limit (squared distance), +inf = none
-    int near_only;          // experiment: stop after the 27 cells, count the unresolved queries in stats[1]
     int sort_cloud[2];      // cloud c is sorted (it is a target cloud, or its queries are wanted in cell order)
     unsigned long long *stats;
 };
@@ -480,9 +479,7 @@ __global__ __launch_bounds__(kBlock) void grid_query_kernel(GridArgs a)
         // everything outside the 27 cells differs by >= 2 cells on some axis: distance >= h - 2 slack
         float reach = fmaxf(0.0f, h - 2.0f * smax);
         bool done = __fmul_rn(__fmul_rn(reach, reach), kShrink) > __uint_as_float((unsigned)(best >> 32));
-        if (!done && a.near_only) {
-            if (a.stats && sub == 0 && live) atomicAdd(&a.stats[1], 1ull);
-        } else if (!done) {
+        if (!done) {
             // Far phase.  Coarse cells (4 x 4 x 4 fine cells, one contiguous run of the sorted cloud
             // each) are tested against the best so far, the lanes of the group taking LPQ of them at
             // a time; inside a surviving coarse cell the 64 fine cells are tested the same way and
@@ -582,8 +579,6 @@ int launch_nn_grid(const NNArgs &na, hipStream_t st)
     a.fma = na.fma;
     a.stats = na.stats;
     a.radius2 = na.radius2;
-    static const int near_env = (tune_env("GENPC_GRID_NEARONLY", 0, "cell-sorted nearest-neighbour search: experiment, stop after the 27 near cells") != 0 ? 1 : 0);
-    a.near_only = near_env;
     // one direction: only the target cloud is sorted (the queries lose some locality, a whole cloud less to sort)
     a.sort_cloud[0] = na.ndir > 1 ? 1 : 0;
     a.sort_cloud[1] = 1;
@@ -607,8 +602,7 @@ int launch_nn_grid(const NNArgs &na, hipStream_t st)
     }
     const int nmax = std::max(a.sort_cloud[0] ? a.n[0] : 0, a.n[1]);      // the grid follows the density of the sorted (target) clouds
     // about three points per cell of the denser cloud if it filled the box; surfaces fill ~ G^2 of G^3 cells
-    static const int env_ppc = tune_env("GENPC_GRID_PPC_X10", 30, "cell-sorted nearest-neighbour search: target points per cell x 10");      // points per cell x 10
-    int target = (int)((long long)nmax * 10 / (env_ppc > 0 ? env_ppc : 30));
+    int target = (int)((long long)nmax * 10 / 30);
     target = std::max(8, std::min(target, kGridMaxCells / 2));
     a.cells_target = target;
     a.cells_max = std::min(kGridMaxCells - 256, 2 * target + 512);      // coarse cells are padded to 4 x 4 x 4
@@ -629,10 +623,8 @@ int launch_nn_grid(const NNArgs &na, hipStream_t st)
     a.sorted_off[0] = 0;
     a.sorted_off[1] = (size_t)a.b * a.n[0];
     // slabs per cloud: enough blocks to occupy a good part of the chip when the batch is small
-    static const int env_k = tune_env("GENPC_GRID_K", 0, "cell-sorted nearest-neighbour search: slab blocks per cloud of the build (0 = pick)");
     int K = std::max(1, std::min(8, 64 / (2 * a.b)));
     K = std::min(K, std::max(1, nmax / 2048));
-    if (env_k > 0) K = std::min(env_k, 64);
     if ((long long)a.b * 2 * K > 0x7fffffffLL) {
         set_error("nn grid: problem too large for one launch");
         return 0;
@@ -645,9 +637,7 @@ int launch_nn_grid(const NNArgs &na, hipStream_t st)
     long long queries = 0;
     for (int d = 0; d < a.ndir; d++) queries += (long long)a.b * a.n[a.qcloud[d]];
     const long long want = 8LL * (4 * num_cus()) * kWave;
-    static const int env_lpq = tune_env("GENPC_GRID_LPQ", 0, "cell-sorted nearest-neighbour search: lanes per query (1 | 4 | 16 | 32, 0 = pick)");
-    int lpq = queries * 16 <= want ? 32 : (queries * 4 <= want ? 16 : (queries <= want ? 4 : 1));
-    if (env_lpq == 1 || env_lpq == 4 || env_lpq == 16 || env_lpq == 32) lpq = env_lpq;
+    const int lpq = queries * 16 <= want ? 32 : (queries * 4 <= want ? 16 : (queries <= want ? 4 : 1));
     long long tb = 0;
     for (int d = 0; d < a.ndir; d++) {
         a.qblocks[d] = ceil_div(a.n[a.qcloud[d]] * lpq, kBlock);

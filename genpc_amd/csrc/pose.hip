@@ -1855,12 +1855,11 @@ static int mask_tiles(int S) { const int t = ceil_div(S, kMaskTile); return t * 
 
 // Which blend the images of the mask term are drawn with: 1 Pulsar's published blending function (softmax in depth; the
 // default), 0 the round-2 coverage splat (order-independent; kept for A/B and for the numbers quoted before round 5).
-// genpc_render_tune() sets it per calling thread; GENPC_RENDER_BLEND for the process.
+// genpc_render_tune() sets it per calling thread.
 thread_local int t_render_blend = -1;
 static int render_blend()
 {
-    static const int env = tune_env("GENPC_RENDER_BLEND", 1, "mask term's renderer: 1 = Pulsar's blending function (softmax in depth), 0 = the coverage splat");
-    return (t_render_blend >= 0 ? t_render_blend : env) ? 1 : 0;
+    return t_render_blend != 0 ? 1 : 0;
 }
 
 // scratch of the mask term for b scans of P pixels and up to nmax points (bytes, 256-aligned pieces)
@@ -1953,26 +1952,23 @@ static int mask_step(int b, int nc, const float *complete, const float *complete
         hipLaunchKernelGGL(mask_splat_kernel<0>, dim3(mask_tiles(S) * b), dim3(kSplatBlock), 0, st, nc, (const float4 *)m.uvr, complete_col,
                            S, m.planes, accum, use_bins(S) ? m.bins : (int *)nullptr, b, zex, m.clean);
     // few blocks per image: every block ends in 22 double atomics on the image's accumulators, and 196 blocks x 22 on the
-    // same addresses serialise in L2 (17.5 us for 0.2 M pixels; GENPC_MASK_SUMS_BLOCKS for A/B)
-    static const int env_sb = tune_env("GENPC_MASK_SUMS_BLOCKS", 0, "alignment loop: blocks per image of mask_sums_kernel (0 = pick)");
-    const int gs = std::min(gp, env_sb > 0 ? env_sb : 48);      // 196: 221 ms per 8-scan call, 48: 210, 24: 210, 12: 210 (single scan: 42.1 / 41.4 / 41.8 / 43.3)
+    // same addresses serialise in L2 (17.5 us for 0.2 M pixels)
+    const int gs = std::min(gp, 48);      // 196: 221 ms per 8-scan call, 48: 210, 24: 210, 12: 210 (single scan: 42.1 / 41.4 / 41.8 / 43.3)
     hipLaunchKernelGGL(mask_sums_kernel, dim3(gs, b), dim3(kQBlock), 0, st, S, (const float *)m.planes, mode, (const float *)m.mref,
                        (const float *)m.stats, accum);
     // the weights per pixel as a launch of their own, or evaluated inside the gather
-    static const int env_fw = tune_env("GENPC_MASK_FUSE_W", 1, "alignment loop: 1 = the silhouette gradient evaluates the per-pixel weights where it gathers them (no mask_w launch), 0 = mask_w_kernel + gather");
     // (only where the gather touches fewer pixels than ~three and a half passes over the image (config 2: 4493 points): a point's disc covers ~pi rho^2 pixels, rho =
     //  S/2 * focal * radius / 3 at the camera's distance -- 2451 points: 0.4 of the image; 16384 points: 2.9 images' worth of
     //  weights, each 60 instructions where the launch of its own computes them once per pixel)
     const float rho_px = 0.5f * (float)S * kMaskFocal * rad / kMaskEyeZ;
-    const bool fuse_w = env_fw != 0 && (double)nc * 3.1416 * rho_px * rho_px <= 3.5 * (double)S * S;
+    const bool fuse_w = (double)nc * 3.1416 * rho_px * rho_px <= 3.5 * (double)S * S;
     if (!fuse_w)
         hipLaunchKernelGGL(mask_w_kernel, dim3(gp, b), dim3(kQBlock), 0, st, S, (const float *)m.planes, mode, (const float *)m.mref,
                            (const float *)m.stats, mask_weight, m.W1, m.W4, accum);
     // lanes per point: a thread per point walks its whole pixel box alone (a chain of ~35 dependent gathers at the loop's
     // radius: 21 us for 4 x 2451 points), eight lanes share it row by row (12.9 us) -- until the points fill the chip by
     // themselves (measured at 4 x 16384 points, the four starts in lock-step: <1> 35 us, <8> 42)
-    static const int env_sub = tune_env("GENPC_MASK_GRAD_SUB", 0, "alignment loop: lanes per point of the per-point silhouette gradient (0 = pick)");
-    const int sub = env_sub ? env_sub : ((long long)b * nc <= 24576 || b <= 2 ? 8 : 1);
+    const bool sub8 = (long long)b * nc <= 24576 || b <= 2;
     const PoseGradArgs pgx = ride ? *ride : PoseGradArgs{};
 #define GENPC_LAUNCH_MASK_GRAD3(SUB, BL, FW)                                                                                         \
     hipLaunchKernelGGL((mask_grad_kernel<SUB, BL, FW>), dim3(lin_grid((long long)nc * SUB) * b + pgx.gx * b), dim3(kQBlock), 0, st, nc, complete, \
@@ -1981,9 +1977,7 @@ static int mask_step(int b, int nc, const float *complete, const float *complete
                        mask_weight, pgx)
 #define GENPC_LAUNCH_MASK_GRAD2(SUB, BL) do { if (fuse_w) GENPC_LAUNCH_MASK_GRAD3(SUB, BL, 1); else GENPC_LAUNCH_MASK_GRAD3(SUB, BL, 0); } while (0)
 #define GENPC_LAUNCH_MASK_GRAD(SUB) do { if (blend) GENPC_LAUNCH_MASK_GRAD2(SUB, 1); else GENPC_LAUNCH_MASK_GRAD2(SUB, 0); } while (0)
-    if (sub == 8) GENPC_LAUNCH_MASK_GRAD(8);
-    else if (sub == 4) GENPC_LAUNCH_MASK_GRAD(4);
-    else if (sub == 2) GENPC_LAUNCH_MASK_GRAD(2);
+    if (sub8) GENPC_LAUNCH_MASK_GRAD(8);
     else GENPC_LAUNCH_MASK_GRAD(1);
 #undef GENPC_LAUNCH_MASK_GRAD3
 #undef GENPC_LAUNCH_MASK_GRAD2
@@ -2108,7 +2102,7 @@ namespace genpc { thread_local int t_pose_seeded = -1; }
  * real shapes), 0 the brute-force filter at every step, 2 whichever of the two the call measures to be faster (the
  * default), < 0 the default / environment (GENPC_POSE_SEEDED).  All give the same bits.  Returns the previous setting. */
 /* The renderer of the mask term, per calling host thread: 1 Pulsar's blending function (default), 0 the coverage splat,
- * < 0 back to the default / GENPC_RENDER_BLEND.  Returns the previous setting (-1 = default). */
+ * < 0 back to the default.  Returns the previous setting (-1 = default). */
 GENPC_API int genpc_render_tune(int blend)
 {
     const int prev = genpc::t_render_blend;
@@ -2302,8 +2296,8 @@ GENPC_API int genpc_pose_optimize_batch(int b, int nc, const float *complete, co
     // (tools/time_c2_streams.py, one scan at a time: 24.4 scans/s without a side stream; 25.7 with it on the null stream but 21.2
     // on a stream of the caller's own; with its own class 25.3 / 25.9).
     static const int env_dual0 = tune_env("GENPC_POSE_DUAL", 1, "alignment loop, full objective, small clouds: 1 = the Chamfer half of a step (nearest neighbours + gradient) on a side stream beside the silhouette half, 0 = one stream");
-    static const int env_dual_max = tune_env("GENPC_POSE_DUAL_MAX", 65536, "alignment loop: the side stream for up to this many points per call (elements x points)");
-    const bool dual_small = mask && (t_pose_dual >= 0 ? t_pose_dual != 0 : env_dual0 != 0) && (long long)b * nc <= env_dual_max;
+    // (up to 65536 points per call, elements x points)
+    const bool dual_small = mask && (t_pose_dual >= 0 ? t_pose_dual != 0 : env_dual0 != 0) && (long long)b * nc <= 65536;
     int seed_mode = nc >= 256 && np >= 256 ? (t_pose_seeded >= 0 ? t_pose_seeded : env_seeded) : 0;
     if (dual_small && t_pose_seeded < 0 && seed_mode == 2) seed_mode = 0;
     // ... and so it is for small clouds in general: at the post-voxel sizes of reg() (4 x 4493 against 886 points) a step's
@@ -2342,10 +2336,9 @@ GENPC_API int genpc_pose_optimize_batch(int b, int nc, const float *complete, co
     const int gb = ceil_div(b, 64);
     hipLaunchKernelGGL(pose_begin_kernel, dim3(gb), dim3(64), 0, st, b, S, accum, -1, 0);
     // (every block of the gradient kernels ends in 13-22 double atomics on its image's accumulators: with many images in
-    // flight fewer, longer blocks per image -- GENPC_POSE_GRAD_BLOCKS for A/B)
-    static const int env_gb = tune_env("GENPC_POSE_GRAD_BLOCKS", 0, "alignment loop: blocks per image of the gradient kernels (0 = pick)");
+    // flight fewer, longer blocks per image)
     // 32 images (8 scans x 4 starts): 96 blocks per image 153.1 ms per call, 48: 151.0, 24: 150.2, 12: 150.4
-    const int g_t = lin_grid(nc), g_g = std::min(env_gb > 0 ? env_gb : (b >= 16 ? 24 : 1024), lin_grid((long long)nc + np));
+    const int g_t = lin_grid(nc), g_g = std::min(b >= 16 ? 24 : 1024, lin_grid((long long)nc + np));
     const int hstride = starts * (iters + 1);
     PoseSide *dual = dual_small ? pose_side_of(st) : nullptr;      // (small clouds only: where the launches fill the chip by themselves the two
                                                                    //  halves only take each other's compute units -- 8 scans in lock-step 77.6 -> 53.2 scans/s)

@@ -719,9 +719,9 @@ GENPC_API int genpc_paint_pixels(int res, int n, const int *pix, const float *co
     using namespace genpc;
     if (res <= 0 || ch <= 0 || point_size < 1) return -1;
     hipStream_t st = (hipStream_t)stream;
-    // many points: binned by pixel tile, elected in LDS (paint_bin / paint_tile kernels above); few: the two kernels below
-    static const int env_bin = tune_env("GENPC_PAINT_BINNED_MIN", 262144, "paintPixels: points from which the owners are elected per 64 x 64-pixel tile in LDS (0 = never)");
-    if (env_bin > 0 && n >= env_bin && res <= kPaintTile * 64 && point_size <= 32) {
+    // from 262144 points: binned by 64 x 64-pixel tile, the owners elected in LDS (paint_bin / paint_tile kernels above);
+    // fewer: the two kernels below
+    if (n >= 262144 && res <= kPaintTile * 64 && point_size <= 32) {
         const int tiles_x = ceil_div(res, kPaintTile), tiles = tiles_x * tiles_x;
         const size_t per_point = point_size == 1 ? 1 : 4;
         int chunk = ceil_div(ceil_div(n, 512), kPBlock) * kPBlock;        // at most 512 blocks of whole 256-point strides
@@ -758,8 +758,7 @@ GENPC_API int genpc_gather_colors(int n, const int *pix, const float *img, int c
     // Many points on a three-channel image: one 16-byte gather per point from an interleaved copy of the image instead of three
     // 4-byte gathers from its planes (each a 64-byte line of its own: 9.4 x the algorithmic traffic at 2 M points on 1024^2).
     // The copy costs a pass over the image (28 B per pixel), so only where the points outnumber a quarter of the pixels.
-    static const int env_pack = tune_env("GENPC_GATHER_PACK", 1, "colour gather: 1 = many points read one 16-byte word per point from an interleaved copy of the image, 0 = always three planar gathers");
-    if (env_pack && ch == 3 && (long long)n * 4 >= (long long)h * w && (long long)h * w <= 0x7fffffffLL) {
+    if (ch == 3 && (long long)n * 4 >= (long long)h * w && (long long)h * w <= 0x7fffffffLL) {
         hipStream_t st = (hipStream_t)stream;
         float4 *packed = (float4 *)workspace(33, (size_t)h * w * sizeof(float4), st);
         if (!packed) return 0;

@@ -31,7 +31,7 @@ import torch
 
 from .DepthPrompting import DepthPrompting
 from .ScaleAdapter import ScaleAdapter
-from .fps import fps_sampling, FpsCombiner
+from .fps import fps_sampling
 from .metric import evaluate_scans
 from . import reg_xyz
 from . import _lib
@@ -55,9 +55,7 @@ def fps_to(xyz, k):
 
 _SIDE = {}
 _LANE = {}
-_NO_OVERLAP = __import__("os").environ.get("GENPC_C2_NO_OVERLAP", "0") == "1"      # A/B switch
-_FPS_DEFER = __import__("os").environ.get("GENPC_FPS_DEFER", "1") != "0"              # A/B switch: the samplings' check beside the tail (complete_scan)
-_NO_COMBINER = __import__("os").environ.get("GENPC_FPS_COMBINER", "0") != "1"        # A/B switch (off: see run_in_lanes)
+_FPS_DEFER = True          # the samplings' check beside the tail (complete_scan; tests switch it off)
 
 
 _SIDE_LOCK = threading.Lock()
@@ -87,10 +85,10 @@ def _side_stream(device, main):
             # A stream of ANOTHER priority class: the runtime deals a class's streams onto a handful of hardware queues (four by
             # default), and two streams that land on one queue do not overlap at all -- in a process that has made many streams
             # (bench.py by the time it reaches this line) stage 1 then simply ran behind the tail: 20.4 scans/s where a fresh
-            # process measured 24.6.  The high-priority class has queues of its own.  (GENPC_C2_SIDE_PRIORITY=0: the old choice.)
+            # process measured 24.6.  The high-priority class has queues of its own.
             # Several scans in flight (run_in_lanes) keep the caller's class: six high-priority stage-1 streams crowd the few queues
             # of that class (six lanes, three runs each: 46.8 scans/s with the caller's class, 44.8 with the high one).
-            prio = -1 if __import__("os").environ.get("GENPC_C2_SIDE_PRIORITY", "-1") != "0" and getattr(_TLS, "lanes", 1) <= 1 else 0
+            prio = -1 if getattr(_TLS, "lanes", 1) <= 1 else 0
             _SIDE[key] = _fresh_stream(dev, avoid=(main.cuda_stream,), priority=prio)
         return _SIDE[key]
 
@@ -179,7 +177,7 @@ def complete_scan(partial_xyz, generated_xyz, generated_img, gt_xyz=None, cfg=No
         return t
 
     main = side = None
-    if overlap and partial_xyz.is_cuda and not _NO_OVERLAP:
+    if overlap and partial_xyz.is_cuda:
         main = torch.cuda.current_stream(partial_xyz.device)
         side = _side_stream(partial_xyz.device, main)
         if side.cuda_stream == main.cuda_stream:        # (torch's stream pool wrapped around onto the caller's stream)
@@ -250,8 +248,7 @@ def run_in_lanes(fn, items, lanes, device):
     dev = torch.device(device)
     lanes = max(1, min(int(lanes), len(items), 8))
     caller = torch.cuda.current_stream(dev)
-    if __import__("os").environ.get("GENPC_PREPARE_STREAMS", "1") != "0":
-        prepare_streams(dev)             # (the single-scan path's side streams get their queues before the lanes' streams exist)
+    prepare_streams(dev)                 # (the single-scan path's side streams get their queues before the lanes' streams exist)
     results, errors = [None] * len(items), []
     nxt = [0]
     lock = threading.Lock()
@@ -262,7 +259,7 @@ def run_in_lanes(fn, items, lanes, device):
         try:
             _lib.apply_thread_state(state)
             _TLS.lanes = lanes
-            if lanes > 1 and __import__("os").environ.get("GENPC_LANES_DUAL", "0") != "1":
+            if lanes > 1:
                 # several scans in flight share the chip already: the alignment loop's second stream (csrc/pose.hip) costs
                 # throughput there (six lanes 30 scans/s with it, 40 without) where it saves a scan alone 6 % of its time
                 _lib.lib.genpc_pose_dual(0)
@@ -282,15 +279,13 @@ def run_in_lanes(fn, items, lanes, device):
             errors.append(e)
 
     threads = [threading.Thread(target=lane, args=(i,), name="genpc-lane-%d" % i) for i in range(lanes)]
-    # GENPC_FPS_COMBINER=1: the lanes' farthest-point samplings leave in shared launches (fps.FpsCombiner).  Measured on
-    # config 2's chain, scans/s with / without: four lanes 29.4 / 34.4, six 31.1 / 35.5, eight 35.7 / 36.1 -- the samplings of
-    # different lanes are not what the lanes wait for, and a launch of many clouds gives each fewer workgroups: off.
-    import contextlib
-    with (FpsCombiner.installed(dev) if lanes > 1 and not _NO_COMBINER else contextlib.nullcontext()):
-        for t in threads:
-            t.start()
-        for t in threads:
-            t.join()
+    # (The lanes' farthest-point samplings each leave in a launch of their own.  Combining them into shared launches was
+    # measured on config 2's chain, scans/s combined / separate: four lanes 29.4 / 34.4, six 31.1 / 35.5, eight 35.7 / 36.1 --
+    # the samplings of different lanes are not what the lanes wait for, and a launch of many clouds gives each fewer workgroups.)
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
     if errors:
         raise errors[0]
     return results

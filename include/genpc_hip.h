@@ -62,7 +62,7 @@ int genpc_release_workspace(void);
  * filter off / on whatever the policy says), < 0 keep.  Applies to calls made by the CALLING
  * host thread only (thread-local; other threads keep the defaults).  Returns the previous
  * path.  Environment (read once, at first use): GENPC_NN_PATH (valu | mfma32 | f16 |
- * grid), GENPC_NN_DEBUG; A/B switches of the f16 filter: GENPC_NN_HT=1024, GENPC_NN_NOWIDE.                                                          */
+ * grid), GENPC_NN_DEBUG.                                                         */
 int genpc_nn_tune(int path, int hooks);
 /* Counters of the filtered nearest-neighbour paths, accumulated on the current device
  * while hook 512 is set: out[0] queries answered, out[1] queries re-done by the exhaustive
@@ -322,7 +322,7 @@ int genpc_pose_loss_grad(int nc, const float *v, const float *vert_col, const fl
  *     with the coverage a_i and the camera of the splat above -- a near surface hides a far one.  THE DEFAULT.  What of it is
  *     from memory (pytorch3d is absent and unpinned) is listed in oracle/genpc_oracle_geom.c;
  * 0 = the coverage splat described above (order-independent: front and back surfaces are averaged; rounds 2-4);
- * < 0 = back to the default (environment GENPC_RENDER_BLEND).  Returns the previous setting (-1 = default). */
+ * < 0 = back to the default.  Returns the previous setting (-1 = default). */
 int genpc_render_tune(int blend);
 
 /* Nearest-neighbour path of genpc_pose_optimize_batch, for tests and A/B (applies to the calling host thread): 1 the
@@ -416,7 +416,7 @@ int genpc_fastdiv_probe(long long n, const float *num, const float *den, float *
  * unless 0 < k <= n <= 262144.  out_idx[c][0] is 0 for a good sequence; -1: the
  * hand-off among the cloud's workgroups timed out (something kept them from running
  * together); -2: the finished sequence failed the device-side check of every step
- * against the definition (GENPC_FPS_VERIFY, on by default) -- sample that cloud again
+ * against the definition -- sample that cloud again
  * (genpc_amd/fps.py does).                                                       */
 int genpc_fps(int c, int n, const float *xyz, int k, int *out_idx, void *stream);
 

@@ -95,8 +95,6 @@ def test_no_packed_fp32_instructions_in_the_shipped_code():
         with open(src, errors="replace") as f:
             assert "packed-fp32-ops" not in f.read(), src
     build.build(verbose=False)
-    if os.environ.get("GENPC_PACKED_FP32", "0") == "1":
-        pytest.skip("built with packed fp32 on purpose")
     llvm = "/opt/rocm/lib/llvm/bin"
     objs = sorted(glob.glob(os.path.join(ROOT, "genpc_amd", "lib", "obj", "*.o")))
     assert objs, "no objects under genpc_amd/lib/obj"
@@ -120,3 +118,32 @@ def test_no_packed_fp32_instructions_in_the_shipped_code():
                 elif re.search(r"\bv_pk_(add|mul|fma)_f32\b", line):
                     bad.append((os.path.basename(o), func, line.strip()))
     assert not bad, bad[:5]
+
+
+# The library's tuning switches (environment variables read through genpc::tune_env / tune_env_str): only those that a test
+# (tests/test_gpu_hpr_paths.py, tests/test_gpu_pose_update_forms.py) or a tool cited for its numbers (tools/nn_sweep.py,
+# tools/prof_c2*.py) sets.  A switch nothing sets is a default written as code.
+KEPT_SWITCHES = {
+    "GENPC_HPR_SPLIT", "GENPC_HPR_NOCULL", "GENPC_HPR_HOME_TILES", "GENPC_HPR_HOME_CHUNKS", "GENPC_HPR_DECIDE_KERNEL",
+    "GENPC_HPR_PARK_MB",
+    "GENPC_POSE_DUAL", "GENPC_POSE_DUAL_FLAGS", "GENPC_POSE_FUSE_UPDATE", "GENPC_POSE_GRAD_RIDES", "GENPC_POSE_LOCKSTEP",
+    "GENPC_POSE_SEEDED",
+    "GENPC_NN_PATH", "GENPC_NN_Q", "GENPC_NN_U", "GENPC_NN_R", "GENPC_NN_WPS", "GENPC_NN_DEBUG",
+}
+
+
+def test_tuning_switches_are_the_kept_ones():
+    """Every GENPC_* name the library passes to tune_env / tune_env_str is one of KEPT_SWITCHES and each of them is read; the
+    Python package reads no GENPC_* variable from the environment but the library's path and the build's job count."""
+    import glob
+    found = set()
+    for src in glob.glob(os.path.join(ROOT, "genpc_amd", "csrc", "*")):
+        with open(src, errors="replace") as f:
+            found |= set(re.findall(r"\btune_env(?:_str)?\s*\(\s*\"(GENPC_\w+)\"", f.read()))
+    assert found == KEPT_SWITCHES, (sorted(found - KEPT_SWITCHES), sorted(KEPT_SWITCHES - found))
+    py = set()
+    for src in glob.glob(os.path.join(ROOT, "genpc_amd", "**", "*.py"), recursive=True):
+        with open(src, errors="replace") as f:
+            txt = f.read()
+        py |= set(re.findall(r"\b(?:environ(?:\.get)?|getenv)\s*[\[(]\s*[\"'](GENPC_\w+)", txt))
+    assert py == {"GENPC_LIB", "GENPC_BUILD_JOBS"}, sorted(py)
