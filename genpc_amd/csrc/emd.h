@@ -1,7 +1,8 @@
 // emd.h -- device helpers shared by the auction kernels (emd.hip: tiled bid, settle / resolve; emd_grid.hip: the
-// cell-sorted culled bid).
+// cell-sorted culled bid; emd_auction.hip: all rounds in one launch).  The objects' spatial index is grid.h's.
 #pragma once
 #include "common.h"
+#include "grid.h"
 
 namespace genpc {
 
@@ -97,15 +98,7 @@ __device__ __forceinline__ int pick_p(int U, int G)
 }
 
 // ---- cell-sorted culled bid (emd_grid.hip) ----
-constexpr int kEGMaxCells = 15360;      // LDS counters of the build kernel (60 KiB)
-struct EGridHdr {            // one per batch element, written by emd_grid_build_kernel
-    float lo[3];
-    float inv, h;           // cells per unit length, cell side
-    float slack[3];         // 16u (|lo| + (g + 1) h) per axis; the bidder adds 16u |x1|
-    int g[3];               // cells per axis
-    int cells;
-    int bad;                // a non-finite coordinate or a negative / non-finite initial price: search without culling
-};
+constexpr int kTwoPassRows = 25;        // boxes of more (y, z) rows than this take the near cells first (both culled bid searches)
 struct EmdGridBid {
     int n, G, nb, cells_max, force_lpb, lpb_max;      // lpb_max > 0: at most this many lanes per bidder
     float eps;
@@ -115,15 +108,13 @@ struct EmdGridBid {
     int *cnt_next, *bid, *second;
     float *bid_increments, *max_increments;
     const float4 *sorted;
-    const EGridHdr *hdr;
+    const CellGridHdr *hdr;
     unsigned long long *chain_head, *chain_next;
     int *chain_cnt;                // bidders per object this round (emd_settle_kernel)
     int *feedback;                 // round 3 only (else null): pinned host word that receives cloud 0's bidder count (emd_auction.hip: which path suits the data)
     const float *cell_pmin;        // per cloud, cells_max + 1 floats: a lower bound of the prices in every cell, +inf for an empty one (emd_cell_pmin_kernel); null: rows are not culled by price
     unsigned long long *stats;     // hook (genpc_emd_tune): [0] bidders, [1] rows of their boxes, [2] rows kept, [3] objects tested, [4] exact evaluations, [5] first-place ties, [6] unseeded bidders; else null
 };
-int launch_emd_grid_build(int b, int n, const float *xyz2, const float *price, EGridHdr *hdr, int *start, float4 *sorted, int *pos_of,
-                          int *orig_of, int cells_target, int cells_max, hipStream_t st, float *price_sep = nullptr);
 // ---- all rounds in one launch, threads own the points (emd_auction.hip) ----
 int launch_emd_auction(int b, int n, const float *xyz1, const float *xyz2, float *dist, int *assignment, float *price, int *assignment_inv,
                        int *bid, float *bid_increments, float *max_increments, int *max_idx, float eps, int iters, int fma, hipStream_t st, bool forced);
@@ -131,17 +122,6 @@ int *emd_feedback_slot(int b, int n, bool device);
 bool persist_reserve(int wgs, int capacity, hipStream_t st);
 void persist_commit(int wgs, hipStream_t st);
 int launch_emd_bid_grid(const EmdGridBid &a, int fma, hipStream_t st);
-int launch_emd_cell_pmin(int b, int cells_max, const EGridHdr *hdr, const int *start, const float4 *sorted, int n, float *pmin, hipStream_t st);
-
-// ---- seeded nearest neighbours of the alignment loop (nn_seeded.hip) ----
-struct SeededGrids {
-    const EGridHdr *hdr_static, *hdr_rest;
-    const int *start_static, *start_rest;
-    const float4 *sorted_static, *sorted_rest;
-};
-size_t seeded_grids_bytes(int b, int nm, int ns);
-int build_seeded_grids(int b, int nm, const float *rest_pts, int ns, const float *static_pts, void *ws, SeededGrids &g, hipStream_t st);
-int launch_nn_seeded(int b, int nm, const float *moving_pts, int ns, const float *static_pts, const SeededGrids &g, const float *center,
-                     int cstride, const float *params, int pstride, float *d1, int *i1, float *d2, int *i2, int fma, hipStream_t st, int sample = 1);
+int launch_emd_cell_pmin(int b, int cells_max, const CellGridHdr *hdr, const int *start, const float4 *sorted, int n, float *pmin, hipStream_t st);
 
 }  // namespace genpc

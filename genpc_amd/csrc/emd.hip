@@ -743,8 +743,8 @@ GENPC_API int genpc_emd_forward(int b, int n, int m, const float *xyz1, const fl
     // cell-sorted copy of the objects for the culled bid (emd_grid.hip): needs prices >= 0 (eps >= 0) and the seeds
     const bool grid = (t_emd_grid >= 0 ? t_emd_grid != 0 : (n >= 4096 || (long long)b * n >= 65536)) && eps >= 0.0f;
     auto al256 = [](size_t v) { return (v + 255) / 256 * 256; };
-    const int cells_max = kEGMaxCells;
-    const size_t g_hdr = grid ? al256((size_t)b * sizeof(EGridHdr)) : 0, g_start = grid ? al256((size_t)b * (cells_max + 1) * sizeof(int)) : 0;
+    const int cells_max = kCellGridMaxCells;
+    const size_t g_hdr = grid ? al256((size_t)b * sizeof(CellGridHdr)) : 0, g_start = grid ? al256((size_t)b * (cells_max + 1) * sizeof(int)) : 0;
     const size_t g_sorted = grid ? al256((size_t)total * sizeof(float4)) : 0, g_pos = grid ? al256((size_t)total * sizeof(int)) : 0;
     const size_t g_ps = grid ? al256((size_t)total * sizeof(float)) : 0;
     // per-cell lower bounds of the prices (emd_grid.hip: the bid culls cell by cell with them), refreshed in front of every
@@ -753,7 +753,7 @@ GENPC_API int genpc_emd_forward(int b, int n, int m, const float *xyz1, const fl
     const size_t grid_off = arrive_bytes + list_bytes + second_bytes + parts_bytes + chain_bytes;
     char *ws = (char *)workspace(1, grid_off + g_hdr + g_start + g_sorted + g_pos + g_ps + g_pm, st, nullptr, arrive_bytes);
     if (!ws) return 0;
-    EGridHdr *g_hdr_p = (EGridHdr *)(ws + grid_off);
+    CellGridHdr *g_hdr_p = (CellGridHdr *)(ws + grid_off);
     int *g_start_p = (int *)(ws + grid_off + g_hdr);
     float4 *g_sorted_p = (float4 *)(ws + grid_off + g_hdr + g_start);
     int *g_pos_p = grid ? (int *)(ws + grid_off + g_hdr + g_start + g_sorted) : nullptr;
@@ -790,7 +790,7 @@ GENPC_API int genpc_emd_forward(int b, int n, int m, const float *xyz1, const fl
         const int ppc_x10 = heavy ? 40 : 20;
         int target = (int)((long long)n * 10 / ppc_x10);
         target = target < 8 ? 8 : (target > cells_max * 3 / 4 ? cells_max * 3 / 4 : target);
-        if (!launch_emd_grid_build(b, n, xyz2, price, g_hdr_p, g_start_p, g_sorted_p, g_pos_p, g_of_p, target, cells_max, st)) return 0;
+        if (!launch_cell_grid_build(b, n, xyz2, price, g_hdr_p, g_start_p, g_sorted_p, g_pos_p, g_of_p, target, cells_max, st)) return 0;
     }
 
     // Blocks per batch element for the bid kernel: ~16 blocks per CU overall (the bid

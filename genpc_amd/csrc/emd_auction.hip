@@ -45,8 +45,6 @@ namespace genpc {
 
 constexpr int kABlock = 256;
 constexpr int kAWaves = kABlock / kWave;
-constexpr float kAU16 = 9.5367431640625e-7f;      // 16 u
-constexpr int kATwoPassRows = 25;
 constexpr unsigned kAStampBits = 14, kAWhoBits = 18;   // chain record: inc << 32 | stamp << 18 | bidder
 constexpr unsigned kAStampPeriod = (1u << kAStampBits) - 1u;
 // per-cloud control block, 16 words (one 128-byte line) per item: lines 0..7 the arrival counters of the eight workgroup
@@ -82,14 +80,6 @@ __device__ __forceinline__ void merge_top2_64(float &b, float &bb, long long &bi
 
 struct __attribute__((aligned(16))) F3A { float x, y, z; };      // the coordinates of a sorted entry as one 12-byte load
 
-__device__ __forceinline__ int acell1(float p, float lo, float inv, int g)
-{
-    const float t = __fmul_rn(__fsub_rn(p, lo), inv);
-    int c = (int)floorf(t);
-    c = c < 0 ? 0 : c;
-    return c > g - 1 ? g - 1 : c;
-}
-
 struct EmdAuction {
     int n, nb, cells_max, iters;
     int K;                                  // lanes that own a point (a power of two <= 64): the cloud has n K / 256 workgroups
@@ -99,7 +89,7 @@ struct EmdAuction {
     float *price, *price_s;                 // object order (the ABI's array) | sorted order
     const float4 *sorted;                   // (x, y, z, object index)
     const int *start, *pos_of;
-    const EGridHdr *hdr;
+    const CellGridHdr *hdr;
     int *assignment, *assignment_inv, *bid, *max_idx;
     float *bid_increments, *max_increments, *dist;
     unsigned long long *chain_head, *chain_next;
@@ -180,10 +170,9 @@ __global__ __launch_bounds__(kABlock, 4) void emd_auction_kernel(EmdAuction a)
     const int *__restrict__ PO = a.pos_of + base;
     unsigned long long *bar = a.ctrl + (size_t)batch * kCtrlWords;
     int *ucnt = (int *)(bar + 17 * 16);
-    const EGridHdr H = a.hdr[batch];
+    const CellGridHdr H = a.hdr[batch];
     const int gx = H.g[0], gy = H.g[1], gz = H.g[2];
     const float h = H.h, inf = __builtin_inff();
-    const float kShrink = 0.99999905f;      // 1 - 2^-20
     const int block_cnt = n / 256;
     // per point, in LDS (slot of the owner lane): [1], [2] the sorted positions of the objects ranked first and second at its
     // last bid (the seeds of its next one), and what Settle needs of this round's bid
@@ -250,12 +239,7 @@ __global__ __launch_bounds__(kABlock, 4) void emd_auction_kernel(EmdAuction a)
                     seeded = true;
                 }
                 float cb = filter_cb(fmaxf(better, seed));
-                const float sx = H.slack[0] + kAU16 * fabsf(x1), sy = H.slack[1] + kAU16 * fabsf(y1), sz = H.slack[2] + kAU16 * fabsf(z1);
-                auto gap1 = [&](int c, int g, float lo, float q, float s) {
-                    const float wl = c > 0 ? __fadd_rn(lo, __fmul_rn((float)c, h)) : -inf;
-                    const float wh = c + 1 < g ? __fadd_rn(lo, __fmul_rn((float)(c + 1), h)) : inf;
-                    return fmaxf(0.0f, fmaxf((wl - s) - q, (q - s) - wh));
-                };
+                const float sx = grid_slack(H.slack[0], x1), sy = grid_slack(H.slack[1], y1), sz = grid_slack(H.slack[2], z1);
                 int *pre = s_pre[wave] + grp * (LPB + 1), *pp0 = s_p0[wave] + grp * (LPB + 1);
                 int *que = s_que[wave] + grp * (8 * LPB);
                 float *qpr = s_qpr[wave] + grp * (8 * LPB);
@@ -378,16 +362,16 @@ __global__ __launch_bounds__(kABlock, 4) void emd_auction_kernel(EmdAuction a)
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
                 };
-                const int cqx = acell1(x1, H.lo[0], H.inv, gx), cqy = acell1(y1, H.lo[1], H.inv, gy), cqz = acell1(z1, H.lo[2], H.inv, gz);
+                const int cqx = grid_cell1(x1, H.lo[0], H.inv, gx), cqy = grid_cell1(y1, H.lo[1], H.inv, gy), cqz = grid_cell1(z1, H.lo[2], H.inv, gz);
                 const bool cull = !H.bad && (fabsf(x1) + fabsf(y1)) + fabsf(z1) < inf;
                 int bx0 = 0, bx1 = gx - 1, by0 = 0, by1 = gy - 1, bz0 = 0, bz1 = gz - 1;
                 auto set_box = [&](float R) {
-                    bx0 = acell1((x1 - R) - sx, H.lo[0], H.inv, gx); bx1 = acell1((x1 + R) + sx, H.lo[0], H.inv, gx);
-                    by0 = acell1((y1 - R) - sy, H.lo[1], H.inv, gy); by1 = acell1((y1 + R) + sy, H.lo[1], H.inv, gy);
-                    bz0 = acell1((z1 - R) - sz, H.lo[2], H.inv, gz); bz1 = acell1((z1 + R) + sz, H.lo[2], H.inv, gz);
+                    bx0 = grid_cell1((x1 - R) - sx, H.lo[0], H.inv, gx); bx1 = grid_cell1((x1 + R) + sx, H.lo[0], H.inv, gx);
+                    by0 = grid_cell1((y1 - R) - sy, H.lo[1], H.inv, gy); by1 = grid_cell1((y1 + R) + sy, H.lo[1], H.inv, gy);
+                    bz0 = grid_cell1((z1 - R) - sz, H.lo[2], H.inv, gz); bz1 = grid_cell1((z1 + R) + sz, H.lo[2], H.inv, gz);
                 };
                 if (cull) set_box(cb);
-                if (cull && (!seeded || (by1 - by0 + 1) * (bz1 - bz0 + 1) > kATwoPassRows)) {
+                if (cull && (!seeded || (by1 - by0 + 1) * (bz1 - bz0 + 1) > kTwoPassRows)) {
                     mode = 2;
                     const int ex0 = max(0, cqx - 1), ex1 = min(gx - 1, cqx + 1);
                     for (int r0 = 0; r0 < 9; r0 += LPB) {
@@ -427,14 +411,14 @@ __global__ __launch_bounds__(kABlock, 4) void emd_auction_kernel(EmdAuction a)
                             int cx0 = bx0, cx1 = bx1;
                             bool keep = true;
                             if (cull) {
-                                const float gyv = gap1(cy, gy, H.lo[1], y1, sy), gzv = gap1(cz, gz, H.lo[2], z1, sz);
-                                const float lb = __fmaf_rn(gyv, gyv, __fmul_rn(gzv, gzv)) * kShrink;
+                                const float gyv = grid_gap(cy, 1, gy, H.lo[1], h, y1, sy), gzv = grid_gap(cz, 1, gz, H.lo[2], h, z1, sz);
+                                const float lb = __fmaf_rn(gyv, gyv, __fmul_rn(gzv, gzv)) * kGridShrink;
                                 const float c2 = __fmul_rn(cb, cb);
                                 keep = lb < c2;
                                 if (keep) {
                                     const float W = sqrtf(fmaxf(0.0f, __fmul_rn(c2, 1.000001f) - lb)) * 1.000001f;
-                                    cx0 = max(bx0, acell1((x1 - W) - sx, H.lo[0], H.inv, gx));
-                                    cx1 = min(bx1, acell1((x1 + W) + sx, H.lo[0], H.inv, gx));
+                                    cx0 = max(bx0, grid_cell1((x1 - W) - sx, H.lo[0], H.inv, gx));
+                                    cx1 = min(bx1, grid_cell1((x1 + W) + sx, H.lo[0], H.inv, gx));
                                 }
                             }
                             if (keep && cx0 <= cx1) {
@@ -686,7 +670,7 @@ size_t emd_auction_bytes(int b, int n)
 {
     auto al = [](size_t v) { return (v + 255) / 256 * 256; };
     const size_t total = (size_t)b * n;
-    return 256 /* status */ + al((size_t)b * kCtrlWords * 8) + al((size_t)b * sizeof(EGridHdr)) + al((size_t)b * (kEGMaxCells + 1) * sizeof(int)) +
+    return 256 /* status */ + al((size_t)b * kCtrlWords * 8) + al((size_t)b * sizeof(CellGridHdr)) + al((size_t)b * (kCellGridMaxCells + 1) * sizeof(int)) +
            al(total * sizeof(float4)) + al(total * sizeof(float)) + 2 * al(total * sizeof(int)) + 2 * al(total * 8) + 2 * al(total * sizeof(int));
 }
 
@@ -736,8 +720,8 @@ int launch_emd_auction(int b, int n, const float *xyz1, const float *xyz2, float
     int *status = (int *)ws;
     char *p = ws + 256;
     unsigned long long *ctrl = (unsigned long long *)p; p += al((size_t)b * kCtrlWords * 8);
-    EGridHdr *hdr = (EGridHdr *)p; p += al((size_t)b * sizeof(EGridHdr));
-    int *start = (int *)p; p += al((size_t)b * (kEGMaxCells + 1) * sizeof(int));
+    CellGridHdr *hdr = (CellGridHdr *)p; p += al((size_t)b * sizeof(CellGridHdr));
+    int *start = (int *)p; p += al((size_t)b * (kCellGridMaxCells + 1) * sizeof(int));
     float4 *sorted = (float4 *)p; p += al(total * sizeof(float4));
     float *price_s = (float *)p; p += al(total * sizeof(float));
     int *pos_of = (int *)p; p += al(total * sizeof(int));
@@ -755,13 +739,13 @@ int launch_emd_auction(int b, int n, const float *xyz1, const float *xyz2, float
     //  1.70 ms, 40 -> 0.95 / 1.68, 60 -> 0.89 / 1.67, 80 -> 0.89 / 1.69, 120 -> 0.93 / 1.74: a bidder's ball is a handful of
     //  longer runs instead of dozens of short ones, each a dependent read of the cell table; the launch-per-round path keeps its own)
     int target = (int)((long long)n * 10 / 60);
-    target = target < 8 ? 8 : (target > kEGMaxCells * 3 / 4 ? kEGMaxCells * 3 / 4 : target);
-    if (!launch_emd_grid_build(b, n, xyz2, price, hdr, start, sorted, pos_of, orig_of, target, kEGMaxCells, st, price_s)) {
+    target = target < 8 ? 8 : (target > kCellGridMaxCells * 3 / 4 ? kCellGridMaxCells * 3 / 4 : target);
+    if (!launch_cell_grid_build(b, n, xyz2, price, hdr, start, sorted, pos_of, orig_of, target, kCellGridMaxCells, st, price_s)) {
         persist_cancel(wgs, st);
         return 0;
     }
     EmdAuction a{};
-    a.n = n; a.nb = b; a.cells_max = kEGMaxCells; a.iters = iters; a.eps = eps; a.K = K;
+    a.n = n; a.nb = b; a.cells_max = kCellGridMaxCells; a.iters = iters; a.eps = eps; a.K = K;
     a.feedback = emd_feedback_slot(b, n, true);
     a.xyz1 = xyz1; a.xyz2 = xyz2; a.price = price; a.price_s = price_s; a.sorted = sorted; a.start = start; a.pos_of = pos_of; a.hdr = hdr;
     a.assignment = assignment; a.assignment_inv = assignment_inv; a.bid = bid; a.max_idx = max_idx;

@@ -6,10 +6,10 @@
 // 0 and every increment is best - better + eps >= eps >= 0).  An object can change a bidder's (best, better) only if
 // its value 3 - |x2 - x1| - price exceeds m = max(better so far, seed), hence only if its squared distance is below
 // fl(cb^2), cb = filter_cb(m) -- the pre-filter's own threshold at price 0 (emd.h).  So the objects are sorted ONCE
-// per call into a uniform grid (emd_grid_build_kernel: one block per cloud, counting sort in LDS, cells numbered
+// per call into a uniform grid (grid.h: cell_grid_build_kernel, counting sort in LDS, cells numbered
 // x-fastest so that the cells [cx0, cx1] of a (cy, cz) ROW are one contiguous run of the sorted array), and a bidder
 // visits only the rows of the box |p - x1| <= cb around itself whose (y, z) gap is below cb -- with the bound of
-// nn_grid.hip, every rounding accounted for: a skipped row provably holds nothing that could matter, what is visited
+// grid.h, every rounding accounted for: a skipped row provably holds nothing that could matter, what is visited
 // goes through the SAME per-object pre-filter and the SAME exact fp64 value as before, every object at most once.
 // The top-2 VALUES (duplicates count) and the index of a unique best are therefore the reference's; an exact tie for
 // first place takes the thread-major re-scan of the tiled kernel unchanged.  Bit-identical assignments and prices
@@ -30,206 +30,9 @@
 
 namespace genpc {
 
-constexpr int kEGBlock = 1024;          // build kernel: one block per cloud
-constexpr int kEGWaves = kEGBlock / kWave;
-constexpr float kEGU16 = 9.5367431640625e-7f;      // 16 u
-constexpr int kTwoPassRows = 25;        // boxes of more (y, z) rows than this take the near cells first (emd_bid_grid_kernel)
-
-__device__ __forceinline__ int egrid_cell1(float p, float lo, float inv, int g)
-{
-    const float t = __fmul_rn(__fsub_rn(p, lo), inv);
-    int c = (int)floorf(t);          // NaN -> 0 (v_cvt_i32_f32); a cloud with non-finite coordinates is searched without culling
-    c = c < 0 ? 0 : c;
-    return c > g - 1 ? g - 1 : c;
-}
-
-// One block per batch element: exact bounding box of the objects, a grid of about cells_target cubic cells over
-// the axes wider than a cell, counting sort in LDS.  Outputs: hdr[batch], start[batch][cells + 1] (first sorted
-// position of every cell, cells numbered (cz gy + cy) gx + cx), sorted[batch][n] = (x, y, z, price),
-// orig_of[batch][position] = object index, pos_of[batch][object] = position.  The order inside a cell is whatever the LDS atomics give: it does not reach any result.
-__global__ __launch_bounds__(kEGBlock) void emd_grid_build_kernel(int n, const float *__restrict__ xyz2, const float *__restrict__ price,
-                                                                  EGridHdr *__restrict__ hdr, int *__restrict__ start,
-                                                                  float4 *__restrict__ sorted, int *__restrict__ pos_of,
-                                                                  int *__restrict__ orig_of, int cells_target, int cells_max, int K,
-                                                                  float *__restrict__ price_sep)
-{
-    // K blocks per cloud (a single cloud on one CU took 48 us of a 1 ms call): block k sorts the cells [c0, c1) of the
-    // cell index space -- a contiguous piece of the sorted output.  Every block reads ALL points of the cloud (box, cell of
-    // each point: arithmetic only), but only the points of its own cells go through the LDS histogram, the scan and the
-    // scatter; the piece's first output position is the number of points in lower cells, which the block counts while it
-    // classifies: no communication between the blocks (the scheme of nn_grid.hip's grid_build_kernel).
-    extern __shared__ int s_cnt[];            // cells_max counters, then 2 kEGWaves ints, then 6 kEGWaves floats
-    int *s_w = s_cnt + cells_max;
-    float *s_red = (float *)(s_w + 2 * kEGWaves);
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-    const int batch = blockIdx.x / K, kb = blockIdx.x % K;
-    const float *__restrict__ P = xyz2 + (size_t)batch * n * 3;
-    float mn[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
-    float mx[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-    int bad = 0;
-    // price == null: a plain spatial index (nn_seeded.hip): the entries' .w is the point's index
-    const float *__restrict__ PR0 = price ? price + (size_t)batch * n : nullptr;
-    for (int j = threadIdx.x; j < n; j += kEGBlock) {
-        if (PR0) bad |= !(PR0[j] >= 0.0f && PR0[j] < __builtin_inff());      // the culling needs prices >= 0 (the caller's initial state: zeros)
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const float w = P[(size_t)j * 3 + k];
-            if (fabsf(w) < __builtin_inff()) {
-                mn[k] = fminf(mn[k], w);
-                mx[k] = fmaxf(mx[k], w);
-            } else {
-                bad = 1;
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            mn[k] = fminf(mn[k], __shfl_xor(mn[k], o));
-            mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], o));
-        }
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) { s_red[wave * 6 + k] = mn[k]; s_red[wave * 6 + 3 + k] = mx[k]; }
-    }
-    bad = __syncthreads_or(bad);
-    for (int w = 0; w < kEGWaves; w++) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            mn[k] = fminf(mn[k], s_red[w * 6 + k]);
-            mx[k] = fmaxf(mx[k], s_red[w * 6 + 3 + k]);
-        }
-    }
-    // cubic cells of side h, about cells_target of them over the axes wider than h (as nn_grid.hip's grid_setup)
-    float ext[3];
-    bool act[3];
-    int nact = 0;
-    float emax = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        if (!(mn[k] <= mx[k])) { mn[k] = 0.0f; mx[k] = 0.0f; }
-        ext[k] = mx[k] - mn[k];
-        if (!(ext[k] < __builtin_inff())) ext[k] = 0.0f;
-        act[k] = ext[k] > 0.0f;
-        nact += act[k] ? 1 : 0;
-        emax = fmaxf(emax, ext[k]);
-    }
-    float h = 0.0f;
-    for (int it = 0; it < 3 && nact > 0; it++) {
-        float vol = 1.0f;
-        for (int k = 0; k < 3; k++) if (act[k]) vol *= ext[k] / emax;
-        const float r = vol / (float)cells_target;
-        h = emax * (nact == 3 ? cbrtf(r) : (nact == 2 ? sqrtf(r) : r));
-        bool dropped = false;
-        for (int k = 0; k < 3; k++) {
-            if (act[k] && !(ext[k] > h)) { act[k] = false; nact--; dropped = true; }
-        }
-        if (!dropped) break;
-    }
-    if (!(h > 0.0f) || !(h < __builtin_inff()) || nact == 0) {
-        h = 1.0f;
-        for (int k = 0; k < 3; k++) act[k] = false;
-    }
-    int g[3];
-    for (int rep = 0; rep < 16; rep++) {
-        long long cells = 1;
-        for (int k = 0; k < 3; k++) {
-            float q = act[k] ? ceilf(ext[k] / h) : 1.0f;
-            if (!(q >= 1.0f)) q = 1.0f;
-            if (q > 1024.0f) q = 1024.0f;
-            g[k] = (int)q;
-            cells *= g[k];
-        }
-        if (cells <= cells_max) break;
-        h *= 1.26f;
-        if (rep == 15) { act[0] = act[1] = act[2] = false; }
-    }
-    float inv = 1.0f / h;
-    if (!(inv > 0.0f) || !(inv < __builtin_inff())) {
-        inv = 1.0f; h = 1.0f;
-        for (int k = 0; k < 3; k++) g[k] = 1;
-    }
-    EGridHdr H;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        if (!act[k]) g[k] = 1;
-        H.lo[k] = mn[k];
-        H.g[k] = g[k];
-        H.slack[k] = kEGU16 * (fabsf(mn[k]) + (float)(g[k] + 1) * h);
-    }
-    H.inv = inv;
-    H.h = h;
-    H.cells = g[0] * g[1] * g[2];
-    H.bad = bad;
-    if (threadIdx.x == 0 && kb == 0) hdr[batch] = H;
-    const int cells = H.cells;
-    const int c0 = (int)(((long long)kb * cells) / K), c1 = (int)(((long long)(kb + 1) * cells) / K), width = c1 - c0;
-    for (int i = threadIdx.x; i < width; i += kEGBlock) s_cnt[i] = 0;
-    __syncthreads();
-    auto cell_of = [&](int j) {
-        const int cx = egrid_cell1(P[(size_t)j * 3 + 0], H.lo[0], inv, g[0]), cy = egrid_cell1(P[(size_t)j * 3 + 1], H.lo[1], inv, g[1]);
-        const int cz = egrid_cell1(P[(size_t)j * 3 + 2], H.lo[2], inv, g[2]);
-        return (cz * g[1] + cy) * g[0] + cx;
-    };
-    int below = 0;
-    for (int j = threadIdx.x; j < n; j += kEGBlock) {
-        const int c = cell_of(j);
-        below += c < c0 ? 1 : 0;
-        if (c >= c0 && c < c1) atomicAdd(&s_cnt[c - c0], 1);
-    }
-    __syncthreads();
-    // exclusive scan: thread t owns the segment [t per, (t + 1) per); per is odd (LDS banks)
-    const int per = ((width + kEGBlock - 1) / kEGBlock) | 1;
-    int sum = 0;
-    for (int i = 0; i < per; i++) {
-        const int q = threadIdx.x * per + i;
-        if (q < width) { const int w = s_cnt[q]; s_cnt[q] = sum; sum += w; }
-    }
-    int inc = sum;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const int t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) below += __shfl_xor(below, o);
-    if (lane == kWave - 1) s_w[wave] = inc;
-    if (lane == 0) s_w[kEGWaves + wave] = below;
-    __syncthreads();
-    int base = inc - sum;
-    for (int w = 0; w < kEGWaves; w++) {
-        base += w < wave ? s_w[w] : 0;
-        base += s_w[kEGWaves + w];
-    }
-    for (int i = 0; i < per; i++) {
-        const int q = threadIdx.x * per + i;
-        if (q < width) s_cnt[q] += base;
-    }
-    __syncthreads();
-    int *st = start + (size_t)batch * (cells_max + 1);
-    for (int i = threadIdx.x; i < width; i += kEGBlock) st[c0 + i] = s_cnt[i];
-    if (threadIdx.x == 0 && kb == K - 1) st[cells] = n;
-    __syncthreads();
-    float4 *out = sorted + (size_t)batch * n;
-    int *po = pos_of ? pos_of + (size_t)batch * n : nullptr;
-    int *ps = orig_of ? orig_of + (size_t)batch * n : nullptr;
-    for (int j = threadIdx.x; j < n; j += kEGBlock) {
-        const int c = cell_of(j);
-        if (c < c0 || c >= c1) continue;
-        const int pos = atomicAdd(&s_cnt[c - c0], 1);
-        // price_sep != null (emd_auction.hip): the entry carries the object's index, the prices of the sorted order are an array of their own
-        out[pos] = make_float4(P[(size_t)j * 3 + 0], P[(size_t)j * 3 + 1], P[(size_t)j * 3 + 2], (PR0 && !price_sep) ? PR0[j] : __int_as_float(j));
-        if (price_sep) price_sep[(size_t)batch * n + pos] = PR0 ? PR0[j] : 0.0f;
-        if (po) po[j] = pos;
-        if (ps) ps[pos] = j;
-    }
-}
-
 // pmin[batch][c] = the smallest price among the objects of cell c as the sorted copy holds them now, +inf for an empty cell.
 // Prices only rise: a table computed before any later round stays a lower bound.
-__global__ __launch_bounds__(256) void emd_cell_pmin_kernel(int cells_max, const EGridHdr *__restrict__ hdr, const int *__restrict__ start,
+__global__ __launch_bounds__(256) void emd_cell_pmin_kernel(int cells_max, const CellGridHdr *__restrict__ hdr, const int *__restrict__ start,
                                                             const float4 *__restrict__ sorted, int n, float *__restrict__ pmin)
 {
     const int batch = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;
@@ -277,10 +80,9 @@ __global__ __launch_bounds__(kEBlock) __attribute__((amdgpu_waves_per_eu(4, 8)))
     const int *__restrict__ OF = a.orig_of + base;       // object index of a sorted position: read only for the rare object that passes
     const int *__restrict__ ST = a.start + (size_t)batch * (a.cells_max + 1);
     const float *__restrict__ PM = a.cell_pmin ? a.cell_pmin + (size_t)batch * (a.cells_max + 1) : nullptr;
-    const EGridHdr H = a.hdr[batch];
+    const CellGridHdr H = a.hdr[batch];
     const int gx = H.g[0], gy = H.g[1], gz = H.g[2];
     const float h = H.h, inf = __builtin_inff();
-    const float kShrink = 0.99999905f;      // 1 - 2^-20
     // reference partition, needed only to order exactly tied candidates
     const int block_cnt = n / 256;
     const int unass_per_block = (U + block_cnt - 1) / block_cnt;
@@ -311,13 +113,7 @@ __global__ __launch_bounds__(kEBlock) __attribute__((amdgpu_waves_per_eu(4, 8)))
             }
         }
         float cb = filter_cb(fmaxf(better, seed));
-        const float sx = H.slack[0] + kEGU16 * fabsf(x1), sy = H.slack[1] + kEGU16 * fabsf(y1), sz = H.slack[2] + kEGU16 * fabsf(z1);
-        // lower bound of |p_a - q_a| over the points p of cell c of an axis (border cells unbounded outwards)
-        auto gap1 = [&](int c, int g, float lo, float q, float s) {
-            const float wl = c > 0 ? __fadd_rn(lo, __fmul_rn((float)c, h)) : -inf;
-            const float wh = c + 1 < g ? __fadd_rn(lo, __fmul_rn((float)(c + 1), h)) : inf;
-            return fmaxf(0.0f, fmaxf((wl - s) - q, (q - s) - wh));
-        };
+        const float sx = grid_slack(H.slack[0], x1), sy = grid_slack(H.slack[1], y1), sz = grid_slack(H.slack[2], z1);
         // One batch of runs of the sorted array, one per lane ([pA, pA + lA), possibly empty), spread
         // EVENLY over the group's lanes: exclusive scan of the lengths, then lane `sub` takes the items sub, sub + LPB, ...
         // of the concatenation (a run of a dense row is hundreds of objects: a lane per row left 63 lanes waiting for one --
@@ -446,14 +242,14 @@ __global__ __launch_bounds__(kEBlock) __attribute__((amdgpu_waves_per_eu(4, 8)))
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();       // the lists are rewritten by the next batch
         };
-        const int cqx = egrid_cell1(x1, H.lo[0], H.inv, gx), cqy = egrid_cell1(y1, H.lo[1], H.inv, gy), cqz = egrid_cell1(z1, H.lo[2], H.inv, gz);
+        const int cqx = grid_cell1(x1, H.lo[0], H.inv, gx), cqy = grid_cell1(y1, H.lo[1], H.inv, gy), cqz = grid_cell1(z1, H.lo[2], H.inv, gz);
         const bool cull = !H.bad && (fabsf(x1) + fabsf(y1)) + fabsf(z1) < inf;
         // the box |p - x1| <= cb (cell function monotone: a point within cb of x1 on an axis lies in [cell(x1 - cb), cell(x1 + cb)])
         int bx0 = 0, bx1 = gx - 1, by0 = 0, by1 = gy - 1, bz0 = 0, bz1 = gz - 1;
         auto set_box = [&](float R) {
-            bx0 = egrid_cell1((x1 - R) - sx, H.lo[0], H.inv, gx); bx1 = egrid_cell1((x1 + R) + sx, H.lo[0], H.inv, gx);
-            by0 = egrid_cell1((y1 - R) - sy, H.lo[1], H.inv, gy); by1 = egrid_cell1((y1 + R) + sy, H.lo[1], H.inv, gy);
-            bz0 = egrid_cell1((z1 - R) - sz, H.lo[2], H.inv, gz); bz1 = egrid_cell1((z1 + R) + sz, H.lo[2], H.inv, gz);
+            bx0 = grid_cell1((x1 - R) - sx, H.lo[0], H.inv, gx); bx1 = grid_cell1((x1 + R) + sx, H.lo[0], H.inv, gx);
+            by0 = grid_cell1((y1 - R) - sy, H.lo[1], H.inv, gy); by1 = grid_cell1((y1 + R) + sy, H.lo[1], H.inv, gy);
+            bz0 = grid_cell1((z1 - R) - sz, H.lo[2], H.inv, gz); bz1 = grid_cell1((z1 + R) + sz, H.lo[2], H.inv, gz);
         };
         if (cull) set_box(cb);
         // A point without a seed (its first bid) or with a stale one (the prices of the two objects it knew have risen since
@@ -511,15 +307,15 @@ __global__ __launch_bounds__(kEBlock) __attribute__((amdgpu_waves_per_eu(4, 8)))
                 float lb0 = 0.0f;
                 if (cull) {
                     // the row's (y, z) gap against the threshold; what is left of it bounds |dx|: the box becomes a ball
-                    const float gyv = gap1(cy, gy, H.lo[1], y1, sy), gzv = gap1(cz, gz, H.lo[2], z1, sz);
+                    const float gyv = grid_gap(cy, 1, gy, H.lo[1], h, y1, sy), gzv = grid_gap(cz, 1, gz, H.lo[2], h, z1, sz);
                     lb0 = __fmaf_rn(gyv, gyv, __fmul_rn(gzv, gzv));
-                    const float lb = lb0 * kShrink;
+                    const float lb = lb0 * kGridShrink;
                     const float c2 = __fmul_rn(cb, cb);
                     keep = lb < c2;                          // else nothing in this row can matter (prices >= 0)
                     if (keep) {
                         const float W = sqrtf(fmaxf(0.0f, __fmul_rn(c2, 1.000001f) - lb)) * 1.000001f;
-                        cx0 = max(bx0, egrid_cell1((x1 - W) - sx, H.lo[0], H.inv, gx));
-                        cx1 = min(bx1, egrid_cell1((x1 + W) + sx, H.lo[0], H.inv, gx));
+                        cx0 = max(bx0, grid_cell1((x1 - W) - sx, H.lo[0], H.inv, gx));
+                        cx1 = min(bx1, grid_cell1((x1 + W) + sx, H.lo[0], H.inv, gx));
                     }
                 }
                 if (keep && cx0 <= cx1) {
@@ -539,8 +335,8 @@ __global__ __launch_bounds__(kEBlock) __attribute__((amdgpu_waves_per_eu(4, 8)))
 #pragma unroll
                             for (int k = 0; k < 4; k++) {
                                 if (!(pm[k] < inf)) continue;              // empty (or past the range)
-                                const float gxv = gap1(cx0 + i0 + k, gx, H.lo[0], x1, sx);
-                                const float lbc = __fmaf_rn(gxv, gxv, lb0) * kShrink;
+                                const float gxv = grid_gap(cx0 + i0 + k, 1, gx, H.lo[0], h, x1, sx);
+                                const float lbc = __fmaf_rn(gxv, gxv, lb0) * kGridShrink;
                                 const float tt = cb - pm[k];
                                 const bool kc = tt > 0.0f && lbc < tt * tt;
                                 km |= kc ? 1ull << (i0 + k) : 0ull;
@@ -639,18 +435,7 @@ __global__ __launch_bounds__(kEBlock) __attribute__((amdgpu_waves_per_eu(4, 8)))
     }
 }
 
-int launch_emd_grid_build(int b, int n, const float *xyz2, const float *price, EGridHdr *hdr, int *start, float4 *sorted, int *pos_of,
-                          int *orig_of, int cells_target, int cells_max, hipStream_t st, float *price_sep)
-{
-    const size_t lds = ((size_t)cells_max + 2 * kEGWaves) * sizeof(int) + 6 * kEGWaves * sizeof(float);
-    // pieces per cloud: enough blocks to spread a few clouds over the chip, one when there are many clouds anyway
-    const int K = b >= 32 ? 1 : (b >= 8 ? 2 : (n >= 8192 ? 8 : 4));
-    hipLaunchKernelGGL(emd_grid_build_kernel, dim3(b * K), dim3(kEGBlock), lds, st, n, xyz2, price, hdr, start, sorted, pos_of, orig_of,
-                       cells_target, cells_max, K, price_sep);
-    return check(hipGetLastError(), "emd_grid_build_kernel launch") ? 1 : 0;
-}
-
-int launch_emd_cell_pmin(int b, int cells_max, const EGridHdr *hdr, const int *start, const float4 *sorted, int n, float *pmin, hipStream_t st)
+int launch_emd_cell_pmin(int b, int cells_max, const CellGridHdr *hdr, const int *start, const float4 *sorted, int n, float *pmin, hipStream_t st)
 {
     hipLaunchKernelGGL(emd_cell_pmin_kernel, dim3(ceil_div(cells_max + 1, 256), b), dim3(256), 0, st, cells_max, hdr, start, sorted, n, pmin);
     return check(hipGetLastError(), "emd_cell_pmin_kernel launch") ? 1 : 0;

@@ -1,0 +1,195 @@
+// grid.h -- the uniform grid under every pruned search of the library (nn_grid.hip, emd_grid.hip, emd_auction.hip,
+// nn_seeded.hip): the frame of a grid, the cell function, the sizing, the pieces of the LDS counting sort that the build
+// kernels share, and the bound by which a cell or a row of cells is skipped.
+//
+// Bound.  cell(p) = clamp(floor(fl(fl(p - lo) * inv)), 0, G - 1) is monotone in p, and a point of
+// cell c satisfies  lo + c h (1 - 3u) <= p < lo + (c + 1) h (1 + 3u)  (u = 2^-24, h = 1 / inv;
+// border cells unbounded outwards).  With walls evaluated in fp32 and a slack of
+// 16u (|lo| + G h + |q|) per axis, gap_a = max(0, wall_lo - s - q, q - wall_hi - s) <= |p_a - q_a|
+// for every point p of the cell; the reference's distance is >= (sum gap_a^2)(1 - 6u); a cell is
+// skipped iff  (sum gap_a^2)(1 - 2^-20) > best  (strictly: ties with lower indices are still
+// found).  Underflow only weakens the bound; an overflowing bound equals +inf and is only used
+// against a finite best.  The helpers below ARE that arithmetic: a search that changes an intrinsic, an operand order or
+// an association in its own copy has left the proof behind, which is why there are no copies.
+#pragma once
+#include "common.h"
+
+namespace genpc {
+
+constexpr float kGridU16 = 9.5367431640625e-7f;      // 16 u
+constexpr float kGridShrink = 0.99999905f;           // 1 - 2^-20
+
+struct GridFrame {          // what the helpers need of a grid; the headers of the two cell numberings start with it
+    float lo[3];
+    float inv;              // cells per unit length (cubic cells of side h)
+    float h;
+    float slack[3];         // 16u (|lo| + (g + 1) h) per axis; grid_slack adds the query's 16u |q|
+    int g[3];               // cells per axis
+};
+
+__device__ __forceinline__ int grid_cell1(float p, float lo, float inv, int g)
+{
+    const float t = __fmul_rn(__fsub_rn(p, lo), inv);
+    int c = (int)floorf(t);          // NaN -> 0 on gfx950 (v_cvt_i32_f32); clouds with non-finite coordinates are searched without culling
+    c = c < 0 ? 0 : c;
+    return c > g - 1 ? g - 1 : c;
+}
+
+__device__ __forceinline__ float grid_slack(float slack, float q) { return slack + kGridU16 * fabsf(q); }
+
+// lower bound of |p_a - q_a| over the points p of cells [c, c + w) of an axis (g cells of side h from lo; border cells
+// unbounded outwards); s = grid_slack of q on that axis
+__device__ __forceinline__ float grid_gap(int c, int w, int g, float lo, float h, float q, float s)
+{
+    const float inf = __builtin_inff();
+    const float wl = c > 0 ? __fadd_rn(lo, __fmul_rn((float)c, h)) : -inf;
+    const float wh = c + w < g ? __fadd_rn(lo, __fmul_rn((float)(c + w), h)) : inf;
+    return fmaxf(0.0f, fmaxf((wl - s) - q, (q - s) - wh));
+}
+
+// Block-wide box: every thread brings the (mn, mx) of its own points and leaves with the block's.  s_red: 6 floats per wave.
+template <int BLOCK>
+__device__ __forceinline__ void grid_block_box(float mn[3], float mx[3], float *s_red)
+{
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) {
+            mn[k] = fminf(mn[k], __shfl_xor(mn[k], o));
+            mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], o));
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) { s_red[wave * 6 + k] = mn[k]; s_red[wave * 6 + 3 + k] = mx[k]; }
+    }
+    __syncthreads();
+    for (int w = 0; w < BLOCK / kWave; w++) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            mn[k] = fminf(mn[k], s_red[w * 6 + k]);
+            mx[k] = fmaxf(mx[k], s_red[w * 6 + 3 + k]);
+        }
+    }
+}
+
+// Box (mn, mx) -> cubic cells of side h, about cells_target of them over the axes that are wider than h, at most
+// cells_max as the numbering counts them: COARSE (nn_grid.hip: 4 x 4 x 4 blocks, partial ones padded) 64 x the product of
+// (g + 3) / 4, else the product of g.  h grows by 1.26 (a doubling of the cell volume) up to REPS times to get there;
+// a box that still does not fit becomes one cell.  An axis without a finite coordinate gets lo = 0.
+template <int REPS, bool COARSE>
+__device__ __forceinline__ void grid_size(float mn[3], float mx[3], int cells_target, int cells_max, GridFrame &F)
+{
+    float ext[3];
+    bool act[3];
+    int nact = 0;
+    float emax = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        if (!(mn[k] <= mx[k])) { mn[k] = 0.0f; mx[k] = 0.0f; }      // no finite coordinate on this axis
+        ext[k] = mx[k] - mn[k];
+        if (!(ext[k] < __builtin_inff())) ext[k] = 0.0f;             // overflowing extent: one cell on this axis
+        act[k] = ext[k] > 0.0f;
+        nact += act[k] ? 1 : 0;
+        emax = fmaxf(emax, ext[k]);
+    }
+    // (extents relative to the largest one: no overflow for clouds 1e-18 or 1e+18 across)
+    float h = 0.0f;
+    for (int it = 0; it < 3 && nact > 0; it++) {
+        float vol = 1.0f;
+        for (int k = 0; k < 3; k++) if (act[k]) vol *= ext[k] / emax;
+        const float r = vol / (float)cells_target;
+        h = emax * (nact == 3 ? cbrtf(r) : (nact == 2 ? sqrtf(r) : r));
+        bool dropped = false;
+        for (int k = 0; k < 3; k++) {
+            if (act[k] && !(ext[k] > h)) { act[k] = false; nact--; dropped = true; }
+        }
+        if (!dropped) break;
+    }
+    if (!(h > 0.0f) || !(h < __builtin_inff()) || nact == 0) {
+        h = 1.0f;
+        for (int k = 0; k < 3; k++) act[k] = false;
+    }
+    int g[3];
+    for (int rep = 0; rep < REPS; rep++) {
+        long long cells = COARSE ? 64 : 1;
+        for (int k = 0; k < 3; k++) {
+            float q = act[k] ? ceilf(ext[k] / h) : 1.0f;
+            if (!(q >= 1.0f)) q = 1.0f;
+            if (q > 1024.0f) q = 1024.0f;
+            g[k] = (int)q;
+            cells *= COARSE ? (g[k] + 3) >> 2 : g[k];
+        }
+        if (cells <= cells_max) break;
+        h *= 1.26f;
+        if (rep == REPS - 1) { act[0] = act[1] = act[2] = false; }
+    }
+    float inv = 1.0f / h;
+    if (!(inv > 0.0f) || !(inv < __builtin_inff())) {
+        inv = 1.0f; h = 1.0f;
+        for (int k = 0; k < 3; k++) g[k] = 1;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        if (!act[k]) g[k] = 1;
+        F.lo[k] = mn[k];
+        F.g[k] = g[k];
+        F.slack[k] = kGridU16 * (fabsf(mn[k]) + (float)(g[k] + 1) * h);
+    }
+    F.inv = inv;
+    F.h = h;
+}
+
+// The scan between the histogram and the scatter of a counting sort in LDS: s_cnt[0 .. width) holds counts on entry and
+// start offsets on return (a barrier passed either time); the first offset is the block's sum of `below`, each thread's
+// count of the points in front of the slab.  Thread t owns [t per, (t + 1) per); per is odd (LDS banks).  s_w: 2 ints per wave.
+template <int BLOCK>
+__device__ __forceinline__ void grid_scan_counts(int *s_cnt, int width, int below, int *s_w)
+{
+    constexpr int kWaves = BLOCK / kWave;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    const int per = ((width + BLOCK - 1) / BLOCK) | 1;
+    int sum = 0;
+    for (int i = 0; i < per; i++) {
+        const int q = threadIdx.x * per + i;
+        if (q < width) { const int w = s_cnt[q]; s_cnt[q] = sum; sum += w; }
+    }
+    int inc = sum;
+#pragma unroll
+    for (int o = 1; o < kWave; o <<= 1) {
+        const int t = __shfl_up(inc, o);
+        if (lane >= o) inc += t;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) below += __shfl_xor(below, o);
+    if (lane == kWave - 1) s_w[wave] = inc;
+    if (lane == 0) s_w[kWaves + wave] = below;
+    __syncthreads();
+    int base = inc - sum;
+    for (int w = 0; w < kWaves; w++) {
+        base += w < wave ? s_w[w] : 0;
+        base += s_w[kWaves + w];
+    }
+    for (int i = 0; i < per; i++) {
+        const int q = threadIdx.x * per + i;
+        if (q < width) s_cnt[q] += base;
+    }
+    __syncthreads();
+}
+
+// ---- the x-fastest grid (grid.hip; emd_grid.hip, emd_auction.hip, nn_seeded.hip): cells numbered (cz g[1] + cy) g[0] + cx,
+// so the cells [cx0, cx1] of a (cy, cz) ROW are one contiguous run of the sorted cloud ----
+constexpr int kCellGridMaxCells = 15360;      // LDS counters of the build kernel (60 KiB)
+struct CellGridHdr : GridFrame {     // one per batch element, written by cell_grid_build_kernel
+    int cells;
+    int bad;                // a non-finite coordinate or a negative / non-finite initial price: search without culling
+};
+// One cloud per batch element: hdr[b], start[b][cells_max + 1] (first sorted position of every cell), sorted[b][n] =
+// (x, y, z, w).  price == null: w is the point's index.  price != null (the auction's objects): w is the price, or with
+// price_sep the index while price_sep[b][position] gets the price; pos_of[b][point] = position and orig_of[b][position]
+// = point when not null.
+int launch_cell_grid_build(int b, int n, const float *xyz, const float *price, CellGridHdr *hdr, int *start, float4 *sorted, int *pos_of,
+                           int *orig_of, int cells_target, int cells_max, hipStream_t st, float *price_sep = nullptr);
+
+}  // namespace genpc

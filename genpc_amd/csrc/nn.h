@@ -3,6 +3,7 @@
 // reference's distance arithmetic, candidate lists and the exact re-scan.
 #pragma once
 #include "common.h"
+#include "grid.h"
 
 namespace genpc {
 
@@ -310,5 +311,16 @@ int launch_nn_dedupe(int b, int nclouds, const float *const pts[2], const int n[
 int nn_forward(int b, int ndir, const float *q0, int n0, const float *t0, int m0, float *d0, int *i0, const float *q1,
                int n1, const float *t1, int m1, float *d1, int *i1, hipStream_t st, float radius2 = __builtin_inff(),
                const unsigned *dup0 = nullptr, const unsigned *dup1 = nullptr, int dup_shared = 0);
+
+// ---- seeded nearest neighbours of the alignment loop (nn_seeded.hip) ----
+struct SeededGrids {
+    const CellGridHdr *hdr_static, *hdr_rest;
+    const int *start_static, *start_rest;
+    const float4 *sorted_static, *sorted_rest;
+};
+size_t seeded_grids_bytes(int b, int nm, int ns);
+int build_seeded_grids(int b, int nm, const float *rest_pts, int ns, const float *static_pts, void *ws, SeededGrids &g, hipStream_t st);
+int launch_nn_seeded(int b, int nm, const float *moving_pts, int ns, const float *static_pts, const SeededGrids &g, const float *center,
+                     int cstride, const float *params, int pstride, float *d1, int *i1, float *d2, int *i2, int fma, hipStream_t st, int sample = 1);
 
 }  // namespace genpc

@@ -28,15 +28,9 @@
 //                                  minimum is the reference's (distance, lowest index), whatever
 //                                  order the atomics of launch 1 left inside a cell.
 //
-// Bound.  cell(p) = clamp(floor(fl(fl(p - lo) * inv)), 0, G - 1) is monotone in p, and a point of
-// cell c satisfies  lo + c h (1 - 3u) <= p < lo + (c + 1) h (1 + 3u)  (u = 2^-24, h = 1 / inv;
-// border cells unbounded outwards).  With walls evaluated in fp32 and a slack of
-// 16u (|lo| + G h + |q|) per axis, gap_a = max(0, wall_lo - s - q, q - wall_hi - s) <= |p_a - q_a|
-// for every point p of the cell; the reference's distance is >= (sum gap_a^2)(1 - 6u); a cell is
-// skipped iff  (sum gap_a^2)(1 - 2^-20) > best  (strictly: ties with lower indices are still
-// found).  Underflow only weakens the bound; an overflowing bound equals +inf and is only used
-// against a finite best.  Non-finite input (flags raised by launch 1) takes the per-query
-// exhaustive scan with the reference's 512-target tile semantics (see nn_exhaustive in nn.h).
+// Bound.  grid.h states it and holds the arithmetic (cell function, axis gap, slack, shrink).  Non-finite input
+// (flags raised by launch 1) takes the per-query exhaustive scan with the reference's 512-target tile semantics (see
+// nn_exhaustive in nn.h).
 //
 // Cost.  O(N) work for clouds of bounded density; a cloud crammed into one cell degenerates to
 // the brute force (one lane per query): correct, slow.  Distances to far-away targets (a partial
@@ -51,14 +45,8 @@ namespace genpc {
 constexpr int kGridMaxCells = 16000;     // LDS scan / offsets: < 64 KiB of int per block
 constexpr int kGridBlock = 1024;         // build kernel: one block per (batch element, cloud)
 constexpr int kGridWaves = kGridBlock / kWave;
-constexpr float kU16 = 9.5367431640625e-7f;      // 16 u
 
-struct GridHdr {            // one per batch element, written by launch 1
-    float lo[3];
-    float inv;              // cells per unit length (cubic cells of side h)
-    float h;
-    float slack[3];         // 16u (|lo| + (G + 1) h) per axis; the query adds 16u |q|
-    int g[3];               // fine cells per axis
+struct GridHdr : GridFrame {      // one per batch element, written by launch 1; g[] counts FINE cells
     int gc[3];              // coarse cells per axis: (g + 3) / 4
     int cells;              // gc[0] gc[1] gc[2] * 64 (fine cells incl. the padding of partial coarse cells)
     int pad;
@@ -90,14 +78,6 @@ struct GridArgs {
     unsigned long long *stats;
 };
 
-__device__ __forceinline__ int grid_cell1(float p, float lo, float inv, int g)
-{
-    const float t = __fmul_rn(__fsub_rn(p, lo), inv);
-    int c = (int)floorf(t);          // NaN -> 0 on gfx950 (v_cvt_i32_f32); such clouds take the exhaustive path anyway
-    c = c < 0 ? 0 : c;
-    return c > g - 1 ? g - 1 : c;
-}
-
 // coarse-major numbering: 4 x 4 x 4 fine cells of a coarse cell are consecutive
 __device__ __forceinline__ int grid_index(const GridHdr &H, int cx, int cy, int cz)
 {
@@ -117,7 +97,6 @@ __device__ __forceinline__ int grid_cell(const GridHdr &H, float x, float y, flo
 // cells.  Both blocks of a batch element compute the same header (min / max are order independent).
 __device__ void grid_setup(const GridArgs &a, int batch, GridHdr &H, float *s_red)
 {
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
     float v[2][3];
 #pragma unroll
     for (int c = 0; c < 2; c++) {
@@ -141,88 +120,11 @@ __device__ void grid_setup(const GridArgs &a, int batch, GridHdr &H, float *s_re
                 mx[k] = fmaxf(mx[k], w);
             }
         }
+    grid_block_box<kGridBlock>(mn, mx, s_red);
+    grid_size<12, true>(mn, mx, a.cells_target, a.cells_max, H);
 #pragma unroll
-    for (int k = 0; k < 3; k++) {
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            mn[k] = fminf(mn[k], __shfl_xor(mn[k], o));
-            mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], o));
-        }
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) { s_red[wave * 6 + k] = mn[k]; s_red[wave * 6 + 3 + k] = mx[k]; }
-    }
-    __syncthreads();
-    for (int w = 0; w < kGridWaves; w++) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            mn[k] = fminf(mn[k], s_red[w * 6 + k]);
-            mx[k] = fmaxf(mx[k], s_red[w * 6 + 3 + k]);
-        }
-    }
-    float ext[3];
-    bool act[3];
-    int nact = 0;
-    float emax = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        if (!(mn[k] <= mx[k])) { mn[k] = 0.0f; mx[k] = 0.0f; }      // no finite sample on this axis
-        ext[k] = mx[k] - mn[k];
-        if (!(ext[k] < __builtin_inff())) ext[k] = 0.0f;             // overflowing extent: one cell on this axis
-        act[k] = ext[k] > 0.0f;
-        nact += act[k] ? 1 : 0;
-        emax = fmaxf(emax, ext[k]);
-    }
-    // cubic cells of side h with about cells_target cells over the axes that are wider than h
-    // (extents relative to the largest one: no overflow for clouds 1e-18 or 1e+18 across)
-    float h = 0.0f;
-    for (int it = 0; it < 3 && nact > 0; it++) {
-        float vol = 1.0f;
-        for (int k = 0; k < 3; k++) if (act[k]) vol *= ext[k] / emax;
-        const float r = vol / (float)a.cells_target;
-        h = emax * (nact == 3 ? cbrtf(r) : (nact == 2 ? sqrtf(r) : r));
-        bool dropped = false;
-        for (int k = 0; k < 3; k++) {
-            if (act[k] && !(ext[k] > h)) { act[k] = false; nact--; dropped = true; }
-        }
-        if (!dropped) break;
-    }
-    if (!(h > 0.0f) || !(h < __builtin_inff()) || nact == 0) {
-        h = 1.0f;
-        for (int k = 0; k < 3; k++) act[k] = false;
-    }
-    int g[3], gc[3];
-    for (int rep = 0; rep < 12; rep++) {
-        long long cells = 64;
-        for (int k = 0; k < 3; k++) {
-            float q = act[k] ? ceilf(ext[k] / h) : 1.0f;
-            if (!(q >= 1.0f)) q = 1.0f;
-            if (q > 1024.0f) q = 1024.0f;
-            g[k] = (int)q;
-            gc[k] = (g[k] + 3) >> 2;
-            cells *= gc[k];
-        }
-        if (cells <= a.cells_max) break;
-        h *= 1.26f;
-        if (rep == 11) { act[0] = act[1] = act[2] = false; }
-    }
-    float inv = 1.0f / h;
-    if (!(inv > 0.0f) || !(inv < __builtin_inff())) {
-        inv = 1.0f; h = 1.0f;
-        for (int k = 0; k < 3; k++) { g[k] = 1; gc[k] = 1; }
-    }
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        if (!act[k]) { g[k] = 1; gc[k] = 1; }
-        H.lo[k] = mn[k];
-        H.g[k] = g[k];
-        H.gc[k] = gc[k];
-        H.slack[k] = kU16 * (fabsf(mn[k]) + (float)(g[k] + 1) * h);
-    }
-    H.inv = inv;
-    H.h = h;
-    H.cells = gc[0] * gc[1] * gc[2] * 64;
+    for (int k = 0; k < 3; k++) H.gc[k] = (H.g[k] + 3) >> 2;
+    H.cells = H.gc[0] * H.gc[1] * H.gc[2] * 64;
     H.pad = 0;
 }
 
@@ -238,7 +140,6 @@ typedef float f3u __attribute__((ext_vector_type(3), aligned(4)));
 __global__ __launch_bounds__(kGridBlock) void grid_build_kernel(GridArgs a, int K)
 {
     extern __shared__ int s_cnt[];            // the slab's counters, then kGridWaves wave totals (x2), then the box reduction
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
     int bid = blockIdx.x;
     const int k = bid % K;
     bid /= K;
@@ -287,34 +188,7 @@ __global__ __launch_bounds__(kGridBlock) void grid_build_kernel(GridArgs a, int 
     }
     bad = __syncthreads_or(bad);
     if (k == 0 && threadIdx.x == 0) a.bad[batch * 2 + c] = bad;
-    // exclusive scan of the slab: thread t owns the segment [t per, (t + 1) per); per is odd (LDS banks)
-    const int per = ((width + kGridBlock - 1) / kGridBlock) | 1;
-    int sum = 0;
-    for (int i = 0; i < per; i++) {
-        const int q = threadIdx.x * per + i;
-        if (q < width) { const int w = s_cnt[q]; s_cnt[q] = sum; sum += w; }
-    }
-    int inc = sum;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const int t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) below += __shfl_xor(below, o);
-    if (lane == kWave - 1) s_w[wave] = inc;
-    if (lane == 0) s_w[kGridWaves + wave] = below;
-    __syncthreads();
-    int base = inc - sum;
-    for (int w = 0; w < kGridWaves; w++) {
-        base += w < wave ? s_w[w] : 0;
-        base += s_w[kGridWaves + w];
-    }
-    for (int i = 0; i < per; i++) {
-        const int q = threadIdx.x * per + i;
-        if (q < width) s_cnt[q] += base;
-    }
-    __syncthreads();
+    grid_scan_counts<kGridBlock>(s_cnt, width, below, s_w);
     int *start = a.start + ((size_t)batch * 2 + c) * (a.cells_max + 1);
     int *cstart = a.cstart + ((size_t)batch * 2 + c) * (a.cells_max / 64 + 2);
     for (int i = threadIdx.x; i < width; i += kGridBlock) {
@@ -446,18 +320,8 @@ __global__ __launch_bounds__(kBlock) void grid_query_kernel(GridArgs a)
         const int gx = H.g[0], gy = H.g[1], gz = H.g[2];
         const int cells = H.cells;
         const float h = H.h;
-        const float sx = H.slack[0] + kU16 * fabsf(x);
-        const float sy = H.slack[1] + kU16 * fabsf(y);
-        const float sz = H.slack[2] + kU16 * fabsf(z);
+        const float sx = grid_slack(H.slack[0], x), sy = grid_slack(H.slack[1], y), sz = grid_slack(H.slack[2], z);
         const float smax = fmaxf(sx, fmaxf(sy, sz));
-        const float kShrink = 0.99999905f;      // 1 - 2^-20
-        const float inf = __builtin_inff();
-        // lower bound of |p_a - q_a| over the points p of cells [c, c + w) of axis a (g cells in all)
-        auto gap1 = [&](int c, int w, int g, float lo, float q, float s) {
-            const float wl = c > 0 ? __fadd_rn(lo, __fmul_rn((float)c, h)) : -inf;
-            const float wh = c + w < g ? __fadd_rn(lo, __fmul_rn((float)(c + w), h)) : inf;
-            return fmaxf(0.0f, fmaxf((wl - s) - q, (q - s) - wh));
-        };
         // near phase: the 3 x 3 x 3 fine cells around the query's cell
         for (int i = sub; i < 27; i += LPQ) {
             const int dz = i / 9, dy = (i / 3) % 3, dx = i % 3;
@@ -467,9 +331,9 @@ __global__ __launch_bounds__(kBlock) void grid_query_kernel(GridArgs a)
             const int p0 = s_start[cell], p1 = s_start[cell + 1];
             if (p0 == p1) continue;
             if (LPQ < 27) {
-                const float gxv = gap1(cx, 1, gx, H.lo[0], x, sx), gyv = gap1(cy, 1, gy, H.lo[1], y, sy);
-                const float gzv = gap1(cz, 1, gz, H.lo[2], z, sz);
-                const float lb = __fmaf_rn(gxv, gxv, __fmaf_rn(gyv, gyv, __fmul_rn(gzv, gzv))) * kShrink;
+                const float gxv = grid_gap(cx, 1, gx, H.lo[0], h, x, sx), gyv = grid_gap(cy, 1, gy, H.lo[1], h, y, sy);
+                const float gzv = grid_gap(cz, 1, gz, H.lo[2], h, z, sz);
+                const float lb = __fmaf_rn(gxv, gxv, __fmaf_rn(gyv, gyv, __fmul_rn(gzv, gzv))) * kGridShrink;
                 if (lb > __uint_as_float((unsigned)(best >> 32))) continue;      // false while nothing is found (NaN key)
             }
             grid_eval<FMA>(ST, p0, p1, 0, 1, x, y, z, best);
@@ -478,7 +342,7 @@ __global__ __launch_bounds__(kBlock) void grid_query_kernel(GridArgs a)
         best = group_min<LPQ>(best);
         // everything outside the 27 cells differs by >= 2 cells on some axis: distance >= h - 2 slack
         float reach = fmaxf(0.0f, h - 2.0f * smax);
-        bool done = __fmul_rn(__fmul_rn(reach, reach), kShrink) > __uint_as_float((unsigned)(best >> 32));
+        bool done = __fmul_rn(__fmul_rn(reach, reach), kGridShrink) > __uint_as_float((unsigned)(best >> 32));
         if (!done) {
             // Far phase.  Coarse cells (4 x 4 x 4 fine cells, one contiguous run of the sorted cloud
             // each) are tested against the best so far, the lanes of the group taking LPQ of them at
@@ -490,9 +354,9 @@ __global__ __launch_bounds__(kBlock) void grid_query_kernel(GridArgs a)
             const int *__restrict__ cst = a.cstart + ((size_t)batch * 2 + tc) * (a.cells_max / 64 + 2);
             auto coarse_lb = [&](int C) {
                 const int Cx = C % Gx, Cy = (C / Gx) % Gy, Cz = C / (Gx * Gy);
-                const float gxv = gap1(Cx * 4, 4, gx, H.lo[0], x, sx), gyv = gap1(Cy * 4, 4, gy, H.lo[1], y, sy);
-                const float gzv = gap1(Cz * 4, 4, gz, H.lo[2], z, sz);
-                return __fmaf_rn(gxv, gxv, __fmaf_rn(gyv, gyv, __fmul_rn(gzv, gzv))) * kShrink;
+                const float gxv = grid_gap(Cx * 4, 4, gx, H.lo[0], h, x, sx), gyv = grid_gap(Cy * 4, 4, gy, H.lo[1], h, y, sy);
+                const float gzv = grid_gap(Cz * 4, 4, gz, H.lo[2], h, z, sz);
+                return __fmaf_rn(gxv, gxv, __fmaf_rn(gyv, gyv, __fmul_rn(gzv, gzv))) * kGridShrink;
             };
             // the fine cells of coarse cell C against the bound, survivors evaluated
             auto coarse_eval = [&](int C) {
@@ -500,8 +364,8 @@ __global__ __launch_bounds__(kBlock) void grid_query_kernel(GridArgs a)
                 float g2[3][4];
 #pragma unroll
                 for (int f = 0; f < 4; f++) {
-                    const float vx = gap1(Cx * 4 + f, 1, gx, H.lo[0], x, sx), vy = gap1(Cy * 4 + f, 1, gy, H.lo[1], y, sy);
-                    const float vz = gap1(Cz * 4 + f, 1, gz, H.lo[2], z, sz);
+                    const float vx = grid_gap(Cx * 4 + f, 1, gx, H.lo[0], h, x, sx), vy = grid_gap(Cy * 4 + f, 1, gy, H.lo[1], h, y, sy);
+                    const float vz = grid_gap(Cz * 4 + f, 1, gz, H.lo[2], h, z, sz);
                     g2[0][f] = __fmul_rn(vx, vx); g2[1][f] = __fmul_rn(vy, vy); g2[2][f] = __fmul_rn(vz, vz);
                 }
                 const float bd = __uint_as_float((unsigned)(best >> 32));
@@ -513,7 +377,7 @@ __global__ __launch_bounds__(kBlock) void grid_query_kernel(GridArgs a)
                     const float ax = fx == 0 ? g2[0][0] : (fx == 1 ? g2[0][1] : (fx == 2 ? g2[0][2] : g2[0][3]));
                     const float ay = fy == 0 ? g2[1][0] : (fy == 1 ? g2[1][1] : (fy == 2 ? g2[1][2] : g2[1][3]));
                     const float az = fz == 0 ? g2[2][0] : (fz == 1 ? g2[2][1] : (fz == 2 ? g2[2][2] : g2[2][3]));
-                    const float lb = __fadd_rn(__fadd_rn(ax, ay), az) * kShrink;
+                    const float lb = __fadd_rn(__fadd_rn(ax, ay), az) * kGridShrink;
                     if (lb > bd) continue;
                     grid_eval<FMA>(ST, p0, p1, 0, 1, x, y, z, best);
                     evals += (unsigned)(p1 - p0);

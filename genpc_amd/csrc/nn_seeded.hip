@@ -5,7 +5,7 @@
 // its learning rate per step.  The brute-force filter (nn_f16.hip) re-solves the query from nothing every time: 61 of the
 // ~170 us of a step.  Here every query starts from the index it was answered with at the previous step:
 // the reference's distance to THAT target is an upper bound on the answer, and only the targets inside that ball can
-// change it.  Both clouds are sorted ONCE per call into uniform grids (emd_grid_build_kernel, cells numbered x-fastest):
+// change it.  Both clouds are sorted ONCE per call into uniform grids (grid.h: cell_grid_build_kernel, cells numbered x-fastest):
 //   * the partial cloud does not move: the posed points search its grid directly;
 //   * the complete cloud moves rigidly (similarity): its grid is built in the REST frame and a partial point searches it
 //     from where the inverse pose puts it, q' = c + R^T (q - c - t) / s.  That frame is used for culling only, with a margin
@@ -13,10 +13,9 @@
 //     candidate that survives is valued with the reference's arithmetic on the POSED coordinates of this step.
 // Results are the reference's (distance, first index): the running best is the 64-bit key distance bits << 32 | index, a row
 // of cells is skipped only if its bound is STRICTLY above the best distance (ties with lower indices are still found), the
-// bound itself is nn_grid.hip's (every rounding accounted for).  The loop's histories are bit-identical to the brute-force
+// bound itself is grid.h's (every rounding accounted for).  The loop's histories are bit-identical to the brute-force
 // path (tests/test_gpu_pipeline.py, GENPC_POSE_SEEDED=0 for A/B).
 #include "nn.h"
-#include "emd.h"
 #include "../../include/genpc_hip.h"
 
 #include <stdlib.h>
@@ -24,14 +23,13 @@
 namespace genpc {
 
 constexpr int kSLPQ = 4;            // lanes per query
-constexpr float kSU16 = 9.5367431640625e-7f;
 
 struct SeededDir {
     const float *q;            // queries [b][nq][3], world frame
     const float *tpos;         // the targets' coordinates of THIS step, world frame [b][nt][3] (what distances are taken to)
     const float4 *sorted;      // the targets in cell order of their grid's frame: (x, y, z, index)
     const int *start;          // [b][cells_max + 1]
-    const EGridHdr *hdr;       // [b]
+    const CellGridHdr *hdr;       // [b]
     const int *seed;           // [b][nq] last step's answers
     float *out_d;
     int *out_i;
@@ -45,14 +43,6 @@ struct SeededArgs {
     const float *center; int cstride;
     const float *params; int pstride;
 };
-
-__device__ __forceinline__ int sgrid_cell1(float p, float lo, float inv, int g)
-{
-    const float t = __fmul_rn(__fsub_rn(p, lo), inv);
-    int c = (int)floorf(t);
-    c = c < 0 ? 0 : c;
-    return c > g - 1 ? g - 1 : c;
-}
 
 template <int FMA>
 __global__ __launch_bounds__(kBlock) void nn_seeded_kernel(SeededArgs a)
@@ -71,7 +61,7 @@ __global__ __launch_bounds__(kBlock) void nn_seeded_kernel(SeededArgs a)
     const float *__restrict__ TP = D.tpos + (size_t)batch * D.nt * 3;
     const float4 *__restrict__ S = D.sorted + (size_t)batch * D.nt;
     const int *__restrict__ ST = D.start + (size_t)batch * (a.cells_max + 1);
-    const EGridHdr H = D.hdr[batch];
+    const CellGridHdr H = D.hdr[batch];
     const float inf = __builtin_inff();
     // the query in the grid's frame; what a unit of grid distance is worth in the world, and the culling margins
     float gx_ = qx, gy_ = qy, gz_ = qz, scale = 1.0f, rel = 1.0f, dg = 0.0f;
@@ -118,13 +108,7 @@ __global__ __launch_bounds__(kBlock) void nn_seeded_kernel(SeededArgs a)
     }
     const int gx = H.g[0], gy = H.g[1], gz = H.g[2];
     const float h = H.h;
-    const float sx = H.slack[0] + kSU16 * fabsf(gx_), sy = H.slack[1] + kSU16 * fabsf(gy_), sz = H.slack[2] + kSU16 * fabsf(gz_);
-    const float kShrink = 0.99999905f;
-    auto gap1 = [&](int c, int g, float lo, float q, float s) {
-        const float wl = c > 0 ? __fadd_rn(lo, __fmul_rn((float)c, h)) : -inf;
-        const float wh = c + 1 < g ? __fadd_rn(lo, __fmul_rn((float)(c + 1), h)) : inf;
-        return fmaxf(0.0f, fmaxf((wl - s) - q, (q - s) - wh));
-    };
+    const float sx = grid_slack(H.slack[0], gx_), sy = grid_slack(H.slack[1], gy_), sz = grid_slack(H.slack[2], gz_);
     // squared grid-frame radius inside which a target can still beat (or tie) the best: static grid: the best distance
     // itself (the bound is exact there); moving grid: with the margins.  NaN (no seed yet / non-finite input): nothing is culled
     auto reach2 = [&](unsigned long long k) {
@@ -137,9 +121,9 @@ __global__ __launch_bounds__(kBlock) void nn_seeded_kernel(SeededArgs a)
     int bx0 = 0, bx1 = gx - 1, by0 = 0, by1 = gy - 1, bz0 = 0, bz1 = gz - 1;
     if (rg2 == rg2 && rg2 < inf) {
         const float R = sqrtf(rg2) * 1.000001f;
-        bx0 = sgrid_cell1((gx_ - R) - sx, H.lo[0], H.inv, gx); bx1 = sgrid_cell1((gx_ + R) + sx, H.lo[0], H.inv, gx);
-        by0 = sgrid_cell1((gy_ - R) - sy, H.lo[1], H.inv, gy); by1 = sgrid_cell1((gy_ + R) + sy, H.lo[1], H.inv, gy);
-        bz0 = sgrid_cell1((gz_ - R) - sz, H.lo[2], H.inv, gz); bz1 = sgrid_cell1((gz_ + R) + sz, H.lo[2], H.inv, gz);
+        bx0 = grid_cell1((gx_ - R) - sx, H.lo[0], H.inv, gx); bx1 = grid_cell1((gx_ + R) + sx, H.lo[0], H.inv, gx);
+        by0 = grid_cell1((gy_ - R) - sy, H.lo[1], H.inv, gy); by1 = grid_cell1((gy_ + R) + sy, H.lo[1], H.inv, gy);
+        bz0 = grid_cell1((gz_ - R) - sz, H.lo[2], H.inv, gz); bz1 = grid_cell1((gz_ + R) + sz, H.lo[2], H.inv, gz);
     }
     // Rows of the box, kSLPQ lanes striding over them four at a time: the extent of a row inside the box's x range is
     // fetched FIRST, for four rows at once -- a query with no target nearby (the back of the complete shape against a partial
@@ -164,12 +148,12 @@ __global__ __launch_bounds__(kBlock) void nn_seeded_kernel(SeededArgs a)
             if (q1[k] <= q0[k]) continue;                // nothing of this row inside the box (or past the last row)
             int p0 = q0[k], p1 = q1[k];
             if (rg2 == rg2) {
-                const float gyv = gap1(cyv[k], gy, H.lo[1], gy_, sy), gzv = gap1(czv[k], gz, H.lo[2], gz_, sz);
-                const float lb = __fmaf_rn(gyv, gyv, __fmul_rn(gzv, gzv)) * kShrink;
+                const float gyv = grid_gap(cyv[k], 1, gy, H.lo[1], h, gy_, sy), gzv = grid_gap(czv[k], 1, gz, H.lo[2], h, gz_, sz);
+                const float lb = __fmaf_rn(gyv, gyv, __fmul_rn(gzv, gzv)) * kGridShrink;
                 if (lb > rg2) continue;                  // strictly farther than the best: not even a tie
                 const float W = sqrtf(fmaxf(0.0f, __fmul_rn(rg2, 1.000001f) - lb)) * 1.000001f;
-                const int cx0 = max(bx0, sgrid_cell1((gx_ - W) - sx, H.lo[0], H.inv, gx));
-                const int cx1 = min(bx1, sgrid_cell1((gx_ + W) + sx, H.lo[0], H.inv, gx));
+                const int cx0 = max(bx0, grid_cell1((gx_ - W) - sx, H.lo[0], H.inv, gx));
+                const int cx1 = min(bx1, grid_cell1((gx_ + W) + sx, H.lo[0], H.inv, gx));
                 if (cx0 > cx1) continue;
                 if (cx0 > bx0) p0 = ST[rowb[k] + cx0];
                 if (cx1 < bx1) p1 = ST[rowb[k] + cx1 + 1];
@@ -216,7 +200,7 @@ int launch_nn_seeded(int b, int nm, const float *moving_pts, int ns, const float
                      int cstride, const float *params, int pstride, float *d1, int *i1, float *d2, int *i2, int fma, hipStream_t st, int sample)
 {
     SeededArgs a{};
-    a.b = b; a.cells_max = kEGMaxCells;
+    a.b = b; a.cells_max = kCellGridMaxCells;
     a.sample = sample > 1 ? sample : 1;
     a.center = center; a.cstride = cstride; a.params = params; a.pstride = pstride;
     SeededDir &A = a.d[0], &B = a.d[1];
@@ -236,7 +220,7 @@ int launch_nn_seeded(int b, int nm, const float *moving_pts, int ns, const float
 size_t seeded_grids_bytes(int b, int nm, int ns)
 {
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    return 2 * al((size_t)b * sizeof(EGridHdr)) + 2 * al((size_t)b * (kEGMaxCells + 1) * sizeof(int)) + al((size_t)b * nm * sizeof(float4)) +
+    return 2 * al((size_t)b * sizeof(CellGridHdr)) + 2 * al((size_t)b * (kCellGridMaxCells + 1) * sizeof(int)) + al((size_t)b * nm * sizeof(float4)) +
            al((size_t)b * ns * sizeof(float4));
 }
 
@@ -245,18 +229,18 @@ int build_seeded_grids(int b, int nm, const float *rest_pts, int ns, const float
 {
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     char *p = (char *)ws;
-    g.hdr_static = (EGridHdr *)p; p += al((size_t)b * sizeof(EGridHdr));
-    g.hdr_rest = (EGridHdr *)p; p += al((size_t)b * sizeof(EGridHdr));
-    g.start_static = (int *)p; p += al((size_t)b * (kEGMaxCells + 1) * sizeof(int));
-    g.start_rest = (int *)p; p += al((size_t)b * (kEGMaxCells + 1) * sizeof(int));
+    g.hdr_static = (CellGridHdr *)p; p += al((size_t)b * sizeof(CellGridHdr));
+    g.hdr_rest = (CellGridHdr *)p; p += al((size_t)b * sizeof(CellGridHdr));
+    g.start_static = (int *)p; p += al((size_t)b * (kCellGridMaxCells + 1) * sizeof(int));
+    g.start_rest = (int *)p; p += al((size_t)b * (kCellGridMaxCells + 1) * sizeof(int));
     g.sorted_static = (float4 *)p; p += al((size_t)b * ns * sizeof(float4));
     g.sorted_rest = (float4 *)p;
-    auto target = [](int n) { int t = n / 2; return t < 8 ? 8 : (t > kEGMaxCells * 3 / 4 ? kEGMaxCells * 3 / 4 : t); };
-    if (!launch_emd_grid_build(b, ns, static_pts, nullptr, (EGridHdr *)g.hdr_static, (int *)g.start_static, (float4 *)g.sorted_static, nullptr,
-                               nullptr, target(ns), kEGMaxCells, st))
+    auto target = [](int n) { int t = n / 2; return t < 8 ? 8 : (t > kCellGridMaxCells * 3 / 4 ? kCellGridMaxCells * 3 / 4 : t); };
+    if (!launch_cell_grid_build(b, ns, static_pts, nullptr, (CellGridHdr *)g.hdr_static, (int *)g.start_static, (float4 *)g.sorted_static, nullptr,
+                               nullptr, target(ns), kCellGridMaxCells, st))
         return 0;
-    return launch_emd_grid_build(b, nm, rest_pts, nullptr, (EGridHdr *)g.hdr_rest, (int *)g.start_rest, (float4 *)g.sorted_rest, nullptr, nullptr,
-                                 target(nm), kEGMaxCells, st);
+    return launch_cell_grid_build(b, nm, rest_pts, nullptr, (CellGridHdr *)g.hdr_rest, (int *)g.start_rest, (float4 *)g.sorted_rest, nullptr, nullptr,
+                                 target(nm), kCellGridMaxCells, st);
 }
 
 }  // namespace genpc

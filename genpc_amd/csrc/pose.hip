@@ -24,7 +24,6 @@
 // HBM traffic per iteration is O(N): ~24 B/point for the transform, ~28 B/point for
 // the gradient pass; the NN launch dominates (VALU-bound, see chamfer.hip).
 #include "nn.h"
-#include "emd.h"
 #include "../../include/genpc_hip.h"
 
 #include <math.h>
