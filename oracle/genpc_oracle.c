@@ -5,11 +5,11 @@
  * cpu_baseline leg and __graft_entry__.smoke() may load it, and only as the
  * checker.  The product path (genpc_amd/) never links, imports or calls it.
  *
- * Parity status: the reference (liannuaa/GenPC) ships no tests, no golden
- * vectors and no CPU implementation of this path, and its two CUDA extensions
- * need nvcc + ATen to build, so they cannot be compiled in this image without
- * writing stand-ins for the CUDA toolchain.  "PARITY UNPINNED" by the
- * reference's own artefacts.  What the restatement IS pinned against:
+ * Parity status: pinned to the reference's own kernel text.  oracle/ref_build.py
+ * compiles the kernels of chamfer3D.cu and emd_cuda.cu, unmodified, for the CPU
+ * (ref_simt.h, ref_driver.cpp -> oracle/_ref/), and tests/test_oracle_vs_reference.py
+ * compares every function below with them bit for bit, in both arithmetic modes
+ * (mode 1 = the contraction LLVM chooses; nvcc's is unverifiable).  Also pinned against:
  *   - the survey-time values in BASELINE.md section 2 (tests/test_oracle_golden.py)
  *   - an independent numpy restatement (tests/test_oracle_numpy.py)
  *   - float64 brute force / analytic gradients / exact-LAP bounds (properties)

@@ -3,9 +3,8 @@
 TEST INFRASTRUCTURE ONLY.  May be imported by tests/, by bench.py's
 ``cpu_baseline`` leg and by ``__graft_entry__.smoke()`` -- never by genpc_amd/.
 Parity status: the reference's own pure-Python functions pin the rows they cover
-(tests/golden/ref_py_*.npz, see genpc_oracle_geom.c); for the CUDA kernels see the
-header of genpc_oracle.c ("parity unpinned" by the
-reference's own artefacts; pinned against BASELINE.md section 2 values).
+(tests/golden/ref_py_*.npz, see genpc_oracle_geom.c); the Chamfer / EMD restatements are pinned
+to the reference's own kernels run on the CPU (ref_* below, tests/test_oracle_vs_reference.py).
 
 All arrays are numpy, C-contiguous, float32 / int32, shaped like the reference's
 tensors ([B,N,3] clouds, [B,N] distances and indices).
@@ -31,6 +30,8 @@ def build(force=False):
         os.path.getmtime(s) > os.path.getmtime(_LIB_PATH) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-s", "-C", _HERE] + (["-B"] if force else []))
+    from . import ref_build               # the reference's own kernels for the CPU (oracle/_ref/), where its checkout is
+    ref_build.build(force=force)
     return _LIB_PATH
 
 
@@ -147,6 +148,148 @@ def emd_backward(xyz1, xyz2, graddist, assignment):
     rc = lib().oracle_emd_backward(b, n, p1, p2, gx.ctypes.data_as(_f32p), pg, pa)
     assert rc == 1
     return gx
+
+
+# --------------------------------------------------------------------------
+# The reference's OWN kernels, executed on the CPU (oracle/_ref/libgenpc_ref_m{0,1}.so, made by
+# oracle/ref_build.py from the reference checkout's kernel text; ref_simt.h, ref_driver.cpp).
+# `schedule` 0 visits blocks and threads in ascending index order, 1 in descending order.
+# --------------------------------------------------------------------------
+_f64p_ = ctypes.POINTER(ctypes.c_double)
+_ref_libs = {}
+
+
+def ref_lib_path(fma_mode=0):
+    return os.path.join(_HERE, "_ref", "libgenpc_ref_m%d.so" % int(fma_mode))
+
+
+def cpu_has_fma():
+    """The mode-1 binary is compiled with -mfma: it needs a CPU with FMA3 (flag `fma` of /proc/cpuinfo)."""
+    try:
+        with open("/proc/cpuinfo") as f:
+            for line in f:
+                if line.startswith("flags"):
+                    return "fma" in line.split(":", 1)[1].split()
+    except OSError:
+        pass
+    return False
+
+
+def ref_available(fma_mode=0):
+    """True when the reference-kernel binary of that arithmetic mode exists (built here from the reference
+    checkout, or shipped with the tree) and this CPU can run it."""
+    build()
+    if int(fma_mode) == 1 and not cpu_has_fma():
+        return False
+    return os.path.exists(ref_lib_path(fma_mode))
+
+
+def _ref(fma_mode):
+    m = int(fma_mode)
+    if m not in _ref_libs:
+        if not ref_available(m):
+            raise RuntimeError("cannot use %s: neither the reference checkout nor a built oracle/_ref/, or (mode 1) a "
+                               "CPU without FMA" % ref_lib_path(m))
+        L = ctypes.CDLL(ref_lib_path(m))
+        assert L.ref_arith_mode() == m
+        _ref_libs[m] = L
+    return _ref_libs[m]
+
+
+def ref_chamfer_forward(xyz1, xyz2, fma_mode=0, schedule=0):
+    """chamfer_cuda_forward -> dist1, dist2, idx1, idx2 (outputs start as zeros, dist_chamfer_3D.py:33-37)."""
+    xyz1, p1 = _f(xyz1)
+    xyz2, p2 = _f(xyz2)
+    b, n, _ = xyz1.shape
+    m = xyz2.shape[1]
+    assert xyz2.shape[0] == b
+    d1 = np.zeros((b, n), np.float32)
+    d2 = np.zeros((b, m), np.float32)
+    i1 = np.zeros((b, n), np.int32)
+    i2 = np.zeros((b, m), np.int32)
+    rc = _ref(fma_mode).ref_chamfer_forward(
+        b, n, p1, m, p2, d1.ctypes.data_as(_f32p), i1.ctypes.data_as(_i32p),
+        d2.ctypes.data_as(_f32p), i2.ctypes.data_as(_i32p), int(schedule))
+    assert rc == 1
+    return d1, d2, i1, i2
+
+
+def ref_chamfer_backward(xyz1, xyz2, graddist1, graddist2, idx1, idx2, fma_mode=0, schedule=0):
+    """chamfer_cuda_backward -> gradxyz1, gradxyz2 (fp32, atomicAdd in schedule order), wide1, wide2 (the
+    float64 sums of the kernels' own fp32 terms, which no order can change)."""
+    xyz1, p1 = _f(xyz1)
+    xyz2, p2 = _f(xyz2)
+    g1, pg1 = _f(graddist1)
+    g2, pg2 = _f(graddist2)
+    i1, pi1 = _i(idx1)
+    i2, pi2 = _i(idx2)
+    b, n, _ = xyz1.shape
+    m = xyz2.shape[1]
+    assert i1.shape == (b, n) and i2.shape == (b, m) and g1.shape == (b, n) and g2.shape == (b, m)
+    assert (n == 0 or m > 0) and (i1 >= 0).all() and (i1 < max(m, 1)).all() and (i2 >= 0).all() and (i2 < max(n, 1)).all()
+    gx1 = np.zeros((b, n, 3), np.float32)
+    gx2 = np.zeros((b, m, 3), np.float32)
+    w1 = np.zeros((b, n, 3), np.float64)
+    w2 = np.zeros((b, m, 3), np.float64)
+    rc = _ref(fma_mode).ref_chamfer_backward(
+        b, n, p1, m, p2, pg1, pi1, pg2, pi2, gx1.ctypes.data_as(_f32p), gx2.ctypes.data_as(_f32p),
+        w1.ctypes.data_as(_f64p_), w2.ctypes.data_as(_f64p_), int(schedule))
+    assert rc == 1
+    return gx1, gx2, w1, w2
+
+
+def ref_emd_forward(xyz1, xyz2, eps, iters, fma_mode=0, schedule=0, return_state=False):
+    """emd_cuda_forward on buffers initialised as emd_module.py:43-54 -> dist, assignment (and every buffer
+    after `iters` rounds).  The reference's input checks return -1: ValueError, like emd_forward."""
+    xyz1, p1 = _f(xyz1)
+    xyz2, p2 = _f(xyz2)
+    b, n, _ = xyz1.shape
+    m = xyz2.shape[1]
+    # a non-finite bidder bids on object -1 in the reference (a write before its buffer), and without a round
+    # CalcDist reads object -1: neither is executed
+    assert int(iters) >= 1 and np.isfinite(xyz1).all() and xyz2.shape[0] == b
+    st = dict(
+        dist=np.zeros((b, n), np.float32),
+        assignment=np.zeros((b, n), np.int32),
+        price=np.zeros((b, m), np.float32),
+        assignment_inv=np.zeros((b, m), np.int32),
+        bid=np.zeros((b, n), np.int32),
+        bid_increments=np.zeros((b, n), np.float32),
+        max_increments=np.zeros((b, m), np.float32),
+        unass_idx=np.zeros(b * n, np.int32),
+        unass_cnt=np.zeros(512, np.int32),
+        unass_cnt_sum=np.zeros(512, np.int32),
+        cnt_tmp=np.zeros(512, np.int32),
+        max_idx=np.zeros(b * m, np.int32),
+    )
+    c = {k: (v.ctypes.data_as(_f32p) if v.dtype == np.float32 else v.ctypes.data_as(_i32p))
+         for k, v in st.items()}
+    fn = _ref(fma_mode).ref_emd_forward
+    rc = fn(b, n, m, p1, p2, c["dist"], c["assignment"], c["price"], c["assignment_inv"],
+            c["bid"], c["bid_increments"], c["max_increments"], c["unass_idx"],
+            c["unass_cnt"], c["unass_cnt_sum"], c["cnt_tmp"], c["max_idx"],
+            ctypes.c_float(eps), int(iters), int(schedule))
+    if rc != 1:
+        raise ValueError("ref_emd_forward rc=%d (n!=m, B>512 or n%%256!=0)" % rc)
+    if return_state:
+        return st["dist"], st["assignment"], st
+    return st["dist"], st["assignment"]
+
+
+def ref_emd_backward(xyz1, xyz2, graddist, assignment, fma_mode=0, schedule=0):
+    """emd_cuda_backward -> gradxyz (fp32), wide (float64 sum of the kernel's fp32 terms)."""
+    xyz1, p1 = _f(xyz1)
+    xyz2, p2 = _f(xyz2)
+    g, pg = _f(graddist)
+    a, pa = _i(assignment)
+    b, n, _ = xyz1.shape
+    assert xyz2.shape == xyz1.shape and a.shape == (b, n) and g.shape == (b, n) and (a >= 0).all() and (a < n).all()
+    gx = np.zeros((b, n, 3), np.float32)
+    w = np.zeros((b, n, 3), np.float64)
+    rc = _ref(fma_mode).ref_emd_backward(b, n, p1, p2, gx.ctypes.data_as(_f32p), pg, pa,
+                                         w.ctypes.data_as(_f64p_), int(schedule))
+    assert rc == 1
+    return gx, w
 
 
 # --------------------------------------------------------------------------
