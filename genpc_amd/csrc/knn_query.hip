@@ -1,0 +1,214 @@
+// knn_query.hip -- the exact k nearest targets of every query, with their indices (1 <= k <= 32).
+//
+// The reference densifies the partial scan before stage 1 with a KD-tree query of k = 2 or 5 neighbours and inverse-distance
+// weights (utils/dataUtils.py:128-134); every other search of the library answers "which target is nearest" only, and
+// knn.hip returns a mean distance inside one cloud.  Here queries [B, NQ, 3] meet targets [B, NT, 3]:
+//   * the targets are sorted once per call into the x-fastest grid of grid.h (launch_cell_grid_build): the cells
+//     [x0, x1] of a (cy, cz) row are one contiguous run of `sorted`;
+//   * the query ids are sorted by their cell in the TARGET grid (knn_query_order_kernel, the counting-sort pieces of grid.h),
+//     so the 64 lanes of a wave walk neighbouring cells;
+//   * one lane owns a query.  Its k best candidates live in registers as an ascending list of the 64-bit keys
+//     distance bits << 32 | target index (nn_grid.hip's): distances ascend, among bit-equal distances the lower index comes
+//     first, and the same order decides which of several equal candidates holds the k-th place.  The list has CAP entries
+//     (4, 8, 16 or 32, the next capacity above k); its first CAP - k entries are pinned to key 0, below every candidate, so
+//     the k-th best is always the LAST entry and the call's k results are the last k;
+//   * the lane walks shells of cells by Chebyshev distance r = 0, 1, 2 ... from its own (clamped) cell.  A row, or a cell of an
+//     inner row, is skipped only if grid.h's bound is STRICTLY above the k-th best distance (ties with lower indices are still
+//     found); the walk stops once every cell outside the shells visited so far is that far, or at the grid's border.  While
+//     fewer than k candidates are listed the k-th best is +inf and nothing is above it.  The bounds are grid_gap /
+//     grid_slack / kGridShrink themselves;
+//   * the distance is sqdist<FMA> of nn.h in the call's arithmetic mode: column 0 holds the bits of genpc_nm_distance.  Only
+//     candidates with d < +inf are listed (NaN and infinite distances never enter); slots past the listed ones hold
+//     (+inf, -1).  A target cloud with a non-finite coordinate (CellGridHdr.bad) is searched without culling.
+// One path for every size: a tiny or degenerate cloud is a one-cell grid.
+#include "nn.h"
+#include "../../include/genpc_hip.h"
+
+namespace genpc {
+
+constexpr int kKQOBlock = 1024;                                  // query ordering: one block per batch element
+constexpr unsigned long long kKQEmpty = 0x7f800000ffffffffull;   // (+inf, -1): above every listed candidate
+
+struct KnnQueryArgs {
+    const float *q;            // [b][nq][3]
+    const float4 *sorted;      // [b][nt]: (x, y, z, index) in cell order
+    const int *start;          // [b][cells_max + 1]
+    const CellGridHdr *hdr;    // [b]
+    const int *order;          // [b][nq]: query ids by cell of the target grid
+    float *out_d;              // [b][nq][k]
+    int *out_i;
+    int nq, nt, k, cells_max, qblocks;
+};
+
+// order[batch][.] = the query ids of a batch element sorted by their cell in the element's target grid (a counting sort in LDS;
+// the order inside a cell is whatever the atomics give: every query writes its own results, so it reaches none of them)
+__global__ __launch_bounds__(kKQOBlock) void knn_query_order_kernel(int nq, const float *__restrict__ q, const CellGridHdr *__restrict__ hdr,
+                                                                    int *__restrict__ order, int cells_max)
+{
+    extern __shared__ int s_cnt[];            // cells_max counters, then 2 ints per wave
+    int *s_w = s_cnt + cells_max;
+    const int batch = blockIdx.x;
+    const CellGridHdr H = hdr[batch];
+    const float *__restrict__ Q = q + (size_t)batch * nq * 3;
+    int *__restrict__ O = order + (size_t)batch * nq;
+    for (int i = threadIdx.x; i < H.cells; i += kKQOBlock) s_cnt[i] = 0;
+    __syncthreads();
+    auto cell_of = [&](int j) {
+        const int cx = grid_cell1(Q[(size_t)j * 3 + 0], H.lo[0], H.inv, H.g[0]), cy = grid_cell1(Q[(size_t)j * 3 + 1], H.lo[1], H.inv, H.g[1]);
+        const int cz = grid_cell1(Q[(size_t)j * 3 + 2], H.lo[2], H.inv, H.g[2]);
+        return (cz * H.g[1] + cy) * H.g[0] + cx;
+    };
+    for (int j = threadIdx.x; j < nq; j += kKQOBlock) atomicAdd(&s_cnt[cell_of(j)], 1);
+    __syncthreads();
+    grid_scan_counts<kKQOBlock>(s_cnt, H.cells, 0, s_w);
+    for (int j = threadIdx.x; j < nq; j += kKQOBlock) O[atomicAdd(&s_cnt[cell_of(j)], 1)] = j;
+}
+
+template <int CAP, int FMA>
+__global__ __launch_bounds__(kBlock) void knn_query_kernel(KnnQueryArgs a)
+{
+    const int batch = blockIdx.x / a.qblocks, pos = (blockIdx.x - batch * a.qblocks) * kBlock + threadIdx.x;
+    if (pos >= a.nq) return;
+    const int j = a.order[(size_t)batch * a.nq + pos];
+    const float *qp = a.q + ((size_t)batch * a.nq + j) * 3;
+    const float qx = qp[0], qy = qp[1], qz = qp[2];
+    const float4 *__restrict__ S = a.sorted + (size_t)batch * a.nt;
+    const int *__restrict__ ST = a.start + (size_t)batch * (a.cells_max + 1);
+    const CellGridHdr H = a.hdr[batch];
+    const int gx = H.g[0], gy = H.g[1], gz = H.g[2];
+    const float h = H.h;
+    const bool cull = !H.bad;
+    const float sx = grid_slack(H.slack[0], qx), sy = grid_slack(H.slack[1], qy), sz = grid_slack(H.slack[2], qz);
+    const int cx = grid_cell1(qx, H.lo[0], H.inv, gx), cy = grid_cell1(qy, H.lo[1], H.inv, gy), cz = grid_cell1(qz, H.lo[2], H.inv, gz);
+
+    unsigned long long L[CAP];           // ascending; L[0 .. CAP - k) pinned to 0, L[CAP - 1] is the k-th best
+#pragma unroll
+    for (int i = 0; i < CAP; i++) L[i] = i < CAP - a.k ? 0ull : kKQEmpty;
+    auto kth = [&]() { return __uint_as_float((unsigned)(L[CAP - 1] >> 32)); };      // +inf while fewer than k are listed
+    auto run = [&](int p0, int p1) {     // the targets at positions [p0, p1) of the sorted cloud
+        for (int p = p0; p < p1; p++) {
+            const float4 e = S[p];
+            const float dd = sqdist<FMA>(e.x - qx, e.y - qy, e.z - qz);
+            const unsigned long long key = ((unsigned long long)__float_as_uint(dd) << 32) | (unsigned)__float_as_int(e.w);
+            if (dd < __builtin_inff() && key < L[CAP - 1]) {
+                // sorted insertion, the largest falls off:  L'[i] = max(L[i - 1], min(key, L[i]))
+#pragma unroll
+                for (int i = CAP - 1; i > 0; i--) {
+                    const unsigned long long m = key < L[i] ? key : L[i];
+                    L[i] = L[i - 1] > m ? L[i - 1] : m;
+                }
+                L[0] = key < L[0] ? key : L[0];
+            }
+        }
+    };
+
+    const int rmax = max(max(max(cx, gx - 1 - cx), max(cy, gy - 1 - cy)), max(cz, gz - 1 - cz));
+    for (int r = 0;; r++) {
+        const int z0 = max(cz - r, 0), z1 = min(cz + r, gz - 1), y0 = max(cy - r, 0), y1 = min(cy + r, gy - 1);
+        const int x0 = max(cx - r, 0), x1 = min(cx + r, gx - 1);
+        for (int z = z0; z <= z1; z++) {
+            const bool zface = z == cz - r || z == cz + r;
+            const float gzv = grid_gap(z, 1, gz, H.lo[2], h, qz, sz);
+            for (int y = y0; y <= y1; y++) {
+                const float gyv = grid_gap(y, 1, gy, H.lo[1], h, qy, sy);
+                const float lb0 = __fmaf_rn(gyv, gyv, __fmul_rn(gzv, gzv));
+                if (cull && lb0 * kGridShrink > kth()) continue;          // strictly farther than the k-th best: not even a tie
+                const int row = (z * gy + y) * gx;
+                if (zface || y == cy - r || y == cy + r) {                 // a row of the shell's faces: one run
+                    run(ST[row + x0], ST[row + x1 + 1]);
+                } else {                                                   // an inner row: the shell's two cells (r > 0 here)
+                    if (cx - r >= 0) {
+                        const float gxv = grid_gap(cx - r, 1, gx, H.lo[0], h, qx, sx);
+                        if (!(cull && __fmaf_rn(gxv, gxv, lb0) * kGridShrink > kth())) run(ST[row + cx - r], ST[row + cx - r + 1]);
+                    }
+                    if (cx + r < gx) {
+                        const float gxv = grid_gap(cx + r, 1, gx, H.lo[0], h, qx, sx);
+                        if (!(cull && __fmaf_rn(gxv, gxv, lb0) * kGridShrink > kth())) run(ST[row + cx + r], ST[row + cx + r + 1]);
+                    }
+                }
+            }
+        }
+        if (r >= rmax) break;                // the whole grid has been visited
+        if (cull) {
+            // every cell not yet visited lies in one of the (at most six) slabs beyond the shell
+            float m = __builtin_inff();
+            if (cx - r > 0) m = fminf(m, grid_gap(0, cx - r, gx, H.lo[0], h, qx, sx));
+            if (cx + r + 1 < gx) m = fminf(m, grid_gap(cx + r + 1, gx - (cx + r + 1), gx, H.lo[0], h, qx, sx));
+            if (cy - r > 0) m = fminf(m, grid_gap(0, cy - r, gy, H.lo[1], h, qy, sy));
+            if (cy + r + 1 < gy) m = fminf(m, grid_gap(cy + r + 1, gy - (cy + r + 1), gy, H.lo[1], h, qy, sy));
+            if (cz - r > 0) m = fminf(m, grid_gap(0, cz - r, gz, H.lo[2], h, qz, sz));
+            if (cz + r + 1 < gz) m = fminf(m, grid_gap(cz + r + 1, gz - (cz + r + 1), gz, H.lo[2], h, qz, sz));
+            if (__fmul_rn(m, m) * kGridShrink > kth()) break;
+        }
+    }
+    float *od = a.out_d + ((size_t)batch * a.nq + j) * a.k;
+    int *oi = a.out_i + ((size_t)batch * a.nq + j) * a.k;
+    const int skip = CAP - a.k;
+#pragma unroll
+    for (int i = 0; i < CAP; i++) {
+        if (i >= skip) {
+            od[i - skip] = __uint_as_float((unsigned)(L[i] >> 32));
+            oi[i - skip] = (int)(unsigned)L[i];
+        }
+    }
+}
+
+template <int CAP>
+static void launch_knn_query_cap(const KnnQueryArgs &a, unsigned grid, int fma, hipStream_t st)
+{
+    if (fma) hipLaunchKernelGGL((knn_query_kernel<CAP, 1>), dim3(grid), dim3(kBlock), 0, st, a);
+    else hipLaunchKernelGGL((knn_query_kernel<CAP, 0>), dim3(grid), dim3(kBlock), 0, st, a);
+}
+
+static int knn_query(int b, int nq, const float *xyz, int nt, const float *xyz2, int k, float *dist, int *idx, hipStream_t st)
+{
+    const int fma = arith_mode() != 0;
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t o_start = al((size_t)b * sizeof(CellGridHdr)), o_sorted = o_start + al((size_t)b * (kCellGridMaxCells + 1) * sizeof(int));
+    const size_t o_order = o_sorted + al((size_t)b * nt * sizeof(float4)), bytes = o_order + al((size_t)b * nq * sizeof(int));
+    char *ws = (char *)workspace(36, bytes, st);
+    if (!ws) return 0;
+    KnnQueryArgs a{};
+    a.q = xyz; a.out_d = dist; a.out_i = idx; a.nq = nq; a.nt = nt; a.k = k; a.cells_max = kCellGridMaxCells;
+    a.hdr = (const CellGridHdr *)ws; a.start = (const int *)(ws + o_start); a.sorted = (const float4 *)(ws + o_sorted);
+    a.order = (const int *)(ws + o_order);
+    a.qblocks = ceil_div(nq, kBlock);
+    if ((long long)b * a.qblocks > 0x7fffffffLL) { set_error("knn query: problem too large for one launch"); return 0; }
+    // cells of about max(2, k / 2) targets: the 27 cells around a query then hold its k neighbours more often than not
+    const int per = k / 2 > 2 ? k / 2 : 2;
+    int target = nt / per;
+    target = target < 8 ? 8 : (target > kCellGridMaxCells * 3 / 4 ? kCellGridMaxCells * 3 / 4 : target);
+    if (!launch_cell_grid_build(b, nt, xyz2, nullptr, (CellGridHdr *)a.hdr, (int *)a.start, (float4 *)a.sorted, nullptr, nullptr, target,
+                                kCellGridMaxCells, st))
+        return 0;
+    const size_t lds = ((size_t)kCellGridMaxCells + 2 * (kKQOBlock / kWave)) * sizeof(int);
+    hipLaunchKernelGGL(knn_query_order_kernel, dim3(b), dim3(kKQOBlock), lds, st, nq, xyz, a.hdr, (int *)a.order, kCellGridMaxCells);
+    if (!check(hipGetLastError(), "knn_query_order_kernel launch")) return 0;
+    const unsigned grid = (unsigned)(b * a.qblocks);
+    if (k <= 4) launch_knn_query_cap<4>(a, grid, fma, st);
+    else if (k <= 8) launch_knn_query_cap<8>(a, grid, fma, st);
+    else if (k <= 16) launch_knn_query_cap<16>(a, grid, fma, st);
+    else launch_knn_query_cap<32>(a, grid, fma, st);
+    return check(hipGetLastError(), "knn_query_kernel launch") ? 1 : 0;
+}
+
+}  // namespace genpc
+
+GENPC_API int genpc_knn_query(int b, int nq, const float *xyz, int nt, const float *xyz2, int k, float *dist, int *idx, void *stream)
+{
+    using namespace genpc;
+    if (k < 1 || k > 32) {
+        set_error("genpc_knn_query: k must be 1 .. 32");
+        return -1;
+    }
+    if (b < 0 || nq < 0 || nt < 0) {
+        set_error("genpc_knn_query: negative size");
+        return -1;
+    }
+    if (b == 0 || nq == 0) return 1;
+    if (nt < 1) {
+        set_error("genpc_knn_query: no targets");
+        return -1;
+    }
+    return knn_query(b, nq, xyz, nt, xyz2, k, dist, idx, (hipStream_t)stream);
+}

@@ -2,7 +2,9 @@
 needs, without open3d / trimesh: binary-little-endian PLY
 point I/O in the layout Open3D writes for the reference's data/*.ply (double x,y,z,
 optional uchar red,green,blue), ``normalize_numpy`` (:561-581) and
-``get_rotate_matrix`` (:455-472).  Host-side format code, numpy only."""
+``get_rotate_matrix`` (:455-472) -- host-side format code, numpy only -- and the densification of the
+partial scan before stage 1 (:98-155: ``random_add_points``, ``generate_interpolation_points``,
+``linear_interpolation``, ``xyz2xyzrgb``), whose neighbour searches run on the HIP library."""
 import numpy as np
 
 _PLY_TYPES = {"double": "<f8", "float": "<f4", "float32": "<f4", "float64": "<f8", "uchar": "u1", "uint8": "u1",
@@ -139,3 +141,114 @@ def getCategory(flag):
     kv = {"01184": "Wheelie Bin", "05117": "chair", "05452": "armchair", "06127": "Plant vases", "06145": "table",
           "06188": "vespa", "06830": "Kid tricycle", "07136": "sofa", "07306": "trash can", "09639": "swivel chair"}
     return kv.get(str(flag), "object")
+
+
+# ---- densification of the partial scan (utils/dataUtils.py:98-155) ----
+C0 = 0.28209479177387814
+
+
+def SH2RGB(sh):
+    """utils/sh_utils.py:117-118."""
+    return sh * C0 + 0.5
+
+
+def _to_gpu(a, device=None):
+    """(float32 GPU tensor, float64 tensor on the same device, was_numpy) of a numpy array or a GPU tensor."""
+    import torch
+    if isinstance(a, torch.Tensor):
+        if not a.is_cuda:
+            raise RuntimeError("genpc_amd: GPU tensors only (got a %s tensor); the HIP path has no CPU fallback" % a.device)
+        return a.float().contiguous(), a.double(), False
+    a64 = torch.as_tensor(np.ascontiguousarray(a, np.float64), device=torch.device("cuda" if device is None else device))
+    return a64.float().contiguous(), a64, True
+
+
+def random_add_points(coords):
+    """utils/dataUtils.py:99-116: 100000 points drawn uniformly in the bounding box (np.random.seed(0), as the reference
+    draws them); those closer than 0.01 to their nearest point of the cloud are kept and put in FRONT of the cloud.
+    The reference asks open3d's KD-tree for every candidate's nearest point; here one radius-limited search
+    (chamfer_3D.nm_distance_within, fp32, a limit a little above 0.01^2) names it, and the reference's test
+    ||p - nearest|| < 0.01 is made in float64 on the survivors.  numpy in: numpy float64 out; GPU tensor in: GPU tensor
+    (float64) out."""
+    import torch
+    from .. import _lib, chamfer_3D
+    c32, c64, was_numpy = _to_gpu(coords)
+    host = c64.cpu().numpy()                   # (float64, as open3d's Vector3dVector holds the cloud)
+    np.random.seed(0)
+    num_points = 100000
+    points = np.random.uniform(low=host.min(axis=0), high=host.max(axis=0), size=(num_points, 3))
+    p64 = torch.as_tensor(points, device=c32.device)
+    p32 = p64.float().contiguous()
+    # the fp32 search sees both clouds rounded by <= 2^-24 |x| per coordinate: its distances are the float64 ones within
+    # 2 sqrt(3) 2^-24 max|x| (rounding) -- a limit of 1.01 x 0.01 plus 8 x 2^-24 max|x| loses no candidate of the float64 test
+    mag = float(max(np.abs(host).max(), np.abs(points).max())) if host.size else 0.0
+    limit = 0.01 * 1.01 + 8.0 * 2.0 ** -24 * mag
+    d = torch.empty((1, num_points), dtype=torch.float32, device=c32.device)
+    i = torch.empty((1, num_points), dtype=torch.int32, device=c32.device)
+    if chamfer_3D.nm_distance_within(p32[None], c32[None], limit * limit, d, i) != 1:
+        raise RuntimeError("nm_distance_within failed: " + _lib.last_error())
+    near = torch.nonzero(i[0] >= 0)[:, 0]
+    if was_numpy:                     # the reference's own float64 test, on the host
+        near, idx = near.cpu().numpy(), i[0][near].cpu().numpy()
+        inside = points[near][np.linalg.norm(points[near] - host[idx], axis=1) < 0.01]
+        return np.concatenate([inside, coords], axis=0)
+    nearest = c64[i[0][near].long()]
+    inside = p64[near][torch.linalg.norm(p64[near] - nearest, dim=1) < 0.01]
+    return torch.cat([inside, c64], dim=0)
+
+
+def generate_interpolation_points(points, num_points=10000):
+    """utils/dataUtils.py:120-124: num_points uniform draws (numpy's global generator) in the bounding box."""
+    import torch
+    if isinstance(points, torch.Tensor):
+        host = points.detach().cpu().numpy()
+        new_points = np.random.uniform(host.min(axis=0), host.max(axis=0), (num_points, 3))
+        return torch.as_tensor(new_points, device=points.device)
+    points = np.asarray(points)
+    return np.random.uniform(points.min(axis=0), points.max(axis=0), (num_points, 3))
+
+
+def linear_interpolation(points, new_points, k=2):
+    """utils/dataUtils.py:128-134: every new point becomes the inverse-distance-weighted mean of its k nearest points of
+    the cloud.  The neighbour INDICES come from the exact fp32 search of the HIP library (knn.knn_query; the reference:
+    scipy's KDTree.query); the rest is the reference's arithmetic in float64 on the gathered neighbours -- Euclidean
+    distance, 1 / (d + 1e-8), normalise, weighted sum.  numpy in: numpy float64 out; GPU tensors in: GPU tensor
+    (float64) out."""
+    from ..knn import knn_query
+    p32, p64, was_numpy = _to_gpu(points)
+    q32, q64, _ = _to_gpu(new_points, p32.device)
+    if p32.shape[0] < k:
+        raise ValueError("linear_interpolation: k = %d neighbours of a cloud of %d points" % (k, p32.shape[0]))
+    _, idx = knn_query(q32, p32, k)
+    if bool((idx < 0).any()):
+        raise ValueError("linear_interpolation: a point without k neighbours at a finite distance (non-finite input)")
+    if was_numpy:                     # the reference's own float64 lines, on the host
+        points, new_points, indices = p64.cpu().numpy(), q64.cpu().numpy(), idx.cpu().numpy()
+        distances = np.sqrt(((points[indices] - new_points[:, None, :]) ** 2).sum(axis=2))
+        weights = 1 / (distances + 1e-8)
+        weights /= weights.sum(axis=1)[:, np.newaxis]
+        return np.sum(points[indices] * weights[:, :, np.newaxis], axis=1)
+    near = p64[idx.long()]                                            # [N, k, 3]
+    distances = ((near - q64[:, None, :]) ** 2).sum(dim=2).sqrt()
+    weights = 1 / (distances + 1e-8)
+    weights = weights / weights.sum(dim=1)[:, None]
+    return (near * weights[:, :, None]).sum(dim=1)
+
+
+def xyz2xyzrgb(partial_path, add_point_type='random', add_num_points=5000):
+    """utils/dataUtils.py:137-155: the partial scan of a PLY file densified ('random': random_add_points; 'linear':
+    add_num_points box samples interpolated with k = 5; anything else: as it is), with the reference's
+    SH2RGB(random / 255) colours.  Returns (coords, rgb) as numpy arrays."""
+    xyz, _ = read_ply(partial_path, want_color=False)
+    points = xyz.astype(np.float32)
+    if add_point_type == 'random':
+        coords = random_add_points(points)
+    elif add_point_type == 'linear':
+        add_points = generate_interpolation_points(points, num_points=add_num_points)
+        coords = linear_interpolation(points, add_points, k=5)
+    else:
+        coords = points
+    num_pts = len(coords)
+    shs = np.random.random((num_pts, 3)) / 255.0
+    rgb = SH2RGB(shs)
+    return coords, rgb

@@ -33,8 +33,8 @@ extern "C" {
 #define GENPC_ARITH_FMA 1
 
 /* Library / device ------------------------------------------------------- */
-int genpc_abi_version(void);              /* bumps when a signature or a documented behaviour changes (17: genpc_fps_tune takes 0 or
-                                           * 256 only; 16: genpc_hpr_* asynchronous, counts -1 on an internal error;
+int genpc_abi_version(void);              /* bumps when a signature or a documented behaviour changes (18: genpc_knn_query added;
+                                           * 17: genpc_fps_tune takes 0 or 256 only; 16: genpc_hpr_* asynchronous, counts -1 on an internal error;
                                            * genpc_fps*: out_idx[0] -2 = failed the check) */
 const char *genpc_last_error(void);       /* last HIP error string, "" if none */
 int genpc_set_arith(int mode);            /* process default; returns the previous one */
@@ -454,6 +454,19 @@ int genpc_fps_stats(int c, int *rounds, void *stream);
  * k in {8, 16, 20, 32}; -1 otherwise.                                           */
 int genpc_knn_mean_distance(int n, const float *xyz, int k, float *mean_out,
                             void *stream);
+
+/* k nearest neighbours ------------------------------------------------------- *
+ * For every query of xyz[B,NQ,3] its k nearest targets of xyz2[B,NT,3], 1 <= k <= 32: dist[B,NQ,k] (squared distances)
+ * and idx[B,NQ,k] (what the reference asks of scipy's KDTree.query in linear_interpolation, utils/dataUtils.py:128-134,
+ * with k = 2 or 5).  Order: that of the 64-bit key distance bits << 32 | target index -- distances ascend, among
+ * bit-equal distances the lower index comes first, and the same order decides which of several equal candidates holds
+ * the k-th place.  The distance is the library's (arithmetic mode of the call): column 0 holds the bits of
+ * genpc_nm_distance on finite input.  Only targets at a distance < +inf are listed (a NaN or infinite distance never
+ * enters); the slots past the listed ones -- NT < k, non-finite input -- hold (+inf, -1).  Every output word is written.
+ * Exact: a pruned search on the uniform grid (csrc/knn_query.hip).  Returns -1 and writes nothing for k < 1, k > 32 or
+ * NT < 1 with NQ > 0; 1 at once for NQ == 0 or B == 0.                                                                */
+int genpc_knn_query(int b, int nq, const float *xyz, int nt, const float *xyz2, int k,
+                    float *dist, int *idx, void *stream);
 
 #ifdef __cplusplus
 }
