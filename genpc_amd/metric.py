@@ -8,6 +8,13 @@ over ranks (genpc_amd.sharding) with one all_gather of the per-scan scalars.
 
     python -m genpc_amd.metric [--npz tests/golden/scans13_fps16384.npz]
     torchrun --nproc-per-node 4 -m genpc_amd.metric --npz ...
+
+The reference's second evaluation file, ``metric.py``, adds what needs no ground truth: ``UHD`` (:105-132), the directed
+Hausdorff distance from the partial scan to the completed cloud -- the one score of the LiDAR path -- and ``cd_emd``
+(:135-148).  ``uhd`` / ``UHD`` / ``evaluate_uhd`` / ``cd_emd`` below; UHD runs on the library's fp64 all-pairs kernel
+(csrc/uhd.hip) and has the bits of scipy's float64 ``cdist``.
+
+    python -m genpc_amd.metric --uhd PARTIAL.ply COMPLETE.ply
 """
 import argparse
 import os
@@ -15,7 +22,7 @@ import os
 import numpy as np
 import torch
 
-from . import sharding
+from . import _lib, sharding
 from .loss_functions import chamfer_3DDist, emdModule
 
 
@@ -50,6 +57,106 @@ def cd_l1_cpu_plumbing(pred, gt, chunk=512):
     return torch.stack(rows)
 
 
+def _uhd_cloud(t, name):
+    """A cloud as contiguous float32.  float64 is taken only if every value survives the trip through float32 (checked on the
+    device): PLY clouds are float32 that open3d widens, and the kernel widens them again, so nothing is lost; a genuinely
+    float64 cloud would be answered for different coordinates than the caller's, and is refused."""
+    if t.dtype == torch.float64:
+        t32 = t.float()
+        if not bool((t32.double() == t).all()):
+            raise ValueError("uhd: %s is float64 and not representable in float32 (the kernel reads float32 coordinates)" % name)
+        t = t32
+    elif t.dtype != torch.float32:
+        raise TypeError("uhd: %s must be torch.float32 (or float32-representable float64), got %s" % (name, t.dtype))
+    return t.contiguous()
+
+
+def uhd(partial, complete, return_witness=False):
+    """Directed Hausdorff distance from ``partial`` to ``complete``: max over the points of partial of the distance to the
+    nearest point of complete, with the bits of the reference's ``np.max(np.min(cdist(partial, complete), axis=1))``
+    (metric.py:124-130; float64, ((dx*dx) + (dy*dy)) + (dz*dz), one sqrt).  [B,N,3] with [B,M,3] -> float64 [B]; [N,3] with
+    [M,3] -> a 0-d float64 tensor; float32 GPU tensors (float64 only if float32-representable).  The result stays on the
+    device: nothing here waits for it (a float64 input costs one synchronising check).
+
+    return_witness=True also returns int32 [B,2] (or [2]): (i, j) = numpy's ``argmax`` of the row minima and ``argmin`` of
+    that row -- the lowest indices among ties, judged on the float64 squared distances."""
+    if partial.dim() != complete.dim() or partial.dim() not in (2, 3) or partial.shape[-1] != 3 or complete.shape[-1] != 3:
+        raise ValueError("uhd: partial [N,3] with complete [M,3], or [B,N,3] with [B,M,3]")
+    single = partial.dim() == 2
+    p = partial.unsqueeze(0) if single else partial
+    c = complete.unsqueeze(0) if single else complete
+    if p.shape[0] != c.shape[0]:
+        raise ValueError("uhd: batch sizes differ (%d, %d)" % (p.shape[0], c.shape[0]))
+    if p.device != c.device:
+        raise ValueError("uhd: partial and complete are on different devices")
+    b, n, m = p.shape[0], p.shape[1], c.shape[1]
+    if n < 1 or m < 1:
+        raise ValueError("uhd: the maximum or minimum over an empty cloud is undefined (N = %d, M = %d)" % (n, m))
+    p, c = _uhd_cloud(p, "partial"), _uhd_cloud(c, "complete")      # (the dtype is judged where the tensor lives)
+    _lib.require_gpu(p, c)
+    d2 = torch.empty((b,), dtype=torch.float64, device=p.device)
+    ij = torch.empty((b, 2), dtype=torch.int32, device=p.device)
+    if b:
+        rc = _lib.on_device_of(p, _lib.lib.genpc_uhd, b, n, _lib.ptr(p), m, _lib.ptr(c), _lib.ptr(d2), _lib.ptr(ij))
+        if rc != 0:
+            raise RuntimeError("genpc_uhd failed (%d): %s" % (rc, _lib.last_error()))
+    hd = torch.sqrt(d2)
+    if single:
+        hd, ij = hd[0], ij[0]
+    return (hd, ij) if return_witness else hd
+
+
+def _read_cloud(path, fps_at, fps_to, device):
+    """A PLY's points on the device; a cloud of >= fps_at points is farthest-point-subsampled to fps_to through float32
+    (metric.py:117-122)."""
+    from .fps import fps_subsample
+    from .utils.dataUtils import read_ply
+    xyz, _ = read_ply(path, want_color=False)
+    t = torch.from_numpy(np.ascontiguousarray(xyz)).to(device)
+    if fps_at is not None and len(xyz) >= fps_at:
+        t = fps_subsample(t.unsqueeze(0).float().contiguous(), fps_to).squeeze(0)
+    return t
+
+
+def UHD(partial_path, complete_path):
+    """The reference's ``UHD(partial_path, complete_path)`` (metric.py:105-132), same signature and thresholds: both PLY
+    clouds are read, one with >= 20000 points is FPS-subsampled (through float32) to 10000 (partial) / 20000 (complete)
+    points, and the directed Hausdorff distance partial -> complete comes back as a Python float.
+
+    Below the threshold the result has the reference's bits (``uhd``).  At or above it the reference's ``fps_subsample``
+    starts at a random point and is not reproducible from run to run; ours (genpc_amd.fps) is deterministic, so that branch
+    returns the same number every time and is not pinned to the reference."""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    p = _read_cloud(partial_path, 20000, 10000, dev)
+    c = _read_cloud(complete_path, 20000, 20000, dev)
+    return float(uhd(p, c))
+
+
+def cd_emd(pcdpath1, pcdpath2):
+    """The reference's ``cd_emd`` (metric.py:135-148): both PLY clouds FPS-subsampled to 16384 points, then CD-L1 with
+    gen = cloud 2, gt = cloud 1 and EMD (eps 0.005, 50 rounds) with p1 = cloud 2, p2 = cloud 1.  Returns the two 0-d
+    tensors (cdloss, emdloss)."""
+    from .fps import fps_subsample
+    from .utils.dataUtils import read_ply
+    from .utils.loss_util import Completionloss
+    dev = torch.device("cuda", torch.cuda.current_device())
+    clouds = []
+    for path in (pcdpath1, pcdpath2):
+        xyz, _ = read_ply(path, want_color=False)
+        t = torch.from_numpy(np.ascontiguousarray(xyz)).unsqueeze(0).float().to(dev)
+        clouds.append(fps_subsample(t.contiguous(), 16384).float())
+    pcd1, pcd2 = clouds
+    cdloss = Completionloss(loss_func='cd_l1').get_loss(gen=pcd2, gt=pcd1)
+    emdloss = Completionloss(loss_func='emd').emd_loss(p1=pcd2, p2=pcd1)
+    return cdloss, emdloss
+
+
+def evaluate_uhd(pred, gt):
+    """metric_fn for evaluate_sharded: pred [S,N,3] are the partial scans (queries), gt [S,M,3] the completed clouds
+    (targets).  Returns float64 [S,1] = uhd(pred, gt); the all-gather keeps the dtype."""
+    return uhd(pred, gt).unsqueeze(1)
+
+
 def evaluate_sharded(pred_np, gt_np, device=None, max_batch=16, metric_fn=None, backend=None):
     """Round-robin shard of the S scans over the ranks of the default process group
     (initialised here if the launcher's WORLD_SIZE > 1 and nobody did yet); every rank
@@ -76,7 +183,10 @@ def evaluate_sharded(pred_np, gt_np, device=None, max_batch=16, metric_fn=None, 
         raise ValueError("evaluate_sharded: no rank owns a scan")
     if rows and any(r.shape[1] != k for r in rows):
         raise ValueError("evaluate_sharded: metric_fn returned %d columns here, %d elsewhere" % (k_local, k))
-    local = torch.cat(rows) if rows else torch.empty(0, k, device=device)
+    # ... and so is the dtype (evaluate_uhd returns float64): the all_gather needs one on every rank
+    red_dev = device if (world > 1 and torch.device(device).type == "cuda") else "cpu"
+    wide = sharding.max_over_ranks(1.0 if rows and rows[0].dtype == torch.float64 else 0.0, device=red_dev) > 0
+    local = torch.cat(rows) if rows else torch.empty(0, k, device=device, dtype=torch.float64 if wide else torch.float32)
     return sharding.gather_scan_metrics(local, s_total, rank, world)
 
 
@@ -85,7 +195,12 @@ def main():
     here = os.path.dirname(os.path.abspath(__file__))
     ap.add_argument("--npz", default=os.path.join(here, "..", "tests", "golden", "scans13_fps16384.npz"))
     ap.add_argument("--cpu", action="store_true", help="BASELINE config 1: CD-L1 only, plain torch on the CPU (plumbing, no GPU)")
+    ap.add_argument("--uhd", nargs=2, metavar=("PARTIAL.ply", "COMPLETE.ply"),
+                    help="directed Hausdorff distance partial -> complete of two PLY clouds (the reference's UHD), printed x100")
     args = ap.parse_args()
+    if args.uhd:
+        print(f"UHD: {UHD(*args.uhd) * 100:.2f}")                                   # metric.py:195
+        return
     if args.cpu:
         z = np.load(args.npz)
         cd = cd_l1_cpu_plumbing(torch.from_numpy(z["partial"]), torch.from_numpy(z["gt"]))

@@ -33,7 +33,7 @@ extern "C" {
 #define GENPC_ARITH_FMA 1
 
 /* Library / device ------------------------------------------------------- */
-int genpc_abi_version(void);              /* bumps when a signature or a documented behaviour changes (18: genpc_knn_query added;
+int genpc_abi_version(void);              /* bumps when a signature or a documented behaviour changes (19: genpc_uhd added; 18: genpc_knn_query added;
                                            * 17: genpc_fps_tune takes 0 or 256 only; 16: genpc_hpr_* asynchronous, counts -1 on an internal error;
                                            * genpc_fps*: out_idx[0] -2 = failed the check) */
 const char *genpc_last_error(void);       /* last HIP error string, "" if none */
@@ -467,6 +467,23 @@ int genpc_knn_mean_distance(int n, const float *xyz, int k, float *mean_out,
  * NT < 1 with NQ > 0; 1 at once for NQ == 0 or B == 0.                                                                */
 int genpc_knn_query(int b, int nq, const float *xyz, int nt, const float *xyz2, int k,
                     float *dist, int *idx, void *stream);
+
+/* Directed Hausdorff distance (UHD) ------------------------------------------ *
+ * From the queries xyz[B,N,3] to the targets xyz2[B,M,3] (fp32, device), exact in fp64: the coordinates are widened and
+ * every pair's s = ((dx*dx) + (dy*dy)) + (dz*dz), d = query - target, is evaluated in fp64 in that order with no fused
+ * multiply-add -- scipy's cdist(.., 'euclidean') before its sqrt, which is what the reference's UHD (metric.py:105-132)
+ * takes min over axis 1 and max of.  out_d2[B] (fp64) = max_i min_j s_ij: sqrt is monotone, so sqrt(out_d2) has the bits
+ * of the reference's hd.  out_ij[B,2] = the witness (i*, j*): i* the lowest query index that attains the maximum, j* the
+ * lowest target index that attains query i*'s minimum, both judged on the fp64 s (numpy's argmax / argmin).
+ * Non-finite coordinates: a pair whose s is NaN is skipped (the minimum is IEEE minNum), a query all of whose pairs are
+ * NaN has the minimum +inf; so out_d2 is never NaN, it is +inf if any query has no finite pair or an infinite minimum,
+ * i* is always a valid query index, and j* is -1 when no target of i* attains its minimum (every pair NaN).  numpy
+ * returns NaN there; finite input is the contract.
+ * Asynchronous on `stream`, scratch from the library's workspace, no host read-back (csrc/uhd.hip).  Returns 0 on success;
+ * 1 with nothing written if B == 0; -1 with genpc_last_error set and nothing written if N <= 0, M <= 0, a pointer is
+ * null, or the problem is too large for one launch (B > 65535, N > 2^30, M > 65535 * 512).                            */
+int genpc_uhd(int b, int n, const float *xyz, int m, const float *xyz2,
+              double *out_d2, int *out_ij, void *stream);
 
 #ifdef __cplusplus
 }
