@@ -76,6 +76,23 @@ __device__ __forceinline__ int wave_scan_incl(int x)
     return x;
 }
 
+// The squared distance of every search, in the two arithmetic modes of the library (arith_mode()): fused, or every product
+// and sum rounded on its own.  The one definition: the bit-exact tests rest on it.
+template <int FMA>
+__device__ __forceinline__ float sqdist(float dx, float dy, float dz)
+{
+    if (FMA) {
+        float t = __fmul_rn(dy, dy);
+        t = __fmaf_rn(dx, dx, t);
+        return __fmaf_rn(dz, dz, t);
+    } else {
+        float a = __fmul_rn(dx, dx);
+        float b = __fmul_rn(dy, dy);
+        float c = __fmul_rn(dz, dz);
+        return __fadd_rn(__fadd_rn(a, b), c);
+    }
+}
+
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 inline long long ceil_div64(long long a, long long b) { return (a + b - 1) / b; }
 

@@ -13,26 +13,11 @@ constexpr int kZMax = 4;            // object slices per bidder group in the lat
 constexpr int kSplitMaxBidders = 4096;   // bidders per batch element the split scratch can hold
 constexpr int kArrivePerBatch = 1024;    // arrival counters per batch element (>= kSplitMaxBidders * 64 / 256)
 
-template <int FMA>
-__device__ __forceinline__ float sqdist_e(float dx, float dy, float dz)
-{
-    if (FMA) {
-        float t = __fmul_rn(dy, dy);
-        t = __fmaf_rn(dx, dx, t);
-        return __fmaf_rn(dz, dz, t);
-    } else {
-        float a = __fmul_rn(dx, dx);
-        float b = __fmul_rn(dy, dy);
-        float c = __fmul_rn(dz, dz);
-        return __fadd_rn(__fadd_rn(a, b), c);
-    }
-}
-
 // emd_cuda.cu:142-146
 template <int FMA>
 __device__ __forceinline__ float bid_value(float x1, float y1, float z1, float x2, float y2, float z2, float price)
 {
-    float s = sqdist_e<FMA>(x2 - x1, y2 - y1, z2 - z1);
+    float s = sqdist<FMA>(x2 - x1, y2 - y1, z2 - z1);
     float r = sqrtf(s);   // correctly rounded (hipcc default); __fsqrt_rn is the ~1 ulp native sqrt
     return (float)((3.0 - (double)r) - (double)price);
 }

@@ -213,7 +213,7 @@ __global__ __launch_bounds__(kEBlock) void emd_bid_kernel(int n, const float *__
             // without the filter.
             // Four CONSECUTIVE objects per lane and iteration (4*P divides every tile length: n % 256 == 0,
             // P <= 64), evaluated two per instruction (packed fp32: same operations, same roundings as
-            // sqdist_e and filter_cb's test); a lane's verdicts stay in SGPRs (one ballot per object), so a
+            // sqdist and filter_cb's test); a lane's verdicts stay in SGPRs (one ballot per object), so a
             // group none of whose members can matter costs 16 packed operations, 4 compares and one scalar branch
             // (28 instead of 51 instructions per four objects; in-run A/B with the 1024-object tiles: 13 x 16384 7.68 ->
             // 7.31 ms, 8 x 32768 16.05 -> 15.05 -- with 2048-object tiles and half the resident waves it LOST 6 %;
@@ -640,7 +640,7 @@ __global__ __launch_bounds__(kEBlock) void emd_calc_dist_kernel(long long total,
     }
     const float *p1 = xyz1 + t * 3;
     const float *p2 = xyz2 + (i * n + k) * 3;
-    dist[t] = sqdist_e<FMA>(p1[0] - p2[0], p1[1] - p2[1], p1[2] - p2[2]);
+    dist[t] = sqdist<FMA>(p1[0] - p2[0], p1[1] - p2[1], p1[2] - p2[2]);
 }
 
 // emd_cuda.cu:284-300

@@ -295,7 +295,7 @@ __global__ __launch_bounds__(kABlock, 4) void emd_auction_kernel(EmdAuction a)
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
                     auto test = [&](const F3A &o, float w, int pos, bool in) -> bool {
                         if (!in) return false;
-                        const float sq = sqdist_e<FMA>(o.x - x1, o.y - y1, o.z - z1);
+                        const float sq = sqdist<FMA>(o.x - x1, o.y - y1, o.z - z1);
                         if (mode == 2) {
                             const float key = sqrtf(sq) + w;
                             if (key < k1) { k2 = k1; q2 = q1; k1 = key; q1 = pos; }
@@ -572,7 +572,7 @@ __global__ __launch_bounds__(kABlock, 4) void emd_auction_kernel(EmdAuction a)
         a.dist[base + j] = 0.0f;            // iters == 0: the reference would read out of bounds
     } else {
         const float *p2 = X2 + (size_t)my_asg * 3;
-        a.dist[base + j] = sqdist_e<FMA>(X1[(size_t)j * 3 + 0] - p2[0], X1[(size_t)j * 3 + 1] - p2[1], X1[(size_t)j * 3 + 2] - p2[2]);
+        a.dist[base + j] = sqdist<FMA>(X1[(size_t)j * 3 + 0] - p2[0], X1[(size_t)j * 3 + 1] - p2[1], X1[(size_t)j * 3 + 2] - p2[2]);
     }
 }
 

@@ -179,7 +179,7 @@ __global__ __launch_bounds__(kEBlock) __attribute__((amdgpu_waves_per_eu(4, 8)))
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             auto test = [&](const float4 &o, int pos, bool in) -> bool {
                 if (!in) return false;
-                const float sq = sqdist_e<FMA>(o.x - x1, o.y - y1, o.z - z1);
+                const float sq = sqdist<FMA>(o.x - x1, o.y - y1, o.z - z1);
                 if (mode == 2) {
                     const float key = sqrtf(sq) + o.w;
                     if (key < k1) { k2 = k1; q2 = q1; k1 = key; q1 = pos; }

@@ -63,21 +63,6 @@ struct FpsJobs {
     int segoff[kFMaxJobs];       // first point of the job in the verification's per-(point, segment) minima
 };
 
-template <int FMA>
-__device__ __forceinline__ float sqdist_f(float dx, float dy, float dz)
-{
-    if (FMA) {
-        float t = __fmul_rn(dy, dy);
-        t = __fmaf_rn(dx, dx, t);
-        return __fmaf_rn(dz, dz, t);
-    } else {
-        float a = __fmul_rn(dx, dx);
-        float b = __fmul_rn(dy, dy);
-        float c = __fmul_rn(dz, dz);
-        return __fadd_rn(__fadd_rn(a, b), c);
-    }
-}
-
 // Wave-wide integer max / min, uniform result, in seven instructions: four row rotations (each one v_max_i32 with a
 // DPP operand -- written in assembly: the compiler emits v_mov_b32 + v_mov_b32_dpp + v_max_i32 per step) leave every
 // row's result in all of its lanes, row_bcast:15 / row_bcast:31 fold the rows into lane 63, one v_readlane fetches it.
@@ -297,7 +282,7 @@ static __device__ __forceinline__ void fps_body(const FpsJobs &jobs, FpsSlot *sl
                     for (int r = 0; r < R; r++) {
                         float dx = px[r] - cx, dy = py[r] - cy, dz = pz[r] - cz;
                         asm volatile("" : "+v"(dx), "+v"(dy), "+v"(dz));
-                        float dd = sqdist_f<FMA>(dx, dy, dz);
+                        float dd = sqdist<FMA>(dx, dy, dz);
                         asm volatile("" : "+v"(dd));
                         d[r] = d[r] < dd ? d[r] : dd;       // padding slots stay at -1
                     }
@@ -470,7 +455,7 @@ static __device__ __forceinline__ void fps_body(const FpsJobs &jobs, FpsSlot *sl
                 // (one candidate at a time, like the workers' update: no packed fp32 instructions)
                 float dx = cxs[c] - qx, dy = cys[c] - qy, dz = czs[c] - qz;
                 asm volatile("" : "+v"(dx), "+v"(dy), "+v"(dz));
-                float dd = sqdist_f<FMA>(dx, dy, dz);
+                float dd = sqdist<FMA>(dx, dy, dz);
                 asm volatile("" : "+v"(dd));
                 cd[c] = cd[c] < dd ? cd[c] : dd;        // dead entries stay at -2
             }
@@ -558,7 +543,7 @@ __global__ __launch_bounds__(kFVBlock) void fps_verify_kernel(FpsJobs jobs, floa
 #pragma unroll
                 for (int u = 0; u < 8; u++) q[u] = s_s[t + u];
 #pragma unroll
-                for (int u = 0; u < 8; u++) dd[u] = sqdist_f<FMA>(px - q[u].x, py - q[u].y, pz - q[u].z);
+                for (int u = 0; u < 8; u++) dd[u] = sqdist<FMA>(px - q[u].x, py - q[u].y, pz - q[u].z);
                 if (!CHECK) {
 #pragma unroll
                     for (int u = 0; u < 8; u++) D = D < dd[u] ? D : dd[u];
@@ -589,7 +574,7 @@ __global__ __launch_bounds__(kFVBlock) void fps_verify_kernel(FpsJobs jobs, floa
             }
             for (; t < cnt; t++) {
                 const float4 q = s_s[t];
-                const float dd = sqdist_f<FMA>(px - q.x, py - q.y, pz - q.z);
+                const float dd = sqdist<FMA>(px - q.x, py - q.y, pz - q.z);
                 D = D < dd ? D : dd;
                 const int sj = s_i[t];
                 if (CHECK) bad |= !(D < q.w || (D == q.w && i >= sj)) || (i == sj && D != q.w);

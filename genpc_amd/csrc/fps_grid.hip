@@ -63,19 +63,6 @@ __host__ __device__ inline size_t fps_grid_lds(int n)
     return (size_t)npad * 4 + (size_t)(npad / 8) * 4 + (size_t)(cmaxn + 8) * 2 + (size_t)kGQueue * 4 + 1792 * 4;
 }
 
-template <int FMA>
-__device__ __forceinline__ float gsq(float dx, float dy, float dz)
-{
-    if (FMA) {
-        float t = __fmul_rn(dy, dy);
-        t = __fmaf_rn(dx, dx, t);
-        return __fmaf_rn(dz, dz, t);
-    } else {
-        const float a = __fmul_rn(dx, dx), b = __fmul_rn(dy, dy), c = __fmul_rn(dz, dz);
-        return __fadd_rn(__fadd_rn(a, b), c);
-    }
-}
-
 // q / d for 0 <= q < 2^19 / d (rd = 1 / d rounded): (q + 1/2) / d is never within rounding of an integer
 __device__ __forceinline__ int gdiv(int q, float rd) { return (int)(((float)q + 0.5f) * rd); }
 
@@ -270,7 +257,7 @@ __global__ __launch_bounds__(kGT) void fps_grid_kernel(FpsGridJobs jobs, int *__
 #pragma unroll
         for (int u = 0; u < 8; u++) {
             if (u < cn) {
-                const float dd = gsq<FMA>(v[u].x - px, v[u].y - py, v[u].z - pz);
+                const float dd = sqdist<FMA>(v[u].x - px, v[u].y - py, v[u].z - pz);
                 atomicMin(&D[a + u], __float_as_uint(dd));
             }
         }
@@ -519,7 +506,7 @@ __global__ __launch_bounds__(kGT) void fps_grid_kernel(FpsGridJobs jobs, int *__
                             const float4 qj = cq[j0 + jj];
                             const int ij = cidx[j0 + jj];
                             const bool front = (qj.w > qi.w) | ((qj.w == qi.w) & (ij < ii));
-                            const float dd = gsq<FMA>(qi.x - qj.x, qi.y - qj.y, qi.z - qj.z);
+                            const float dd = sqdist<FMA>(qi.x - qj.x, qi.y - qj.y, qi.z - qj.z);
                             r += front ? 1 : 0;
                             low |= front & (dd < qi.w);
                         }
@@ -553,7 +540,7 @@ __global__ __launch_bounds__(kGT) void fps_grid_kernel(FpsGridJobs jobs, int *__
                     if (qi.w >= 0.0f) {
                         float mnew = qi.w;
                         for (int jq = Ltot - Lsub + part; jq < Ltot; jq += kGT / kGCand) {
-                            const float dd = gsq<FMA>(qi.x - sx[jq], qi.y - sy[jq], qi.z - sz[jq]);
+                            const float dd = sqdist<FMA>(qi.x - sx[jq], qi.y - sy[jq], qi.z - sz[jq]);
                             mnew = mnew < dd ? mnew : dd;
                         }
                         if (mnew < qi.w) atomicMin((unsigned *)&cq[i].w, __float_as_uint(mnew));

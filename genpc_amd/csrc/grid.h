@@ -1,6 +1,7 @@
 // grid.h -- the uniform grid under every pruned search of the library (nn_grid.hip, emd_grid.hip, emd_auction.hip,
-// nn_seeded.hip): the frame of a grid, the cell function, the sizing, the pieces of the LDS counting sort that the build
-// kernels share, and the bound by which a cell or a row of cells is skipped.
+// nn_seeded.hip, knn_query.hip): the frame of a grid, the cell function, the sizing, the pieces of the LDS counting sort
+// that the build kernels share, the bound by which a cell or a row of cells is skipped, and the walk over shells of cells
+// of the k-nearest search.
 //
 // Bound.  cell(p) = clamp(floor(fl(fl(p - lo) * inv)), 0, G - 1) is monotone in p, and a point of
 // cell c satisfies  lo + c h (1 - 3u) <= p < lo + (c + 1) h (1 + 3u)  (u = 2^-24, h = 1 / inv;
@@ -191,5 +192,61 @@ struct CellGridHdr : GridFrame {     // one per batch element, written by cell_g
 // = point when not null.
 int launch_cell_grid_build(int b, int n, const float *xyz, const float *price, CellGridHdr *hdr, int *start, float4 *sorted, int *pos_of,
                            int *orig_of, int cells_target, int cells_max, hipStream_t st, float *price_sep = nullptr);
+
+// The walk of a k-nearest search (knn_query.hip) over a grid built by launch_cell_grid_build: ST = its start[].
+// The lane walks shells of cells by Chebyshev distance r = 0, 1, 2 ... from the (clamped) cell of its query (qx, qy, qz).
+// kth() is the caller's current k-th best distance, +inf while its list is short; run(p0, p1) visits the sorted positions
+// [p0, p1).  A row, or a cell of an inner row, is skipped only if the Bound at the top is STRICTLY above kth() (ties with lower
+// indices are still found); the walk stops once every cell outside the shells visited so far is that far, or at the grid's
+// border.  While kth() is +inf nothing is above it.  The bounds are grid_gap / grid_slack / kGridShrink themselves.  A cloud
+// with a non-finite coordinate (H.bad) is walked without culling: every cell is visited.
+template <typename Kth, typename Run>
+__device__ __forceinline__ void cell_grid_shell_walk(const CellGridHdr &H, const int *__restrict__ ST, float qx, float qy, float qz, Kth kth, Run run)
+{
+    const int gx = H.g[0], gy = H.g[1], gz = H.g[2];
+    const float h = H.h;
+    const bool cull = !H.bad;
+    const float sx = grid_slack(H.slack[0], qx), sy = grid_slack(H.slack[1], qy), sz = grid_slack(H.slack[2], qz);
+    const int cx = grid_cell1(qx, H.lo[0], H.inv, gx), cy = grid_cell1(qy, H.lo[1], H.inv, gy), cz = grid_cell1(qz, H.lo[2], H.inv, gz);
+    const int rmax = max(max(max(cx, gx - 1 - cx), max(cy, gy - 1 - cy)), max(cz, gz - 1 - cz));
+    for (int r = 0;; r++) {
+        const int z0 = max(cz - r, 0), z1 = min(cz + r, gz - 1), y0 = max(cy - r, 0), y1 = min(cy + r, gy - 1);
+        const int x0 = max(cx - r, 0), x1 = min(cx + r, gx - 1);
+        for (int z = z0; z <= z1; z++) {
+            const bool zface = z == cz - r || z == cz + r;
+            const float gzv = grid_gap(z, 1, gz, H.lo[2], h, qz, sz);
+            for (int y = y0; y <= y1; y++) {
+                const float gyv = grid_gap(y, 1, gy, H.lo[1], h, qy, sy);
+                const float lb0 = __fmaf_rn(gyv, gyv, __fmul_rn(gzv, gzv));
+                if (cull && lb0 * kGridShrink > kth()) continue;          // strictly farther than the k-th best: not even a tie
+                const int row = (z * gy + y) * gx;
+                if (zface || y == cy - r || y == cy + r) {                 // a row of the shell's faces: one run
+                    run(ST[row + x0], ST[row + x1 + 1]);
+                } else {                                                   // an inner row: the shell's two cells (r > 0 here)
+                    if (cx - r >= 0) {
+                        const float gxv = grid_gap(cx - r, 1, gx, H.lo[0], h, qx, sx);
+                        if (!(cull && __fmaf_rn(gxv, gxv, lb0) * kGridShrink > kth())) run(ST[row + cx - r], ST[row + cx - r + 1]);
+                    }
+                    if (cx + r < gx) {
+                        const float gxv = grid_gap(cx + r, 1, gx, H.lo[0], h, qx, sx);
+                        if (!(cull && __fmaf_rn(gxv, gxv, lb0) * kGridShrink > kth())) run(ST[row + cx + r], ST[row + cx + r + 1]);
+                    }
+                }
+            }
+        }
+        if (r >= rmax) break;                // the whole grid has been visited
+        if (cull) {
+            // every cell not yet visited lies in one of the (at most six) slabs beyond the shell
+            float m = __builtin_inff();
+            if (cx - r > 0) m = fminf(m, grid_gap(0, cx - r, gx, H.lo[0], h, qx, sx));
+            if (cx + r + 1 < gx) m = fminf(m, grid_gap(cx + r + 1, gx - (cx + r + 1), gx, H.lo[0], h, qx, sx));
+            if (cy - r > 0) m = fminf(m, grid_gap(0, cy - r, gy, H.lo[1], h, qy, sy));
+            if (cy + r + 1 < gy) m = fminf(m, grid_gap(cy + r + 1, gy - (cy + r + 1), gy, H.lo[1], h, qy, sy));
+            if (cz - r > 0) m = fminf(m, grid_gap(0, cz - r, gz, H.lo[2], h, qz, sz));
+            if (cz + r + 1 < gz) m = fminf(m, grid_gap(cz + r + 1, gz - (cz + r + 1), gz, H.lo[2], h, qz, sz));
+            if (__fmul_rn(m, m) * kGridShrink > kth()) break;
+        }
+    }
+}
 
 }  // namespace genpc

@@ -21,21 +21,6 @@ namespace genpc {
 
 constexpr int kKTile = 1024;
 
-template <int FMA>
-__device__ __forceinline__ float sqdist_k(float dx, float dy, float dz)
-{
-    if (FMA) {
-        float t = __fmul_rn(dy, dy);
-        t = __fmaf_rn(dx, dx, t);
-        return __fmaf_rn(dz, dz, t);
-    } else {
-        float a = __fmul_rn(dx, dx);
-        float b = __fmul_rn(dy, dy);
-        float c = __fmul_rn(dz, dz);
-        return __fadd_rn(__fadd_rn(a, b), c);
-    }
-}
-
 template <int K, int FMA>
 __global__ __launch_bounds__(kWave) void knn_mean_kernel(int n, const float *__restrict__ xyz,
                                                          float *__restrict__ mean_out)
@@ -67,10 +52,10 @@ __global__ __launch_bounds__(kWave) void knn_mean_kernel(int n, const float *__r
         for (int g = 0; g < tn_pad / 4; g++) {
             const float4 X = tile[g * 3 + 0], Y = tile[g * 3 + 1], Z = tile[g * 3 + 2];
             float d[4];
-            d[0] = sqdist_k<FMA>(X.x - qx, Y.x - qy, Z.x - qz);
-            d[1] = sqdist_k<FMA>(X.y - qx, Y.y - qy, Z.y - qz);
-            d[2] = sqdist_k<FMA>(X.z - qx, Y.z - qy, Z.z - qz);
-            d[3] = sqdist_k<FMA>(X.w - qx, Y.w - qy, Z.w - qz);
+            d[0] = sqdist<FMA>(X.x - qx, Y.x - qy, Z.x - qz);
+            d[1] = sqdist<FMA>(X.y - qx, Y.y - qy, Z.y - qz);
+            d[2] = sqdist<FMA>(X.z - qx, Y.z - qy, Z.z - qz);
+            d[3] = sqdist<FMA>(X.w - qx, Y.w - qy, Z.w - qz);
             const float dmin = fminf(fminf(d[0], d[1]), fminf(d[2], d[3]));
             if (__any(dmin < t[K - 1])) {
 #pragma unroll
@@ -108,7 +93,7 @@ __global__ __launch_bounds__(kWave) void knn_mean_kernel(int n, const float *__r
 // in order of Chebyshev distance r = 0, 1, 2 ... (a row of a shell's face is one run of the sorted array) and stops once its
 // K-th best squared distance is no larger than what any unvisited cell can hold, (r h - 2 eps)^2 (1 - 1e-5): eps covers the
 // rounding of the cell assignment, the factor that of the distance itself.  The K smallest squared distances are the same
-// multiset as the exhaustive search's (the same sqdist_k arithmetic), so the ascending list and the mean are the same bits.
+// multiset as the exhaustive search's (the same sqdist arithmetic), so the ascending list and the mean are the same bits.
 struct KnnGrid {
     float lo[3], h, inv_h, eps;
     int c[3];
@@ -257,7 +242,7 @@ __global__ __launch_bounds__(kKGBlock) void knn_grid_kernel(int n, const float4 
         const unsigned b = a ? cend[a - 1] : 0u, e = cend[z];
         for (unsigned u = b; u < e; u++) {
             const float4 v = P[u];
-            const float d = sqdist_k<FMA>(v.x - me.x, v.y - me.y, v.z - me.z);
+            const float d = sqdist<FMA>(v.x - me.x, v.y - me.y, v.z - me.z);
             if (d < t[K - 1]) {
 #pragma unroll
                 for (int i = K - 1; i > 0; i--) t[i] = __builtin_amdgcn_fmed3f(d, t[i - 1], t[i]);

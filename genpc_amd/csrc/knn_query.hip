@@ -12,13 +12,9 @@
 //     first, and the same order decides which of several equal candidates holds the k-th place.  The list has CAP entries
 //     (4, 8, 16 or 32, the next capacity above k); its first CAP - k entries are pinned to key 0, below every candidate, so
 //     the k-th best is always the LAST entry and the call's k results are the last k;
-//   * the lane walks shells of cells by Chebyshev distance r = 0, 1, 2 ... from its own (clamped) cell.  A row, or a cell of an
-//     inner row, is skipped only if grid.h's bound is STRICTLY above the k-th best distance (ties with lower indices are still
-//     found); the walk stops once every cell outside the shells visited so far is that far, or at the grid's border.  While
-//     fewer than k candidates are listed the k-th best is +inf and nothing is above it.  The bounds are grid_gap /
-//     grid_slack / kGridShrink themselves;
-//   * the distance is sqdist<FMA> of nn.h in the call's arithmetic mode: column 0 holds the bits of genpc_nm_distance.  Only
-//     candidates with d < +inf are listed (NaN and infinite distances never enter); slots past the listed ones hold
+//   * the lane visits the targets by grid.h's cell_grid_shell_walk, which skips and stops against that k-th best;
+//   * the distance is sqdist<FMA> of common.h in the call's arithmetic mode: column 0 holds the bits of genpc_nm_distance.
+//     Only candidates with d < +inf are listed (NaN and infinite distances never enter); slots past the listed ones hold
 //     (+inf, -1).  A target cloud with a non-finite coordinate (CellGridHdr.bad) is searched without culling.
 // One path for every size: a tiny or degenerate cloud is a one-cell grid.
 #include "nn.h"
@@ -75,11 +71,6 @@ __global__ __launch_bounds__(kBlock) void knn_query_kernel(KnnQueryArgs a)
     const float4 *__restrict__ S = a.sorted + (size_t)batch * a.nt;
     const int *__restrict__ ST = a.start + (size_t)batch * (a.cells_max + 1);
     const CellGridHdr H = a.hdr[batch];
-    const int gx = H.g[0], gy = H.g[1], gz = H.g[2];
-    const float h = H.h;
-    const bool cull = !H.bad;
-    const float sx = grid_slack(H.slack[0], qx), sy = grid_slack(H.slack[1], qy), sz = grid_slack(H.slack[2], qz);
-    const int cx = grid_cell1(qx, H.lo[0], H.inv, gx), cy = grid_cell1(qy, H.lo[1], H.inv, gy), cz = grid_cell1(qz, H.lo[2], H.inv, gz);
 
     unsigned long long L[CAP];           // ascending; L[0 .. CAP - k) pinned to 0, L[CAP - 1] is the k-th best
 #pragma unroll
@@ -102,45 +93,7 @@ __global__ __launch_bounds__(kBlock) void knn_query_kernel(KnnQueryArgs a)
         }
     };
 
-    const int rmax = max(max(max(cx, gx - 1 - cx), max(cy, gy - 1 - cy)), max(cz, gz - 1 - cz));
-    for (int r = 0;; r++) {
-        const int z0 = max(cz - r, 0), z1 = min(cz + r, gz - 1), y0 = max(cy - r, 0), y1 = min(cy + r, gy - 1);
-        const int x0 = max(cx - r, 0), x1 = min(cx + r, gx - 1);
-        for (int z = z0; z <= z1; z++) {
-            const bool zface = z == cz - r || z == cz + r;
-            const float gzv = grid_gap(z, 1, gz, H.lo[2], h, qz, sz);
-            for (int y = y0; y <= y1; y++) {
-                const float gyv = grid_gap(y, 1, gy, H.lo[1], h, qy, sy);
-                const float lb0 = __fmaf_rn(gyv, gyv, __fmul_rn(gzv, gzv));
-                if (cull && lb0 * kGridShrink > kth()) continue;          // strictly farther than the k-th best: not even a tie
-                const int row = (z * gy + y) * gx;
-                if (zface || y == cy - r || y == cy + r) {                 // a row of the shell's faces: one run
-                    run(ST[row + x0], ST[row + x1 + 1]);
-                } else {                                                   // an inner row: the shell's two cells (r > 0 here)
-                    if (cx - r >= 0) {
-                        const float gxv = grid_gap(cx - r, 1, gx, H.lo[0], h, qx, sx);
-                        if (!(cull && __fmaf_rn(gxv, gxv, lb0) * kGridShrink > kth())) run(ST[row + cx - r], ST[row + cx - r + 1]);
-                    }
-                    if (cx + r < gx) {
-                        const float gxv = grid_gap(cx + r, 1, gx, H.lo[0], h, qx, sx);
-                        if (!(cull && __fmaf_rn(gxv, gxv, lb0) * kGridShrink > kth())) run(ST[row + cx + r], ST[row + cx + r + 1]);
-                    }
-                }
-            }
-        }
-        if (r >= rmax) break;                // the whole grid has been visited
-        if (cull) {
-            // every cell not yet visited lies in one of the (at most six) slabs beyond the shell
-            float m = __builtin_inff();
-            if (cx - r > 0) m = fminf(m, grid_gap(0, cx - r, gx, H.lo[0], h, qx, sx));
-            if (cx + r + 1 < gx) m = fminf(m, grid_gap(cx + r + 1, gx - (cx + r + 1), gx, H.lo[0], h, qx, sx));
-            if (cy - r > 0) m = fminf(m, grid_gap(0, cy - r, gy, H.lo[1], h, qy, sy));
-            if (cy + r + 1 < gy) m = fminf(m, grid_gap(cy + r + 1, gy - (cy + r + 1), gy, H.lo[1], h, qy, sy));
-            if (cz - r > 0) m = fminf(m, grid_gap(0, cz - r, gz, H.lo[2], h, qz, sz));
-            if (cz + r + 1 < gz) m = fminf(m, grid_gap(cz + r + 1, gz - (cz + r + 1), gz, H.lo[2], h, qz, sz));
-            if (__fmul_rn(m, m) * kGridShrink > kth()) break;
-        }
-    }
+    cell_grid_shell_walk(H, ST, qx, qy, qz, kth, run);
     float *od = a.out_d + ((size_t)batch * a.nq + j) * a.k;
     int *oi = a.out_i + ((size_t)batch * a.nq + j) * a.k;
     const int skip = CAP - a.k;

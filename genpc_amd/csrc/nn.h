@@ -1,6 +1,6 @@
 // nn.h -- declarations shared by the nearest-neighbour kernels (chamfer.hip: VALU and
-// fp32-MFMA paths, nn_f16.hip + nn_finish.hip: split-f16 MFMA filter and its exact finish): launch descriptor, the
-// reference's distance arithmetic, candidate lists and the exact re-scan.
+// fp32-MFMA paths, nn_f16.hip + nn_finish.hip: split-f16 MFMA filter and its exact finish): launch descriptor,
+// candidate lists and the exact re-scan (the distance arithmetic is common.h's sqdist).
 #pragma once
 #include "common.h"
 #include "grid.h"
@@ -10,21 +10,6 @@ namespace genpc {
 constexpr int kChunk = 32;       // targets per min-only chunk (re-scan granularity)
 constexpr int kBlock = 256;      // 4 waves
 constexpr int kWavesPerBlock = kBlock / kWave;
-
-template <int FMA>
-__device__ __forceinline__ float sqdist(float dx, float dy, float dz)
-{
-    if (FMA) {
-        float t = __fmul_rn(dy, dy);
-        t = __fmaf_rn(dx, dx, t);
-        return __fmaf_rn(dz, dz, t);
-    } else {
-        float a = __fmul_rn(dx, dx);
-        float b = __fmul_rn(dy, dy);
-        float c = __fmul_rn(dz, dz);
-        return __fadd_rn(__fadd_rn(a, b), c);
-    }
-}
 
 struct NNDir {
     const float *q;    // queries  [B, nq, 3]
