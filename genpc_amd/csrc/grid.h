@@ -1,5 +1,5 @@
 // grid.h -- the uniform grid under every pruned search of the library (nn_grid.hip, emd_grid.hip, emd_auction.hip,
-// nn_seeded.hip, knn_query.hip): the frame of a grid, the cell function, the sizing, the pieces of the LDS counting sort
+// nn_seeded.hip, knn_query.hip, knn.hip): the frame of a grid, the cell function, the sizing, the pieces of the LDS counting sort
 // that the build kernels share, the bound by which a cell or a row of cells is skipped, and the walk over shells of cells
 // of the k-nearest search.
 //
@@ -193,7 +193,7 @@ struct CellGridHdr : GridFrame {     // one per batch element, written by cell_g
 int launch_cell_grid_build(int b, int n, const float *xyz, const float *price, CellGridHdr *hdr, int *start, float4 *sorted, int *pos_of,
                            int *orig_of, int cells_target, int cells_max, hipStream_t st, float *price_sep = nullptr);
 
-// The walk of a k-nearest search (knn_query.hip) over a grid built by launch_cell_grid_build: ST = its start[].
+// The walk of a k-nearest search (knn_query.hip, knn.hip) over a grid built by launch_cell_grid_build: ST = its start[].
 // The lane walks shells of cells by Chebyshev distance r = 0, 1, 2 ... from the (clamped) cell of its query (qx, qy, qz).
 // kth() is the caller's current k-th best distance, +inf while its list is short; run(p0, p1) visits the sorted positions
 // [p0, p1).  A row, or a cell of an inner row, is skipped only if the Bound at the top is STRICTLY above kth() (ties with lower

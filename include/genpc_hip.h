@@ -451,7 +451,9 @@ int genpc_fps_stats(int c, int *rounds, void *stream);
  * mean_out[N] = mean Euclidean distance of every point to its k nearest points of
  * the same cloud, itself included (the per-point statistic of open3d's
  * remove_statistical_outlier, utils/dataUtils.py:648-662 -> reg_xyz.py:134,217).
- * k in {8, 16, 20, 32}; -1 otherwise.                                           */
+ * k in {8, 16, 20, 32}; -1 otherwise.  NaN and infinite distances are never among the
+ * k: a point with a non-finite coordinate gets 0 / 0 = NaN, every other point the mean
+ * it has without those points.                                                   */
 int genpc_knn_mean_distance(int n, const float *xyz, int k, float *mean_out,
                             void *stream);
 
