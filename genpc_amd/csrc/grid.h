@@ -11,7 +11,9 @@
 // skipped iff  (sum gap_a^2)(1 - 2^-20) > best  (strictly: ties with lower indices are still
 // found).  Underflow only weakens the bound; an overflowing bound equals +inf and is only used
 // against a finite best.  The helpers below ARE that arithmetic: a search that changes an intrinsic, an operand order or
-// an association in its own copy has left the proof behind, which is why there are no copies.
+// an association in its own copy has left the proof behind, which is why there are no copies -- but two, owed: fps_grid.hip
+// (gcell, box_margin, 0.9999f) and icp.hip's icp_fused_kernel (IcpGrid, icp_cell_of, icp_axis_gap) keep grids and margins of
+// their own that nothing here proves (DESIGN_NOTEBOOK.md, "fps_grid.hip and icp_fused_kernel on grid.h").
 #pragma once
 #include "common.h"
 

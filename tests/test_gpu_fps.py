@@ -90,6 +90,48 @@ def test_fps_one_workgroup_kernel_in_the_pipelines_regime(fg, oracle, golden):
         np.testing.assert_array_equal(got, oracle.fps(x, k, mode), err_msg=name + " (against the oracle)")
 
 
+def grid_bound_clouds():
+    """Clouds on which the bound of csrc/grid.h, as fps_grid.hip uses it, has least room (name, cloud, k)."""
+    rng = np.random.default_rng(41)
+    seg = np.zeros((2000, 3), np.float32)
+    seg[:, 0] = rng.random(2000, dtype=np.float32)
+    seg[:, 1:] = np.float32([0.25, -0.5])
+    blob = np.concatenate([rng.random((4000, 3), dtype=np.float32) * np.float32(1e-3), np.full((1, 3), 50.0, np.float32)])
+    far = (rng.random((3000, 3), dtype=np.float32) * np.float32(0.05) + np.float32(1e4)).astype(np.float32)
+    walls = (np.round(np.linspace(0, 64, 16)) / 64.0).astype(np.float32)           # multiples of the extent / 64, exact in fp32
+    lat = np.stack(np.meshgrid(walls, walls, walls, indexing="ij"), -1).reshape(-1, 3)
+    lat = lat[rng.permutation(len(lat))].copy()
+    cases = [("segment 2000", seg, 2000), ("blob of 4000 and one point 50 away", blob, 4001), ("3000 at 1e4", far, 3000)]
+    cases += [("uniform %d" % n, rng.random((n, 3), dtype=np.float32) - np.float32(0.5), n) for n in (63, 64, 65, 1025)]
+    cases.append(("16^3 lattice on cell walls -> 1000", lat, 1000))
+    return cases
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_fps_one_workgroup_kernel_where_the_grid_bound_is_tight(fg, oracle, mode):
+    """The one-workgroup kernel leaves a cell out of an update by the bound of csrc/grid.h: a segment (one cell on two axes, every
+    cell a border cell there), a blob beside one far point (nearly everything in one cell, 64 cells on every axis, the slack set
+    by the grid's width), a cloud at 1e4 whose spacing is a few ulps (the slack is as large as a cell), sizes round the wave
+    and the block (63, 64, 65, 1025), a lattice whose points have coordinates that are multiples of the extent / 64 (the strict
+    comparison and equal distances decide).  Every sequence equals the oracle's AND the multi-workgroup kernel's."""
+    torch = fg["torch"]
+    L = fg["lib"].lib
+    for name, x, k in grid_bound_clouds():
+        X = torch.from_numpy(x).cuda()
+        prev_a = L.genpc_set_arith(mode)
+        try:
+            got = fg["fps"](X, k).cpu().numpy()
+            prev = L.genpc_fps_tune(256)
+            try:
+                old = fg["fps"](X, k).cpu().numpy()
+            finally:
+                L.genpc_fps_tune(prev)
+        finally:
+            L.genpc_set_arith(prev_a)
+        np.testing.assert_array_equal(got, old, err_msg=name + " (against the multi-workgroup kernel)")
+        np.testing.assert_array_equal(got, oracle.fps(x, k, mode), err_msg=name + " (against the oracle)")
+
+
 def test_fps_check_beside_the_callers_stream(fg):
     """genpc_fps_defer: the indices leave without waiting for the device-side check, which runs on copies on a side stream;
     genpc_fps_deferred_check collects the verdict.  Same indices as the in-line form; a check that fails (hook 2 zeroes one

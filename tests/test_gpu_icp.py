@@ -200,6 +200,39 @@ def test_knn_mean_distance_fuzz(rg, oracle):
         np.testing.assert_array_equal(m, oracle.knn_mean_distance(P, k, mode), err_msg="case %d n %d k %d" % (case, n, k))
 
 
+def grid_edge_cases():
+    """Solves in which the grid of the one-workgroup kernel has least room (name, source, target, max_dist)."""
+    rng = np.random.default_rng(29)
+    base = shape(8, 2600)
+    cases = []
+    plane = np.concatenate([rng.random((2000, 2)) - 0.5, np.zeros((2000, 1))], 1).astype(np.float32)
+    src = (plane[::2].astype(np.float64) @ rot([0, 0, 1], 2.0).T + [0.01, -0.006, 0.5 * 0.075]).astype(np.float32)
+    cases.append(("target in a plane, source lifted", src, plane, 0.075))
+    tgt = (base + np.float32(1000.0)).astype(np.float32)
+    cases.append(("offset 1000, max_dist 1e-3", (tgt[::2] + np.float32(2.5e-4)).astype(np.float32), tgt, 1e-3))
+    p = np.float32(0.0625)
+    lat = (np.stack(np.meshgrid(*([np.arange(10)] * 3), indexing="ij"), -1).reshape(-1, 3) * p).astype(np.float32)
+    cases.append(("lattice, source one pitch along x, max_dist = pitch", (lat + np.float32([p, 0, 0])).astype(np.float32), lat, float(p)))
+    cases.append(("source outside on two axes", (base[::4] + np.float32([1.5, 1.5, 0])).astype(np.float32), base, 0.075))
+    cases.append(("one source point", (base[7:8] + np.float32(0.01)).astype(np.float32), base, 0.075))
+    cases.append(("one target point", (base[:40] + np.float32(0.01)).astype(np.float32), base[:1].copy(), 0.075))
+    return cases
+
+
+def test_icp_one_workgroup_grid_edges(rg, oracle):
+    """The assertions of the fuzz below on solves that sit at the edge of what the kernel's grid claims: a target in a plane (one
+    layer of cells) under a source half a max_dist above it, coordinates at 1000 with max_dist = 1e-3 (a cell is a few ulps
+    wide), a lattice of pitch p with max_dist = p under a source moved by exactly p (correspondences at exactly max_dist, one
+    cell away), a source farther than max_dist from the target's box on two axes (no inlier), one source point, one target point."""
+    torch = rg["torch"]
+    for name, src, tgt, md in grid_edge_cases():
+        T, fit, rmse, its = rg["R"].registration_icp(torch.from_numpy(src).cuda(), torch.from_numpy(tgt).cuda(), md)
+        oT, ofit, ormse, oits = oracle.icp(src, tgt, md)
+        assert fit == ofit and its == oits, (name, fit, ofit, its, oits)
+        np.testing.assert_allclose(T, oT, atol=1e-6 * max(1.0, float(np.abs(tgt).max())), err_msg=name)
+        assert abs(rmse - ormse) < 1e-7, name
+
+
 def test_icp_one_workgroup_fuzz(rg, oracle):
     """The one-workgroup solve (csrc/icp.hip icp_fused_kernel: target grid in LDS, 27-cell search) against the oracle's
     exhaustive search on inputs that stress the grid: coordinates far from the origin, a correspondence distance far below
