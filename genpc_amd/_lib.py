@@ -11,7 +11,7 @@ import torch  # noqa: F401  (loads torch's libamdhip64.so.7 first; ours binds to
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GENPC_LIB: an alternative build of the same library (kernel experiments only)
 LIB_PATH = os.environ.get("GENPC_LIB") or os.path.join(_HERE, "lib", "libgenpc_hip.so")
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -79,6 +79,8 @@ SIGNATURES = {
     "genpc_knn_mean_distance": (_i, [_i, _vp, _i, _vp, _vp]),
     "genpc_knn_query": (_i, [_i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp]),
     "genpc_uhd": (_i, [_i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "genpc_mesh_sample_bytes": (_i, [_i]),
+    "genpc_mesh_sample": (_i, [_i, _vp, _vp, _i, _vp, _i, ctypes.c_ulonglong, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 

@@ -12,7 +12,8 @@ over ranks (genpc_amd.sharding) with one all_gather of the per-scan scalars.
 The reference's second evaluation file, ``metric.py``, adds what needs no ground truth: ``UHD`` (:105-132), the directed
 Hausdorff distance from the partial scan to the completed cloud -- the one score of the LiDAR path -- and ``cd_emd``
 (:135-148).  ``uhd`` / ``UHD`` / ``evaluate_uhd`` / ``cd_emd`` below; UHD runs on the library's fp64 all-pairs kernel
-(csrc/uhd.hip) and has the bits of scipy's float64 ``cdist``.
+(csrc/uhd.hip) and has the bits of scipy's float64 ``cdist``.  ``mesh_cd_emd`` is the tensor form of its evaluation of a
+reconstructed mesh against a ground-truth MESH (``metric_sds_redwood``, :49-94), both sampled on the device.
 
     python -m genpc_amd.metric --uhd PARTIAL.ply COMPLETE.ply
 """
@@ -148,6 +149,37 @@ def cd_emd(pcdpath1, pcdpath2):
     pcd1, pcd2 = clouds
     cdloss = Completionloss(loss_func='cd_l1').get_loss(gen=pcd2, gt=pcd1)
     emdloss = Completionloss(loss_func='emd').emd_loss(p1=pcd2, p2=pcd1)
+    return cdloss, emdloss
+
+
+def mesh_cd_emd(gt_vertices, gt_faces, est_vertices, est_faces, seed=0, samples=40000, points=16384):
+    """The reference's evaluation of an estimated mesh against a ground-truth mesh (metric.py:49-94) on tensors: both meshes
+    are translated by the GT's bounding-box centre and scaled by 1 / max(GT extent) (:50-61), each is sampled `samples`
+    times on its surface (:64-65; here on the device, utils/mesh_io.sample_surface_gpu, reproducible from `seed`), both
+    samplings are FPS-subsampled to `points` (:82-87), then CD-L1 and EMD with gen = est, gt = GT (:89-92).  Returns the
+    two 0-d tensors (cdloss, emdloss).  vertices / faces: GPU tensors or numpy arrays.  seed: an int -- both meshes draw
+    the same random words -- or a pair (gt_seed, est_seed).  The reference's visualisation cloud, plane file and OBJ
+    reading (:59,66-81) are not part of it."""
+    from .fps import fps_subsample
+    from .utils.loss_util import Completionloss
+    from .utils.mesh_io import _device_array, sample_surface_gpu
+    seeds = tuple(seed) if isinstance(seed, (tuple, list)) else (seed, seed)
+    if len(seeds) != 2:
+        raise ValueError("mesh_cd_emd: seed is an int or a pair (gt_seed, est_seed)")
+    given = [t for t in (gt_vertices, est_vertices) if torch.is_tensor(t) and t.is_cuda]
+    dev = given[0].device if given else torch.device("cuda", torch.cuda.current_device())
+    gv = _device_array(gt_vertices, torch.float32, dev, "gt_vertices")
+    ev = _device_array(est_vertices, torch.float32, dev, "est_vertices")
+    lo, hi = gv.double().min(0).values, gv.double().max(0).values
+    center, scale = (lo + hi) / 2, 1.0 / (hi - lo).max()
+    clouds = []
+    for v, f, sd in ((gv, gt_faces, seeds[0]), (ev, est_faces, seeds[1])):
+        v = ((v.double() - center) * scale).float()                     # :56-57, :60-61 (open3d moves doubles)
+        pts, _ = sample_surface_gpu(v, f, samples, sd, device=dev)
+        clouds.append(fps_subsample(pts.unsqueeze(0).contiguous(), points).float())
+    gt, est = clouds
+    cdloss = Completionloss(loss_func='cd_l1').get_loss(gen=est, gt=gt)
+    emdloss = Completionloss(loss_func='emd').get_loss(gen=est, gt=gt)
     return cdloss, emdloss
 
 

@@ -176,13 +176,14 @@ def load_point_cloud(point_path, device, radius=0.05, num_points=5000):
 
 def object_pose_optimization(glb_path, point_path, radius=0.005, lr=0.005, iters=300, render_size=224,
                              vis=False, save_path=None, device=None, cam_bias_num=4, return_history=False,
-                             cd_only=False, complete_col=None, partial_col=None):
+                             cd_only=False, complete_col=None, partial_col=None, seed=None):
     """diff_obj_pose.py:496-594, same positional arguments and hyper-parameters, returns the 4x4 numpy
     ``[[sR, t],[0,1]]`` (:464-468).
 
     File form (the reference's): ``glb_path`` / ``point_path`` are paths; the complete cloud is
     sampled from the GLB (120 000 points) and the partial cloud read from the PLY (both voxel
-    down-sampled at ``radius`` with their colours, load_point_cloud).
+    down-sampled at ``radius`` with their colours, load_point_cloud); ``seed`` (an int, file form only) draws those
+    samples on the device, reproducibly (utils/mesh_io.glb2point_gpu).
     Tensor form: ``glb_path`` = complete_xyz [Nc,3] and ``point_path`` = partial_xyz [Np,3] GPU
     tensors -- or [B,Nc,3] / [B,Np,3]: B scans optimised in lock-step, one batched NN launch per Adam
     step (returns [B,4,4]) -- with their colours in ``complete_col`` / ``partial_col`` (None = white).
@@ -199,9 +200,17 @@ def object_pose_optimization(glb_path, point_path, radius=0.005, lr=0.005, iters
         if device is None:
             device = torch.device("cuda:0")
         partial_xyz, partial_col = load_point_cloud(point_path, device, radius=radius, num_points=8000)      # :502
-        complete_xyz, complete_col = load_point_cloud(glb_path, device, radius=radius, num_points=120000)   # :504
+        if seed is None:
+            complete_xyz, complete_col = load_point_cloud(glb_path, device, radius=radius, num_points=120000)   # :504
+        else:                              # the same cloud drawn on the device, reproducibly (colours are in [0,1] already)
+            from ..utils.mesh_io import glb2point_gpu
+            if not glb_path.endswith(".glb"):
+                raise ValueError("Unsupported point cloud format")
+            complete_xyz, complete_col = glb2point_gpu(glb_path, down_sample=radius, num_points=120000, seed=seed, device=device)
         file_form = True
     else:
+        if seed is not None:
+            raise TypeError("object_pose_optimization: seed belongs to the file form (the tensor form samples nothing)")
         complete_xyz, partial_xyz = glb_path, point_path
     batched = complete_xyz.dim() == 3
     complete_xyz = (complete_xyz if batched else complete_xyz[None]).contiguous().float()

@@ -194,7 +194,7 @@ def _is_cfg(x):
     return hasattr(x, "output_path") and not torch.is_tensor(x)
 
 
-def reg(cfg, flag, cd_inv_weight=0.5, diff_init=True, reg_fine_xyz=False, **kwargs):
+def reg(cfg, flag, cd_inv_weight=0.5, diff_init=True, reg_fine_xyz=False, seed=None, **kwargs):
     """reg_xyz.py:99-223, same signature.
 
     (Deviation, file form: the PLY's double coordinates are cast to float32 before the voxel grids hash them; open3d
@@ -204,17 +204,26 @@ def reg(cfg, flag, cd_inv_weight=0.5, diff_init=True, reg_fine_xyz=False, **kwar
     it) and ``{flag}_{cfg.generative_model}.glb`` (the generated mesh; 163 840 surface samples with
     their colours), aligns them and writes ``{flag}_fused.ply`` WITH COLOURS (:207-219); returns the
     dict of `reg_tensors` plus ``fused`` / ``fused_col`` / ``fused_path``.  Raises FileNotFoundError
-    like the reference when an input is missing.
+    like the reference when an input is missing.  ``seed`` (an int; file form only): both samplings of the mesh -- these
+    163 840 and the pose initialisation's 120 000 -- are drawn on the device by ``glb2point_gpu`` and are reproducible from
+    it; with ``seed=None`` the host sampler runs as before (``rng=`` included).  ``seed`` together with ``rng`` raises.
     Tensor form: ``reg(partial_xyz, complete_xyz, ...)`` = `reg_tensors` (no files)."""
     if not _is_cfg(cfg):
+        if seed is not None:
+            raise TypeError("reg(partial_xyz, complete_xyz, ...): seed belongs to the file form (the tensor form samples nothing)")
         return reg_tensors(cfg, flag, cd_inv_weight=cd_inv_weight, diff_init=diff_init, reg_fine_xyz=reg_fine_xyz, **kwargs)
     import os
     from .optim_registration.diff_obj_pose import object_pose_optimization
     from .utils.dataUtils import read_ply, save_ply_xyzrgb
-    from .utils.mesh_io import glb2point
+    from .utils.mesh_io import glb2point, glb2point_gpu
     unknown = set(kwargs) - {"cd_only_pose", "rng"}
-    if unknown:          # (the file form reads two options; anything else -- a misspelt one -- used to be dropped silently: ADVICE r3)
-        raise TypeError("reg(cfg, flag, ...): unexpected keyword argument(s) %s (the file form takes cd_only_pose, rng)" % sorted(unknown))
+    if unknown:          # (the file form reads these options; anything else -- a misspelt one -- used to be dropped silently: ADVICE r3)
+        raise TypeError("reg(cfg, flag, ...): unexpected keyword argument(s) %s (the file form takes cd_only_pose, rng, seed)" % sorted(unknown))
+    if seed is not None:
+        if kwargs.get("rng") is not None:
+            raise TypeError("reg(cfg, flag, ...): seed (the device sampler) and rng (the host sampler) exclude each other")
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+            raise TypeError("reg(cfg, flag, ...): seed must be an int or None, got %r" % (seed,))
     path = cfg.output_path
     ply = f"{path}/{flag}/color_point.ply"
     glb = f"{path}/{flag}/{flag}_{cfg.generative_model}.glb"
@@ -227,9 +236,12 @@ def reg(cfg, flag, cd_inv_weight=0.5, diff_init=True, reg_fine_xyz=False, **kwar
     if diff_init:                                                       # :109-122
         diff_transform = np.linalg.inv(object_pose_optimization(
             glb_path=glb, point_path=ply, radius=0.02, lr=0.01, iters=200, render_size=224, vis=True, device=dev,
-            cd_only=kwargs.get("cd_only_pose", False)).astype(np.float64))
+            cd_only=kwargs.get("cd_only_pose", False), seed=seed).astype(np.float64))
     sxyz, scol = read_ply(ply)                                          # :124 o3d.io.read_point_cloud
-    txyz, tcol = glb2point(glb, num_points=163840, rng=kwargs.get("rng"))                      # :125
+    if seed is None:
+        txyz, tcol = glb2point(glb, num_points=163840, rng=kwargs.get("rng"))                  # :125
+    else:
+        txyz, tcol = glb2point_gpu(glb, num_points=163840, seed=seed, device=dev)              # (device tensors: no upload below)
     if scol is None:
         scol = np.zeros_like(sxyz)                                      # an open3d cloud without colours: fused file stays valid
     out = reg_tensors(torch.as_tensor(sxyz, dtype=torch.float32, device=dev), torch.as_tensor(txyz, dtype=torch.float32, device=dev),

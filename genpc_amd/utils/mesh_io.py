@@ -17,6 +17,10 @@ the "complete" cloud that reg() aligns.  Host-side format code, numpy only.
                probability proportional to area, points by the folded-parallelogram
                trick.  trimesh draws from numpy's unseeded global RNG, so the
                reference's samples are not reproducible; here a Generator is passed.
+``sample_surface_gpu`` / ``glb2point_gpu``  the same sampling on the device (csrc/mesh_sample.hip): counter-based
+               random numbers and integer face weights, so sample i is a function of (mesh, seed, i) alone and the
+               cloud is reproducible from an integer seed on every machine (include/genpc_hip.h: genpc_mesh_sample).
+               The host functions above are untouched by it.
 """
 import base64
 import io
@@ -229,3 +233,119 @@ def _glb2point_full(glb_path, num_points, rng):
     bary = np.stack([1 - b1 - b2, b1, b2], axis=1)
     col = (C[F[fi]] * bary[:, :, None]).sum(axis=1)
     return pts, np.clip(col, 0, 1)
+
+
+# ---------------------------------------------------------------------------
+# The device path: genpc_mesh_sample (csrc/mesh_sample.hip).  Nothing below touches the host sampler above.
+# ---------------------------------------------------------------------------
+MESH_SAMPLE_CHUNK = 1024          # faces per restart of the workspace's cumulative weights (include/genpc_hip.h)
+_WS_HEADER = 256
+
+
+def _device_array(a, dtype, device, name):
+    """`a` as a contiguous device tensor of `dtype`: numpy (or a sequence) is uploaded, a GPU tensor converted in place."""
+    import torch
+    if torch.is_tensor(a):
+        if not a.is_cuda:
+            raise RuntimeError("genpc_amd: GPU tensors only (got a %s tensor for %s); the HIP path has no CPU fallback -- "
+                               "pass numpy arrays to have them uploaded" % (a.device, name))
+        return a.to(dtype).contiguous()
+    np_dtype = np.float32 if dtype == torch.float32 else np.int32
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a), np_dtype)).to(device)
+
+
+def _mesh_sample(vertices, faces, count, seed, colors=None, want_bary=False, device=None):
+    """One genpc_mesh_sample call -> dict(points, face, colors, bary, status (device int32 [1]), workspace (uint8), nf)."""
+    import torch
+    from .. import _lib
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+        raise TypeError("sample_surface_gpu: seed must be an int, got %r" % (seed,))
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError("sample_surface_gpu: seed must be in [0, 2^64)")
+    given = [t for t in (vertices, faces, colors) if torch.is_tensor(t) and t.is_cuda]
+    if device is None:
+        device = given[0].device if given else torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    V = _device_array(vertices, torch.float32, device, "vertices")
+    F = _device_array(faces, torch.int32, device, "faces")
+    C = None if colors is None else _device_array(colors, torch.float32, device, "colors")
+    if V.dim() != 2 or V.shape[1] != 3 or F.dim() != 2 or F.shape[1] != 3:
+        raise ValueError("sample_surface_gpu: vertices [nv,3] and faces [nf,3]")
+    if C is not None and C.shape != V.shape:
+        raise ValueError("sample_surface_gpu: colors must be [nv,3] like vertices")
+    if any(t.device != V.device for t in (F, C) if t is not None):
+        raise ValueError("sample_surface_gpu: vertices, faces and colors are on different devices")
+    nv, nf, count = V.shape[0], F.shape[0], int(count)
+    L = _lib.lib
+    nbytes = L.genpc_mesh_sample_bytes(nf)
+    if nbytes < 0 or count < 1 or nv < 1:
+        raise ValueError("sample_surface_gpu: nv >= 1, 1 <= nf <= 2^24 and count >= 1 are required (nv %d, nf %d, count %d)"
+                         % (nv, nf, count))
+    dev = V.device
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    pts = torch.empty(count, 3, device=dev)
+    fi = torch.empty(count, dtype=torch.int32, device=dev)
+    col = torch.empty(count, 3, device=dev) if C is not None else None
+    bary = torch.empty(count, 3, device=dev) if want_bary else None
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    p = _lib.ptr
+    rc = _lib.on_device_of(V, L.genpc_mesh_sample, nv, p(V), p(C), nf, p(F), count, seed, p(pts), p(col), p(fi), p(bary),
+                           p(status), p(ws))
+    if rc != 1:
+        raise RuntimeError("genpc_mesh_sample failed (%d): %s" % (rc, _lib.last_error()))
+    return dict(points=pts, face=fi, colors=col, bary=bary, status=status, workspace=ws, nf=nf)
+
+
+def mesh_sample_weights(workspace, nf):
+    """The integer face weights a sampling call left in its workspace (layout: include/genpc_hip.h) -> (w, cum), numpy
+    uint64 [nf]: cum is rebuilt from the per-1024-face restarts and the chunk sums, w by differencing."""
+    raw = workspace.cpu().numpy()
+    chunks = (nf + MESH_SAMPLE_CHUNK - 1) // MESH_SAMPLE_CHUNK
+    off = _WS_HEADER + ((nf * 8 + 255) & ~255)
+    local = raw[_WS_HEADER:_WS_HEADER + nf * 8].view(np.uint64)
+    chunk = raw[off:off + chunks * 8].view(np.uint64)
+    before = np.concatenate([np.zeros(1, np.uint64), chunk[:-1]])
+    cum = local + np.repeat(before, MESH_SAMPLE_CHUNK)[:nf]
+    w = np.diff(np.concatenate([np.zeros(1, np.uint64), cum]))
+    return w, cum
+
+
+def sample_surface_gpu(vertices, faces, count, seed, colors=None, return_bary=False, device=None):
+    """`count` area-weighted surface samples drawn on the device, every bit a function of (mesh, seed, sample index): the
+    definition is in include/genpc_hip.h (genpc_mesh_sample) and restated in numpy by tests/mesh_sample_ref.py.  vertices
+    [nv,3], faces [nf,3] and colors [nv,3] are GPU tensors (converted to float32 / int32) or numpy arrays, which are
+    uploaded to `device`; a CPU tensor raises.  Returns device tensors ``(points float32 [count,3], face_index int32
+    [count][, colors float32 [count,3]][, bary float32 [count,3]])``; the barycentric weights are the drawn ones.
+    Waits for one status word: ValueError when a face has an index outside [0, nv), a vertex of a face is not finite, or
+    every face weighs 0 (all degenerate)."""
+    r = _mesh_sample(vertices, faces, count, seed, colors, return_bary, device)
+    if int(r["status"].item()) != 1:
+        raise ValueError("sample_surface_gpu: the mesh cannot be sampled -- a face index outside [0, nv), a non-finite "
+                         "vertex of a face, or all face weights zero (every face degenerate)")
+    out = (r["points"], r["face"])
+    if colors is not None:
+        out += (r["colors"],)
+    if return_bary:
+        out += (r["bary"],)
+    return out
+
+
+def glb2point_gpu(glb_path, down_sample=None, num_points=16384, seed=0, device=None):
+    """`glb2point` with the cloud born on the device and reproducible from `seed`: load_glb on the host, one upload of
+    vertices / faces / colours, sample_surface_gpu, then -- with down_sample -- the library's voxel_down_sample on the same
+    device buffers.  Returns device tensors (points float32 [n,3], colours float32 [n,3]); a file without colours gives 0.5
+    grey.  No array comes back to the host."""
+    import torch
+    V, F, C = load_glb(glb_path)
+    if C is None:
+        pts, _ = sample_surface_gpu(V, F, num_points, seed, device=device)
+        col = torch.full_like(pts, 0.5)
+    else:
+        pts, _, col = sample_surface_gpu(V, F, num_points, seed, colors=C, device=device)
+    if down_sample:
+        from ..reg_xyz import voxel_down_sample
+        pts, col = voxel_down_sample(pts, down_sample, colors=col)
+    return pts, col

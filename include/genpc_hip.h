@@ -33,7 +33,7 @@ extern "C" {
 #define GENPC_ARITH_FMA 1
 
 /* Library / device ------------------------------------------------------- */
-int genpc_abi_version(void);              /* bumps when a signature or a documented behaviour changes (19: genpc_uhd added; 18: genpc_knn_query added;
+int genpc_abi_version(void);              /* bumps when a signature or a documented behaviour changes (20: genpc_mesh_sample added; 19: genpc_uhd added; 18: genpc_knn_query added;
                                            * 17: genpc_fps_tune takes 0 or 256 only; 16: genpc_hpr_* asynchronous, counts -1 on an internal error;
                                            * genpc_fps*: out_idx[0] -2 = failed the check) */
 const char *genpc_last_error(void);       /* last HIP error string, "" if none */
@@ -486,6 +486,43 @@ int genpc_knn_query(int b, int nq, const float *xyz, int nt, const float *xyz2, 
  * null, or the problem is too large for one launch (B > 65535, N > 2^30, M > 65535 * 512).                            */
 int genpc_uhd(int b, int n, const float *xyz, int m, const float *xyz2,
               double *out_d2, int *out_ij, void *stream);
+
+/* Surface samples of a triangle mesh ----------------------------------------- *
+ * count area-weighted samples of the mesh vertices[nv,3] (fp32) / faces[nf,3] (int32), uniform inside a face: the published
+ * algorithm of trimesh.sample.sample_surface (what glb2point draws its clouds with, utils/dataUtils.py:217-250), with this
+ * library's own random numbers and INTEGER face weights, so that every bit of sample i follows from (mesh, seed, i) alone --
+ * not from count, the launch shape or the order of a parallel sum.  The definition:
+ *   areas    face f with vertices v0, v1, v2 widened to fp64: e1 = v1 - v0, e2 = v2 - v0, c = e1 x e2 with every component
+ *            (a*b) - (c*d) = (e1y*e2z - e1z*e2y, e1z*e2x - e1x*e2z, e1x*e2y - e1y*e2x), nothing fused,
+ *            s = ((cx*cx) + (cy*cy)) + (cz*cz), A_f = sqrt(s) correctly rounded (twice the area: the factor cancels).
+ *   weights  Amax = max_f A_f, e = ilogb(Amax), w_f = (uint64) floor(ldexp(A_f, 38 - e)): the largest face weighs
+ *            [2^38, 2^39), a face 2^38 times smaller than the largest -- a degenerate one too -- weighs 0 and is never
+ *            drawn.  cum[f] = sum_{g <= f} w_g in uint64 and W = cum[nf - 1] < 2^63.
+ *   words    (x0, x1, x2, x3) = Philox4x32-10 with counter (i & 0xffffffff, i >> 32, 0, 0) and key
+ *            (seed & 0xffffffff, seed >> 32); multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85.
+ *   face     t = the high 64 bits of (x0 | x1 << 32) * W; the face is the first f with cum[f] > t
+ *            (numpy's searchsorted(cum, t, side="right")).
+ *   place    r1 = (x2 >> 8) * 2^-24, r2 = (x3 >> 8) * 2^-24 in fp32; if r1 + r2 > 1 (the fp32 sum) both are replaced by
+ *            1 - r (exact); b0 = (1 - r1) - r2.  (The one fp32 sum that rounds, 1 + 2^-24 -> 1, is not folded and gives
+ *            b0 = -2^-24: once in 2^24 samples a point lies that far, in units of an edge, outside its face.)
+ *   point    per component in fp64 (v0 + (e1*r1)) + (e2*r2), rounded once to fp32  -> out_xyz[count,3].
+ *   colour   with vertex_colors[nv,3]: ((c0*b0) + (c1*r1)) + (c2*r2) in fp64, rounded to fp32, then x < 0 -> 0, x > 1 -> 1
+ *            -> out_colors[count,3].  The barycentric weights ARE (b0, r1, r2): nothing is solved for.
+ * out_face[count] (the drawn face) and out_bary[count,3] = (b0, r1, r2) are optional (NULL), as are the colours.
+ * *out_status (device int): 1 when done; -1 if a face has an index outside [0, nv) (checked before anything is loaded
+ * through it), if a vertex of a face is not finite (a vertex no face uses may be anything), or if every weight is 0.
+ * With -1 the outputs are unspecified, but every word of them is written and nothing is read or written out of range.
+ * workspace: genpc_mesh_sample_bytes(nf) bytes of device memory (-1: nf outside [1, 2^24]), the caller's.  After the call
+ * it holds, at byte 256, uint64 local[nf] -- cum restarted every 1024 faces (local[f] = cum[f] - cum[1024*(f/1024) - 1]) --
+ * and, at byte 256 + 8 nf rounded up to a multiple of 256, uint64 chunk[ceil(nf / 1024)] = cum[min(1024 (k+1), nf) - 1].
+ * Asynchronous on `stream`: a memset and four launches, no host read-back (csrc/mesh_sample.hip).  Returns 1; -1 with
+ * genpc_last_error set and nothing enqueued for nf < 1, nf > 2^24, count < 1, nv < 1, out_colors without vertex_colors or
+ * a null required pointer.                                                                                            */
+int genpc_mesh_sample_bytes(int nf);
+int genpc_mesh_sample(int nv, const float *vertices, const float *vertex_colors, int nf,
+                      const int *faces, int count, unsigned long long seed, float *out_xyz,
+                      float *out_colors, int *out_face, float *out_bary, int *out_status,
+                      void *workspace, void *stream);
 
 #ifdef __cplusplus
 }
