@@ -804,7 +804,7 @@ int nn_forward(int b, int ndir, const float *q0, int n0, const float *t0, int m0
     a.radius2 = radius2;
     a.debug = t_tune_hooks >= 0 ? t_tune_hooks : cfg.dbg;
     if (a.debug & 512) {
-        a.stats = (unsigned long long *)workspace(12, 256, nullptr, nullptr, 256);      // one block per device, shared by all streams
+        a.stats = (unsigned long long *)workspace(kWsNnStats, 256, nullptr, nullptr, 256);      // one block per device, shared by all streams
         if (!a.stats) return 0;
     }
     const float *qs[2] = {q0, q1};
@@ -980,13 +980,13 @@ int nn_forward(int b, int ndir, const float *q0, int n0, const float *t0, int m0
         // which earlier calls used for partials: it is cleared on the stream first (the kernels hand
         // every counter back as zero, so the 64 KiB invariant survives such a call).
         const size_t cnt_min = (size_t)1 << 16;
-        size_t cnt_bytes = cnt_min;
-        if ((size_t)units * sizeof(int) > cnt_bytes) cnt_bytes = ((size_t)units * sizeof(int) + 255) & ~(size_t)255;
-        char *ws = (char *)workspace(0, cnt_bytes + part * 8, st, nullptr, cnt_min);
-        if (!ws) return 0;
-        if (cnt_bytes > cnt_min && !check(hipMemsetAsync(ws, 0, cnt_bytes, st), "hipMemsetAsync(arrival counters)")) return 0;
-        a.arrive = (int *)ws;
-        unsigned long long *wp = (unsigned long long *)(ws + cnt_bytes);
+        const size_t cnt_ints = std::max(cnt_min / sizeof(int), (size_t)units);
+        unsigned long long *wp;
+        WsLayout L;
+        L.add(a.arrive, cnt_ints);
+        L.add_tail(wp, part);          // (both directions' partials, handed out below)
+        if (!ws_alloc(L, kWsNnForward, st, nullptr, cnt_min)) return 0;
+        if (cnt_ints * sizeof(int) > cnt_min && !check(hipMemsetAsync(a.arrive, 0, (char *)wp - (char *)a.arrive, st), "hipMemsetAsync(arrival counters)")) return 0;
         size_t off = 0;
         for (int d = 0; d < nd; d++) {
             if (a.dir[d].slices > 1 || path == 2) {
@@ -1035,7 +1035,7 @@ int nn_forward(int b, int ndir, const float *q0, int n0, const float *t0, int m0
                     words[nc] = (nn_dedupe_mask_words(b, pn[nc]) + 63) & ~(size_t)63;
                     nc++;
                 }
-                unsigned *mw = (unsigned *)workspace(25, (words[0] + (nc > 1 ? words[1] : 0)) * sizeof(unsigned), st);
+                unsigned *mw = (unsigned *)workspace(kWsNnDupMasks, (words[0] + (nc > 1 ? words[1] : 0)) * sizeof(unsigned), st);
                 if (!mw) return 0;
                 pm[0] = mw;
                 pm[1] = mw + words[0];
@@ -1073,7 +1073,7 @@ GENPC_API int genpc_nn_tune(int path, int hooks)
 GENPC_API int genpc_nn_stats(unsigned long long out[3], int reset, void *stream)
 {
     using namespace genpc;
-    unsigned long long *dev = (unsigned long long *)workspace(12, 256, nullptr, nullptr, 256);
+    unsigned long long *dev = (unsigned long long *)workspace(kWsNnStats, 256, nullptr, nullptr, 256);
     if (!dev) return 0;
     if (!check(hipStreamSynchronize((hipStream_t)stream), "genpc_nn_stats sync")) return 0;
     if (!check(hipMemcpy(out, dev, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost), "genpc_nn_stats copy")) return 0;

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include "ws_layout.h"
 
 #define GENPC_API extern "C" __attribute__((visibility("default")))
 
@@ -27,13 +28,52 @@ const char *tune_env_str(const char *name, const char *what);     // string-valu
 bool check(hipError_t e, const char *what);
 void set_error(const char *msg);
 
-// Grow-only per-device scratch (split-target partial minima, EMD work lists).
-// Stream-ordered use only: every consumer is enqueued on the same stream as
-// its producer, so reuse across calls on one stream is safe; calls on different
-// streams of one device get different slots.
-// If `zero_prefix` > 0 the first zero_prefix bytes of a NEWLY allocated block are
-// zeroed (stream-ordered) and *fresh is set; an existing block is returned as is.
-void *workspace(int slot, size_t bytes, hipStream_t stream, bool *fresh = nullptr, size_t zero_prefix = 0);
+// The slots of the scratch pool.  Two users of one slot on one stream overwrite each other: a new user takes a NEW enumerator
+// (10, 11, 19, 21, 23 and 32 are retired) unless sharing is the point, and then the comment says so.  The values are map keys only.
+enum Ws : int {
+    kWsNnForward = 0,         // chamfer.hip nn_forward: arrival counters (zero between calls) | per-slice partials / lists
+    kWsEmdRounds = 1,         // emd.hip genpc_emd_forward, launch-per-round path: counters | lists | chains | cell grid
+    kWsGetUvs = 2,            // project.hip genpc_get_uvs: per-(camera, slice) boxes | the cameras' keys
+    kWsPoseLossGrad = 3,      // pose.hip genpc_pose_loss_grad: accumulators | state | mask scratch
+    kWsPoseLoop = 4,          // pose.hip genpc_pose_optimize_batch: accumulators | states | posed cloud | neighbours | mask scratch
+    kWsIcp = 5,               // icp.hip genpc_icp_batch (launch-per-pass path): sums | states | clouds | neighbours
+    kWsScaleSearch = 6,       // icp.hip genpc_scale_search_scores: scaled copies | neighbours
+    kWsFps = 7,               // fps.hip genpc_fps_multi: status block | hand-off slots | check scratch.  SHARED: genpc_fps_stats reads the status block of the stream's last call back
+    kWsZbuffer = 8,           // project.hip genpc_zbuffer_visibility: the z-buffers of a camera group
+    kWsNnTmax = 9,            // nn_f16.hip launch_nn_f16: partial maxima of the split targets
+    kWsNnStats = 12,          // chamfer.hip: hook counters, one block per DEVICE (null stream).  SHARED: nn_forward hands it to the kernels, genpc_nn_stats reads it back
+    kWsNnGrid = 13,           // nn_grid.hip launch_nn_grid: headers | cell tables | sorted clouds
+    kWsSplatImage = 14,       // pose.hip genpc_splat_image: mask scratch
+    kWsPoseCdLoss = 15,       // pose.hip genpc_pose_cd_grad: the four losses of the call it wraps
+    kWsVoxel = 16,            // voxel.hip genpc_voxel_down_sample: bounds | keys | indices | sort / scan scratch
+    kWsHpr = 17,              // hpr.hip hpr_run: status header | flipped points | sort buffers | tiles | lists
+    kWsMaskLoss = 18,         // pose.hip genpc_mask_loss: accumulators | mask scratch
+    kWsHprParked = 20,        // hpr.hip hpr_run: the parked points' polygons (sized by GENPC_HPR_PARK_MB)
+    kWsPoseReplicas = 22,     // pose.hip genpc_pose_optimize_batch: the clouds replicated per start (lock-step)
+    kWsDedupeTable = 24,      // nn_dedupe.hip launch_nn_dedupe: hash tables (zeroed whole when new)
+    kWsNnDupMasks = 25,       // chamfer.hip nn_forward: duplicate masks of a call that brought none
+    kWsPoseDupMasks = 26,     // pose.hip genpc_pose_optimize_batch: duplicate masks of both clouds, made once per call
+    kWsIcpDupMasks = 27,      // icp.hip: duplicate masks.  SHARED by genpc_icp_batch and genpc_scale_search_scores: a scan calls them in turn, each makes its masks afresh and is done with them at its last launch
+    kWsEmdStats = 28,         // emd.hip: hook counters, one block per DEVICE (null stream).  SHARED: genpc_emd_forward hands it to the bid kernel, genpc_emd_stats reads it back
+    kWsPoseSeededGrids = 29,  // pose.hip genpc_pose_optimize_batch: both clouds' grids of the seeded search (nn_seeded.hip)
+    kWsHprGlobalPolys = 30,   // hpr.hip hpr_run: polygon buffers of the over-1024-vertex tier
+    kWsEmdAuction = 31,       // emd_auction.hip launch_emd_auction: status block | control words | cell grid | chains.  SHARED: genpc_emd_status reads the status block back
+    kWsPackedImage = 33,      // project.hip genpc_gather_colors: the image as float4 pixels
+    kWsPaintBins = 34,        // project.hip genpc_paint_pixels (binned): histograms | tile totals | entries
+    kWsKnnMean = 35,          // knn.hip launch_knn: the cloud's cell grid
+    kWsKnnQuery = 36,         // knn_query.hip knn_query: the targets' cell grid | query order
+    kWsUhd = 37,              // uhd.hip uhd: per-tile partial maxima | per-block records
+};
+
+// The scratch pool: one grow-only block of device memory per (device, slot, stream); null on failure, the error recorded.
+//  - Stream order is the only protection: a caller enqueues every consumer of its block on `stream`, so the next call on
+//    that stream may reuse it; other streams get blocks of their own (the null stream is a key like any other).
+//  - A block that is too small is replaced, once the stream has drained, by one of max(1 MiB, request + 25 %): contents are lost.
+//  - zero_prefix > 0: the first zero_prefix bytes of a NEW block are zeroed on the stream (the request is at least that long;
+//    zero_prefix >= bytes zeroes the whole allocation, slack included) and *fresh is set; an existing block is returned as it is.
+void *workspace(Ws slot, size_t bytes, hipStream_t stream, bool *fresh = nullptr, size_t zero_prefix = 0);
+// workspace() for L.bytes(), then L.bind() -- how every block of more than one piece is had.  False: no block, or L refused a piece.
+bool ws_alloc(WsLayout &L, Ws slot, hipStream_t stream, bool *fresh = nullptr, size_t zero_prefix = 0);
 int arith_mode();
 // The per-thread modes of the library (each set through its own genpc_*_tune / genpc_set_arith_thread entry point); a host
 // thread that starts worker threads hands them over with genpc_thread_state_export / _import (the lanes of

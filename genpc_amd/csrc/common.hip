@@ -98,7 +98,7 @@ int num_cus()
     return v;
 }
 
-void *workspace(int slot, size_t bytes, hipStream_t stream, bool *fresh, size_t zero_prefix)
+void *workspace(Ws slot, size_t bytes, hipStream_t stream, bool *fresh, size_t zero_prefix)
 {
     if (fresh) *fresh = false;
     if (zero_prefix > bytes) bytes = zero_prefix;
@@ -138,6 +138,14 @@ void *workspace(int slot, size_t bytes, hipStream_t stream, bool *fresh, size_t 
     s.ptr = p;
     s.bytes = want;
     return p;
+}
+
+bool ws_alloc(WsLayout &L, Ws slot, hipStream_t stream, bool *fresh, size_t zero_prefix)
+{
+    if (!L.ok()) { set_error("workspace layout: a piece was refused (WsLayout::kMaxPieces, add_tail)"); return false; }
+    void *base = workspace(slot, L.bytes(), stream, fresh, zero_prefix);
+    if (base) L.bind(base);
+    return base != nullptr;
 }
 
 }  // namespace genpc

@@ -681,7 +681,7 @@ GENPC_API int genpc_emd_tune(int grid, int hooks)
 GENPC_API int genpc_emd_stats(unsigned long long out[8], int reset, void *stream)
 {
     using namespace genpc;
-    unsigned long long *dev = (unsigned long long *)workspace(28, 256, nullptr, nullptr, 256);
+    unsigned long long *dev = (unsigned long long *)workspace(kWsEmdStats, 256, nullptr, nullptr, 256);
     if (!dev) return 0;
     if (!check(hipStreamSynchronize((hipStream_t)stream), "genpc_emd_stats sync")) return 0;
     if (!check(hipMemcpy(out, dev, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost), "genpc_emd_stats copy")) return 0;
@@ -727,51 +727,38 @@ GENPC_API int genpc_emd_forward(int b, int n, int m, const float *xyz1, const fl
             if (rc >= 0) return rc;
         }
     }
-    // [second bidder list | arrival counters (zeroed on allocation, restored by the
-    //  merging block) | per-slice partial top-2s]
-    const size_t list_bytes = ((size_t)total * sizeof(int) + 255) / 256 * 256;
-    // fixed size (32 batch elements) so that the zeroed prefix never moves between calls
-    const size_t arrive_bytes = (size_t)32 * kArrivePerBatch * sizeof(int);
     // the late-round object split only matters when few batch elements are in flight
     const bool want_split = b <= 32;
-    const size_t parts_bytes = want_split ? (size_t)b * kSplitMaxBidders * kZMax * sizeof(float4) : 0;
-    const size_t second_bytes = ((size_t)total * sizeof(int) + 255) / 256 * 256;
     // bidder chains per object (emd_settle_kernel): head word per object, link word per bidder
     const bool settle = eps >= 0.0f && n <= (1 << 24);
-    // chain_head | chain_next | whead | wnext (8-byte words per object / bidder), chain_cnt | arrived (ints per object)
-    const size_t chain_bytes = settle ? (4 * (size_t)total * sizeof(unsigned long long) + 2 * (size_t)total * sizeof(int) + 255) / 256 * 256 : 0;
     // cell-sorted copy of the objects for the culled bid (emd_grid.hip): needs prices >= 0 (eps >= 0) and the seeds
     const bool grid = (t_emd_grid >= 0 ? t_emd_grid != 0 : (n >= 4096 || (long long)b * n >= 65536)) && eps >= 0.0f;
-    auto al256 = [](size_t v) { return (v + 255) / 256 * 256; };
     const int cells_max = kCellGridMaxCells;
-    const size_t g_hdr = grid ? al256((size_t)b * sizeof(CellGridHdr)) : 0, g_start = grid ? al256((size_t)b * (cells_max + 1) * sizeof(int)) : 0;
-    const size_t g_sorted = grid ? al256((size_t)total * sizeof(float4)) : 0, g_pos = grid ? al256((size_t)total * sizeof(int)) : 0;
-    const size_t g_ps = grid ? al256((size_t)total * sizeof(float)) : 0;
-    // per-cell lower bounds of the prices (emd_grid.hip: the bid culls cell by cell with them), refreshed in front of every
-    // second round's bid
-    const size_t g_pm = grid ? al256((size_t)b * (cells_max + 1) * sizeof(float)) : 0;
-    const size_t grid_off = arrive_bytes + list_bytes + second_bytes + parts_bytes + chain_bytes;
-    char *ws = (char *)workspace(1, grid_off + g_hdr + g_start + g_sorted + g_pos + g_ps + g_pm, st, nullptr, arrive_bytes);
-    if (!ws) return 0;
-    CellGridHdr *g_hdr_p = (CellGridHdr *)(ws + grid_off);
-    int *g_start_p = (int *)(ws + grid_off + g_hdr);
-    float4 *g_sorted_p = (float4 *)(ws + grid_off + g_hdr + g_start);
-    int *g_pos_p = grid ? (int *)(ws + grid_off + g_hdr + g_start + g_sorted) : nullptr;
-    int *g_of_p = grid ? (int *)(ws + grid_off + g_hdr + g_start + g_sorted + g_pos) : nullptr;
-    float *g_pm_p = g_pm ? (float *)(ws + grid_off + g_hdr + g_start + g_sorted + g_pos + g_ps) : nullptr;
+    // fixed size (32 batch elements) so that the zeroed prefix never moves between calls
+    constexpr size_t kArriveInts = (size_t)32 * kArrivePerBatch;
+    int *arrive, *list_b, *second, *g_start_p, *g_pos_p, *g_of_p; float4 *parts, *g_sorted_p; float *g_pm_p;
+    unsigned long long *chain_head; CellGridHdr *g_hdr_p;
+    static_assert(kArrivePerBatch % 2 == 0 && kSplitMaxBidders * kZMax % 16 == 0, "counters and partials are whole 256-byte lines: add() reserves what was reserved unrounded before");
+    WsLayout L;
+    L.add(arrive, kArriveInts);                       // arrival counters (zeroed on allocation, restored by the merging block)
+    L.add(list_b, total);                             // second bidder list
+    L.add(second, total);                             // second-best object of each point's last bid (-1: has not bid yet; set by emd_init_kernel)
+    L.add_if(want_split, parts, (size_t)b * kSplitMaxBidders * kZMax);      // per-slice partial top-2s
+    L.add_if(settle, chain_head, (size_t)5 * total);      // ONE piece: chain_head | chain_next | whead | wnext (8-byte words per object / bidder), chain_cnt | arrived (ints per object)
+    L.add_if(grid, g_hdr_p, b);
+    L.add_if(grid, g_start_p, (size_t)b * (cells_max + 1));
+    L.add_if(grid, g_sorted_p, total);
+    L.add_if(grid, g_pos_p, total);
+    L.add_if(grid, g_of_p, total);
+    // per-cell lower bounds of the prices (emd_grid.hip: the bid culls cell by cell with them), refreshed in front of every second round's bid
+    L.add_if(grid, g_pm_p, (size_t)b * (cells_max + 1));
+    if (!ws_alloc(L, kWsEmdRounds, st, nullptr, kArriveInts * sizeof(int))) return 0;
     float *g_ps_p = grid ? (float *)g_sorted_p + 3 : nullptr;      // the price of sorted position p: g_ps_p[4 p] (the .w of its entry)
-    unsigned long long *chain_head = settle ? (unsigned long long *)(ws + arrive_bytes + list_bytes + second_bytes + parts_bytes) : nullptr;
     unsigned long long *chain_next = settle ? chain_head + total : nullptr;
     unsigned long long *whead = settle ? chain_head + 2 * total : nullptr, *wnext = settle ? chain_head + 3 * total : nullptr;
     int *chain_cnt = settle ? (int *)(chain_head + 4 * total) : nullptr, *arrived = settle ? chain_cnt + total : nullptr;
     // (bidder counts and tickets are zero between rounds by construction -- the settling thread hands them back --; they
     // are cleared once per call with everything else, by emd_init_kernel)
-    int *arrive = (int *)ws;
-    int *list_b = (int *)(ws + arrive_bytes);
-    int *second = (int *)(ws + arrive_bytes + list_bytes);
-    float4 *parts = (float4 *)(ws + arrive_bytes + list_bytes + second_bytes);
-    // second-best object of each point's last bid (-1: has not bid yet; set by emd_init_kernel)
-    if (!want_split) parts = nullptr;
     int *lists[2] = {unass_idx, list_b};
     int *cnts[2] = {unass_cnt, cnt_tmp};
     const bool fma = arith_mode() != 0;
@@ -844,7 +831,7 @@ GENPC_API int genpc_emd_forward(int b, int n, int m, const float *xyz1, const fl
             }
             ga.chain_head = use_chain ? chain_head : nullptr; ga.chain_next = chain_next; ga.chain_cnt = chain_cnt;
             ga.feedback = it == 3 ? emd_feedback_slot(b, n, true) : nullptr;
-            ga.stats = (t_emd_hooks & 1) ? (unsigned long long *)workspace(28, 256, nullptr, nullptr, 256) : nullptr;
+            ga.stats = (t_emd_hooks & 1) ? (unsigned long long *)workspace(kWsEmdStats, 256, nullptr, nullptr, 256) : nullptr;
             launch_emd_bid_grid(ga, fma ? 1 : 0, st);
         } else {
             typedef void (*bid_fn)(int, const float *, const float *, const float *, float, const int *, const int *,

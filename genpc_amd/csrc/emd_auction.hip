@@ -666,14 +666,6 @@ int emd_auction_capacity()
     return num_cus() * 7 / 2;
 }
 
-size_t emd_auction_bytes(int b, int n)
-{
-    auto al = [](size_t v) { return (v + 255) / 256 * 256; };
-    const size_t total = (size_t)b * n;
-    return 256 /* status */ + al((size_t)b * kCtrlWords * 8) + al((size_t)b * sizeof(CellGridHdr)) + al((size_t)b * (kCellGridMaxCells + 1) * sizeof(int)) +
-           al(total * sizeof(float4)) + al(total * sizeof(float)) + 2 * al(total * sizeof(int)) + 2 * al(total * 8) + 2 * al(total * sizeof(int));
-}
-
 // Which path suits the data is known only on the device: how many points still bid after the first rounds (uniform clouds:
 // a fifth; a partial scan against its ground truth: two thirds, for all 50 rounds -- there a round is throughput, and the
 // launch-per-round path, which spreads the bidders over the whole chip whatever the cloud count, is the faster one).  Both
@@ -713,23 +705,24 @@ int launch_emd_auction(int b, int n, const float *xyz1, const float *xyz2, float
     while (K < 64 && (long long)b * n * (2 * K) / kABlock <= fill) K <<= 1;
     while (K > 1 && (long long)b * n * K / kABlock > cap) K >>= 1;
     const int G = (int)((long long)n * K / kABlock), wgs = b * G;
-    auto al = [](size_t v) { return (v + 255) / 256 * 256; };
     const size_t total = (size_t)b * n;
-    char *ws = (char *)workspace(31, emd_auction_bytes(b, n), st, nullptr, 256);
-    if (!ws) return 0;
-    int *status = (int *)ws;
-    char *p = ws + 256;
-    unsigned long long *ctrl = (unsigned long long *)p; p += al((size_t)b * kCtrlWords * 8);
-    CellGridHdr *hdr = (CellGridHdr *)p; p += al((size_t)b * sizeof(CellGridHdr));
-    int *start = (int *)p; p += al((size_t)b * (kCellGridMaxCells + 1) * sizeof(int));
-    float4 *sorted = (float4 *)p; p += al(total * sizeof(float4));
-    float *price_s = (float *)p; p += al(total * sizeof(float));
-    int *pos_of = (int *)p; p += al(total * sizeof(int));
-    int *orig_of = (int *)p; p += al(total * sizeof(int));
-    unsigned long long *chain_head = (unsigned long long *)p; p += al(total * 8);
-    unsigned long long *chain_next = (unsigned long long *)p; p += al(total * 8);
-    int *chain_cnt = (int *)p; p += al(total * sizeof(int));
-    int *arrived = (int *)p;
+    int *status, *start, *pos_of, *orig_of, *chain_cnt, *arrived;
+    unsigned long long *ctrl, *chain_head, *chain_next;
+    CellGridHdr *hdr; float4 *sorted; float *price_s;
+    WsLayout L;
+    L.add(status, 64);          // the 256-byte status block (zero when new; genpc_emd_status reads its first word back): its words stay hand-placed
+    L.add(ctrl, (size_t)b * kCtrlWords);
+    L.add(hdr, b);
+    L.add(start, (size_t)b * (kCellGridMaxCells + 1));
+    L.add(sorted, total);
+    L.add(price_s, total);
+    L.add(pos_of, total);
+    L.add(orig_of, total);
+    L.add(chain_head, total);
+    L.add(chain_next, total);
+    L.add(chain_cnt, total);
+    L.add(arrived, total);
+    if (!ws_alloc(L, kWsEmdAuction, st, nullptr, 256)) return 0;
     if (!persist_reserve(wgs, cap, st)) return -1;
     {
         const size_t items = total > (size_t)b * kCtrlWords ? total : (size_t)b * kCtrlWords;      // (a 256-point cloud has fewer points than control words)
@@ -775,7 +768,7 @@ GENPC_API int genpc_emd_contended(void)
 GENPC_API int genpc_emd_status(int reset, void *stream)
 {
     using namespace genpc;
-    int *dev = (int *)workspace(31, 256, (hipStream_t)stream, nullptr, 256);
+    int *dev = (int *)workspace(kWsEmdAuction, 256, (hipStream_t)stream, nullptr, 256);
     if (!dev) return -1;
     if (!check(hipStreamSynchronize((hipStream_t)stream), "genpc_emd_status sync")) return -1;
     int v = 0;

@@ -744,20 +744,19 @@ GENPC_API int genpc_fps_multi(int c, const int *n, const int *k, const float *co
     for (int j : big) total_slots += 2 * (size_t)fps_workgroups(n[j]);
     for (int j : small) spt_pts += ((size_t)n[j] + 63) & ~(size_t)63;
     for (int j = 0; j < c; j++) total_k += ((size_t)k[j] + 63) / 64 * 64;
-    const size_t head = 256 + total_slots * sizeof(FpsSlot), verr_bytes = ((size_t)c * sizeof(int) + 255) / 256 * 256;
     size_t total_n = 0;
     for (int j = 0; j < c; j++) total_n += (size_t)n[j];
-    const size_t pd_bytes = (total_k * sizeof(float) + 255) / 256 * 256;
-    const size_t seg_bytes = (total_n * kFVMaxSeg * sizeof(float) + 255) / 256 * 256;
-    char *ws = (char *)workspace(7, head + verr_bytes + pd_bytes + seg_bytes + spt_pts * sizeof(float4), st);
-    if (!ws) return 0;
-    int *err = (int *)ws;
-    FpsSlot *slots = (FpsSlot *)(ws + 256);
-    int *verr = (int *)(ws + head);
-    float *pdist = (float *)(ws + head + verr_bytes);
-    float *segmin = (float *)(ws + head + verr_bytes + pd_bytes);
-    float4 *spt = (float4 *)(ws + head + verr_bytes + pd_bytes + seg_bytes);
-    if (!check(hipMemsetAsync(ws, 0, head + verr_bytes, st), "hipMemsetAsync(fps)")) return 0;
+    int *err, *verr; FpsSlot *slots; float *pdist, *segmin; float4 *spt;
+    WsLayout L;
+    L.add(err, 64);          // the 256-byte status block: [0] error, [1 ..] the clouds' hand-off rounds (genpc_fps_stats reads them back)
+    static_assert(sizeof(FpsSlot) == 128, "two slots per workgroup (total_slots is even) are whole 256-byte lines: add() reserves what was reserved unrounded before");
+    L.add(slots, total_slots);
+    L.add(verr, c);
+    L.add(pdist, total_k);
+    L.add(segmin, total_n * kFVMaxSeg);
+    L.add(spt, spt_pts);
+    if (!ws_alloc(L, kWsFps, st)) return 0;
+    if (!check(hipMemsetAsync(err, 0, (size_t)((char *)pdist - (char *)err), st), "hipMemsetAsync(fps)")) return 0;
     std::vector<float *> pd_of(c);
     std::vector<int> seg_of(c);
     {
@@ -788,7 +787,8 @@ GENPC_API int genpc_fps_multi(int c, const int *n, const int *k, const float *co
     };
     // deferred form: the group's arrays copied behind the sampling, the check on the side stream
     auto verify_deferred = [&](const FpsJobs &jobs, int nj, FpsDeferred *d) -> bool {
-        auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+        // (buffers of the check's own, not the pool's; three pieces per cloud: the layout is a loop, rounded by the one rule)
+        constexpr auto up = WsLayout::up;
         size_t bytes = 256, pts = 0;
         for (int q = 0; q < nj; q++) {
             bytes += up((size_t)jobs.n[q] * 12) + 2 * up((size_t)jobs.k[q] * 4);
@@ -940,7 +940,7 @@ GENPC_API int genpc_fps_stats(int c, int *rounds, void *stream)
     using namespace genpc;
     if (c < 0 || c > 60) return -1;
     hipStream_t st = (hipStream_t)stream;
-    char *ws = (char *)workspace(7, 256, st);
+    char *ws = (char *)workspace(kWsFps, 256, st);
     if (!ws) return 0;
     if (!check(hipMemcpyAsync(rounds, ws + 4, (size_t)c * sizeof(int), hipMemcpyDeviceToHost, st), "fps stats copy")) return 0;
     return check(hipStreamSynchronize(st), "fps stats sync") ? 1 : 0;

@@ -1791,24 +1791,7 @@ static int hpr_run(int c, int n, const float *points, const double *eyes, double
                                          (size_t)c * n, 0u, 32u, stream),
                "hpr sort size"))
         return 0;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    size_t off = 256;
-    const size_t o_fl = off; off += up(total * 3 * sizeof(double));
-    const size_t o_list = off; off += up(total * sizeof(int));
-    const size_t o_k0 = off; off += up(total * 4);
-    const size_t o_k1 = off; off += up(total * 4);
-    const size_t o_i0 = off; off += up(total * 4);
-    const size_t o_i1 = off; off += up(total * 4);
-    const size_t o_tmp = off; off += up(sort_bytes);
     const int ntiles = ceil_div(n, kHprThreads);
-    const size_t o_tiles = off; off += up((size_t)c * ntiles * sizeof(HprTile));
-    const size_t o_hard = off; off += up(total);
-    const size_t o_hl = off; off += up(total * sizeof(int));
-    const size_t o_hc = off; off += up((size_t)c * sizeof(int));
-    const size_t o_und = off; off += up((size_t)c * sizeof(int));
-    const size_t o_alive = off; off += up((size_t)c);
-    const size_t o_dup = off; off += up((size_t)n);
-    const size_t o_work = off; off += up((size_t)kHprWorkWords * sizeof(int));
     // Split form (the first kernel stops after the home tiles + verification and saves the undecided points' polygons; a
     // wave per point continues from them): for clouds of < 256 tiles.  Round 3, first half: only for >= 4 M (view, point)
     // pairs, with a dense one-thread-per-survivor second kernel (1024 x 10000: 128 -> 88 ms; 64 x 10000 14.3 -> 16.6).  With
@@ -1818,27 +1801,41 @@ static int hpr_run(int c, int n, const float *points, const double *eyes, double
     // (GENPC_HPR_SPLIT=0/1 overrides).
     static const int env_split = tune_env("GENPC_HPR_SPLIT", -1, "hidden-point removal: 1 two-kernel form (first kernel stops after the home tiles, a wave per point continues), 0 one kernel, -1 pick by size");
     const int split = env_split >= 0 ? env_split : (ntiles < kHprRimTiles && (long long)c * n >= 100000ll ? 1 : 0);
-    const size_t o_surv = off; off += split ? up(total * sizeof(int4)) : 0;
+    int *status, *list, *i0, *i1, *hardlist, *hardcnt, *und_p, *work;
+    double *fl; unsigned *k0, *k1; char *sort_tmp; HprTile *tiles; unsigned char *hard, *alive_p, *dup; int4 *surv;
+    WsLayout L;
+    L.add(status, 64);          // the 256-byte header, hand-placed and to stay so: status words 0 .. 15 and 32 .. 44, the bounds in 16 .. 21, the segment record in 48 .. 58
+    L.add(fl, total * 3);
+    L.add(list, total);
+    L.add(k0, total);
+    L.add(k1, total);
+    L.add(i0, total);
+    L.add(i1, total);
+    L.add(sort_tmp, sort_bytes);
+    L.add(tiles, (size_t)c * ntiles);
+    L.add(hard, total);
+    L.add(hardlist, total);
+    L.add(hardcnt, c);
+    L.add(und_p, c);
+    L.add(alive_p, c);
+    L.add(dup, n);
+    L.add(work, kHprWorkWords);          // line x: the first try's counter of segment x; lines 8 .. 11: the other passes'
+    L.add(surv, split ? total : 0);
     // (the survivors' polygons are sized after the accept pass has counted the listed points: a second workspace)
-    char *ws = (char *)workspace(17, off, stream);
-    if (!ws) return 0;
-    int *status = (int *)ws;
-    unsigned *bounds = (unsigned *)(ws + 64);
-    double *fl = (double *)(ws + o_fl);
-    int *list = (int *)(ws + o_list);
-    unsigned *k0 = (unsigned *)(ws + o_k0), *k1 = (unsigned *)(ws + o_k1);
-    int *i0 = (int *)(ws + o_i0), *i1 = (int *)(ws + o_i1);
+    if (!ws_alloc(L, kWsHpr, stream)) return 0;
+    unsigned *bounds = (unsigned *)(status + 16);
+    HprSegs *segs = (HprSegs *)(status + 48);
+    static_assert(sizeof(HprSegs) <= 64, "the segment record shares the header with the status words");
     if (!check(hipMemsetAsync(status, 0, 256, stream), "hipMemsetAsync(hpr status)")) return 0;
     if (!check(hipMemsetAsync(bounds, 0xff, 12, stream), "hipMemsetAsync(hpr bounds)")) return 0;
     const int g256 = ceil_div(n, 256);
     // later copies of exact duplicates (the key / index buffers of the view sort are free until then)
-    unsigned char *dup = (unsigned char *)(ws + o_dup);
     {
         int *ia = i0, *ib = i1;
         for (int axis = 2; axis >= 0; axis--) {
             hipLaunchKernelGGL(hpr_dupkey_kernel, dim3(g256), dim3(256), 0, stream, n, points, axis, axis == 2 ? (const int *)nullptr : (const int *)ia, k0, ia);
             size_t sb = sort_bytes;
-            if (!check(rocprim::radix_sort_pairs(ws + o_tmp, sb, (const unsigned *)k0, k1, (const int *)ia, ib, (size_t)n, 0u, 32u, stream), "hpr duplicate sort"))
+            if (!check(rocprim::radix_sort_pairs(sort_tmp, sb, (const unsigned *)k0, k1, (const int *)ia, ib, (size_t)n, 0u, 32u, stream), "hpr duplicate sort"))
                 return 0;
             std::swap(ia, ib);
         }
@@ -1848,18 +1845,15 @@ static int hpr_run(int c, int n, const float *points, const double *eyes, double
     hipLaunchKernelGGL(hpr_key_kernel, dim3(g256, c), dim3(256), 0, stream, n, points, (const unsigned *)bounds, eyes, k0, i0);
     int key_bits = 20;
     while ((1 << (key_bits - 20)) < c) key_bits++;
-    if (!check(rocprim::radix_sort_pairs(ws + o_tmp, sort_bytes, (const unsigned *)k0, k1, (const int *)i0, i1, total, 0u, (unsigned)key_bits, stream),
+    if (!check(rocprim::radix_sort_pairs(sort_tmp, sort_bytes, (const unsigned *)k0, k1, (const int *)i0, i1, total, 0u, (unsigned)key_bits, stream),
                "hpr radix sort"))
         return 0;
-    HprTile *tiles = (HprTile *)(ws + o_tiles);
     static const int no_cull = tune_env("GENPC_HPR_NOCULL", 0, "hidden-point removal: measurement mask (1 every tile, 8 no silhouette hand-off, 16 no early accept, 32 no verify, 64 no hand-off of much-cut polygons, 128 no decisions without the walk in the wave-per-point pass, 256 count those decisions on stderr, 512 two-kernel form WITH the first kernel's own verify phase)");      // measurement knob: 1 = every tile examined, 8 = no silhouette hand-off, 16 = no early accept, 32 = no verify phase, 64 = no hand-off of much-cut polygons (results unchanged)
     hipLaunchKernelGGL(hpr_flip_kernel, dim3(g256, c), dim3(256), 0, stream, n, points, (const int *)i1, eyes, radius, fl, (const unsigned char *)dup);
     hipLaunchKernelGGL(hpr_tile_kernel, dim3(ntiles, c), dim3(kHprThreads), 0, stream, n, (const double *)fl, tiles);
     // clips after which a polygon goes to the wave-per-point pass (large clouds: 96 -- 2 x 165546 points 46 -> 40 ms; many views of a small cloud: the second pass fills up
     //  instead -- 1024 x 10000 points 154 ms with 256, 168 with 128, 180 with 96)
     const int max_clips = (no_cull & 64) ? 0x7fffffff : (ntiles >= kHprRimTiles ? 48 : 256);      // (large clouds: 96 -> 48 once the wave-per-point pass clipped by all lanes: 2 x 165546 24.9 -> 21.5 ms)
-    unsigned char *hard = (unsigned char *)(ws + o_hard);
-    int *hardlist = (int *)(ws + o_hl), *hardcnt = (int *)(ws + o_hc);
     hipLaunchKernelGGL(hpr_accept_kernel, dim3(ntiles * c), dim3(kHprThreads), 0, stream, n, (const double *)fl, (const int *)i1,
                        (const HprTile *)tiles, hard, visible, counts, (no_cull & 16) ? 1 : 0, c);
     hipLaunchKernelGGL(hpr_compact_kernel, dim3(c), dim3(1024), 0, stream, n, (const unsigned char *)hard, hardlist, hardcnt);
@@ -1867,23 +1861,19 @@ static int hpr_run(int c, int n, const float *points, const double *eyes, double
     // (round 4 fetched it to size the store, the first of six stream synchronisations of this entry point): the store is
     // sized for every (view, point) pair up to GENPC_HPR_PARK_MB, and a point whose slot would lie beyond it is listed
     // for the wave-per-point pass instead of parked (it restarts from the box there: same result, computed again).
-    int4 *surv = (int4 *)(ws + o_surv);
     // best_only (viewpoint_select): views that cannot be the best any more are dropped after the first polygon kernel
     const bool prune = best_only && split;
-    int *und = prune ? (int *)(ws + o_und) : nullptr;
-    unsigned char *alive = prune ? (unsigned char *)(ws + o_alive) : nullptr;
+    int *und = prune ? und_p : nullptr;
+    unsigned char *alive = prune ? alive_p : nullptr;
     if (prune && !check(hipMemsetAsync(und, 0, sizeof(int) * (size_t)c, stream), "hipMemsetAsync(hpr und)")) return 0;
-    HprSegs *segs = (HprSegs *)(ws + 192);          // (the 256-byte header: status words 0 .. 15 and 32 .. 44, the bounds in words 16 .. 21, this record in 48 .. 58)
-    static_assert(sizeof(HprSegs) <= 64, "the segment record shares the header with the status words");
     static const int env_park = tune_env("GENPC_HPR_PARK_MB", 3072, "hidden-point removal, two-kernel form: MiB of polygon store (256 bytes per parked point; points beyond it restart in the wave-per-point pass)");
     const size_t poly_bytes = (size_t)kHprMaxV * sizeof(double2);
     const size_t park_cap = split ? std::min<size_t>(total, std::max<size_t>(1, ((size_t)(env_park > 0 ? env_park : 1) << 20) / poly_bytes)) : 0;
     double2 *surv_poly = nullptr;
     if (split) {
-        surv_poly = (double2 *)workspace(20, park_cap * poly_bytes, stream);
+        surv_poly = (double2 *)workspace(kWsHprParked, park_cap * poly_bytes, stream);
         if (!surv_poly) return 0;
     }
-    int *work = (int *)(ws + o_work);          // line x: the first try's counter of segment x; lines 8 .. 11: the other passes'
     hipLaunchKernelGGL(hpr_segs_kernel, dim3(1), dim3(1024), 0, stream, c, (const int *)hardcnt, segs, (int)park_cap, work);
     // the first kernel hands a block's undecided points over after 4 tile batches, all of them (see the kernel)
     const int straggle_from = 4, straggle_lanes = kHprThreads;
@@ -1951,7 +1941,7 @@ static int hpr_run(int c, int n, const float *points, const double *eyes, double
             const size_t per = (size_t)2 * gcap * sizeof(double2);
             // (256 MiB of buffers at most)
             const int g3 = (int)std::min<size_t>(std::min<size_t>(total, 1024), std::max<size_t>(1, ((size_t)256 << 20) / per));
-            double2 *gbuf = (double2 *)workspace(30, (size_t)g3 * per, stream);
+            double2 *gbuf = (double2 *)workspace(kWsHprGlobalPolys, (size_t)g3 * per, stream);
             if (!gbuf) return 0;
             hipLaunchKernelGGL(hpr_overflow_kernel<0>, dim3(g3), dim3(kWave), 0, stream, n, (const double *)fl, (const HprTile *)tiles,
                                visible, counts, status, (const int *)list3, (const int *)i1, (const int *)hardlist,

@@ -667,7 +667,7 @@ __global__ __launch_bounds__(kFT) void icp_fused_kernel(int ns, const float *__r
 // LDS of the one-workgroup solve for nt targets with `cells` grid cells
 static size_t icp_fused_lds(int nt, int cells) { return (size_t)((nt + 3) & ~3) * 16 + (size_t)cells * 4 + kFFixed; }
 
-static int gx(int n)
+static int gx(int n)          // (not pose.hip's lin_grid: the same block of 256, but at most 64 blocks per row where that one allows 1024)
 {
     int g = ceil_div(n, kIBlock);
     return g > 64 ? 64 : (g < 1 ? 1 : g);
@@ -704,20 +704,15 @@ GENPC_API int genpc_icp_batch(int k, int ns, const float *source, int nt, const 
                                rel_fitness, rel_rmse, cells, out_T, stats);
         return check(hipGetLastError(), "icp (one workgroup) launch") ? 1 : 0;
     }
-    // scratch: accum[k,17] | state[k] | pts[k,ns,3] | target_rep[k,nt,3] | d[k,ns] | idx[k,ns]
-    size_t off = 0;
-    const size_t o_acc = off; off += ((size_t)k * 17 * 8 + 255) / 256 * 256;
-    const size_t o_state = off; off += ((size_t)k * sizeof(IcpState) + 255) / 256 * 256;
-    const size_t o_pts = off; off += ((size_t)k * ns * 12 + 255) / 256 * 256;
-    const size_t o_tgt = off; off += ((size_t)k * nt * 12 + 255) / 256 * 256;
-    const size_t o_d = off; off += ((size_t)k * ns * 4 + 255) / 256 * 256;
-    const size_t o_i = off; off += ((size_t)k * ns * 4 + 255) / 256 * 256;
-    char *ws = (char *)workspace(5, off, st);
-    if (!ws) return 0;
-    double *accum = (double *)(ws + o_acc);
-    IcpState *state = (IcpState *)(ws + o_state);
-    float *pts = (float *)(ws + o_pts), *tgt = (float *)(ws + o_tgt), *d = (float *)(ws + o_d);
-    int *idx = (int *)(ws + o_i);
+    double *accum; IcpState *state; float *pts, *tgt, *d; int *idx;
+    WsLayout L;
+    L.add(accum, (size_t)k * 17);
+    L.add(state, k);
+    L.add(pts, (size_t)k * ns * 3);
+    L.add(tgt, (size_t)k * nt * 3);          // the target once per candidate (k > 1)
+    L.add(d, (size_t)k * ns);
+    L.add(idx, (size_t)k * ns);
+    if (!ws_alloc(L, kWsIcp, st)) return 0;
     if (!check(hipMemsetAsync(accum, 0, (size_t)k * 17 * 8, st), "hipMemsetAsync(icp accum)")) return 0;
     if (!check(hipMemcpyAsync(out_T, init, (size_t)k * 16 * 8, hipMemcpyDeviceToDevice, st), "copy init")) return 0;
     const float *tq = target;
@@ -728,7 +723,7 @@ GENPC_API int genpc_icp_batch(int k, int ns, const float *source, int nt, const 
     }
     // the target does not move: its duplicate mask (nn_dedupe.hip) is made once for all passes
     // (one row: the k candidates share the target)
-    unsigned *dup_t = (unsigned *)workspace(27, nn_dedupe_mask_words(1, nt) * sizeof(unsigned), st);
+    unsigned *dup_t = (unsigned *)workspace(kWsIcpDupMasks, nn_dedupe_mask_words(1, nt) * sizeof(unsigned), st);
     if (!dup_t) return 0;
     {
         const float *dp[2] = {target, nullptr};
@@ -763,25 +758,22 @@ GENPC_API int genpc_scale_search_scores(int k, int ns, const float *source, int 
     using namespace genpc;
     if (k <= 0 || ns <= 0 || nt <= 0) return -1;
     hipStream_t st = (hipStream_t)stream;
-    size_t off = 0;
-    const size_t o_src = off; off += ((size_t)k * ns * 12 + 255) / 256 * 256;
-    const size_t o_tgt = off; off += ((size_t)k * nt * 12 + 255) / 256 * 256;
-    const size_t o_d1 = off; off += ((size_t)k * ns * 4 + 255) / 256 * 256;
-    const size_t o_i1 = off; off += ((size_t)k * ns * 4 + 255) / 256 * 256;
-    const size_t o_d2 = off; off += ((size_t)k * nt * 4 + 255) / 256 * 256;
-    const size_t o_i2 = off; off += ((size_t)k * nt * 4 + 255) / 256 * 256;
-    char *ws = (char *)workspace(6, off, st);
-    if (!ws) return 0;
-    float *src = (float *)(ws + o_src), *tgt = (float *)(ws + o_tgt);
-    float *d1 = (float *)(ws + o_d1), *d2 = (float *)(ws + o_d2);
-    int *i1 = (int *)(ws + o_i1), *i2 = (int *)(ws + o_i2);
+    float *src, *tgt, *d1, *d2; int *i1, *i2;
+    WsLayout L;
+    L.add(src, (size_t)k * ns * 3);
+    L.add(tgt, (size_t)k * nt * 3);
+    L.add(d1, (size_t)k * ns);
+    L.add(i1, (size_t)k * ns);
+    L.add(d2, (size_t)k * nt);
+    L.add(i2, (size_t)k * nt);
+    if (!ws_alloc(L, kWsScaleSearch, st)) return 0;
     hipLaunchKernelGGL(replicate_scale_kernel, dim3(gx(ns), k), dim3(kIBlock), 0, st, ns, source, scales, src);
     hipLaunchKernelGGL(replicate_scale_kernel, dim3(gx(nt), k), dim3(kIBlock), 0, st, nt, target,
                        (const float *)nullptr, tgt);
     // every candidate is a scaled copy of the one source against a copy of the one target: equal points stay equal under
     // any scale, so ONE row of duplicate marks per cloud (nn_dedupe.hip) serves all k candidates
     const size_t w_s = (nn_dedupe_mask_words(1, ns) + 63) & ~(size_t)63;
-    unsigned *dup_s = (unsigned *)workspace(27, (w_s + nn_dedupe_mask_words(1, nt)) * sizeof(unsigned), st);
+    unsigned *dup_s = (unsigned *)workspace(kWsIcpDupMasks, (w_s + nn_dedupe_mask_words(1, nt)) * sizeof(unsigned), st);
     if (!dup_s) return 0;
     unsigned *dup_t = dup_s + w_s;
     {

@@ -61,13 +61,12 @@ __global__ __launch_bounds__(kKGBlock) void knn_grid_kernel(int n, const float4 
 template <int K>
 static int launch_knn(int n, const float *xyz, float *out, hipStream_t st)
 {
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_start = al(sizeof(CellGridHdr)), o_sorted = o_start + al((size_t)(kCellGridMaxCells + 1) * sizeof(int));
-    char *ws = (char *)workspace(35, o_sorted + al((size_t)n * sizeof(float4)), st);
-    if (!ws) return 0;
-    CellGridHdr *hdr = (CellGridHdr *)ws;
-    int *start = (int *)(ws + o_start);
-    float4 *sorted = (float4 *)(ws + o_sorted);
+    CellGridHdr *hdr; int *start; float4 *sorted;
+    WsLayout L;
+    L.add(hdr, 1);
+    L.add(start, (size_t)kCellGridMaxCells + 1);
+    L.add(sorted, n);
+    if (!ws_alloc(L, kWsKnnMean, st)) return 0;
     // cells of about half a point: the shells around a query stay small while its list fills
     int target = 2 * n;
     target = target < 64 ? 64 : (target > 8192 ? 8192 : target);

@@ -116,15 +116,14 @@ static void launch_knn_query_cap(const KnnQueryArgs &a, unsigned grid, int fma, 
 static int knn_query(int b, int nq, const float *xyz, int nt, const float *xyz2, int k, float *dist, int *idx, hipStream_t st)
 {
     const int fma = arith_mode() != 0;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_start = al((size_t)b * sizeof(CellGridHdr)), o_sorted = o_start + al((size_t)b * (kCellGridMaxCells + 1) * sizeof(int));
-    const size_t o_order = o_sorted + al((size_t)b * nt * sizeof(float4)), bytes = o_order + al((size_t)b * nq * sizeof(int));
-    char *ws = (char *)workspace(36, bytes, st);
-    if (!ws) return 0;
     KnnQueryArgs a{};
     a.q = xyz; a.out_d = dist; a.out_i = idx; a.nq = nq; a.nt = nt; a.k = k; a.cells_max = kCellGridMaxCells;
-    a.hdr = (const CellGridHdr *)ws; a.start = (const int *)(ws + o_start); a.sorted = (const float4 *)(ws + o_sorted);
-    a.order = (const int *)(ws + o_order);
+    WsLayout L;
+    L.add(a.hdr, b);
+    L.add(a.start, (size_t)b * (kCellGridMaxCells + 1));
+    L.add(a.sorted, (size_t)b * nt);
+    L.add(a.order, (size_t)b * nq);
+    if (!ws_alloc(L, kWsKnnQuery, st)) return 0;
     a.qblocks = ceil_div(nq, kBlock);
     if ((long long)b * a.qblocks > 0x7fffffffLL) { set_error("knn query: problem too large for one launch"); return 0; }
     // cells of about max(2, k / 2) targets: the 27 cells around a query then hold its k neighbours more often than not

@@ -303,8 +303,8 @@ struct SeededGrids {
     const int *start_static, *start_rest;
     const float4 *sorted_static, *sorted_rest;
 };
-size_t seeded_grids_bytes(int b, int nm, int ns);
-int build_seeded_grids(int b, int nm, const float *rest_pts, int ns, const float *static_pts, void *ws, SeededGrids &g, hipStream_t st);
+void seeded_grids_layout(WsLayout &L, SeededGrids &g, int b, int nm, int ns);      // the grids' pieces behind whatever L holds (g stays put until L is bound)
+int build_seeded_grids(int b, int nm, const float *rest_pts, int ns, const float *static_pts, const SeededGrids &g, hipStream_t st);
 int launch_nn_seeded(int b, int nm, const float *moving_pts, int ns, const float *static_pts, const SeededGrids &g, const float *center,
                      int cstride, const float *params, int pstride, float *d1, int *i1, float *d2, int *i2, int fma, hipStream_t st, int sample = 1);
 

@@ -140,7 +140,7 @@ int launch_nn_dedupe(int b, int nclouds, const float *const pts[2], const int n[
     unsigned g = g_dedupe_gen.fetch_add(1, std::memory_order_relaxed);
     if (g == 0) g = g_dedupe_gen.fetch_add(1, std::memory_order_relaxed);     // 0 is what a fresh table holds
     a.gen = g;
-    size_t bytes = 0, off[2] = {0, 0};
+    WsLayout L;
     long long blocks = 0;
     for (int c = 0; c < nclouds; c++) {
         if (n[c] <= 0 || n[c] > (1 << 30)) return 0;
@@ -150,15 +150,12 @@ int launch_nn_dedupe(int b, int nclouds, const float *const pts[2], const int n[
         a.c[c].mask = masks[c];
         a.c[c].n = n[c];
         a.c[c].cap_mask = (int)(cap - 1);
-        off[c] = bytes;
-        bytes += (size_t)b * cap * sizeof(unsigned long long);
+        L.add(a.c[c].table, (size_t)b * cap);          // (whole 256-byte lines: cap >= 64)
         if (c == 0) a.blocks0 = ceil_div(n[c], kDBlock);
         blocks += ceil_div(n[c], kDBlock);
     }
     // a NEW block is zeroed whole (generation 0 = free); an old one holds older generations = free
-    char *tab = (char *)workspace(24, bytes, st, nullptr, bytes);
-    if (!tab) return 0;
-    for (int c = 0; c < nclouds; c++) a.c[c].table = (unsigned long long *)(tab + off[c]);
+    if (!ws_alloc(L, kWsDedupeTable, st, nullptr, L.bytes())) return 0;
     a.hint_stride = (int)ceil_div64(blocks, 16);
     hipLaunchKernelGGL(dedupe_insert_kernel, dim3((unsigned)blocks, b), dim3(kDBlock), 0, st, a);
     hipLaunchKernelGGL(dedupe_resolve_kernel, dim3((unsigned)blocks, b), dim3(kDBlock), 0, st, a);

@@ -385,16 +385,12 @@ static thread_local hipEvent_t g_prof_e0 = nullptr, g_prof_e1 = nullptr;
 // Launches the filter and the finish kernel.  q / u / nl as chosen by the planner in chamfer.hip.
 int launch_nn_f16(NNArgs &a, int q, int u, int nl, int tight, long long total_blocks, hipStream_t st)
 {
-    size_t bytes = 0;
-    size_t off_t[2];
+    WsLayout L;
     for (int d = 0; d < a.ndir; d++) {
         a.dir[d].ntmax = a.dir[d].slices;
-        off_t[d] = bytes;
-        bytes += ((size_t)a.b * a.dir[d].ntmax * sizeof(float) + 255) & ~(size_t)255;
+        L.add(a.dir[d].tmaxp, (size_t)a.b * a.dir[d].ntmax);
     }
-    char *ws = (char *)workspace(9, bytes, st);
-    if (!ws) return 0;
-    for (int d = 0; d < a.ndir; d++) a.dir[d].tmaxp = (float *)(ws + off_t[d]);
+    if (!ws_alloc(L, kWsNnTmax, st)) return 0;
     const int blocks = (int)total_blocks;
     hipEvent_t pe0 = nullptr, pe1 = nullptr;
     if (g_prof_on) {

@@ -471,19 +471,13 @@ int launch_nn_grid(const NNArgs &na, hipStream_t st)
     a.cells_target = target;
     a.cells_max = std::min(kGridMaxCells - 256, 2 * target + 512);      // coarse cells are padded to 4 x 4 x 4
     const int stride = a.cells_max + 1;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t hdr_bytes = al((size_t)a.b * sizeof(GridHdr));
-    const size_t bad_bytes = al((size_t)a.b * 2 * sizeof(int));
-    const size_t start_bytes = al((size_t)a.b * 2 * stride * sizeof(int));
-    const size_t cstart_bytes = al((size_t)a.b * 2 * (a.cells_max / 64 + 2) * sizeof(int));
-    const size_t sorted_bytes = al((size_t)a.b * ((size_t)a.n[0] + a.n[1]) * sizeof(float4));
-    char *ws = (char *)workspace(13, hdr_bytes + bad_bytes + start_bytes + cstart_bytes + sorted_bytes, st);
-    if (!ws) return 0;
-    a.hdr = (GridHdr *)ws;
-    a.bad = (int *)(ws + hdr_bytes);
-    a.start = (int *)(ws + hdr_bytes + bad_bytes);
-    a.cstart = (int *)(ws + hdr_bytes + bad_bytes + start_bytes);
-    a.sorted = (float4 *)(ws + hdr_bytes + bad_bytes + start_bytes + cstart_bytes);
+    WsLayout L;
+    L.add(a.hdr, a.b);
+    L.add(a.bad, (size_t)a.b * 2);
+    L.add(a.start, (size_t)a.b * 2 * stride);
+    L.add(a.cstart, (size_t)a.b * 2 * (a.cells_max / 64 + 2));
+    L.add(a.sorted, (size_t)a.b * ((size_t)a.n[0] + a.n[1]));
+    if (!ws_alloc(L, kWsNnGrid, st)) return 0;
     a.sorted_off[0] = 0;
     a.sorted_off[1] = (size_t)a.b * a.n[0];
     // slabs per cloud: enough blocks to occupy a good part of the chip when the batch is small

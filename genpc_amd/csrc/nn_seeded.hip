@@ -217,24 +217,19 @@ int launch_nn_seeded(int b, int nm, const float *moving_pts, int ns, const float
     return check(hipGetLastError(), "nn_seeded_kernel launch") ? 1 : 0;
 }
 
-size_t seeded_grids_bytes(int b, int nm, int ns)
+// Both grids of a call: the static cloud in the world frame, the moving cloud in its rest frame.
+void seeded_grids_layout(WsLayout &L, SeededGrids &g, int b, int nm, int ns)
 {
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    return 2 * al((size_t)b * sizeof(CellGridHdr)) + 2 * al((size_t)b * (kCellGridMaxCells + 1) * sizeof(int)) + al((size_t)b * nm * sizeof(float4)) +
-           al((size_t)b * ns * sizeof(float4));
+    L.add(g.hdr_static, b);
+    L.add(g.hdr_rest, b);
+    L.add(g.start_static, (size_t)b * (kCellGridMaxCells + 1));
+    L.add(g.start_rest, (size_t)b * (kCellGridMaxCells + 1));
+    L.add(g.sorted_static, (size_t)b * ns);
+    L.add(g.sorted_rest, (size_t)b * nm);
 }
 
-// Both grids of a call: the static cloud in the world frame, the moving cloud in its rest frame.
-int build_seeded_grids(int b, int nm, const float *rest_pts, int ns, const float *static_pts, void *ws, SeededGrids &g, hipStream_t st)
+int build_seeded_grids(int b, int nm, const float *rest_pts, int ns, const float *static_pts, const SeededGrids &g, hipStream_t st)
 {
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    char *p = (char *)ws;
-    g.hdr_static = (CellGridHdr *)p; p += al((size_t)b * sizeof(CellGridHdr));
-    g.hdr_rest = (CellGridHdr *)p; p += al((size_t)b * sizeof(CellGridHdr));
-    g.start_static = (int *)p; p += al((size_t)b * (kCellGridMaxCells + 1) * sizeof(int));
-    g.start_rest = (int *)p; p += al((size_t)b * (kCellGridMaxCells + 1) * sizeof(int));
-    g.sorted_static = (float4 *)p; p += al((size_t)b * ns * sizeof(float4));
-    g.sorted_rest = (float4 *)p;
     auto target = [](int n) { int t = n / 2; return t < 8 ? 8 : (t > kCellGridMaxCells * 3 / 4 ? kCellGridMaxCells * 3 / 4 : t); };
     if (!launch_cell_grid_build(b, ns, static_pts, nullptr, (CellGridHdr *)g.hdr_static, (int *)g.start_static, (float4 *)g.sorted_static, nullptr,
                                nullptr, target(ns), kCellGridMaxCells, st))

@@ -1876,33 +1876,27 @@ struct MaskScratch {
     int *clean;        // [b, tiles]: 1 = the tile's pixels hold the background in all five planes (mask_splat_kernel: an empty tile leaves at once)
     size_t clean_bytes;
     size_t bins_count_bytes;
-    static size_t up(size_t x) { return (x + 255) / 256 * 256; }
     static size_t side(size_t P) { size_t S = (size_t)sqrt((double)P); while (S * S < P) S++; return S; }
-    static size_t bins_bytes(int b, size_t P)
+    static size_t bins_ints(int b, size_t P)
     {
         const size_t t = bins_tiles((int)side(P));
-        return t <= (size_t)kBinTiles ? (size_t)b * t * (1 + (size_t)kTileCap) * sizeof(int) : 0;      // (no lists for such an image: use_bins)
+        return t <= (size_t)kBinTiles ? (size_t)b * t * (1 + (size_t)kTileCap) : 0;      // (no lists for such an image: use_bins)
     }
-    static size_t bytes(int b, size_t P, size_t nmax)
+    // the pieces, behind whatever L holds already (this object must stay where it is until L is bound)
+    void layout(WsLayout &L, int b, size_t P, size_t nmax)
     {
-        return up((size_t)b * 8 * 4) + up((size_t)b * P * 4) + up((size_t)b * 5 * P * 4) + up((size_t)b * P * 4) +
-               up((size_t)b * P * 16) + up((size_t)b * nmax * 16) + up((size_t)b * nmax * 4) + up(bins_bytes(b, P)) +
-               up((size_t)b * bins_tiles((int)side(P)) * sizeof(int));
-    }
-    void carve(char *base, int b, size_t P, size_t nmax)
-    {
-        size_t off = 0;
-        stats = (float *)(base + off); off += up((size_t)b * 8 * 4);
-        mref = (float *)(base + off); off += up((size_t)b * P * 4);
-        planes = (float *)(base + off); off += up((size_t)b * 5 * P * 4);
-        W1 = (float *)(base + off); off += up((size_t)b * P * 4);
-        W4 = (float4 *)(base + off); off += up((size_t)b * P * 16);
-        uvr = (float4 *)(base + off); off += up((size_t)b * nmax * 16);
-        zex = (float *)(base + off); off += up((size_t)b * nmax * 4);
-        bins = (int *)(base + off); off += up(bins_bytes(b, P));
-        clean = (int *)(base + off);
-        clean_bytes = (size_t)b * bins_tiles((int)side(P)) * sizeof(int);
-        bins_count_bytes = bins_bytes(b, P) ? (size_t)b * bins_tiles((int)side(P)) * sizeof(int) : 0;
+        const size_t tiles = (size_t)b * bins_tiles((int)side(P));
+        L.add(stats, (size_t)b * 8);
+        L.add(mref, (size_t)b * P);
+        L.add(planes, (size_t)b * 5 * P);
+        L.add(W1, (size_t)b * P);
+        L.add(W4, (size_t)b * P);
+        L.add(uvr, (size_t)b * nmax);
+        L.add(zex, (size_t)b * nmax);
+        L.add(bins, bins_ints(b, P));
+        L.add(clean, tiles);
+        clean_bytes = tiles * sizeof(int);
+        bins_count_bytes = bins_ints(b, P) ? tiles * sizeof(int) : 0;
     }
     // the tile counters are zero between launches (the splat kernel resets what it reads); once per API call for a
     // workspace that is new or was last used with another batch size
@@ -1999,10 +1993,10 @@ GENPC_API int genpc_splat_image(int n, const float *pts, const float *col, float
     if (n < 0 || size <= 0 || !(radius > 0.0f)) return -1;
     hipStream_t st = (hipStream_t)stream;
     const size_t P = (size_t)size * size;
-    char *ws = (char *)workspace(14, MaskScratch::bytes(1, P, n > 0 ? n : 1), st);
-    if (!ws) return 0;
     MaskScratch m;
-    m.carve(ws, 1, P, n > 0 ? n : 1);
+    WsLayout L;
+    m.layout(L, 1, P, n > 0 ? n : 1);
+    if (!ws_alloc(L, kWsSplatImage, st)) return 0;
     if (!m.zero_bins(st)) return 0;
     const int blend = render_blend();
     hipLaunchKernelGGL(mask_project_kernel, dim3(lin_grid(n > 0 ? n : 1), 1), dim3(kQBlock), 0, st, n, pts, (const float *)nullptr, 0,
@@ -2023,11 +2017,12 @@ GENPC_API int genpc_mask_loss(int size, const float *img, const float *ref, floa
     if (size <= 1) return -1;
     hipStream_t st = (hipStream_t)stream;
     const int P = size * size;
-    char *ws = (char *)workspace(18, 512 + MaskScratch::bytes(2, (size_t)P, 1), st);
-    if (!ws) return 0;
-    double *accum = (double *)ws;
+    double *accum;
     MaskScratch m;
-    m.carve(ws + 512, 2, (size_t)P, 1);
+    WsLayout L;
+    L.add(accum, 64);          // (kAcc sums in a 512-byte piece)
+    m.layout(L, 2, (size_t)P, 1);
+    if (!ws_alloc(L, kWsMaskLoss, st)) return 0;
     float *pl_img = m.planes, *pl_ref = m.planes + (size_t)5 * P;
     if (!check(hipMemsetAsync(accum, 0, kAcc * sizeof(double), st), "hipMemsetAsync(accum)")) return 0;
     const int g256 = ceil_div(P, 256), gp = lin_grid(P);
@@ -2055,13 +2050,13 @@ GENPC_API int genpc_pose_loss_grad(int nc, const float *v, const float *vert_col
     hipStream_t st = (hipStream_t)stream;
     const size_t P = mask ? (size_t)render_size * render_size : 0;
     const size_t nmax = (size_t)(nc > np ? nc : np);
-    const size_t o_state = 512, o_mask = o_state + MaskScratch::up(sizeof(PoseState));
-    char *ws = (char *)workspace(3, o_mask + MaskScratch::bytes(1, P, nmax), st);
-    if (!ws) return 0;
-    double *accum = (double *)ws;
-    PoseState *S = (PoseState *)(ws + o_state);
+    double *accum; PoseState *S;
     MaskScratch m;
-    m.carve(ws + o_mask, 1, P, nmax);
+    WsLayout L;
+    L.add(accum, 64);          // (kAcc sums in a 512-byte piece)
+    L.add(S, 1);
+    m.layout(L, 1, P, nmax);
+    if (!ws_alloc(L, kWsPoseLossGrad, st)) return 0;
     if (P && !m.zero_bins(st)) return 0;
     if (!check(hipMemsetAsync(accum, 0, kAcc * sizeof(double), st), "hipMemsetAsync(accum)")) return 0;
     if (!check(hipMemcpyAsync(S->params, params, 10 * sizeof(float), hipMemcpyDeviceToDevice, st), "copy params"))
@@ -2086,7 +2081,7 @@ GENPC_API int genpc_pose_cd_grad(int nc, const float *v, const float *center, co
     // loss_out[3]: total, cd, ortho (the Chamfer half alone)
     using namespace genpc;
     hipStream_t st = (hipStream_t)stream;
-    float *tmp = (float *)workspace(15, 256, st);
+    float *tmp = (float *)workspace(kWsPoseCdLoss, 256, st);
     if (!tmp) return 0;
     const int rc = genpc_pose_loss_grad(nc, v, nullptr, center, params, np, partial, nullptr, d1, i1, d2, i2, cd_weight,
                                         reg_weight, 0.0f, 0.0f, 0, tmp, grad, stream);
@@ -2210,49 +2205,38 @@ GENPC_API int genpc_pose_optimize_batch(int b, int nc, const float *complete, co
     const int scans = b, starts_in = starts;
     float *x_complete = nullptr, *x_partial = nullptr, *x_ccol = nullptr, *x_pcol = nullptr;
     if (lock) {
-        auto up0 = [](size_t x) { return (x + 255) / 256 * 256; };
-        const size_t bc = (size_t)b * lock * nc * 12, bp = (size_t)b * lock * np * 12;
-        char *xs = (char *)workspace(22, 2 * up0(bc) + 2 * up0(bp), st);
-        if (!xs) return 0;
-        x_complete = (float *)xs;
-        x_partial = (float *)(xs + up0(bc));
+        const size_t xc = (size_t)b * lock * nc * 3, xp = (size_t)b * lock * np * 3;
+        WsLayout X;          // (the colours' pieces are reserved whether or not the call brings colours)
+        X.add(x_complete, xc);
+        X.add(x_partial, xp);
+        X.add(x_ccol, xc);
+        X.add(x_pcol, xp);
+        if (!ws_alloc(X, kWsPoseReplicas, st)) return 0;
         hipLaunchKernelGGL(pose_replicate_kernel, dim3(lin_grid((long long)nc * 3), b), dim3(kQBlock), 0, st, (size_t)nc * 3, lock, complete, x_complete);
         hipLaunchKernelGGL(pose_replicate_kernel, dim3(lin_grid((long long)np * 3), b), dim3(kQBlock), 0, st, (size_t)np * 3, lock, partial, x_partial);
-        if (complete_col) {
-            x_ccol = (float *)(xs + up0(bc) + up0(bp));
+        if (complete_col)
             hipLaunchKernelGGL(pose_replicate_kernel, dim3(lin_grid((long long)nc * 3), b), dim3(kQBlock), 0, st, (size_t)nc * 3, lock, complete_col, x_ccol);
-        }
-        if (partial_col) {
-            x_pcol = (float *)(xs + 2 * up0(bc) + up0(bp));
+        if (partial_col)
             hipLaunchKernelGGL(pose_replicate_kernel, dim3(lin_grid((long long)np * 3), b), dim3(kQBlock), 0, st, (size_t)np * 3, lock, partial_col, x_pcol);
-        }
-        complete = x_complete; partial = x_partial; complete_col = x_ccol; partial_col = x_pcol;
+        complete = x_complete; partial = x_partial;
+        complete_col = complete_col ? x_ccol : nullptr; partial_col = partial_col ? x_pcol : nullptr;
         b *= lock;
         starts = 1;
     }
     const size_t P = mask ? (size_t)render_size * render_size : 0;
-    // scratch: accum[b,kAcc] | state[b] | center[b,4] | pts[b,nc,3] | d1 | d2 | i1 | i2 | mask scratch
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-    size_t off = 0;
-    const size_t o_acc = off; off += up((size_t)2 * b * kAcc * sizeof(double));        // two sets: a step's sums are read by the next step's
-    const size_t o_state = off; off += up((size_t)2 * b * sizeof(PoseState));           // transform (the fused update) while that step fills the other
-    const size_t o_center = off; off += up((size_t)b * 4 * sizeof(float));
-    const size_t o_pts = off; off += up((size_t)b * nc * 12);
-    const size_t o_d1 = off; off += up((size_t)b * nc * 4);
-    const size_t o_d2 = off; off += up((size_t)b * np * 4);
-    const size_t o_i1 = off; off += up((size_t)b * nc * 4);
-    const size_t o_i2 = off; off += up((size_t)b * np * 4);
-    const size_t o_mask = off; off += mask ? MaskScratch::bytes(b, P, (size_t)(nc > np ? nc : np)) : 0;
-    char *ws = (char *)workspace(4, off, st);
-    if (!ws) return 0;
-    double *accum = (double *)(ws + o_acc);
-    PoseState *S = (PoseState *)(ws + o_state);
-    float *center = (float *)(ws + o_center);
-    float *pts = (float *)(ws + o_pts);
-    float *d1 = (float *)(ws + o_d1), *d2 = (float *)(ws + o_d2);
-    int *i1 = (int *)(ws + o_i1), *i2 = (int *)(ws + o_i2);
+    double *accum; PoseState *S; float *center, *pts, *d1, *d2; int *i1, *i2;
     MaskScratch m = {};
-    if (mask) m.carve(ws + o_mask, b, P, (size_t)(nc > np ? nc : np));
+    WsLayout L;
+    L.add(accum, (size_t)2 * b * kAcc);        // two sets: a step's sums are read by the next step's
+    L.add(S, (size_t)2 * b);                   // transform (the fused update) while that step fills the other
+    L.add(center, (size_t)b * 4);
+    L.add(pts, (size_t)b * nc * 3);
+    L.add(d1, (size_t)b * nc);
+    L.add(d2, (size_t)b * np);
+    L.add(i1, (size_t)b * nc);
+    L.add(i2, (size_t)b * np);
+    if (mask) m.layout(L, b, P, (size_t)(nc > np ? nc : np));
+    if (!ws_alloc(L, kWsPoseLoop, st)) return 0;
     if (mask && !m.zero_bins(st)) return 0;
     constexpr int kStateFloats = (int)(sizeof(PoseState) / sizeof(float));
     static_assert(sizeof(PoseState) % sizeof(float) == 0, "PoseState must be float-addressable");
@@ -2267,7 +2251,7 @@ GENPC_API int genpc_pose_optimize_batch(int b, int nc, const float *complete, co
     // at every step -- the partial cloud does not move and equal rest-frame points are posed to equal points -- so
     // the filter's duplicate masks (nn_dedupe.hip) are made once per call, on the rest-frame clouds.
     const size_t w_p = (nn_dedupe_mask_words(b, np) + 63) & ~(size_t)63, w_c = (nn_dedupe_mask_words(b, nc) + 63) & ~(size_t)63;
-    unsigned *dup_p = (unsigned *)workspace(26, (w_p + w_c) * sizeof(unsigned), st);
+    unsigned *dup_p = (unsigned *)workspace(kWsPoseDupMasks, (w_p + w_c) * sizeof(unsigned), st);
     if (!dup_p) return 0;
     unsigned *dup_c = dup_p + w_p;
     {
@@ -2327,8 +2311,9 @@ GENPC_API int genpc_pose_optimize_batch(int b, int nc, const float *complete, co
     // (sequential starts: every start probes afresh)
     SeededGrids sg{};
     if (seeded) {
-        void *gw = workspace(29, seeded_grids_bytes(b, nc, np), st);
-        if (!gw || !build_seeded_grids(b, nc, complete, np, partial, gw, sg, st)) return 0;
+        WsLayout GL;
+        seeded_grids_layout(GL, sg, b, nc, np);
+        if (!ws_alloc(GL, kWsPoseSeededGrids, st) || !build_seeded_grids(b, nc, complete, np, partial, sg, st)) return 0;
     }
     const int fma_mode = arith_mode() != 0 ? 1 : 0;
 

@@ -679,11 +679,11 @@ GENPC_API int genpc_get_uvs(int c, int n, const float *view, float focal, float 
     if (c <= 0 || n <= 0) return 1;
     hipStream_t st = (hipStream_t)stream;
     // scratch: per-(camera, slice) approximate boxes, the cameras' final keys
-    const size_t part_bytes = (size_t)c * kBoxSlices * 4 * sizeof(float);
-    char *ws = (char *)workspace(2, part_bytes + (size_t)c * 4 * sizeof(unsigned), st);
-    if (!ws) return 0;
-    float *part = (float *)ws;
-    unsigned *keys = (unsigned *)(ws + part_bytes);
+    float *part; unsigned *keys;          // (a camera's boxes are whole 256-byte lines: kBoxSlices = 256)
+    WsLayout L;
+    L.add(part, (size_t)c * kBoxSlices * 4);
+    L.add_tail(keys, (size_t)c * 4);
+    if (!ws_alloc(L, kWsGetUvs, st)) return 0;
     const float A = (zfar + znear) / (znear - zfar);
     const float B = (2.0f * zfar * znear) / (znear - zfar);
     const int have_box = (rescale || bbox) ? 1 : 0;
@@ -727,11 +727,12 @@ GENPC_API int genpc_paint_pixels(int res, int n, const int *pix, const float *co
         int chunk = ceil_div(ceil_div(n, 512), kPBlock) * kPBlock;        // at most 512 blocks of whole 256-point strides
         if (chunk < kPaintChunk) chunk = kPaintChunk;
         const int gb = ceil_div(n, chunk);
-        const size_t h_bytes = ((size_t)gb * tiles * sizeof(int) + 255) / 256 * 256, t_bytes = ((size_t)tiles * sizeof(int) + 255) / 256 * 256;
-        char *ws = (char *)workspace(34, h_bytes + t_bytes + (size_t)n * per_point * sizeof(uint2), st);
-        if (!ws) return 0;
-        int *H = (int *)ws, *total = (int *)(ws + h_bytes);
-        uint2 *entries = (uint2 *)(ws + h_bytes + t_bytes);
+        int *H, *total; uint2 *entries;
+        WsLayout L;
+        L.add(H, (size_t)gb * tiles);
+        L.add(total, tiles);
+        L.add_tail(entries, (size_t)n * per_point);
+        if (!ws_alloc(L, kWsPaintBins, st)) return 0;
         hipLaunchKernelGGL(paint_bin_kernel<0>, dim3(gb), dim3(kPBlock), 0, st, res, n, chunk, pix, point_size, tiles_x, tiles, H, (const int *)total, entries);
         hipLaunchKernelGGL(paint_colscan_kernel, dim3(tiles), dim3(kWave), 0, st, gb, tiles, H, total);
         hipLaunchKernelGGL(paint_bin_kernel<1>, dim3(gb), dim3(kPBlock), 0, st, res, n, chunk, pix, point_size, tiles_x, tiles, H, (const int *)total, entries);
@@ -760,7 +761,7 @@ GENPC_API int genpc_gather_colors(int n, const int *pix, const float *img, int c
     // The copy costs a pass over the image (28 B per pixel), so only where the points outnumber a quarter of the pixels.
     if (ch == 3 && (long long)n * 4 >= (long long)h * w && (long long)h * w <= 0x7fffffffLL) {
         hipStream_t st = (hipStream_t)stream;
-        float4 *packed = (float4 *)workspace(33, (size_t)h * w * sizeof(float4), st);
+        float4 *packed = (float4 *)workspace(kWsPackedImage, (size_t)h * w * sizeof(float4), st);
         if (!packed) return 0;
         hipLaunchKernelGGL(pack_rgba_kernel, dim3(grid_for((long long)h * w, 4096)), dim3(kPBlock), 0, st, h * w, img, packed);
         hipLaunchKernelGGL(gather_colors_packed_kernel, dim3(ceil_div(n, kPBlock)), dim3(kPBlock), 0, st, n, pix, (const float4 *)packed, h, w, out);
@@ -782,7 +783,7 @@ GENPC_API int genpc_zbuffer_visibility(int c, int n, const float *uv, const floa
     int group = (int)(((size_t)64 << 20) / ((size_t)res * res * sizeof(unsigned)));
     if (group < 1) group = 1;
     if (group > c) group = c;
-    unsigned *zbuf = (unsigned *)workspace(8, (size_t)group * res * res * sizeof(unsigned), st);
+    unsigned *zbuf = (unsigned *)workspace(kWsZbuffer, (size_t)group * res * res * sizeof(unsigned), st);
     if (!zbuf) return 0;
     if (!check(hipMemsetAsync(counts, 0, (size_t)c * sizeof(int), st), "hipMemsetAsync(counts)")) return 0;
     for (int c0 = 0; c0 < c; c0 += group) {

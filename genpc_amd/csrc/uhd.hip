@@ -149,12 +149,11 @@ static int uhd(int b, int n, const float *xyz, int m, const float *xyz2, double 
         set_error("genpc_uhd: problem too large for one launch (B <= 65535, N <= 2^30, M <= 65535 * 512)");
         return -1;
     }
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_recs = al((size_t)b * tiles * n * sizeof(double)), bytes = o_recs + al((size_t)b * nrecs * sizeof(UhdRec));
-    char *ws = (char *)workspace(37, bytes, st);
-    if (!ws) return -1;
-    double *partial = (double *)ws;
-    UhdRec *recs = (UhdRec *)(ws + o_recs);
+    double *partial; UhdRec *recs;
+    WsLayout L;
+    L.add(partial, (size_t)b * tiles * n);
+    L.add(recs, (size_t)b * nrecs);
+    if (!ws_alloc(L, kWsUhd, st)) return -1;
     hipLaunchKernelGGL(uhd_pairs_kernel, dim3(qblocks, tiles, b), dim3(kUhdBlock), 0, st, n, xyz, m, xyz2, partial);
     if (!check(hipGetLastError(), "uhd_pairs_kernel launch")) return -1;
     hipLaunchKernelGGL(uhd_query_kernel, dim3(nrecs, b), dim3(kUhdBlock), 0, st, n, tiles, (const double *)partial, recs);

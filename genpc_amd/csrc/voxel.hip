@@ -152,27 +152,23 @@ GENPC_API int genpc_voxel_down_sample(int n, const float *xyz, const float *colo
     if (n < 0 || !(voxel_size > 0.0)) return -1;
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) return check(hipMemsetAsync(out_count, 0, sizeof(int), st), "hipMemsetAsync(voxel count)") ? 1 : 0;
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
     size_t sort_bytes = 0, scan_bytes = 0;
     (void)rocprim::radix_sort_pairs(nullptr, sort_bytes, (const unsigned long long *)nullptr, (unsigned long long *)nullptr,
                                     (const int *)nullptr, (int *)nullptr, (size_t)n, 0u, 63u, st);
     (void)rocprim::inclusive_scan(nullptr, scan_bytes, (const int *)nullptr, (int *)nullptr, (size_t)n, rocprim::plus<int>(), st);
-    const size_t tmp_bytes = up(sort_bytes > scan_bytes ? sort_bytes : scan_bytes);
-    size_t off = 0;
-    const size_t o_bounds = off; off += 256;
-    const size_t o_k0 = off; off += up((size_t)n * 8);
-    const size_t o_k1 = off; off += up((size_t)n * 8);
-    const size_t o_i0 = off; off += up((size_t)n * 4);
-    const size_t o_i1 = off; off += up((size_t)n * 4);
-    const size_t o_head = off; off += up((size_t)n * 4);
-    const size_t o_rank = off; off += up((size_t)n * 4);
-    const size_t o_tmp = off; off += tmp_bytes;
-    char *ws = (char *)workspace(16, off, st);
-    if (!ws) return 0;
-    unsigned *bounds = (unsigned *)(ws + o_bounds);
-    int *err = (int *)(ws + o_bounds + 64);
-    unsigned long long *k0 = (unsigned long long *)(ws + o_k0), *k1 = (unsigned long long *)(ws + o_k1);
-    int *i0 = (int *)(ws + o_i0), *i1 = (int *)(ws + o_i1), *head = (int *)(ws + o_head), *rank = (int *)(ws + o_rank);
+    unsigned *bounds; unsigned long long *k0, *k1; int *i0, *i1, *head, *rank; char *tmp;
+    WsLayout L;
+    L.add(bounds, 64);          // a 256-byte header, hand-placed: the bounds in words 0 .. 5, the error flag in word 16
+    L.add(k0, n);
+    L.add(k1, n);
+    L.add(i0, n);
+    L.add(i1, n);
+    L.add(head, n);
+    L.add(rank, n);
+    const size_t tmp_bytes = WsLayout::up(sort_bytes > scan_bytes ? sort_bytes : scan_bytes);
+    L.add(tmp, tmp_bytes);
+    if (!ws_alloc(L, kWsVoxel, st)) return 0;
+    int *err = (int *)(bounds + 16);
     // bounds: min = 0xffffffff x3, max = 0 x3, err = 0
     if (!check(hipMemsetAsync(bounds, 0xff, 12, st), "hipMemsetAsync(voxel)")) return 0;
     if (!check(hipMemsetAsync(bounds + 3, 0, 256 - 12, st), "hipMemsetAsync(voxel)")) return 0;
@@ -181,12 +177,12 @@ GENPC_API int genpc_voxel_down_sample(int n, const float *xyz, const float *colo
     hipLaunchKernelGGL(voxel_key_kernel, dim3(grid), dim3(kVBlock), 0, st, n, xyz, voxel_size, (const unsigned *)bounds, k0,
                        i0, err);
     size_t sb = tmp_bytes;
-    if (!check(rocprim::radix_sort_pairs(ws + o_tmp, sb, (const unsigned long long *)k0, k1, (const int *)i0, i1, (size_t)n, 0u, 63u, st),
+    if (!check(rocprim::radix_sort_pairs(tmp, sb, (const unsigned long long *)k0, k1, (const int *)i0, i1, (size_t)n, 0u, 63u, st),
                "voxel radix sort"))
         return 0;
     hipLaunchKernelGGL(voxel_head_kernel, dim3(grid), dim3(kVBlock), 0, st, n, (const unsigned long long *)k1, head);
     sb = tmp_bytes;
-    if (!check(rocprim::inclusive_scan(ws + o_tmp, sb, (const int *)head, rank, (size_t)n, rocprim::plus<int>(), st), "voxel scan")) return 0;
+    if (!check(rocprim::inclusive_scan(tmp, sb, (const int *)head, rank, (size_t)n, rocprim::plus<int>(), st), "voxel scan")) return 0;
     hipLaunchKernelGGL(voxel_mean_kernel, dim3(grid), dim3(kVBlock), 0, st, n, xyz, (const unsigned long long *)k1, colors,
                        (const int *)i1, (const int *)head, (const int *)rank, out, out_colors, out_count);
     if (!check(hipGetLastError(), "voxel_down_sample launch")) return 0;
