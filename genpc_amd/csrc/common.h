@@ -63,6 +63,7 @@ enum Ws : int {
     kWsKnnMean = 35,          // knn.hip launch_knn: the cloud's cell grid
     kWsKnnQuery = 36,         // knn_query.hip knn_query: the targets' cell grid | query order
     kWsUhd = 37,              // uhd.hip uhd: per-tile partial maxima | per-block records
+    kWsNnRagged = 38,         // nn_ragged.hip nn_ragged: the pairs' grid headers | cell tables | sorted targets
 };
 
 // The scratch pool: one grow-only block of device memory per (device, slot, stream); null on failure, the error recorded.

@@ -16,6 +16,7 @@
 // their own that nothing here proves (DESIGN_NOTEBOOK.md, "fps_grid.hip and icp_fused_kernel on grid.h").
 #pragma once
 #include "common.h"
+#include "ragged_table.h"
 
 namespace genpc {
 
@@ -194,6 +195,14 @@ struct CellGridHdr : GridFrame {     // one per batch element, written by cell_g
 // = point when not null.
 int launch_cell_grid_build(int b, int n, const float *xyz, const float *price, CellGridHdr *hdr, int *start, float4 *sorted, int *pos_of,
                            int *orig_of, int cells_target, int cells_max, hipStream_t st, float *price_sep = nullptr);
+
+// The ragged sibling: cloud j is xyz[t.toff[j] .. t.toff[j + 1]), its grid sized for itself (ragged_cells_target / ragged_cells_max
+// of ITS point count); hdr[j], its cell table at start + t.toff[j] + 65 j, sorted[t.toff[j] ..] = (x, y, z, index inside the
+// cloud).  A cloud whose pair has no queries (t.qoff) is skipped and its pieces stay unwritten.  max_targets: the largest
+// cloud that is built (sizes the LDS counters).  One launch for all clouds.
+static_assert(kRaggedCellsCap == kCellGridMaxCells, "ragged_table.h restates the build's LDS budget");
+int launch_cell_grid_build_ragged(const RaggedTable &t, int max_targets, const float *xyz, CellGridHdr *hdr, int *start, float4 *sorted,
+                                  hipStream_t st);
 
 // The walk of a k-nearest search (knn_query.hip, knn.hip) over a grid built by launch_cell_grid_build: ST = its start[].
 // The lane walks shells of cells by Chebyshev distance r = 0, 1, 2 ... from the (clamped) cell of its query (qx, qy, qz).

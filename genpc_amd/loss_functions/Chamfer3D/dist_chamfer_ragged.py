@@ -1,0 +1,85 @@
+"""``chamfer_ragged``: both Chamfer directions for clouds of different sizes in one call per direction
+(genpc_nm_distance_ragged).  The reference never batches unequal clouds -- it scores one file at a time (metric.py:10-48)
+-- so there is nothing of its interface to keep here; the results per pair are those of ``chamfer_3DDist`` on that pair
+alone.  Forward only: ``chamfer_3DDist`` is the differentiable path.
+"""
+import torch
+
+from ... import _lib, chamfer_3D
+
+
+def _is_offsets(x):
+    if torch.is_tensor(x):
+        return x.dim() == 1 and not x.dtype.is_floating_point and not x.dtype.is_complex
+    if isinstance(x, (list, tuple)) or type(x).__name__ == "ndarray":
+        return all(isinstance(v, int) or (hasattr(v, "dtype") and getattr(v, "ndim", 1) == 0 and "int" in str(v.dtype)) for v in x)
+    return False
+
+
+def pack_clouds(clouds, name="clouds"):
+    """A ragged batch as (points [T,3] float32 contiguous, offsets: c + 1 Python ints).  ``clouds`` is a list of [N_j,3]
+    tensors, or already packed: a tuple (points [T,3], offsets) with offsets a sequence of ints or a 1-D CPU int tensor."""
+    if isinstance(clouds, tuple) and len(clouds) == 2 and torch.is_tensor(clouds[0]) and _is_offsets(clouds[1]):
+        points, off = clouds
+        if torch.is_tensor(off):
+            if off.is_cuda:
+                raise ValueError("chamfer_ragged: the offsets of %s live on the host (a device tensor would have to be read back)" % name)
+            off = off.tolist()
+        off = [int(v) for v in off]
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError("chamfer_ragged: packed %s must be [T,3], got %s" % (name, tuple(points.shape)))
+        if not off or off[0] != 0 or any(b < a for a, b in zip(off, off[1:])) or off[-1] != points.shape[0]:
+            raise ValueError("chamfer_ragged: the offsets of %s must ascend from 0 to its %d points" % (name, points.shape[0]))
+        if points.dtype != torch.float32:
+            raise TypeError("chamfer_ragged: %s must be torch.float32, got %s" % (name, points.dtype))
+        return points.contiguous(), off
+    if not isinstance(clouds, (list, tuple)):
+        raise TypeError("chamfer_ragged: %s is a list of [N,3] tensors or a tuple (points, offsets)" % name)
+    off = [0]
+    for j, t in enumerate(clouds):
+        if not torch.is_tensor(t) or t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError("chamfer_ragged: %s[%d] must be an [N,3] tensor" % (name, j))
+        if t.dtype != torch.float32:
+            raise TypeError("chamfer_ragged: %s[%d] must be torch.float32, got %s" % (name, j, t.dtype))
+        if t.device != clouds[0].device:
+            raise ValueError("chamfer_ragged: %s[%d] is on %s, %s[0] on %s" % (name, j, t.device, name, clouds[0].device))
+        off.append(off[-1] + t.shape[0])
+    if len(clouds) == 0:
+        return torch.empty((0, 3), dtype=torch.float32), off
+    return torch.cat(list(clouds), dim=0).contiguous(), off
+
+
+def _one_way(q, qoff, t, toff):
+    """Queries against targets, at most chamfer_3D.RAGGED_MAX_PAIRS pairs per library call (a longer list takes several)."""
+    dist = torch.empty((q.shape[0],), dtype=torch.float32, device=q.device)
+    idx = torch.empty((q.shape[0],), dtype=torch.int32, device=q.device)
+    step = chamfer_3D.RAGGED_MAX_PAIRS
+    for a in range(0, len(qoff) - 1, step):
+        b = min(a + step, len(qoff) - 1)
+        q0, q1, t0, t1 = qoff[a], qoff[b], toff[a], toff[b]
+        rc = chamfer_3D.nm_distance_ragged(q[q0:q1], [v - q0 for v in qoff[a:b + 1]], t[t0:t1], [v - t0 for v in toff[a:b + 1]],
+                                           dist[q0:q1], idx[q0:q1])
+        if rc != 1:
+            raise RuntimeError("chamfer_3D.nm_distance_ragged failed: " + _lib.last_error())
+    return dist, idx
+
+
+def chamfer_ragged(clouds1, clouds2):
+    """Pair j: clouds1[j] [N_j,3] against clouds2[j] [M_j,3], float32 GPU tensors; each side a list, or packed as
+    (points, offsets).  Returns (dist1, dist2, idx1, idx2, offsets1, offsets2): dist1 / idx1 packed like clouds1 -- the
+    squared distance from each of its points to the nearest point of the pair's clouds2[j] and that point's index INSIDE
+    clouds2[j] -- dist2 / idx2 the converse; offsets as int64 CPU tensors of c + 1 entries.  Per pair the bits of
+    chamfer_3DDist on that pair alone, for finite clouds; a pair with an empty cloud on one side only is an error.
+    Forward only."""
+    p1, off1 = pack_clouds(clouds1, "clouds1")
+    p2, off2 = pack_clouds(clouds2, "clouds2")
+    if len(off1) != len(off2):
+        raise ValueError("chamfer_ragged: %d clouds against %d" % (len(off1) - 1, len(off2) - 1))
+    if p1.requires_grad or p2.requires_grad:
+        raise RuntimeError("chamfer_ragged is forward only and an input requires grad: chamfer_3DDist is the differentiable path")
+    _lib.require_gpu(p1, p2)
+    if p1.device != p2.device:
+        raise ValueError("chamfer_ragged: clouds1 and clouds2 are on different devices")
+    dist1, idx1 = _one_way(p1, off1, p2, off2)
+    dist2, idx2 = _one_way(p2, off2, p1, off1)
+    return dist1, dist2, idx1, idx2, torch.tensor(off1, dtype=torch.int64), torch.tensor(off2, dtype=torch.int64)

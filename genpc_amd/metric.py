@@ -16,6 +16,12 @@ Hausdorff distance from the partial scan to the completed cloud -- the one score
 reconstructed mesh against a ground-truth MESH (``metric_sds_redwood``, :49-94), both sampled on the device.
 
     python -m genpc_amd.metric --uhd PARTIAL.ply COMPLETE.ply
+
+``evaluate_clouds`` is ``evaluate_scans`` for clouds of different sizes -- what ``metric_my_redwood(flag, cd_l1=True)``
+(metric.py:10-48) scores one file at a time: a prediction against a ground truth of whatever size its file has -- on the
+ragged nearest-neighbour search (csrc/nn_ragged.hip), all scans in one call per direction.
+
+    python -m genpc_amd.metric --clouds PRED_DIR GT_DIR
 """
 import argparse
 import os
@@ -36,6 +42,53 @@ def evaluate_scans(pred, gt, eps=0.005, iters=50):
     de, _ = emdModule()(pred, gt, eps, iters)
     emd = torch.sqrt(de).mean(1)
     return torch.stack([cd_l1, cd_l2, emd], dim=1)
+
+
+def evaluate_clouds(preds, gts):
+    """preds, gts: S clouds each, of any sizes -- lists of [N_j,3] / [M_j,3] float32 GPU tensors, or packed as (points,
+    offsets) (loss_functions/Chamfer3D/dist_chamfer_ragged.py).  Returns float64 [S,2] = CD-L1, CD-L2 per scan with the
+    reductions of utils/loss_util.py:25-33: sqrt in fp32 as there, each scan's means accumulated in float64 over its own
+    segment.  No EMD column: the auction needs equal sizes.  Stays on the device; a scan with an empty cloud scores NaN."""
+    from .loss_functions.Chamfer3D.dist_chamfer_ragged import chamfer_ragged
+    d1, d2, _, _, off1, off2 = chamfer_ragged(preds, gts)
+    s = off1.numel() - 1
+
+    def seg_means(d, off):
+        counts = (off[1:] - off[:-1]).to(d.device)
+        seg = torch.repeat_interleave(torch.arange(s, device=d.device), counts, output_size=d.numel())
+        cnt = counts.double()
+        m1 = torch.zeros(s, dtype=torch.float64, device=d.device).index_add_(0, seg, torch.sqrt(d).double()) / cnt
+        m2 = torch.zeros(s, dtype=torch.float64, device=d.device).index_add_(0, seg, d.double()) / cnt
+        return m1, m2
+    a1, a2 = seg_means(d1, off1)
+    b1, b2 = seg_means(d2, off2)
+    return torch.stack([(a1 + b1) / 2, a2 + b2], dim=1)
+
+
+def match_cloud_files(pred_dir, gt_dir):
+    """The PLY files of two folders matched by file name: (pairs, only_pred, only_gt) with pairs = [(name, pred path,
+    gt path)] in name order and the names that lack a counterpart on either side.  Touches no GPU."""
+    def plys(d):
+        return {f for f in os.listdir(d) if f.lower().endswith(".ply") and os.path.isfile(os.path.join(d, f))}
+    p, g = plys(pred_dir), plys(gt_dir)
+    pairs = [(f, os.path.join(pred_dir, f), os.path.join(gt_dir, f)) for f in sorted(p & g)]
+    return pairs, sorted(p - g), sorted(g - p)
+
+
+def score_cloud_folders(pred_dir, gt_dir):
+    """CD-L1 and CD-L2 of every PLY of pred_dir against the PLY of the same name in gt_dir, at the files' own sizes:
+    (names, float64 [S,2] on the host, only_pred, only_gt)."""
+    from .utils.dataUtils import read_ply
+    pairs, only_pred, only_gt = match_cloud_files(pred_dir, gt_dir)
+    dev = torch.device("cuda", torch.cuda.current_device())
+
+    def load(path):
+        xyz, _ = read_ply(path, want_color=False)
+        return torch.from_numpy(np.ascontiguousarray(xyz, dtype=np.float32)).reshape(-1, 3).to(dev)
+    if not pairs:
+        return [], np.zeros((0, 2)), only_pred, only_gt
+    table = evaluate_clouds([load(p) for _, p, _ in pairs], [load(g) for _, _, g in pairs])
+    return [n for n, _, _ in pairs], table.cpu().numpy(), only_pred, only_gt
 
 
 def cd_l1_cpu_plumbing(pred, gt, chunk=512):
@@ -229,7 +282,17 @@ def main():
     ap.add_argument("--cpu", action="store_true", help="BASELINE config 1: CD-L1 only, plain torch on the CPU (plumbing, no GPU)")
     ap.add_argument("--uhd", nargs=2, metavar=("PARTIAL.ply", "COMPLETE.ply"),
                     help="directed Hausdorff distance partial -> complete of two PLY clouds (the reference's UHD), printed x100")
+    ap.add_argument("--clouds", nargs=2, metavar=("PRED_DIR", "GT_DIR"),
+                    help="CD-L1 of every PLY of PRED_DIR against the PLY of the same name in GT_DIR, at the files' own sizes, printed x100")
     args = ap.parse_args()
+    if args.clouds:
+        names, table, only_pred, only_gt = score_cloud_folders(*args.clouds)
+        for name, (cd, _) in zip(names, table):
+            print(f"{name} : {cd * 100:.2f}")                                       # metric.py:40
+        for side, lost in (("GT_DIR", only_pred), ("PRED_DIR", only_gt)):
+            for name in lost:
+                print(f"{name} : no counterpart in {side}")
+        return
     if args.uhd:
         print(f"UHD: {UHD(*args.uhd) * 100:.2f}")                                   # metric.py:195
         return

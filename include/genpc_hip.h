@@ -33,7 +33,7 @@ extern "C" {
 #define GENPC_ARITH_FMA 1
 
 /* Library / device ------------------------------------------------------- */
-int genpc_abi_version(void);              /* bumps when a signature or a documented behaviour changes (20: genpc_mesh_sample added; 19: genpc_uhd added; 18: genpc_knn_query added;
+int genpc_abi_version(void);              /* bumps when a signature or a documented behaviour changes (21: genpc_nm_distance_ragged added; 20: genpc_mesh_sample added; 19: genpc_uhd added; 18: genpc_knn_query added;
                                            * 17: genpc_fps_tune takes 0 or 256 only; 16: genpc_hpr_* asynchronous, counts -1 on an internal error;
                                            * genpc_fps*: out_idx[0] -2 = failed the check) */
 const char *genpc_last_error(void);       /* last HIP error string, "" if none */
@@ -106,6 +106,26 @@ int genpc_nm_distance(int b, int n, const float *xyz, int m, const float *xyz2,
  * than the limit: O(N + M) whatever the overlap of the two clouds.  Returns -1 for radius2 < 0. */
 int genpc_nm_distance_within(int b, int n, const float *xyz, int m, const float *xyz2,
                              float radius2, float *result, int *result_i, void *stream);
+
+/* Ragged NmDistance: c independent pairs of any sizes in one call.  Pair j has queries xyz[noff[j] .. noff[j+1]) and targets
+ * xyz2[moff[j] .. moff[j+1]).  noff, moff: HOST arrays of c + 1 ascending ints, noff[0] = moff[0] = 0; they are copied before
+ * the call returns and may be reused at once.  xyz [noff[c],3], xyz2 [moff[c],3], result [noff[c]] float, result_i [noff[c]] int:
+ * device, packed in pair order.  result_i is the index INSIDE the pair's own target cloud.
+ * Finite clouds: pair j's results are bit for bit what genpc_nm_distance(1, N_j, .., M_j, ..) returns for that pair alone
+ * (the call's arithmetic mode, lowest index among targets at bit-equal distance).
+ * Non-finite coordinates -- a deliberate departure from genpc_nm_distance, whose 512-target tile rule means nothing to a
+ * search that does not tile that way: a query with a non-finite coordinate gets (NaN, -1); every query of a pair whose
+ * TARGET cloud holds a non-finite coordinate gets (NaN, -1); the other pairs of the call are unaffected.  Decided on the
+ * device.
+ * A pair with N_j == 0 is legal and writes nothing (its targets are not looked at).  Returns 1 at once for c == 0 or no
+ * queries in total (after the offsets have been checked); -1 with genpc_last_error set and nothing enqueued for c < 0, null
+ * noff / moff with c > 0, noff[0] != 0 or moff[0] != 0, descending offsets, a pair with queries and no targets, a null device
+ * pointer with work to do, or beyond the limits: c <= 384 pairs per call (the pair table travels in the kernel arguments)
+ * and noff[c], moff[c] <= 2^28 points.
+ * Asynchronous on `stream`: two launches whatever c is, scratch from the library's workspace, no copy, no host read-back,
+ * no synchronisation (csrc/nn_ragged.hip).                                                                              */
+int genpc_nm_distance_ragged(int c, const int *noff, const float *xyz, const int *moff, const float *xyz2,
+                             float *result, int *result_i, void *stream);
 
 /* Replaces chamfer_cuda_backward (chamfer3D.cu:176-195, chamfer_3D.backward in
  * chamfer_cuda.cpp:22-26,32).  gradxyz1[B,N,3] / gradxyz2[B,M,3] must be zeroed
