@@ -72,18 +72,6 @@ __device__ __forceinline__ int gcell(float v, float lo, float inv, int n)
     return (int)fminf(fmaxf((v - lo) * inv, 0.0f), (float)(n - 1));
 }
 
-// slot = counter++ for the lanes of the wave that call it together (one LDS atomic per wave, not per lane)
-__device__ __forceinline__ int wave_push(int *counter)
-{
-    const unsigned long long mask = __ballot(1);
-    const int leader = (int)__ffsll((long long)mask) - 1;
-    const int lane = threadIdx.x & (kWave - 1);
-    int base = 0;
-    if (lane == leader) base = atomicAdd(counter, (int)__popcll(mask));
-    base = __shfl(base, leader);
-    return base + (int)__popcll(mask & ((1ull << lane) - 1ull));
-}
-
 template <int FMA>
 __global__ __launch_bounds__(kGT) void fps_grid_kernel(FpsGridJobs jobs, int *__restrict__ err)
 {

@@ -1,7 +1,7 @@
 // grid.h -- the uniform grid under every pruned search of the library (nn_grid.hip, emd_grid.hip, emd_auction.hip,
-// nn_seeded.hip, knn_query.hip, knn.hip): the frame of a grid, the cell function, the sizing, the pieces of the LDS counting sort
-// that the build kernels share, the bound by which a cell or a row of cells is skipped, and the walk over shells of cells
-// of the k-nearest search.
+// nn_seeded.hip, knn_query.hip, knn.hip, icp.hip): the frame of a grid, the cell function, the sizing, the pieces of
+// the LDS counting sort that the build kernels share, the bound by which a cell or a row of cells is skipped, and the walk over
+// shells of cells of the k-nearest search.
 //
 // Bound.  cell(p) = clamp(floor(fl(fl(p - lo) * inv)), 0, G - 1) is monotone in p, and a point of
 // cell c satisfies  lo + c h (1 - 3u) <= p < lo + (c + 1) h (1 + 3u)  (u = 2^-24, h = 1 / inv;
@@ -9,11 +9,13 @@
 // 16u (|lo| + G h + |q|) per axis, gap_a = max(0, wall_lo - s - q, q - wall_hi - s) <= |p_a - q_a|
 // for every point p of the cell; the reference's distance is >= (sum gap_a^2)(1 - 6u); a cell is
 // skipped iff  (sum gap_a^2)(1 - 2^-20) > best  (strictly: ties with lower indices are still
-// found).  Underflow only weakens the bound; an overflowing bound equals +inf and is only used
+// found).  A search whose queries leave the box (icp.hip) gives the border cells the cloud's exact minimum and maximum for
+// outer walls (grid_wall_gap takes any walls): every point satisfies mn <= p <= mx with no rounding at all, so the inequality
+// holds a fortiori under the same slack.  Underflow only weakens the bound; an overflowing bound equals +inf and is only used
 // against a finite best.  The helpers below ARE that arithmetic: a search that changes an intrinsic, an operand order or
-// an association in its own copy has left the proof behind, which is why there are no copies -- but two, owed: fps_grid.hip
-// (gcell, box_margin, 0.9999f) and icp.hip's icp_fused_kernel (IcpGrid, icp_cell_of, icp_axis_gap) keep grids and margins of
-// their own that nothing here proves (DESIGN_NOTEBOOK.md, "fps_grid.hip and icp_fused_kernel on grid.h").
+// an association in its own copy has left the proof behind, which is why there are no copies -- but one: fps_grid.hip (gcell,
+// box_margin, 0.9999f) keeps a grid and margins of its own that nothing here proves.  On these helpers it returns the same
+// samples 0.8 - 2 % later, which is more than its own spread (DESIGN_NOTEBOOK.md, "icp_fused_kernel on grid.h; fps_grid.hip measured").
 #pragma once
 #include "common.h"
 #include "ragged_table.h"
@@ -41,14 +43,21 @@ __device__ __forceinline__ int grid_cell1(float p, float lo, float inv, int g)
 
 __device__ __forceinline__ float grid_slack(float slack, float q) { return slack + kGridU16 * fabsf(q); }
 
-// lower bound of |p_a - q_a| over the points p of cells [c, c + w) of an axis (g cells of side h from lo; border cells
-// unbounded outwards); s = grid_slack of q on that axis
-__device__ __forceinline__ float grid_gap(int c, int w, int g, float lo, float h, float q, float s)
+// lower bound of |p_a - q_a| over the points p with wl <= p_a <= wh (walls as fp32 values); s = grid_slack of q on that axis
+__device__ __forceinline__ float grid_wall_gap(float wl, float wh, float q, float s)
 {
-    const float inf = __builtin_inff();
-    const float wl = c > 0 ? __fadd_rn(lo, __fmul_rn((float)c, h)) : -inf;
-    const float wh = c + w < g ? __fadd_rn(lo, __fmul_rn((float)(c + w), h)) : inf;
     return fmaxf(0.0f, fmaxf((wl - s) - q, (q - s) - wh));
+}
+
+// lower bound of |p_a - q_a| over the points p of cells [c, c + w) of an axis (g cells of side h from lo; border cells
+// unbounded outwards, or bounded by the cloud's exact minimum mn and maximum mx where the caller has them); s = grid_slack of q
+// on that axis
+__device__ __forceinline__ float grid_gap(int c, int w, int g, float lo, float h, float q, float s, float mn = -__builtin_inff(),
+                                          float mx = __builtin_inff())
+{
+    const float wl = c > 0 ? __fadd_rn(lo, __fmul_rn((float)c, h)) : mn;
+    const float wh = c + w < g ? __fadd_rn(lo, __fmul_rn((float)(c + w), h)) : mx;
+    return grid_wall_gap(wl, wh, q, s);
 }
 
 // Block-wide box: every thread brings the (mn, mx) of its own points and leaves with the block's.  s_red: 6 floats per wave.
@@ -76,6 +85,23 @@ __device__ __forceinline__ void grid_block_box(float mn[3], float mx[3], float *
             mx[k] = fmaxf(mx[k], s_red[w * 6 + 3 + k]);
         }
     }
+}
+
+// The frame of g cells of side h from mn.  A side whose reciprocal is not a positive finite number: one cell of side 1.
+__device__ __forceinline__ void grid_frame(const float mn[3], const int g[3], float h, GridFrame &F)
+{
+    float inv = 1.0f / h;
+    const bool one = !(inv > 0.0f) || !(inv < __builtin_inff());
+    if (one) { inv = 1.0f; h = 1.0f; }
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const int gk = one ? 1 : g[k];
+        F.lo[k] = mn[k];
+        F.g[k] = gk;
+        F.slack[k] = kGridU16 * (fabsf(mn[k]) + (float)(gk + 1) * h);
+    }
+    F.inv = inv;
+    F.h = h;
 }
 
 // Box (mn, mx) -> cubic cells of side h, about cells_target of them over the axes that are wider than h, at most
@@ -129,20 +155,8 @@ __device__ __forceinline__ void grid_size(float mn[3], float mx[3], int cells_ta
         h *= 1.26f;
         if (rep == REPS - 1) { act[0] = act[1] = act[2] = false; }
     }
-    float inv = 1.0f / h;
-    if (!(inv > 0.0f) || !(inv < __builtin_inff())) {
-        inv = 1.0f; h = 1.0f;
-        for (int k = 0; k < 3; k++) g[k] = 1;
-    }
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        if (!act[k]) g[k] = 1;
-        F.lo[k] = mn[k];
-        F.g[k] = g[k];
-        F.slack[k] = kGridU16 * (fabsf(mn[k]) + (float)(g[k] + 1) * h);
-    }
-    F.inv = inv;
-    F.h = h;
+    for (int k = 0; k < 3; k++) if (!act[k]) g[k] = 1;
+    grid_frame(mn, g, h, F);
 }
 
 // The scan between the histogram and the scatter of a counting sort in LDS: s_cnt[0 .. width) holds counts on entry and

@@ -338,43 +338,21 @@ __global__ __launch_bounds__(kIBlock) void cd_score_kernel(int n1, const float *
 // in flight the device runs ~90 k kernels per second whatever the number of queues: the launches are the limit there).
 //
 // ICP uses a correspondence only when its squared distance is <= max_dist^2, so the nearest-neighbour search needs no more than
-// the targets within max_dist of the query: the target cloud goes ONCE into a uniform grid in LDS (cell >= 1.001 max_dist: a
-// target within max_dist lies in the 27 cells around the query's), and a pass is, per wave and 64 queries at a time,
+// the targets within max_dist of the query: the target cloud goes ONCE into a uniform grid in LDS (grid.h's frame, cell function
+// and counting sort; cell >= 1.001 max_dist: a target within max_dist lies in the 27 cells around the query's), and a pass is,
+// per wave and 64 queries at a time,
 //   p' = T p (registers) -> the home cell's points -> three rounds (one plane of 9 neighbour cells each): the (query, cell) pairs
 //   whose box can still hold a point nearer than the query's best so far (or than max_dist) go to a wave-private list in LDS and are
 //   worked off one pair per lane (ds_min_u64 on distance bits << 32 | index: the smallest distance, the lowest index among equals,
 //   which is the order of the exhaustive search) -> Kabsch sums of the inliers in double registers
 // -- no workgroup barrier inside --, then a fixed-order reduction (lane tree, waves in order: the sums do not depend on timing,
 // unlike the atomics above) and the update by one thread.  Distances: sqdist<FMA>, the arithmetic of the exhaustive search.
-// Boxes are widened by 4e-7 of the largest coordinate and compared with 1e-5 relative slack: a cell is skipped only when no
-// point of it can tie or beat the bound in fp32.
+// A (query, cell) pair is left out by the Bound of grid.h alone: only when no point of the cell can tie or beat the limit in fp32.
 constexpr int kFT = 1024;
 constexpr int kFWaves = kFT / kWave;
 constexpr int kFItems = 512;                 // (query, neighbour cell) pairs of one wave per round of the list
 constexpr int kFAxis = 64;                   // cells per axis at most
 constexpr size_t kFFixed = (size_t)kFT * 16 + (size_t)kFT * 8 + (size_t)kFWaves * kFItems * 4 + (size_t)17 * kFWaves * 8 + 16 * 8 + 17 * 8;
-
-struct IcpGrid {
-    float lo[3], hi[3];
-    float h, inv_h, eps;
-    int c[3];
-};
-
-__device__ __forceinline__ int icp_cell_of(const IcpGrid &G, float x, float y, float z)
-{
-    const int ix = (int)fminf(fmaxf((x - G.lo[0]) * G.inv_h, 0.0f), (float)(G.c[0] - 1));
-    const int iy = (int)fminf(fmaxf((y - G.lo[1]) * G.inv_h, 0.0f), (float)(G.c[1] - 1));
-    const int iz = (int)fminf(fmaxf((z - G.lo[2]) * G.inv_h, 0.0f), (float)(G.c[2] - 1));
-    return (iz * G.c[1] + iy) * G.c[0] + ix;
-}
-// squared distance from p to the (widened) box of cell i along one axis
-__device__ __forceinline__ float icp_axis_gap(const IcpGrid &G, int a, int i, float p)
-{
-    const float lo = G.lo[a] + (float)i * G.h - G.eps;
-    const float hi = (i == G.c[a] - 1 ? G.hi[a] : G.lo[a] + (float)(i + 1) * G.h) + G.eps;
-    const float g = fmaxf(fmaxf(lo - p, p - hi), 0.0f);
-    return g * g;
-}
 
 // key of a candidate: distance bits << 32 | index << 16 | position in P -- the smallest distance, the lowest index among equals
 template <int FMA>
@@ -421,10 +399,10 @@ __global__ __launch_bounds__(kFT) void icp_fused_kernel(int ns, const float *__r
                                                         double *__restrict__ stats)
 {
     extern __shared__ __align__(16) unsigned char icp_lds[];
-    __shared__ IcpGrid G;
+    __shared__ GridFrame F;
+    __shared__ float s_mx[3];                  // the cloud's maximum (its minimum is F.lo): the outer walls of the border cells
     __shared__ IcpState s_state;
-    __shared__ float s_bb[6][kFWaves];
-    __shared__ unsigned s_scan[kFWaves];
+    __shared__ float s_red[6 * kFWaves];       // the box reduction's, then the scan's
     const int cand = blockIdx.x, tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
     const int ntp = (nt + 3) & ~3;
     float4 *P = (float4 *)icp_lds;                                   // [ntp] targets in cell order: x, y, z, index
@@ -439,96 +417,65 @@ __global__ __launch_bounds__(kFT) void icp_fused_kernel(int ns, const float *__r
     ICP_STAMP(0);
     // ---- the grid of the target cloud
     {
-        float b[6] = {__builtin_inff(), __builtin_inff(), __builtin_inff(), -__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
+        float mn[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, mx[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
         for (int t = tid; t < nt; t += kFT)
             for (int a = 0; a < 3; a++) {
                 const float v = target[(size_t)t * 3 + a];
-                b[a] = fminf(b[a], v);
-                b[3 + a] = fmaxf(b[3 + a], v);
+                mn[a] = fminf(mn[a], v);
+                mx[a] = fmaxf(mx[a], v);
             }
-#pragma unroll
-        for (int a = 0; a < 6; a++) {
-            float v = b[a];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const float o = __shfl_xor(v, off, kWave);
-                v = a < 3 ? fminf(v, o) : fmaxf(v, o);
-            }
-            if (lane == 0) s_bb[a][wave] = v;
-        }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        float mag = 0.0f, ext[3];
-        for (int a = 0; a < 3; a++) {
-            float lo = __builtin_inff(), hi = -__builtin_inff();
-            for (int w = 0; w < kFWaves; w++) {
-                lo = fminf(lo, s_bb[a][w]);
-                hi = fmaxf(hi, s_bb[3 + a][w]);
-            }
-            G.lo[a] = lo;
-            G.hi[a] = hi;
-            ext[a] = hi - lo;
-            mag = fmaxf(mag, fmaxf(fabsf(lo), fabsf(hi)));
-        }
-        const bool finite = mag < 1e30f;
-        G.eps = finite ? 4e-7f * mag + 1e-30f : 0.0f;
-        float h = (float)(max_dist * 1.001) + 4.0f * G.eps;
-        if (!(h > 1e-30f) || !(h < 1e30f) || !finite) h = __builtin_inff();
-        for (;;) {
-            long long cells = 1;
+        grid_block_box<kFT>(mn, mx, s_red);
+        if (tid == 0) {
+            // The sizing is this kernel's own.  The 27 cells: for |p - q| <= max_dist (1 + 4u) on an axis -- what an fp32 distance of
+            // at most md2 allows -- the exact cell coordinates differ by at most (1 + 5u) / 1.001 < 0.99901; a computed one,
+            // fl(fl(p - lo) * inv), errs by at most 3u |t| (1 + 2u), and |t| <= 66 wherever it matters (the cell function is
+            // monotone and clamped: beyond the grid's ends every floor is the same cell or its sentinel): 2 * 198u < 2.4e-5.  The
+            // computed coordinates differ by less than 1, their floors by at most one.
+            float mag = 0.0f, ext[3];
             for (int a = 0; a < 3; a++) {
-                const float q = h < __builtin_inff() ? ext[a] / h : 0.0f;
-                G.c[a] = q >= (float)(kFAxis - 1) ? kFAxis : (int)q + 1;
-                cells *= G.c[a];
+                ext[a] = mx[a] - mn[a];
+                mag = fmaxf(mag, fmaxf(fabsf(mn[a]), fabsf(mx[a])));
             }
-            if (cells <= cells_cap) break;
-            h *= 1.25f;
+            float h = (float)(max_dist * 1.001);
+            const bool one = !(h > 1e-30f) || !(h < 1e30f) || !(mag < 1e30f);      // one cell: every target is a neighbour of every query
+            int g[3] = {1, 1, 1};
+            while (!one) {
+                long long cells = 1;
+                for (int a = 0; a < 3; a++) {
+                    const float q = ext[a] / h;
+                    g[a] = q >= (float)(kFAxis - 1) ? kFAxis : (int)q + 1;
+                    cells *= g[a];
+                }
+                if (cells <= cells_cap) break;
+                h *= 1.25f;
+            }
+            grid_frame(mn, g, one ? 1.0f : h, F);
+            for (int a = 0; a < 3; a++) s_mx[a] = mx[a];
+            for (int q = 0; q < 16; q++) s_T[q] = init[(size_t)cand * 16 + q];
         }
-        G.h = h < __builtin_inff() ? h : 0.0f;             // (one cell: its box is the cloud's, h plays no part)
-        G.inv_h = h < __builtin_inff() ? 1.0f / h : 0.0f;
-        for (int q = 0; q < 16; q++) s_T[q] = init[(size_t)cand * 16 + q];
     }
     __syncthreads();
-    const int cells = G.c[0] * G.c[1] * G.c[2];
+    const int c0 = F.g[0], c1 = F.g[1], c2 = F.g[2];
+    const float inv = F.inv, h = F.h;
+    auto cell_of = [&](float x, float y, float z) {
+        return (grid_cell1(z, F.lo[2], inv, c2) * c1 + grid_cell1(y, F.lo[1], inv, c1)) * c0 + grid_cell1(x, F.lo[0], inv, c0);
+    };
+    const int cells = c0 * c1 * c2;
     for (int q = tid; q < cells; q += kFT) cend[q] = 0;
     __syncthreads();
     for (int t = tid; t < nt; t += kFT)
-        atomicAdd(&cend[icp_cell_of(G, target[(size_t)t * 3 + 0], target[(size_t)t * 3 + 1], target[(size_t)t * 3 + 2])], 1u);
+        atomicAdd(&cend[cell_of(target[(size_t)t * 3 + 0], target[(size_t)t * 3 + 1], target[(size_t)t * 3 + 2])], 1u);
     __syncthreads();
-    {
-        // exclusive scan of the cell counts: a run of `per` cells per thread
-        const int per = (cells + kFT - 1) / kFT;
-        const int c0 = tid * per, c1 = c0 + per < cells ? c0 + per : cells;
-        unsigned sum = 0;
-        for (int q = c0; q < c1; q++) sum += cend[q];
-        unsigned incl = sum;
-#pragma unroll
-        for (int off = 1; off < kWave; off <<= 1) {
-            const unsigned o = __shfl_up(incl, off, kWave);
-            if (lane >= off) incl += o;
-        }
-        if (lane == kWave - 1) s_scan[wave] = incl;
-        __syncthreads();
-        unsigned base = incl - sum;
-        for (int w = 0; w < wave; w++) base += s_scan[w];
-        for (int q = c0; q < c1; q++) {
-            const unsigned n = cend[q];
-            cend[q] = base;
-            base += n;
-        }
-    }
-    __syncthreads();
+    grid_scan_counts<kFT>((int *)cend, cells, 0, (int *)s_red);
     for (int t = tid; t < nt; t += kFT) {
         const float x = target[(size_t)t * 3 + 0], y = target[(size_t)t * 3 + 1], z = target[(size_t)t * 3 + 2];
-        const unsigned pos = atomicAdd(&cend[icp_cell_of(G, x, y, z)], 1u);        // afterwards cend[c] is the END of cell c's run
+        const unsigned pos = atomicAdd(&cend[cell_of(x, y, z)], 1u);        // afterwards cend[c] is the END of cell c's run
         P[pos] = make_float4(x, y, z, __int_as_float(t));
     }
     __syncthreads();
 
     ICP_STAMP(1);
     const unsigned long long kNone = ((unsigned long long)0x7f800000u << 32) | 0xffffffffu;      // (+inf, nothing)
-    const int c0 = G.c[0], c1 = G.c[1], c2 = G.c[2];
     for (int pass = 0; pass <= max_iter; pass++) {
         double m[12];
 #pragma unroll
@@ -553,10 +500,10 @@ __global__ __launch_bounds__(kFT) void icp_fused_kernel(int ns, const float *__r
                 sx = sp[0]; sy = sp[1]; sz = sp[2];
             }
             if (valid) {
-                // cell coordinates, -1 and c for "before" / "beyond" the grid (NaN: -1)
-                cx = (int)fminf(fmaxf(floorf((px - G.lo[0]) * G.inv_h), -1.0f), (float)c0);
-                cy = (int)fminf(fmaxf(floorf((py - G.lo[1]) * G.inv_h), -1.0f), (float)c1);
-                cz = (int)fminf(fmaxf(floorf((pz - G.lo[2]) * G.inv_h), -1.0f), (float)c2);
+                // cell coordinates by grid_cell1's two operations, but -1 and c for "before" / "beyond" the grid (NaN: -1)
+                cx = (int)fminf(fmaxf(floorf(__fmul_rn(__fsub_rn(px, F.lo[0]), inv)), -1.0f), (float)c0);
+                cy = (int)fminf(fmaxf(floorf(__fmul_rn(__fsub_rn(py, F.lo[1]), inv)), -1.0f), (float)c1);
+                cz = (int)fminf(fmaxf(floorf(__fmul_rn(__fsub_rn(pz, F.lo[2]), inv)), -1.0f), (float)c2);
                 if (cx >= 0 && cx < c0 && cy >= 0 && cy < c1 && cz >= 0 && cz < c2) {
                     const int cell = (cz * c1 + cy) * c0 + cx;
                     key = icp_scan_cell<FMA>(P, cell ? cend[cell - 1] : 0u, cend[cell], px, py, pz, key);
@@ -568,12 +515,15 @@ __global__ __launch_bounds__(kFT) void icp_fused_kernel(int ns, const float *__r
             unsigned mask = 0;
             if (valid) {
                 const float lim = fminf(__uint_as_float((unsigned)(key >> 32)), md2);
+                // (queries lie outside the box: the border cells end at the cloud's own minimum, F.lo, and maximum)
+                const float slx = grid_slack(F.slack[0], px), sly = grid_slack(F.slack[1], py), slz = grid_slack(F.slack[2], pz);
                 float gx[3], gy[3], gz[3];
 #pragma unroll
                 for (int o = 0; o < 3; o++) {
-                    gx[o] = cx + o - 1 >= 0 && cx + o - 1 < c0 ? icp_axis_gap(G, 0, cx + o - 1, px) : __builtin_inff();
-                    gy[o] = cy + o - 1 >= 0 && cy + o - 1 < c1 ? icp_axis_gap(G, 1, cy + o - 1, py) : __builtin_inff();
-                    gz[o] = cz + o - 1 >= 0 && cz + o - 1 < c2 ? icp_axis_gap(G, 2, cz + o - 1, pz) : __builtin_inff();
+                    const int ix = cx + o - 1, iy = cy + o - 1, iz = cz + o - 1;
+                    gx[o] = ix >= 0 && ix < c0 ? grid_gap(ix, 1, c0, F.lo[0], h, px, slx, F.lo[0], s_mx[0]) : __builtin_inff();
+                    gy[o] = iy >= 0 && iy < c1 ? grid_gap(iy, 1, c1, F.lo[1], h, py, sly, F.lo[1], s_mx[1]) : __builtin_inff();
+                    gz[o] = iz >= 0 && iz < c2 ? grid_gap(iz, 1, c2, F.lo[2], h, pz, slz, F.lo[2], s_mx[2]) : __builtin_inff();
                 }
 #pragma unroll
                 for (int pl = 0; pl < 3; pl++) {
@@ -591,8 +541,8 @@ __global__ __launch_bounds__(kFT) void icp_fused_kernel(int ns, const float *__r
 #pragma unroll
                     for (int k = 0; k < 9; k++) {
                         if (pl == 1 && k == 4) continue;
-                        const float g = gz[pl] + gy[k / 3] + gx[k % 3];            // (+inf: outside the grid)
-                        if (g * 0.99999f <= lim && rb[k] != re[k]) mask |= 1u << (pl * 9 + k);
+                        const float g = __fmaf_rn(gx[k % 3], gx[k % 3], __fmaf_rn(gy[k / 3], gy[k / 3], __fmul_rn(gz[pl], gz[pl])));   // (+inf: outside the grid)
+                        if (!(g * kGridShrink > lim) && rb[k] != re[k]) mask |= 1u << (pl * 9 + k);       // (kept at equality: dj <= md2 counts)
                     }
                 }
             }
