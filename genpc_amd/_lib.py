@@ -11,7 +11,7 @@ import torch  # noqa: F401  (loads torch's libamdhip64.so.7 first; ours binds to
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GENPC_LIB: an alternative build of the same library (kernel experiments only)
 LIB_PATH = os.environ.get("GENPC_LIB") or os.path.join(_HERE, "lib", "libgenpc_hip.so")
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -39,6 +39,7 @@ SIGNATURES = {
     "genpc_nm_distance_ragged": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "genpc_nm_distance_within": (_i, [_i, _i, _vp, _i, _vp, _f, _vp, _vp, _vp]),
     "genpc_chamfer_backward": (_i, [_i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "genpc_chamfer_backward_ragged": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "genpc_emd_forward": (_i, [_i, _i, _i] + [_vp] * 14 + [_f, _i, _vp]),
     "genpc_emd_tune": (_i, [_i, _i]),
     "genpc_emd_stats": (_i, [_vp, _i, _vp]),

@@ -11,7 +11,7 @@ from . import _lib
 
 _L = _lib.lib
 _p = _lib.ptr
-RAGGED_MAX_PAIRS = 384          # include/genpc_hip.h: pairs per genpc_nm_distance_ragged call
+RAGGED_MAX_PAIRS = 384          # include/genpc_hip.h: pairs per genpc_nm_distance_ragged / genpc_chamfer_backward_ragged call
 
 
 def forward(xyz1, xyz2, dist1, dist2, idx1, idx2):
@@ -85,3 +85,26 @@ def nm_distance_ragged(xyz, noff, xyz2, moff, result, result_i):
         raise ValueError("genpc_amd: result and result_i must hold noff[-1] = %d elements" % nl[-1])
     return _lib.on_device_of(xyz, _L.genpc_nm_distance_ragged, len(nl) - 1, ctypes.cast(na, ctypes.c_void_p), _p(xyz),
                              ctypes.cast(ma, ctypes.c_void_p), _p(xyz2), _p(result), _p(result_i))
+
+
+def backward_ragged(xyz1, noff, xyz2, moff, gradxyz1, gradxyz2, graddist1, graddist2, idx1, idx2):
+    """Both Chamfer gradients over a ragged batch (genpc_chamfer_backward_ragged): clouds and offsets as for
+    nm_distance_ragged, graddist1 / idx1 [N] and graddist2 / idx2 [M] packed like their clouds with the indices counted inside
+    the pair's own other cloud, as the ragged forward returns them.  gradxyz1 [N,3] and gradxyz2 [M,3] are OVERWRITTEN (no
+    need to zero them), every row summed in a fixed order: the same bits on every run."""
+    _lib.check_tensors((("xyz1", xyz1), ("xyz2", xyz2), ("gradxyz1", gradxyz1), ("gradxyz2", gradxyz2),
+                        ("graddist1", graddist1), ("graddist2", graddist2)), (("idx1", idx1), ("idx2", idx2)))
+    na, nl = _host_offsets(noff, "noff")
+    ma, ml = _host_offsets(moff, "moff")
+    if len(nl) != len(ml):
+        raise ValueError("genpc_amd: noff and moff differ in length (%d, %d)" % (len(nl), len(ml)))
+    # the library checks the offsets against each other; only the caller's buffers can be checked against them, here
+    for name, t, rows in (("xyz1", xyz1, nl[-1]), ("xyz2", xyz2, ml[-1]), ("gradxyz1", gradxyz1, nl[-1]), ("gradxyz2", gradxyz2, ml[-1])):
+        if t.dim() != 2 or t.shape[1] != 3 or t.shape[0] != rows:
+            raise ValueError("genpc_amd: %s must be [%d,3] (the last offset), got %s" % (name, rows, tuple(t.shape)))
+    for name, t, rows in (("graddist1", graddist1, nl[-1]), ("idx1", idx1, nl[-1]), ("graddist2", graddist2, ml[-1]), ("idx2", idx2, ml[-1])):
+        if t.numel() != rows:
+            raise ValueError("genpc_amd: %s must hold %d elements (the last offset), got %d" % (name, rows, t.numel()))
+    return _lib.on_device_of(xyz1, _L.genpc_chamfer_backward_ragged, len(nl) - 1, ctypes.cast(na, ctypes.c_void_p), _p(xyz1),
+                             ctypes.cast(ma, ctypes.c_void_p), _p(xyz2), _p(graddist1), _p(idx1), _p(graddist2), _p(idx2),
+                             _p(gradxyz1), _p(gradxyz2))

@@ -9,6 +9,7 @@ instead (genpc_amd.sharding), so no DataParallel.
 import torch
 
 from ..loss_functions import chamfer_3DDist, emdModule
+from ..loss_functions.Chamfer3D.dist_chamfer_ragged import chamfer_raggedDist
 
 
 class Completionloss:
@@ -55,3 +56,22 @@ class Completionloss:
 
     def get_loss(self, gen, gt):
         return self.metric(gen, gt)
+
+
+def chamfer_ragged_loss(clouds1, clouds2, kind="l1"):
+    """Completionloss.chamfer_l1 / chamfer_l2 (utils/loss_util.py:25-33) for c pairs of clouds of any sizes at once: clouds1,
+    clouds2 as chamfer_raggedDist takes them (lists of [N_j,3] float32 GPU tensors, or (points, offsets)).  Returns a [c]
+    float32 tensor, pair j's loss -- sqrt in fp32 as there, each pair's means accumulated in float64 over its own segment
+    (metric.evaluate_clouds), then cast.  Differentiable in the points; not part of the reference's facade."""
+    if kind not in ("l1", "l2"):
+        raise ValueError("chamfer_ragged_loss: kind is 'l1' or 'l2', got %r" % (kind,))
+    d1, d2, _, _, off1, off2 = chamfer_raggedDist()(clouds1, clouds2)
+    c = off1.numel() - 1
+
+    def seg_mean(d, off):
+        counts = (off[1:] - off[:-1]).to(d.device)
+        seg = torch.repeat_interleave(torch.arange(c, device=d.device), counts, output_size=d.numel())
+        v = torch.sqrt(d) if kind == "l1" else d
+        return torch.zeros(c, dtype=torch.float64, device=d.device).index_add(0, seg, v.double()) / counts.double()
+    a, b = seg_mean(d1, off1), seg_mean(d2, off2)
+    return ((a + b) / 2 if kind == "l1" else a + b).float()

@@ -33,7 +33,7 @@ extern "C" {
 #define GENPC_ARITH_FMA 1
 
 /* Library / device ------------------------------------------------------- */
-int genpc_abi_version(void);              /* bumps when a signature or a documented behaviour changes (21: genpc_nm_distance_ragged added; 20: genpc_mesh_sample added; 19: genpc_uhd added; 18: genpc_knn_query added;
+int genpc_abi_version(void);              /* bumps when a signature or a documented behaviour changes (22: genpc_chamfer_backward_ragged added; 21: genpc_nm_distance_ragged added; 20: genpc_mesh_sample added; 19: genpc_uhd added; 18: genpc_knn_query added;
                                            * 17: genpc_fps_tune takes 0 or 256 only; 16: genpc_hpr_* asynchronous, counts -1 on an internal error;
                                            * genpc_fps*: out_idx[0] -2 = failed the check) */
 const char *genpc_last_error(void);       /* last HIP error string, "" if none */
@@ -135,6 +135,31 @@ int genpc_chamfer_backward(int b, int n, const float *xyz1, int m,
                            const int *idx1, const float *graddist2,
                            const int *idx2, float *gradxyz1, float *gradxyz2,
                            void *stream);
+
+/* Ragged Chamfer backward: both directions for the c pairs of a ragged batch, every gradient row summed in a stated order --
+ * no floating-point atomic, the same bytes on every run, on every stream and wherever a pair stands in the call.
+ * Clouds and HOST offset tables are packed as for genpc_nm_distance_ragged (xyz1 [noff[c],3], xyz2 [moff[c],3]); graddist1,
+ * idx1 [noff[c]] and graddist2, idx2 [moff[c]] are packed like their clouds, idx1 counted INSIDE the pair's own xyz2 slice and
+ * idx2 inside its xyz1 slice, as the ragged forward returns them.  For pair j with slices A, B, g1, i1, g2, i2 of n and m rows,
+ * per component in fp32, every product and sum rounded on its own (nothing is fused, whatever genpc_set_arith says):
+ *     v(i) = (2 g1[i]) (A[i] - B[i1[i]])   present iff 0 <= i1[i] < m,        w(k) = (2 g2[k]) (B[k] - A[i2[k]])   present iff 0 <= i2[k] < n
+ *     gradxyz1[i] = +0 + v(i), then + (-w(k)) for every k in ASCENDING order with i2[k] == i
+ *     gradxyz2[t] = +0 + (-v(i)) for every i in ASCENDING order with i1[i] == t, then + w(t)
+ * -- the order of the CPU oracle (direction 1 ascending, then direction 2 ascending), one of the schedules the rectangular
+ * backward's atomics can produce.  An index outside its range (the forward's -1 for non-finite input) is skipped in both places
+ * and never dereferenced; the other pairs of the call do not notice.
+ * The call OVERWRITES every row of gradxyz1 [noff[c],3] and gradxyz2 [moff[c],3] (they need not be zeroed, unlike
+ * genpc_chamfer_backward's); a row with no term is +0.0f.
+ * Returns 1 at once for c == 0 or no rows at all (after the offsets have been checked); -1 with genpc_last_error set and nothing
+ * enqueued for what genpc_nm_distance_ragged refuses, the offsets being checked in both roles: c < 0, c > 384, null or descending
+ * offsets, noff[0] != 0 or moff[0] != 0, more than 2^28 points on a side, a pair that is empty on ONE side only (empty on both is
+ * fine), a null device pointer with work to do.
+ * Asynchronous on `stream`: a key kernel, one radix sort of the noff[c] + moff[c] (row, owner) pairs and a gradient kernel --
+ * the number of launches does not depend on c; scratch from the library's workspace, the offsets travel in the kernel arguments,
+ * no copy, no host read-back, no synchronisation (csrc/chamfer_grad_ragged.hip).                                              */
+int genpc_chamfer_backward_ragged(int c, const int *noff, const float *xyz1, const int *moff, const float *xyz2,
+                                  const float *graddist1, const int *idx1, const float *graddist2, const int *idx2,
+                                  float *gradxyz1, float *gradxyz2, void *stream);
 
 /* EMD (auction) ---------------------------------------------------------- *
  * Replaces emd_cuda_forward (loss_functions/emd/emd_cuda.cu:228-282, bound as
