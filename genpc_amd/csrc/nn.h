@@ -244,42 +244,78 @@ constexpr int kMaxLists = 16;          // slices x lists per lane, when sliced (
 
 // Exact (reference arithmetic) minimum and first index over the 16 targets base + 16h ..
 // base + 16h + 15 of a 32-target tile: the rows whose approximate values lane half h of the
-// filter held (tile_row()).  Positions past the end are clamped to the last target.
+// filter held (tile_row()).  A run that crosses the end of the cloud counts target nt - 1 for every position past it
+// (how each path gets there: below).
+// In two parts, so that a caller can put work between the request and the use (nn_finish.hip: the fp64 threshold).
+// rescan_half_issue only loads: ONE path, twelve 16-byte loads of a window of 16 consecutive targets, so that nothing
+// has to be copied where two paths would meet (a copy waits for its load).  A run that crosses the end of the cloud
+// takes the LAST 16 targets instead, hence nt >= kHalfMin; rescan_half_eval then skips the window's first `skip`
+// targets.  It visits the targets last to first with <=, so the first index wins a tie, as the clamped scan does:
+// that one sees target nt - 1 once per clamped position, which changes neither the minimum nor its index.
+constexpr int kHalfMin = 16;
+typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
+struct HalfPiece {
+    f4u v[12];      // x, y, z of the window's target e at floats 3e .. 3e + 2
+};
+
+__device__ __forceinline__ int half_window(int nt, int first) { return first < nt - 16 ? first : nt - 16; }
+
+__device__ __forceinline__ void rescan_half_issue(const float *__restrict__ T, int nt, int base, int h, HalfPiece &p)
+{
+    const f4u *tp = (const f4u *)(T + (size_t)half_window(nt, base + 16 * h) * 3);
+#pragma unroll
+    for (int k = 0; k < 12; k++) p.v[k] = tp[k];
+}
+
+template <int FMA>
+__device__ __forceinline__ void rescan_half_eval(const HalfPiece &p, int nt, int base, int h, float qx, float qy, float qz,
+                                                 float &bd, int &bi)
+{
+    const int first = base + 16 * h, start = half_window(nt, first);
+    // a half that begins past the end (h = 1, fewer than 17 targets left in the tile) is its clamped target nt - 1 alone
+    const int skip = first - start < 15 ? first - start : 15;
+    bd = __builtin_inff();
+    int be = skip;
+#pragma unroll
+    for (int e = 15; e >= 0; e--) {
+        const float dd = sqdist<FMA>(p.v[(e * 3) >> 2][(e * 3) & 3] - qx, p.v[(e * 3 + 1) >> 2][(e * 3 + 1) & 3] - qy,
+                                     p.v[(e * 3 + 2) >> 2][(e * 3 + 2) & 3] - qz);
+        const bool le = dd <= bd && e >= skip;
+        bd = le ? dd : bd;
+        be = le ? e : be;
+    }
+    bi = start + be;
+}
+
+// clouds of fewer than kHalfMin targets: every position clamped
+template <int FMA>
+__device__ __forceinline__ void rescan_half_small(const float *__restrict__ T, int nt, int base, int h, float qx, float qy,
+                                                  float qz, float &bd, int &bi)
+{
+    const int first = base + 16 * h;
+    bd = __builtin_inff();
+    bi = first < nt ? first : nt - 1;
+    for (int c = 15; c >= 0; c--) {
+        int kk = first + c;
+        kk = kk < nt ? kk : nt - 1;
+        const float *tp = T + (size_t)kk * 3;
+        const float dd = sqdist<FMA>(tp[0] - qx, tp[1] - qy, tp[2] - qz);
+        const bool le = dd <= bd;
+        bd = le ? dd : bd;
+        bi = le ? kk : bi;
+    }
+}
+
 template <int FMA>
 __device__ __forceinline__ void rescan_half(const float *__restrict__ T, int nt, int base, int h, float qx, float qy,
                                             float qz, float &bd, int &bi)
 {
-    typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
-    const int first = base + 16 * h;
-    bd = __builtin_inff();
-    bi = first < nt ? first : nt - 1;
-    if (first + 16 <= nt) {
-        const f4u *tp = (const f4u *)(T + (size_t)first * 3);
-        f4u v[12];
-#pragma unroll
-        for (int k = 0; k < 12; k++) v[k] = tp[k];
-#pragma unroll
-        for (int g = 3; g >= 0; g--) {
-            const float f[12] = {v[g * 3].x, v[g * 3].y, v[g * 3].z, v[g * 3].w, v[g * 3 + 1].x, v[g * 3 + 1].y,
-                                 v[g * 3 + 1].z, v[g * 3 + 1].w, v[g * 3 + 2].x, v[g * 3 + 2].y, v[g * 3 + 2].z, v[g * 3 + 2].w};
-#pragma unroll
-            for (int c = 3; c >= 0; c--) {
-                const float dd = sqdist<FMA>(f[c * 3 + 0] - qx, f[c * 3 + 1] - qy, f[c * 3 + 2] - qz);
-                const bool le = dd <= bd;
-                bd = le ? dd : bd;
-                bi = le ? first + 4 * g + c : bi;
-            }
-        }
+    if (nt >= kHalfMin) {
+        HalfPiece p;
+        rescan_half_issue(T, nt, base, h, p);
+        rescan_half_eval<FMA>(p, nt, base, h, qx, qy, qz, bd, bi);
     } else {
-        for (int c = 15; c >= 0; c--) {
-            int kk = first + c;
-            kk = kk < nt ? kk : nt - 1;
-            const float *tp = T + (size_t)kk * 3;
-            const float dd = sqdist<FMA>(tp[0] - qx, tp[1] - qy, tp[2] - qz);
-            const bool le = dd <= bd;
-            bd = le ? dd : bd;
-            bi = le ? kk : bi;
-        }
+        rescan_half_small<FMA>(T, nt, base, h, qx, qy, qz, bd, bi);
     }
 }
 

@@ -112,20 +112,20 @@ __global__ __launch_bounds__(WV * kWave, W) void nn_f16_kernel(NNArgs a)
     int k_end = k_begin + a.slice_len;
     if (k_end > nt) k_end = nt;
 
-    // centred queries of this lane; the block's largest |coordinate| over queries and slice
-    float qc0[Q], qc1[Q];
-    float mx = 0.0f;
+    // Prologue loads: this lane's queries and -- when the slice fits one LDS tile -- the block's whole slice are
+    // requested back to back, before any of the values is used: one memory round trip behind the kernel boundary
+    // (with the loads where each value was first needed, the Q query tiles and the slice made Q + 1 round trips in a
+    // row, and every word of the duplicate mask one more -- DESIGN_NOTEBOOK.md, "prologue loads").
+    // raw coordinates of this lane's queries: lanes < 32 carry x and y, lanes >= 32 z (their y is loaded and dropped:
+    // a load that every lane issues needs no branch, and a branch would hold its own wait)
+    float raw0[Q], raw1[Q];
     const int q0 = (qb * WV + wave) * (32 * Q) + col;
 #pragma unroll
     for (int r = 0; r < Q; r++) {
         int j = q0 + r * 32;
         if (j >= nq) j = nq - 1;
-        // lanes < 32 carry x and y of the query, lanes >= 32 z
-        qc0[r] = Qp[(size_t)j * 3 + (half ? 2 : 0)] - (half ? cz : cx);
-        qc1[r] = half ? 0.0f : Qp[(size_t)j * 3 + 1] - cy;
-        // a query at infinity is answered by the exhaustive pass; it must not set the block's scale
-        const float m0 = fabsf(qc0[r]), m1 = fabsf(qc1[r]);
-        mx = fmaxf(mx, fmaxf(m0 < __builtin_inff() ? m0 : 0.0f, m1 < __builtin_inff() ? m1 : 0.0f));
+        raw0[r] = Qp[(size_t)j * 3 + (half ? 2 : 0)];
+        raw1[r] = Qp[(size_t)j * 3 + 1];
     }
     // (A per-launch pre-pass that hands every block its batch element's scale -- so that a slice longer than an LDS tile is
     // not read twice -- was measured: 13 x 16384^2 280.5 -> 278.9 us, 4 x 16384 x 8192 54.0 -> 58.2: the pre-scan of a
@@ -143,18 +143,37 @@ __global__ __launch_bounds__(WV * kWave, W) void nn_f16_kernel(NNArgs a)
     unsigned predup = 0u;
     auto prefetch = [&](int t0) {
         predup = 0u;
+        int tc[kPer];
 #pragma unroll
         for (int i = 0; i < kPer; i++) {
-            int t = t0 + i * kThreads + threadIdx.x;
-            t = t < nt ? t : nt - 1;
+            const int t = t0 + i * kThreads + threadIdx.x;
+            tc[i] = t < nt ? t : nt - 1;
 #pragma unroll
-            for (int k = 0; k < 3; k++) pre[i][k] = T[(size_t)t * 3 + k];
-            if (dupm) predup |= ((dupm[t >> 5] >> (t & 31)) & 1u) << i;
+            for (int k = 0; k < 3; k++) pre[i][k] = T[(size_t)tc[i] * 3 + k];
+        }
+        if (dupm) {
+            // all mask words first, then their bits: no wait per target
+            unsigned mw[kPer];
+#pragma unroll
+            for (int i = 0; i < kPer; i++) mw[i] = dupm[tc[i] >> 5];
+#pragma unroll
+            for (int i = 0; i < kPer; i++) predup |= ((mw[i] >> (tc[i] & 31)) & 1u) << i;
         }
     };
     const bool resident = k_end - k_begin <= HT;        // block-uniform
+    if (resident && k_begin < k_end) prefetch(k_begin);
+    // centred queries of this lane; the block's largest |coordinate| over queries and slice
+    float qc0[Q], qc1[Q];
+    float mx = 0.0f;
+#pragma unroll
+    for (int r = 0; r < Q; r++) {
+        qc0[r] = raw0[r] - (half ? cz : cx);
+        qc1[r] = half ? 0.0f : raw1[r] - cy;
+        // a query at infinity is answered by the exhaustive pass; it must not set the block's scale
+        const float m0 = fabsf(qc0[r]), m1 = fabsf(qc1[r]);
+        mx = fmaxf(mx, fmaxf(m0 < __builtin_inff() ? m0 : 0.0f, m1 < __builtin_inff() ? m1 : 0.0f));
+    }
     if (resident) {
-        if (k_begin < k_end) prefetch(k_begin);
 #pragma unroll
         for (int i = 0; i < kPer; i++)
             if (k_begin + i * kThreads + (int)threadIdx.x < k_end)

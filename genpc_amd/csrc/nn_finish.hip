@@ -30,7 +30,12 @@ __device__ unsigned long long g_timeline_fin[4096 * 8];
 constexpr int kFQ = 64;                // queries per finish block
 constexpr int kFWork = 2048;           // work-item capacity (64 queries x 32 pieces)
 
-template <int FMA>
+// EARLY: the form for launches whose blocks are all resident at once (at most two per CU: the headline step).  There a block's
+// time is memory latency, and the form spends registers on it: every thread of a query loads the query itself, and the best
+// unit's piece is requested BEFORE the fp64 threshold is computed and evaluated after it, 48 registers held across that
+// arithmetic (114 VGPRs, four waves per SIMD).  Launches of several rounds are bound by what is resident, not by one block's
+// latency; they keep the lean order (piece requested and evaluated, then the threshold; five waves per SIMD).
+template <int FMA, int EARLY>
 __global__ __launch_bounds__(kBlock) void nn_finish_kernel(NNArgs a, int nl, int upieces, float kqt, float ktt, float t2min)
 {
     __shared__ unsigned long long s_best[kFQ];   // (distance bits << 32 | index): atomic min == (distance, first index)
@@ -65,8 +70,23 @@ __global__ __launch_bounds__(kBlock) void nn_finish_kernel(NNArgs a, int nl, int
     const bool live = j < nq;
     j = live ? j : nq - 1;
 
+    // Prologue loads: everything the block needs before its first barrier -- the centre, the query, this thread's
+    // element of the per-slice maxima and the list words -- is requested here, back to back, and nothing is consumed
+    // before the last request is out: one memory round trip (the loads do not depend on each other; issued where
+    // each value was first needed they made four round trips in a row -- DESIGN_NOTEBOOK.md, "prologue loads").
+    // The query goes FIRST: it is the one that is not in L2 any more (the lists and maxima were written a moment ago), and
+    // with the lists ahead of it the block was no faster than before (measured).
     const float *cptr = a.dir[0].t + (size_t)batch * a.dir[0].nt * 3;      // common centre of the filter
     const float ccx = cptr[0], ccy = cptr[1], ccz = cptr[2];
+    // EARLY: every thread of a query holds the query itself (s_q serves the work-list phase, where items change hands);
+    // otherwise wave 0 loads it for the block
+    float4 qv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (EARLY || part == 0) qv = make_float4(Qp[(size_t)j * 3 + 0], Qp[(size_t)j * 3 + 1], Qp[(size_t)j * 3 + 2], 0.0f);
+    // per-slice maxima of |t'|^2 (filter kernel): the first trip of the loop below, peeled (ntmax >= 1; index clamped)
+    const int ntmax = D.ntmax;
+    const float *tmp = D.tmaxp + (size_t)batch * ntmax;
+    const bool tm_mine = (int)threadIdx.x < ntmax;
+    const float tm0 = tmp[tm_mine ? (int)threadIdx.x : 0];
     // this thread's lists: li = part + 4k
     unsigned long long w0[kMaxLists / 4], w1[kMaxLists / 4];      // (a1, c1), (codes of a2 | a3, c2): list_enc in nn.h
     float amin = __builtin_inff();
@@ -89,17 +109,16 @@ __global__ __launch_bounds__(kBlock) void nn_finish_kernel(NNArgs a, int nl, int
     }
     s_a[part][ql] = amin;
     s_c[part][ql] = cmin;
-    // max |t'|^2 over the whole target cloud (per-slice maxima of the filter kernel)
-    float tmax2 = 0.0f;
+    // max |t'|^2 over the whole target cloud
+    float tmax2 = tm_mine ? fmaxf(0.0f, tm0) : 0.0f;
     {
-        const float *tp = D.tmaxp + (size_t)batch * D.ntmax;
-        for (int i = threadIdx.x; i < D.ntmax; i += kBlock) tmax2 = fmaxf(tmax2, tp[i]);
+        for (int i = threadIdx.x + kBlock; i < ntmax; i += kBlock) tmax2 = fmaxf(tmax2, tmp[i]);
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) tmax2 = fmaxf(tmax2, __shfl_xor(tmax2, o));
         if (lane == 0) s_red[wave] = tmax2;
     }
     if (part == 0) {
-        s_q[ql] = make_float4(Qp[(size_t)j * 3 + 0], Qp[(size_t)j * 3 + 1], Qp[(size_t)j * 3 + 2], 0.0f);
+        s_q[ql] = qv;
         s_best[ql] = ~0ull;
         s_qflag[ql] = 0;
     }
@@ -121,23 +140,21 @@ __global__ __launch_bounds__(kBlock) void nn_finish_kernel(NNArgs a, int nl, int
         if (v < abest) { abest = v; bp = q2; }
     }
     const int cb = s_c[bp][ql];
-    const float4 qv = s_q[ql];
+    if (!EARLY) qv = s_q[ql];
     unsigned long long mine = ~0ull;
     int pieces = 0;
+    bool has_piece = false;
+    HalfPiece piece;
     if (cb >= 0 && live && !(a.debug & 1)) {
-        const int h = cb & 1, c0 = cb & ~1;
-        const int left = (nt - c0 + 31) >> 5;
-        const int n2 = left < upieces ? left : upieces;
-        if (part < n2) {
-            float dd;
-            int ii;
-            rescan_half<FMA>(T, nt, c0 + 32 * part, h, qv.x, qv.y, qv.z, dd, ii);
-            mine = ((unsigned long long)__float_as_uint(dd) << 32) | (unsigned)ii;
-            pieces = 1;
-        }
+        const int left = (nt - (cb & ~1) + 31) >> 5;
+        has_piece = part < (left < upieces ? left : upieces);
     }
+    const int pbase = (cb & ~1) + 32 * part, ph = cb & 1;
+    const bool windowed = nt >= kHalfMin;       // block-uniform
+    if (EARLY && has_piece && windowed) rescan_half_issue(T, nt, pbase, ph, piece);
     // the threshold is fp64 arithmetic (three square roots); every thread of the query computes it -- the four waves
-    // run side by side, and no barrier stands between it and the lists
+    // run side by side, and no barrier stands between it and the lists.  It stands between the request for the
+    // piece and the piece's evaluation: the arithmetic runs while the targets are on their way.
     float tau, qq;
     {
         const float x = qv.x - ccx, y = qv.y - ccy, z = qv.z - ccz;
@@ -148,6 +165,17 @@ __global__ __launch_bounds__(kBlock) void nn_finish_kernel(NNArgs a, int nl, int
         // the reference's result depends on its 512-target tiling, only nn_exhaustive reproduces it
         if (!(tmax2 < __builtin_inff()) || !(qq < __builtin_inff())) tau = __builtin_nanf("");
         if (a.debug & 16) tau = __builtin_inff();          // test hook: every listed tile is evaluated
+        // (the compiler sinks the arithmetic to the threshold's first use, behind the piece, unless it is held here)
+        if (EARLY) asm volatile("" : "+v"(tau));
+    }
+    if (has_piece) {
+        float dd;
+        int ii;
+        if (!EARLY && windowed) rescan_half_issue(T, nt, pbase, ph, piece);
+        if (windowed) rescan_half_eval<FMA>(piece, nt, pbase, ph, qv.x, qv.y, qv.z, dd, ii);
+        else rescan_half_small<FMA>(T, nt, pbase, ph, qv.x, qv.y, qv.z, dd, ii);
+        mine = ((unsigned long long)__float_as_uint(dd) << 32) | (unsigned)ii;
+        pieces = 1;
     }
     if (mine != ~0ull) atomicMin(&s_best[ql], mine);
     GENPC_TLF(2);
@@ -250,10 +278,12 @@ int launch_nn_finish(NNArgs &a, int nl, int upieces, float kqt, float ktt, float
         return 0;
     }
     a.hint_stride = (int)ceil_div64(fb, 16);
-    if (a.fma)
-        hipLaunchKernelGGL((nn_finish_kernel<1>), dim3((unsigned)fb), dim3(kBlock), 0, st, a, nl, upieces, kqt, ktt, t2min);
-    else
-        hipLaunchKernelGGL((nn_finish_kernel<0>), dim3((unsigned)fb), dim3(kBlock), 0, st, a, nl, upieces, kqt, ktt, t2min);
+    const bool early = fb <= 2 * (long long)num_cus();      // every block resident at once (see nn_finish_kernel)
+#define NN_FINISH_LAUNCH(FMA, EARLY) \
+    hipLaunchKernelGGL((nn_finish_kernel<FMA, EARLY>), dim3((unsigned)fb), dim3(kBlock), 0, st, a, nl, upieces, kqt, ktt, t2min)
+    if (a.fma) { if (early) NN_FINISH_LAUNCH(1, 1); else NN_FINISH_LAUNCH(1, 0); }
+    else { if (early) NN_FINISH_LAUNCH(0, 1); else NN_FINISH_LAUNCH(0, 0); }
+#undef NN_FINISH_LAUNCH
     return check(hipGetLastError(), "nn_finish_kernel launch") ? 1 : 0;
 }
 
