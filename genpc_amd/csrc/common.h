@@ -43,11 +43,11 @@ enum Ws : int {
     kWsNnTmax = 9,            // nn_f16.hip launch_nn_f16: partial maxima of the split targets
     kWsNnStats = 12,          // chamfer.hip: hook counters, one block per DEVICE (null stream).  SHARED: nn_forward hands it to the kernels, genpc_nn_stats reads it back
     kWsNnGrid = 13,           // nn_grid.hip launch_nn_grid: headers | cell tables | sorted clouds
-    kWsSplatImage = 14,       // pose.hip genpc_splat_image: mask scratch
+    kWsSplatImage = 14,       // mask_render.hip genpc_splat_image: mask scratch
     kWsPoseCdLoss = 15,       // pose.hip genpc_pose_cd_grad: the four losses of the call it wraps
     kWsVoxel = 16,            // voxel.hip genpc_voxel_down_sample: bounds | keys | indices | sort / scan scratch
     kWsHpr = 17,              // hpr.hip hpr_run: status header | flipped points | sort buffers | tiles | lists
-    kWsMaskLoss = 18,         // pose.hip genpc_mask_loss: accumulators | mask scratch
+    kWsMaskLoss = 18,         // mask_loss.hip genpc_mask_loss: accumulators | mask scratch
     kWsHprParked = 20,        // hpr.hip hpr_run: the parked points' polygons (sized by GENPC_HPR_PARK_MB)
     kWsPoseReplicas = 22,     // pose.hip genpc_pose_optimize_batch: the clouds replicated per start (lock-step)
     kWsDedupeTable = 24,      // nn_dedupe.hip launch_nn_dedupe: hash tables (zeroed whole when new)

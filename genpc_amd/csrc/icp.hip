@@ -617,7 +617,7 @@ __global__ __launch_bounds__(kFT) void icp_fused_kernel(int ns, const float *__r
 // LDS of the one-workgroup solve for nt targets with `cells` grid cells
 static size_t icp_fused_lds(int nt, int cells) { return (size_t)((nt + 3) & ~3) * 16 + (size_t)cells * 4 + kFFixed; }
 
-static int gx(int n)          // (not pose.hip's lin_grid: the same block of 256, but at most 64 blocks per row where that one allows 1024)
+static int gx(int n)          // (not pose_plan.h's lin_grid: the same block of 256, but at most 64 blocks per row where that one allows 1024)
 {
     int g = ceil_div(n, kIBlock);
     return g > 64 ? 64 : (g < 1 ? 1 : g);

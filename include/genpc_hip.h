@@ -481,7 +481,7 @@ int genpc_fps_multi(int c, const int *n, const int *k, const float *const *xyz,
 int genpc_fps_defer(int on);
 /* Makes the side streams the library pairs with `stream` (alignment loop, sampling check) and gives each a first command: a
  * stream's hardware queue is decided when it is first used, and the pairing overlaps best when these come before other
- * streams of the process (csrc/pose.hip).  Optional; pipeline.run_in_lanes calls it before making its lanes.  Returns 1. */
+ * streams of the process (csrc/pose.hip pose_side_of).  Optional; pipeline.run_in_lanes calls it before making its lanes.  Returns 1. */
 int genpc_streams_prepare(void *stream);
 int genpc_fps_deferred_check(void *stream);
 /* Test hook (calling host thread; returns the previous setting): 256 = every cloud of genpc_fps* takes the multi-workgroup

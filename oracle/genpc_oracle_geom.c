@@ -21,7 +21,8 @@
  * analytic gradients are pinned against torch autograd (tests/test_oracle_pose.py).
  *
  * All arithmetic is fp32 with the operation order spelled out, so that the HIP
- * kernels (genpc_amd/csrc/project.hip, pose.hip) can be compared bit for bit
+ * kernels (genpc_amd/csrc/project.hip, pose.hip, mask_render.hip, mask_loss.hip) can be
+ * compared bit for bit
  * where no reduction order is involved.
  */
 #define _GNU_SOURCE

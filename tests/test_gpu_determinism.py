@@ -130,3 +130,39 @@ def test_seeded_nearest_neighbours_give_the_brute_force_histories(golden):
                 L.genpc_pose_tune(prev)
         for a, b_ in zip(out[0], out[1]):
             np.testing.assert_array_equal(np.asarray(a), np.asarray(b_), err_msg=name)
+
+
+def test_adaptive_nearest_neighbours_give_the_brute_force_histories(env):
+    """Mode 2 (genpc_pose_tune(2), the default where the clouds are large): the loop times the filter at steps 0 and 2, a
+    SAMPLED seeded launch in front of the filter at step 1, and from then on probes again every so often and runs whichever
+    was faster -- 30 steps reach the second probe (step 26), which may be a full seeded search.  Whatever the timings choose,
+    transforms, the loss history of every start and the winning parameters are IDENTICAL to the brute-force filter's
+    (genpc_pose_tune(0)), with the silhouette term and without it.  Small synthetic clouds: 1024 points on an ellipsoid
+    against 512 of its posed front half (a thread that asks for a mode gets it at any size from 256 points)."""
+    torch = env
+    from genpc_amd import _lib
+    from genpc_amd.optim_registration.diff_obj_pose import object_pose_optimization
+    L = _lib.lib
+    rng = np.random.default_rng(17)
+    u = rng.standard_normal((1024, 3))
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    complete = (u * np.array([0.5, 0.3, 0.2])).astype(np.float32)
+    th = math.radians(11.0)
+    Rt = np.array([[math.cos(th), 0, math.sin(th)], [0, 1, 0], [-math.sin(th), 0, math.cos(th)]])
+    c = complete.mean(0)
+    full = ((complete - c) * 0.9) @ Rt.T + c + np.array([0.02, -0.01, 0.015])
+    front = full[full[:, 2] > np.median(full[:, 2])]
+    assert len(front) == 512
+    partial = front.astype(np.float32)
+    C, P = torch.from_numpy(complete).cuda(), torch.from_numpy(partial).cuda()
+    for kw in (dict(radius=0.02, render_size=224), dict(cd_only=True)):
+        out = []
+        for mode in (2, 0):
+            prev = L.genpc_pose_tune(mode)
+            try:
+                out.append(object_pose_optimization(C, P, lr=0.01, iters=30, return_history=True, **kw))
+            finally:
+                L.genpc_pose_tune(prev)
+        assert np.asarray(out[0][1]).shape == (4, 31) and np.isfinite(np.asarray(out[0][1])).all()
+        for a, b_ in zip(out[0], out[1]):
+            np.testing.assert_array_equal(np.asarray(a), np.asarray(b_), err_msg=str(list(kw)))

@@ -198,7 +198,7 @@ def test_splat_image_vs_oracle(gp, oracle, render_blend):
 
 
 def test_splat_tile_lists_and_their_fallbacks(gp, oracle, render_blend):
-    """The splat reads per-tile index lists the projection kernel fills (pose.hip bin_points_block).  The cases a list
+    """The splat reads per-tile index lists the projection kernel fills (mask.h bin_points_block).  The cases a list
     cannot hold must give the same image through the full scan: a tile hit by more points than a list holds (and one whose
     list is longer than one fill of the splat's LDS list), discs
     over more tiles than a point may be listed in, an image with more tiles than the block histogram, and a mixture

@@ -17,7 +17,7 @@ static int g_failed = 0;
         if (!(cond)) { printf("FAILED line %d: %s\n", __LINE__, #cond); g_failed++; } \
     } while (0)
 
-// stand-ins of the device structs, by size (csrc/icp.hip IcpState, csrc/pose.hip PoseState, csrc/grid.h CellGridHdr, float4)
+// stand-ins of the device structs, by size (csrc/icp.hip IcpState, csrc/pose.h PoseState, csrc/grid.h CellGridHdr, float4)
 struct IcpState { char x[24]; };
 struct PoseState { char x[236]; };
 struct CellGridHdr { char x[52]; };

@@ -1,6 +1,6 @@
 """Where a block of mask_splat_kernel spends its time in the alignment loop at config 2's post-voxel size (wall-clock stamps).
 
-    python tools/splat_timeline.py --build     # here: compiles csrc/pose.hip with -DGENPC_SPLAT_TIMELINE into tools/_timeline/
+    python tools/splat_timeline.py --build     # here: compiles csrc/mask_render.hip (the splat kernel's file) with -DGENPC_SPLAT_TIMELINE into tools/_timeline/
     GENPC_LIB=$PWD/tools/_timeline/libgenpc_hip.so python tools/splat_timeline.py        # on the GPU box
 """
 import ctypes, os, subprocess, sys
@@ -12,9 +12,9 @@ if "--build" in sys.argv:
     B.build(verbose=False)
     os.makedirs(OUT, exist_ok=True)
     cflags = [f for f in B.FLAGS if f != "-shared"]
-    obj = os.path.join(OUT, "pose.o")
-    subprocess.check_call([B.HIPCC] + cflags + ["-DGENPC_SPLAT_TIMELINE", "-c", os.path.join(B.CSRC, "pose.hip"), "-o", obj])
-    objs = [os.path.join(B.LIBDIR, "obj", os.path.basename(s)[:-4] + ".o") for s in B.sources() if not s.endswith("pose.hip")]
+    obj = os.path.join(OUT, "mask_render.o")
+    subprocess.check_call([B.HIPCC] + cflags + ["-DGENPC_SPLAT_TIMELINE", "-c", os.path.join(B.CSRC, "mask_render.hip"), "-o", obj])
+    objs = [os.path.join(B.LIBDIR, "obj", os.path.basename(s)[:-4] + ".o") for s in B.sources() if not s.endswith("mask_render.hip")]
     subprocess.check_call([B.HIPCC, "--offload-arch=" + B.ARCH, "-shared", "-fPIC", "-fno-gpu-rdc"] + objs + [obj] + ["-o", os.path.join(OUT, "libgenpc_hip.so")])
     print(os.path.join(OUT, "libgenpc_hip.so"))
     sys.exit(0)
