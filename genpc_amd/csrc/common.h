@@ -65,6 +65,7 @@ enum Ws : int {
     kWsUhd = 37,              // uhd.hip uhd: per-tile partial maxima | per-block records
     kWsNnRagged = 38,         // nn_ragged.hip nn_ragged: the pairs' grid headers | cell tables | sorted targets
     kWsChamferRaggedGrad = 39, // chamfer_grad_ragged.hip chamfer_backward_ragged: keys | owners | sorted keys | sorted owners | sort scratch
+    kWsPoseLossGradBatch = 40, // pose.hip genpc_pose_loss_grad_batch: accumulators | states | posed clouds | neighbours | mask scratch
 };
 
 // The scratch pool: one grow-only block of device memory per (device, slot, stream); null on failure, the error recorded.

@@ -724,6 +724,86 @@ GENPC_API int genpc_pose_optimize_cd(int nc, const float *complete, int np, cons
                                         best_params, stream);
 }
 
+// One step of the loop for b elements, each with its own parameters, and no Adam step: the batched counterpart of
+// genpc_pose_loss_grad, as genpc_pose_optimize_batch is of the single-scan loop.  The launches are the loop's at b elements on
+// one stream (ask: scans = b, one start, no side stream, the switches at their defaults), every width from the two plans -- so
+// the forms the plans select for wide calls (one lane per point, whole images per XCD, capped pose_grad grids, gb > 1) can be
+// compared with an independent reference element by element (tests/test_gpu_pose_step_batch.py).
+GENPC_API int genpc_pose_loss_grad_batch(int b, int nc, const float *v, const float *vert_col, const float *center, const float *params,
+                                         int np, const float *partial, const float *partial_col, float cd_weight, float reg_weight,
+                                         float mask_weight, float radius, int render_size, float *loss_out, float *grad, void *stream)
+{
+    using namespace genpc;
+    if (b <= 0 || nc <= 0 || np <= 0) return -1;
+    const bool mask = mask_weight != 0.0f;
+    if (mask && (render_size <= 1 || !(radius > 0.0f))) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    PoseLoopAsk ask;
+    ask.scans = b; ask.starts = 1; ask.nc = nc; ask.np = np; ask.mask = mask;
+    ask.side_stream_ok = false;
+    ask.counters_ok = false;
+    const PoseLoopPlan plan = pose_loop_plan(ask);
+
+    const size_t P = mask ? (size_t)render_size * render_size : 0;
+    double *accum; PoseState *S; float *pts, *d1, *d2; int *i1, *i2;
+    MaskScratch m = {};
+    WsLayout L;
+    L.add(accum, (size_t)b * kAcc);
+    L.add(S, (size_t)b);
+    L.add(pts, (size_t)b * nc * 3);
+    L.add(d1, (size_t)b * nc);
+    L.add(d2, (size_t)b * np);
+    L.add(i1, (size_t)b * nc);
+    L.add(i2, (size_t)b * np);
+    if (mask) m.layout(L, b, P, (size_t)(nc > np ? nc : np));
+    if (!ws_alloc(L, kWsPoseLossGradBatch, st)) return 0;
+    if (mask && !m.zero_bins(st)) return 0;
+    constexpr int kStateFloats = (int)(sizeof(PoseState) / sizeof(float));
+    if (!check(hipMemsetAsync(accum, 0, (size_t)b * kAcc * sizeof(double), st), "hipMemsetAsync(accum)")) return 0;
+    if (!check(hipMemcpy2DAsync(S->params, sizeof(PoseState), params, 10 * sizeof(float), 10 * sizeof(float), (size_t)b, hipMemcpyDeviceToDevice, st),
+               "copy params"))
+        return 0;
+    // reference image of the partial clouds: first, as in the loop (it projects through the scratch the transform then fills)
+    if (mask && !mask_prepare_ref(b, np, partial, partial_col, radius, render_size, m, st)) return 0;
+    // 1. transform (with the projection, for the full objective)
+    if (mask) {
+        PoseFuse fu{};
+        hipLaunchKernelGGL(pose_transform_project_kernel, dim3(plan.g_t, b), dim3(kQBlock), 0, st, nc, v, center, 3, (const float *)S->params,
+                           kStateFloats, pts, 1.1f * radius, render_size, m.uvr, use_bins(render_size) ? m.bins : (int *)nullptr,
+                           render_blend() ? m.zex : (float *)nullptr, fu);
+    } else
+        hipLaunchKernelGGL(pose_transform_kernel, dim3(plan.g_t, b), dim3(kQBlock), 0, st, nc, v, center, 3, (const float *)S->params,
+                           kStateFloats, pts);
+    // 2. nearest neighbours, both directions.  (The loop makes the duplicate masks of both clouds once per call and hands them to every
+    // step's search; one step is one search, so nn_forward is left to make its own where its policy wants them: the same bits.)
+    if (nn_forward(b, 2, pts, nc, partial, np, d1, i1, partial, np, pts, nc, d2, i2, st) != 1) return 0;
+    // 3. the Chamfer gradient: a launch of its own, or its blocks at the end of the silhouette gradient's launch
+    PoseGradArgs pga{};
+    if (plan.ride) {
+        pga.nc = nc; pga.cstride = 3; pga.pstride = kStateFloats; pga.np = np;
+        pga.v = v; pga.center = center; pga.params = S->params; pga.partial = partial;
+        pga.d1 = d1; pga.d2 = d2; pga.i1 = i1; pga.i2 = i2;
+        pga.cd_weight = cd_weight; pga.accum = accum; pga.gx = plan.g_g;
+    } else
+        hipLaunchKernelGGL(pose_grad_kernel, dim3(plan.g_g, b), dim3(kQBlock), 0, st, nc, v, center, 3, (const float *)S->params, kStateFloats,
+                           np, partial, (const float *)d1, (const int *)i1, (const float *)d2, (const int *)i2, cd_weight, accum,
+                           (unsigned *)nullptr);
+    // 4. silhouette
+    if (mask && !mask_step(b, nc, v, vert_col, center, 3, S->params, kStateFloats, radius, render_size, mask_weight, m, accum, st, true,
+                           plan.ride ? &pga : nullptr))
+        return 0;
+    // 5. the gradient finished per element, no step taken
+    hipLaunchKernelGGL(pose_update_kernel, dim3(plan.gb), dim3(64), 0, st, b, S, accum, nc, np, cd_weight, reg_weight, 0.0f, 0,
+                       (float *)nullptr, 0);
+    if (!check(hipMemcpy2DAsync(grad, 10 * sizeof(float), S->grad, sizeof(PoseState), 10 * sizeof(float), (size_t)b, hipMemcpyDeviceToDevice, st),
+               "copy grad"))
+        return 0;
+    if (!check(hipMemcpy2DAsync(loss_out, 4 * sizeof(float), S->loss, sizeof(PoseState), 4 * sizeof(float), (size_t)b, hipMemcpyDeviceToDevice, st),
+               "copy loss"))
+        return 0;
+    return check(hipGetLastError(), "pose_loss_grad_batch launch") ? 1 : 0;
+}
+
 namespace genpc {
 
 // accum[e*kAcc + 0..2] += sum of v[e, :, 0..2]

@@ -151,6 +151,34 @@ def pose_loss_grad(vert_pos, center, params, partial, radius, render_size=224, c
     return loss, grad
 
 
+def pose_loss_grad_batch(vert_pos, center, params, partial, radius, render_size=224, cd_weight=3.0, reg_weight=0.001,
+                         mask_weight=1.0, vert_col=None, partial_col=None):
+    """pose_loss_grad for B elements in one call, each with its own clouds, centre and parameters: vert_pos [B,nc,3],
+    center [B,3], params [B,10], partial [B,np,3] -> (loss[B,4], grad[B,10]).  The launches are those of one step of
+    object_pose_optimization's loop at B elements (nearest neighbours included), so the kernel forms the loop selects
+    for wide calls are evaluated; no Adam step is taken.  mask_weight = 0: the Chamfer-only objective."""
+    vert_pos = vert_pos.contiguous().float()
+    partial = partial.contiguous().float()
+    center = center.contiguous().float()
+    params = params.contiguous().float()
+    _lib.check_tensors((("vert_pos", vert_pos), ("center", center), ("params", params), ("partial", partial)))
+    if vert_pos.dim() != 3 or vert_pos.shape[2] != 3 or partial.dim() != 3 or partial.shape[2] != 3:
+        raise ValueError("pose_loss_grad_batch: clouds must be [B,N,3], got %s and %s" % (tuple(vert_pos.shape), tuple(partial.shape)))
+    b, nc, np_ = vert_pos.shape[0], vert_pos.shape[1], partial.shape[1]
+    if partial.shape[0] != b or tuple(center.shape) != (b, 3) or tuple(params.shape) != (b, 10):
+        raise ValueError("pose_loss_grad_batch: batch sizes differ: vert_pos %s, center %s, params %s, partial %s"
+                         % (tuple(vert_pos.shape), tuple(center.shape), tuple(params.shape), tuple(partial.shape)))
+    vc, pc = _col(vert_col, vert_pos, "vert_col"), _col(partial_col, partial, "partial_col")
+    loss = torch.empty(b, 4, device=vert_pos.device)
+    grad = torch.empty(b, 10, device=vert_pos.device)
+    rc = _lib.on_device_of(vert_pos, _L.genpc_pose_loss_grad_batch, b, nc, _p(vert_pos), _p(vc), _p(center), _p(params), np_,
+                           _p(partial), _p(pc), float(cd_weight), float(reg_weight), float(mask_weight), float(radius),
+                           int(render_size), _p(loss), _p(grad))
+    if rc != 1:
+        raise RuntimeError("genpc_pose_loss_grad_batch failed (rc=%d): %s" % (rc, _lib.last_error()))
+    return loss, grad
+
+
 def load_point_cloud(point_path, device, radius=0.05, num_points=5000):
     """diff_obj_pose.py:136-164: a .ply through load_xyz, a .glb through glb2point, both voxel
     down-sampled at `radius` WITH their colours -> (vert_pos [N,3], vert_col [N,3] in [0,1]) on

@@ -33,7 +33,7 @@ extern "C" {
 #define GENPC_ARITH_FMA 1
 
 /* Library / device ------------------------------------------------------- */
-int genpc_abi_version(void);              /* bumps when a signature or a documented behaviour changes (22: genpc_chamfer_backward_ragged added; 21: genpc_nm_distance_ragged added; 20: genpc_mesh_sample added; 19: genpc_uhd added; 18: genpc_knn_query added;
+int genpc_abi_version(void);              /* bumps when a signature or a documented behaviour changes (23: genpc_pose_loss_grad_batch added; 22: genpc_chamfer_backward_ragged added; 21: genpc_nm_distance_ragged added; 20: genpc_mesh_sample added; 19: genpc_uhd added; 18: genpc_knn_query added;
                                            * 17: genpc_fps_tune takes 0 or 256 only; 16: genpc_hpr_* asynchronous, counts -1 on an internal error;
                                            * genpc_fps*: out_idx[0] -2 = failed the check) */
 const char *genpc_last_error(void);       /* last HIP error string, "" if none */
@@ -360,7 +360,28 @@ int genpc_pose_loss_grad(int nc, const float *v, const float *vert_col, const fl
                          float mask_weight, float radius, int render_size, float *loss_out,
                          float *grad, void *stream);
 
-/* The renderer of the mask term (genpc_splat_image, genpc_pose_loss_grad, genpc_pose_optimize_batch), per calling host thread:
+/* The same loss and gradient for b elements in one call, each with its own clouds, centre and parameters, evaluated with
+ * the launches ONE STEP of genpc_pose_optimize_batch makes at b elements on one stream (no Adam step is taken): the fused
+ * transform + projection, the bidirectional nearest-neighbour search (so no d1 / i1 / d2 / i2 are passed; without the loop's
+ * once-per-call duplicate masks -- the search makes its own where it wants them, the results are the same bits), the Chamfer
+ * gradient as a launch of its own or inside the silhouette gradient's, the silhouette step, the per-element finish -- every
+ * launch width from csrc/pose_plan.h (an ask of b scans, one start, no side stream, the GENPC_POSE_* switches at their
+ * defaults).  What the plans select for wide calls -- one lane per point, whole images per XCD, at most 24 blocks per element
+ * in the Chamfer gradient from 16 elements on, more than one block of per-element threads above 64 elements -- is thereby
+ * comparable with an independent reference element by element.
+ *   v [b,nc,3], vert_col [b,nc,3] or NULL, center [b,3], params [b,10], partial [b,np,3], partial_col [b,np,3] or NULL
+ *   -> loss_out [b,4] = loss, cd, |RR^T-I|_F, mask_loss;  grad [b,10].
+ * mask_weight = 0: the Chamfer-only objective (render_size, radius and the colours are ignored).
+ * Returns 1 / 0 / -1 (b, nc or np <= 0; with a mask term: render_size <= 1 or radius not positive).  Asynchronous on `stream`;
+ * scratch from a workspace slot of its own.  genpc_pose_loss_grad remains the single-element evaluation with the caller's
+ * neighbours and the projection inside the splat's launch pair. */
+int genpc_pose_loss_grad_batch(int b, int nc, const float *v, const float *vert_col, const float *center,
+                               const float *params, int np, const float *partial,
+                               const float *partial_col, float cd_weight, float reg_weight,
+                               float mask_weight, float radius, int render_size, float *loss_out,
+                               float *grad, void *stream);
+
+/* The renderer of the mask term (genpc_splat_image, genpc_pose_loss_grad, genpc_pose_loss_grad_batch, genpc_pose_optimize_batch), per calling host thread:
  * 1 = Pulsar's published blending function (Lassner & Zollhoefer, CVPR 2021, eq. 1-2) with the reference's arguments
  *     (diff_obj_pose.py:126-131,428-433: gamma 1e-2, znear 1e-4, zfar 5, bg 0): over the discs covering a pixel
  *       I_ch = sum_i a_i e_i c_i,ch / (B + sum_i a_i e_i),  e_i = exp(z_i / gamma),  z_i = (zfar - Zv_i) / (zfar - znear),  B = exp(1e-10 / gamma)

@@ -27,6 +27,8 @@ def test_header_has_the_path():
     assert p["genpc_emd_forward"] == 20        # b,n,m + 14 buffers + eps, iters + stream
     assert p["genpc_chamfer_forward"] == 10
     assert p["genpc_chamfer_backward"] == 12
+    assert p["genpc_pose_loss_grad_batch"] == 17   # b, nc, v, vert_col, center, params, np, partial, partial_col, 3 weights, radius, size, 2 outputs + stream
+    assert p["genpc_pose_loss_grad"] == 20         # (unchanged beside it: the single-element evaluation with the caller's neighbours)
 
 
 def test_library_exports_every_declared_symbol():
@@ -40,6 +42,7 @@ def test_library_exports_every_declared_symbol():
         assert len(_lib.SIGNATURES[name][1]) == nargs, name
         assert fn is not None
     assert _lib.lib.genpc_abi_version() == _lib.ABI_VERSION
+    assert _lib.ABI_VERSION == 23                  # genpc_pose_loss_grad_batch added
 
 
 def test_arith_mode_switch():
