@@ -20,6 +20,7 @@
 // Numerics follow oracle/genpc_oracle_geom.c (oracle_icp): same fp32 NN, sums in
 // double; sums are reduced in a different order (1e-12 relative).
 #include "nn.h"
+#include "icp_plan.h"
 #include "../../include/genpc_hip.h"
 
 #include <math.h>
@@ -348,11 +349,9 @@ __global__ __launch_bounds__(kIBlock) void cd_score_kernel(int n1, const float *
 // -- no workgroup barrier inside --, then a fixed-order reduction (lane tree, waves in order: the sums do not depend on timing,
 // unlike the atomics above) and the update by one thread.  Distances: sqdist<FMA>, the arithmetic of the exhaustive search.
 // A (query, cell) pair is left out by the Bound of grid.h alone: only when no point of the cell can tie or beat the limit in fp32.
-constexpr int kFT = 1024;
-constexpr int kFWaves = kFT / kWave;
-constexpr int kFItems = 512;                 // (query, neighbour cell) pairs of one wave per round of the list
+// (kFT threads, kFWaves waves, kFItems pairs per wave and round, and what of the LDS is whose: icp_plan.h)
+static_assert(kFWaves * kWave == kFT, "icp_plan.h counts waves of 64 lanes");
 constexpr int kFAxis = 64;                   // cells per axis at most
-constexpr size_t kFFixed = (size_t)kFT * 16 + (size_t)kFT * 8 + (size_t)kFWaves * kFItems * 4 + (size_t)17 * kFWaves * 8 + 16 * 8 + 17 * 8;
 
 // key of a candidate: distance bits << 32 | index << 16 | position in P -- the smallest distance, the lowest index among equals
 template <int FMA>
@@ -614,9 +613,6 @@ __global__ __launch_bounds__(kFT) void icp_fused_kernel(int ns, const float *__r
     if (tid < 16) out_T[(size_t)cand * 16 + tid] = s_T[tid];
 }
 
-// LDS of the one-workgroup solve for nt targets with `cells` grid cells
-static size_t icp_fused_lds(int nt, int cells) { return (size_t)((nt + 3) & ~3) * 16 + (size_t)cells * 4 + kFFixed; }
-
 static int gx(int n)          // (not pose_plan.h's lin_grid: the same block of 256, but at most 64 blocks per row where that one allows 1024)
 {
     int g = ceil_div(n, kIBlock);
@@ -632,11 +628,10 @@ GENPC_API int genpc_icp_batch(int k, int ns, const float *source, int nt, const 
     using namespace genpc;
     if (k <= 0 || ns <= 0 || nt <= 0 || max_iter < 0) return -1;
     hipStream_t st = (hipStream_t)stream;
-    // the one-workgroup solve (one launch) when the target cloud and its grid fit a compute unit's LDS
-    int cells = 8192;
-    while (cells >= 1024 && icp_fused_lds(nt, cells) + 1024 > (size_t)160 * 1024) cells >>= 1;
-    if (cells >= 1024 && nt < 65536) {
-        const size_t lds = icp_fused_lds(nt, cells);
+    // the one-workgroup solve (one launch) when the target cloud and its grid fit a compute unit's LDS (icp_plan.h)
+    const IcpPlan plan = icp_plan(nt);
+    if (plan.one_workgroup) {
+        const size_t lds = (size_t)plan.lds_bytes;
         const int fma = arith_mode() != 0 ? 1 : 0;
         static size_t set_bytes[2] = {0, 0};
         if (lds > set_bytes[fma]) {
@@ -648,10 +643,10 @@ GENPC_API int genpc_icp_batch(int k, int ns, const float *source, int nt, const 
         const float md2f = (float)(max_dist * max_dist);
         if (fma)
             hipLaunchKernelGGL((icp_fused_kernel<1>), dim3(k), dim3(kFT), lds, st, ns, source, nt, target, md2f, max_dist, init, max_iter,
-                               rel_fitness, rel_rmse, cells, out_T, stats);
+                               rel_fitness, rel_rmse, plan.cells, out_T, stats);
         else
             hipLaunchKernelGGL((icp_fused_kernel<0>), dim3(k), dim3(kFT), lds, st, ns, source, nt, target, md2f, max_dist, init, max_iter,
-                               rel_fitness, rel_rmse, cells, out_T, stats);
+                               rel_fitness, rel_rmse, plan.cells, out_T, stats);
         return check(hipGetLastError(), "icp (one workgroup) launch") ? 1 : 0;
     }
     double *accum; IcpState *state; float *pts, *tgt, *d; int *idx;
@@ -693,6 +688,16 @@ GENPC_API int genpc_icp_batch(int k, int ns, const float *source, int nt, const 
                            pass, max_iter, rel_fitness, rel_rmse);
     }
     return check(hipGetLastError(), "icp launch") ? 1 : 0;
+}
+
+GENPC_API int genpc_icp_plan(int nt, int out[3])
+{
+    if (!out) return -1;
+    const genpc::IcpPlan p = genpc::icp_plan(nt);
+    out[0] = p.one_workgroup;
+    out[1] = p.cells;
+    out[2] = p.lds_bytes;
+    return 1;
 }
 
 #ifdef GENPC_ICP_TIMELINE

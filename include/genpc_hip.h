@@ -33,7 +33,7 @@ extern "C" {
 #define GENPC_ARITH_FMA 1
 
 /* Library / device ------------------------------------------------------- */
-int genpc_abi_version(void);              /* bumps when a signature or a documented behaviour changes (23: genpc_pose_loss_grad_batch added; 22: genpc_chamfer_backward_ragged added; 21: genpc_nm_distance_ragged added; 20: genpc_mesh_sample added; 19: genpc_uhd added; 18: genpc_knn_query added;
+int genpc_abi_version(void);              /* bumps when a signature or a documented behaviour changes (24: genpc_icp_plan added; 23: genpc_pose_loss_grad_batch added; 22: genpc_chamfer_backward_ragged added; 21: genpc_nm_distance_ragged added; 20: genpc_mesh_sample added; 19: genpc_uhd added; 18: genpc_knn_query added;
                                            * 17: genpc_fps_tune takes 0 or 256 only; 16: genpc_hpr_* asynchronous, counts -1 on an internal error;
                                            * genpc_fps*: out_idx[0] -2 = failed the check) */
 const char *genpc_last_error(void);       /* last HIP error string, "" if none */
@@ -444,6 +444,12 @@ int genpc_icp_batch(int k, int ns, const float *source, int nt, const float *tar
                     double max_dist, const double *init, int max_iter,
                     double rel_fitness, double rel_rmse, double *out_T,
                     double *stats, void *stream);
+
+/* Which implementation genpc_icp_batch runs for nt targets (csrc/icp_plan.h; no GPU is touched):
+ * out[0] = 1 the one-workgroup solve (one launch, target grid in LDS), 0 the multi-launch loop
+ * (five launches per pass); out[1] = the grid's cell budget (8192, 4096, 2048 or 1024; 0 for the
+ * loop); out[2] = the launch's dynamic LDS in bytes (0 for the loop).  Returns -1 for out == NULL. */
+int genpc_icp_plan(int nt, int out[3]);
 
 /* Scores of iterative_scale_search (reg_xyz.py:60-96) for K anisotropic scale
  * candidates scales[K,3] in one batched NN launch:

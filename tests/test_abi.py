@@ -42,7 +42,7 @@ def test_library_exports_every_declared_symbol():
         assert len(_lib.SIGNATURES[name][1]) == nargs, name
         assert fn is not None
     assert _lib.lib.genpc_abi_version() == _lib.ABI_VERSION
-    assert _lib.ABI_VERSION == 23                  # genpc_pose_loss_grad_batch added
+    assert _lib.ABI_VERSION == 24                  # genpc_icp_plan added
 
 
 def test_arith_mode_switch():
