@@ -11,7 +11,7 @@ import torch  # noqa: F401  (loads torch's libamdhip64.so.7 first; ours binds to
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GENPC_LIB: an alternative build of the same library (kernel experiments only)
 LIB_PATH = os.environ.get("GENPC_LIB") or os.path.join(_HERE, "lib", "libgenpc_hip.so")
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -60,6 +60,7 @@ SIGNATURES = {
     "genpc_mask_loss": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
     "genpc_pose_loss_grad": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i, _vp, _vp, _vp]),
     "genpc_pose_loss_grad_batch": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _f, _f, _f, _i, _vp, _vp, _vp]),
+    "genpc_nn_seeded_step": (_i, [_i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "genpc_pose_tune": (_i, [_i]),
     "genpc_pose_dual": (_i, [_i]),
     "genpc_render_tune": (_i, [_i]),

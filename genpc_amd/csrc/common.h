@@ -66,6 +66,7 @@ enum Ws : int {
     kWsNnRagged = 38,         // nn_ragged.hip nn_ragged: the pairs' grid headers | cell tables | sorted targets
     kWsChamferRaggedGrad = 39, // chamfer_grad_ragged.hip chamfer_backward_ragged: keys | owners | sorted keys | sorted owners | sort scratch
     kWsPoseLossGradBatch = 40, // pose.hip genpc_pose_loss_grad_batch: accumulators | states | posed clouds | neighbours | mask scratch
+    kWsNnSeededStep = 41,     // pose.hip genpc_nn_seeded_step: both clouds' grids of one seeded step (nn_seeded.hip)
 };
 
 // The scratch pool: one grow-only block of device memory per (device, slot, stream); null on failure, the error recorded.

@@ -13,8 +13,18 @@
 //     candidate that survives is valued with the reference's arithmetic on the POSED coordinates of this step.
 // Results are the reference's (distance, first index): the running best is the 64-bit key distance bits << 32 | index, a row
 // of cells is skipped only if its bound is STRICTLY above the best distance (ties with lower indices are still found), the
-// bound itself is grid.h's (every rounding accounted for).  The loop's histories are bit-identical to the brute-force
-// path (tests/test_gpu_pipeline.py, GENPC_POSE_SEEDED=0 for A/B).
+// bound itself is grid.h's (every rounding accounted for).
+// What holds it to that: tests/test_gpu_nn_seeded.py runs ONE step of this kernel (genpc_nn_seeded_step, pose.hip: the loop's own
+// grid build, transform and launch) and compares every query's (distance bits, index) with the CPU oracle's exhaustive search on
+// the same posed cloud, in both arithmetic modes, for FINITE clouds under: missing, out-of-range, stale, farthest, random and
+// highest-of-equals seeds; exact ties (a lattice) and duplicated targets; rotations up to 170 degrees, log s in [-50, 50],
+// translations up to 1e6 cloud sizes (the one case that needs the margins of the moving grid),
+// unnormalised and degenerate 6-D parameters (culling given up); one-cell, planar, linear, single-point and cell-capped grids;
+// clouds far from the origin and 1e-3 .. 1e3 across; batches of different poses; tail lanes; the sampled launch.  The loop's
+// loss histories are bit-identical to the brute-force path's (tests/test_gpu_determinism.py, GENPC_POSE_SEEDED=0 for A/B).
+// NOT the reference's answer: a cloud with a NaN coordinate in the first target of a 512-target tile.  The reference drops
+// that whole tile, or answers (NaN, 0) if it is tile 0 (nn.h, nn_exhaustive: the filter's path for non-finite input); the
+// minimum over keys here drops the NaN target alone.  (Every loss of such a call is NaN on either path.)
 #include "nn.h"
 #include "../../include/genpc_hip.h"
 
@@ -151,7 +161,9 @@ __global__ __launch_bounds__(kBlock) void nn_seeded_kernel(SeededArgs a)
                 const float gyv = grid_gap(cyv[k], 1, gy, H.lo[1], h, gy_, sy), gzv = grid_gap(czv[k], 1, gz, H.lo[2], h, gz_, sz);
                 const float lb = __fmaf_rn(gyv, gyv, __fmul_rn(gzv, gzv)) * kGridShrink;
                 if (lb > rg2) continue;                  // strictly farther than the best: not even a tie
-                const float W = sqrtf(fmaxf(0.0f, __fmul_rn(rg2, 1.000001f) - lb)) * 1.000001f;
+                // (a best distance that overflowed to +inf ties with every target that far: the whole row -- inf - inf is a NaN, and
+                //  fmaxf made a width of 0 of it: tests/test_gpu_nn_seeded.py, log s = +50)
+                const float W = rg2 < inf ? sqrtf(fmaxf(0.0f, __fmul_rn(rg2, 1.000001f) - lb)) * 1.000001f : inf;
                 const int cx0 = max(bx0, grid_cell1((gx_ - W) - sx, H.lo[0], H.inv, gx));
                 const int cx1 = min(bx1, grid_cell1((gx_ + W) + sx, H.lo[0], H.inv, gx));
                 if (cx0 > cx1) continue;

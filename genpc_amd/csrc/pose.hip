@@ -304,7 +304,8 @@ namespace genpc { thread_local int t_pose_seeded = -1; }
 /* Nearest-neighbour path of the alignment loop, for tests and A/B (calling host thread): 1 seeded cell search from the
  * second step on (csrc/nn_seeded.hip: it wins when every query keeps a near target and loses on misaligned starts of
  * real shapes), 0 the brute-force filter at every step, 2 whichever of the two the call measures to be faster (the
- * default), < 0 the default / environment (GENPC_POSE_SEEDED).  All give the same bits.  Returns the previous setting. */
+ * default), < 0 the default / environment (GENPC_POSE_SEEDED).  All give the same bits for finite clouds (a NaN coordinate: the head of
+ * nn_seeded.hip).  Returns the previous setting. */
 GENPC_API int genpc_pose_tune(int seeded)
 {
     const int prev = genpc::t_pose_seeded;
@@ -802,6 +803,34 @@ GENPC_API int genpc_pose_loss_grad_batch(int b, int nc, const float *v, const fl
                "copy loss"))
         return 0;
     return check(hipGetLastError(), "pose_loss_grad_batch launch") ? 1 : 0;
+}
+
+// One step of the loop's seeded nearest-neighbour search on the caller's inputs, so that nn_seeded_kernel can be compared with a
+// reference query by query (tests/test_gpu_nn_seeded.py): the loop's own three functions in the loop's order -- both grids
+// (build_seeded_grids), the transform at the loop's width (pose_loop_plan's g_t), ONE launch_nn_seeded with i1 / i2 as seeds --
+// in the calling thread's arithmetic mode.  Nothing of them is restated here and the kernel has no switch for it.
+GENPC_API int genpc_nn_seeded_step(int b, int nm, const float *rest, const float *center, const float *params, int ns, const float *stat,
+                                   float *posed, float *d1, int *i1, float *d2, int *i2, int sample, void *stream)
+{
+    using namespace genpc;
+    if (b <= 0 || nm <= 0 || ns <= 0 || sample < 1) {
+        set_error("genpc_nn_seeded_step: b, nm and ns must be positive and sample at least 1");
+        return -1;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    PoseLoopAsk ask;
+    ask.scans = b; ask.starts = 1; ask.nc = nm; ask.np = ns; ask.mask = false;
+    ask.side_stream_ok = false;
+    ask.counters_ok = false;
+    const PoseLoopPlan plan = pose_loop_plan(ask);
+    SeededGrids sg{};
+    WsLayout GL;
+    seeded_grids_layout(GL, sg, b, nm, ns);
+    if (!ws_alloc(GL, kWsNnSeededStep, st) || !build_seeded_grids(b, nm, rest, ns, stat, sg, st)) return 0;
+    const int fma_mode = arith_mode() != 0 ? 1 : 0;
+    hipLaunchKernelGGL(pose_transform_kernel, dim3(plan.g_t, b), dim3(kQBlock), 0, st, nm, rest, center, 3, params, 10, posed);
+    if (launch_nn_seeded(b, nm, posed, ns, stat, sg, center, 3, params, 10, d1, i1, d2, i2, fma_mode, st, sample) != 1) return 0;
+    return check(hipGetLastError(), "nn_seeded_step launch") ? 1 : 0;
 }
 
 namespace genpc {

@@ -41,6 +41,32 @@ def pose_transform(vert_pos, center, params):
     return pts
 
 
+def nn_seeded_step(rest, center, params, static, seed1, seed2, sample=1, d1=None, d2=None):
+    """One step of the loop's seeded nearest-neighbour search (genpc_nn_seeded_step) for B elements: rest [B,nm,3],
+    center [B,3], params [B,10], static [B,ns,3]; seed1 [B,nm] / seed2 [B,ns] int32 are last step's answers (a value
+    outside the target count is no seed) and are NOT modified.  -> (posed [B,nm,3], d1, i1 [B,nm], d2, i2 [B,ns]).
+    sample > 1: only every sample-th block of queries is answered; the others keep d1 / d2 as given (empty if None) and
+    their seeds."""
+    _lib.check_tensors((("rest", rest), ("center", center), ("params", params), ("static", static)), (("seed1", seed1), ("seed2", seed2)))
+    if rest.dim() != 3 or rest.shape[2] != 3 or static.dim() != 3 or static.shape[2] != 3:
+        raise ValueError("nn_seeded_step: clouds must be [B,N,3], got %s and %s" % (tuple(rest.shape), tuple(static.shape)))
+    b, nm, ns = rest.shape[0], rest.shape[1], static.shape[1]
+    if static.shape[0] != b or tuple(center.shape) != (b, 3) or tuple(params.shape) != (b, 10) or tuple(seed1.shape) != (b, nm) \
+            or tuple(seed2.shape) != (b, ns):
+        raise ValueError("nn_seeded_step: shapes differ: rest %s, center %s, params %s, static %s, seeds %s and %s"
+                         % (tuple(rest.shape), tuple(center.shape), tuple(params.shape), tuple(static.shape), tuple(seed1.shape), tuple(seed2.shape)))
+    posed = torch.empty_like(rest)
+    i1, i2 = seed1.clone(), seed2.clone()
+    d1 = torch.empty(b, nm, device=rest.device) if d1 is None else d1.clone()
+    d2 = torch.empty(b, ns, device=rest.device) if d2 is None else d2.clone()
+    _lib.check_tensors((("d1", d1), ("d2", d2)))
+    rc = _lib.on_device_of(rest, _L.genpc_nn_seeded_step, b, nm, _p(rest), _p(center), _p(params), ns, _p(static), _p(posed),
+                           _p(d1), _p(i1), _p(d2), _p(i2), int(sample))
+    if rc != 1:
+        raise RuntimeError("genpc_nn_seeded_step failed (rc=%d): %s" % (rc, _lib.last_error()))
+    return posed, d1, i1, d2, i2
+
+
 def pose_cd_loss_grad(vert_pos, center, params, partial, cd_weight=3.0, reg_weight=0.001):
     """-> (loss[3] = total, cd, |RR^T-I|_F ; grad[10]) for the current parameters."""
     from .. import chamfer_3D

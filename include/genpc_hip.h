@@ -33,7 +33,7 @@ extern "C" {
 #define GENPC_ARITH_FMA 1
 
 /* Library / device ------------------------------------------------------- */
-int genpc_abi_version(void);              /* bumps when a signature or a documented behaviour changes (24: genpc_icp_plan added; 23: genpc_pose_loss_grad_batch added; 22: genpc_chamfer_backward_ragged added; 21: genpc_nm_distance_ragged added; 20: genpc_mesh_sample added; 19: genpc_uhd added; 18: genpc_knn_query added;
+int genpc_abi_version(void);              /* bumps when a signature or a documented behaviour changes (25: genpc_nn_seeded_step added; 24: genpc_icp_plan added; 23: genpc_pose_loss_grad_batch added; 22: genpc_chamfer_backward_ragged added; 21: genpc_nm_distance_ragged added; 20: genpc_mesh_sample added; 19: genpc_uhd added; 18: genpc_knn_query added;
                                            * 17: genpc_fps_tune takes 0 or 256 only; 16: genpc_hpr_* asynchronous, counts -1 on an internal error;
                                            * genpc_fps*: out_idx[0] -2 = failed the check) */
 const char *genpc_last_error(void);       /* last HIP error string, "" if none */
@@ -397,8 +397,24 @@ int genpc_render_tune(int blend);
  * filter at every step (on real shapes three of the four starts are misaligned, most of their queries have no near
  * target and the seeded search loses), 2 measure both during the call and take the faster one (the default: a few
  * hipEventSynchronize per call on the call's stream), < 0 the default / environment GENPC_POSE_SEEDED.  Same bits in
- * every mode.  Returns the previous setting. */
+ * every mode for finite clouds (a NaN coordinate: see the head of csrc/nn_seeded.hip).  Returns the previous setting.
+ * Where it is tested: the loop's fp32 loss histories are identical in modes 0, 1 and 2 (tests/test_gpu_determinism.py), and
+ * the seeded search itself is held to the reference's (distance, first index) query by query, bit for bit, through
+ * genpc_nn_seeded_step below (tests/test_gpu_nn_seeded.py; its inputs: tests/nn_seeded_cases.py). */
 int genpc_pose_tune(int seeded);
+/* ONE step of the seeded search on the caller's inputs, with the loop's own functions in the loop's order: both grids built
+ * (the static clouds' in the world frame, the rest clouds' in the rest frame), posed = the transform of rest by (center, params)
+ * at the loop's launch width, then one seeded launch with i1 / i2 as the seeds (any int: a value outside [0, count) is no
+ * seed) -- in the calling thread's arithmetic mode.
+ *   rest [b,nm,3], center [b,3], params [b,10], stat [b,ns,3]  ->  posed [b,nm,3];
+ *   d1, i1 [b,nm]: every posed point's nearest static point;  d2, i2 [b,ns]: every static point's nearest posed point.
+ * sample > 1: the loop's timing probe -- only every sample-th block of 64 queries runs (blocks numbered over direction 1's
+ * b * ceil(nm / 64), then direction 2's b * ceil(ns / 64)); the other queries' outputs are left as they were.
+ * Returns 1 / 0 / -1 (b, nm or ns <= 0, sample < 1: nothing is written).  Asynchronous on `stream`; scratch from a workspace
+ * slot of its own. */
+int genpc_nn_seeded_step(int b, int nm, const float *rest, const float *center, const float *params,
+                         int ns, const float *stat, float *posed, float *d1, int *i1, float *d2,
+                         int *i2, int sample, void *stream);
 /* The calling host thread's alignment loops (full objective, small clouds): 1 = the Chamfer half of an Adam step -- nearest
  * neighbours + gradient -- on a side stream of the highest priority class beside the silhouette half, 0 = one stream,
  * < 0 = default (GENPC_POSE_DUAL, on).
