@@ -16,29 +16,10 @@
 //     takes the lowest j whose s equals d2.  That is numpy's argmax over argmin, judged on s.
 // A pair whose s is NaN is skipped by fmin; see include/genpc_hip.h for what non-finite input returns.
 // Everything is enqueued on the caller's stream; nothing is read back.
-#include "common.h"
+#include "uhd.h"
 #include "../../include/genpc_hip.h"
 
 namespace genpc {
-
-constexpr int kUhdBlock = 256;
-constexpr int kUhdQ = 4;                          // queries per lane
-constexpr int kUhdTile = 512;                     // targets per workgroup: 12 KiB of LDS as doubles
-constexpr int kUhdNoIndex = 0x7fffffff;
-
-struct UhdRec {                                   // a candidate witness: query i, its minimum v, the lowest tile that attains it
-    double v;
-    int i, tile;
-};
-
-// a beats b: the greater minimum, among equals the lower query index (minima are never NaN: fmin drops them)
-__device__ __forceinline__ bool uhd_beats(double av, int ai, double bv, int bi) { return av > bv || (av == bv && ai < bi); }
-
-__device__ __forceinline__ double uhd_s(double qx, double qy, double qz, double tx, double ty, double tz)
-{
-    const double dx = qx - tx, dy = qy - ty, dz = qz - tz;
-    return ((dx * dx) + (dy * dy)) + (dz * dz);
-}
 
 __global__ __launch_bounds__(kUhdBlock) void uhd_pairs_kernel(int n, const float *__restrict__ xyz, int m, const float *__restrict__ xyz2,
                                                               double *__restrict__ partial)
@@ -72,21 +53,6 @@ __global__ __launch_bounds__(kUhdBlock) void uhd_pairs_kernel(int n, const float
         const int i = i0 + q * kUhdBlock;
         if (i < n) P[i] = best[q];
     }
-}
-
-// the workgroup's best record, returned to every thread (s_r: kUhdBlock records of scratch)
-__device__ __forceinline__ UhdRec uhd_block_best(UhdRec r, UhdRec *s_r)
-{
-    s_r[threadIdx.x] = r;
-    __syncthreads();
-    for (int w = kUhdBlock / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-            const UhdRec o = s_r[threadIdx.x + w];
-            if (uhd_beats(o.v, o.i, s_r[threadIdx.x].v, s_r[threadIdx.x].i)) s_r[threadIdx.x] = o;
-        }
-        __syncthreads();
-    }
-    return s_r[0];
 }
 
 __global__ __launch_bounds__(kUhdBlock) void uhd_query_kernel(int n, int tiles, const double *__restrict__ partial, UhdRec *__restrict__ recs)

@@ -22,8 +22,16 @@ reconstructed mesh against a ground-truth MESH (``metric_sds_redwood``, :49-94),
 ragged nearest-neighbour search (csrc/nn_ragged.hip), all scans in one call per direction.
 
     python -m genpc_amd.metric --clouds PRED_DIR GT_DIR
+
+``uhd_ragged`` is ``uhd`` for S (partial, complete) pairs of different sizes in one library call (csrc/uhd_ragged.hip) --
+the reference applies ``UHD`` to a list of scans one file pair at a time and averages (metric.py:182-195) -- with the same
+float64 bits per pair; ``score_uhd_folders`` reads two folders of PLY files under ``UHD``'s thresholds and scores all pairs
+at once.
+
+    python -m genpc_amd.metric --uhd-dirs PARTIAL_DIR COMPLETE_DIR
 """
 import argparse
+import ctypes
 import os
 
 import numpy as np
@@ -186,6 +194,79 @@ def UHD(partial_path, complete_path):
     return float(uhd(p, c))
 
 
+UHD_RAGGED_MAX_PAIRS = 384          # include/genpc_hip.h: pairs per genpc_uhd_ragged call
+
+
+def _uhd_ragged_side(clouds, name):
+    """One side of a ragged UHD batch as (points [T,3] float32 contiguous, offsets: S + 1 Python ints): a list of [N_j,3]
+    tensors or packed (points, offsets), as pack_clouds reads them, each cloud under _uhd_cloud's dtype rule."""
+    from .loss_functions.Chamfer3D.dist_chamfer_ragged import _is_offsets, pack_clouds
+    if isinstance(clouds, tuple) and len(clouds) == 2 and torch.is_tensor(clouds[0]) and _is_offsets(clouds[1]):
+        points, off = clouds
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError("uhd_ragged: packed %s must be [T,3], got %s" % (name, tuple(points.shape)))
+        return pack_clouds((_uhd_cloud(points, name), off), name)
+    if not isinstance(clouds, (list, tuple)):
+        raise TypeError("uhd_ragged: %s is a list of [N,3] tensors or a tuple (points, offsets)" % name)
+    for j, t in enumerate(clouds):
+        if not torch.is_tensor(t) or t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError("uhd_ragged: %s[%d] must be an [N,3] tensor" % (name, j))
+    return pack_clouds([_uhd_cloud(t, "%s[%d]" % (name, j)) for j, t in enumerate(clouds)], name)
+
+
+def uhd_ragged(partials, completes, return_witness=False):
+    """``uhd`` for S pairs of clouds of any sizes: pair j is partials[j] [N_j,3] against completes[j] [M_j,3].  Each side is
+    a list of float32 GPU tensors (float64 only if float32-representable, as for ``uhd``) or packed as (points [T,3],
+    offsets) -- S + 1 host ints, ``pack_clouds`` of loss_functions/Chamfer3D/dist_chamfer_ragged.py.  Returns float64 [S] on
+    the device, per pair the bits of ``uhd`` on that pair alone; return_witness=True also returns int32 [S,2], (i, j) counted
+    inside the pair's own clouds.  One library call per 384 pairs (genpc_uhd_ragged; a longer list takes several), nothing
+    waits for the result (a float64 input costs one synchronising check per tensor).  An empty cloud is an error."""
+    from . import chamfer_3D
+    p, poff = _uhd_ragged_side(partials, "partials")
+    c, coff = _uhd_ragged_side(completes, "completes")
+    if len(poff) != len(coff):
+        raise ValueError("uhd_ragged: %d partial clouds against %d complete clouds" % (len(poff) - 1, len(coff) - 1))
+    s = len(poff) - 1
+    for j in range(s):
+        n, m = poff[j + 1] - poff[j], coff[j + 1] - coff[j]
+        if n < 1 or m < 1:
+            raise ValueError("uhd_ragged: pair %d has an empty cloud (N = %d, M = %d): the maximum or minimum over an empty "
+                             "cloud is undefined" % (j, n, m))
+    if s == 0:
+        dev = p.device if p.is_cuda else (c.device if c.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+        hd, ij = torch.empty((0,), dtype=torch.float64, device=dev), torch.empty((0, 2), dtype=torch.int32, device=dev)
+        return (hd, ij) if return_witness else hd
+    _lib.require_gpu(p, c)
+    if p.device != c.device:
+        raise ValueError("uhd_ragged: partials and completes are on different devices")
+    d2 = torch.empty((s,), dtype=torch.float64, device=p.device)
+    ij = torch.empty((s, 2), dtype=torch.int32, device=p.device)
+    for a in range(0, s, UHD_RAGGED_MAX_PAIRS):
+        b = min(a + UHD_RAGGED_MAX_PAIRS, s)
+        n0, m0 = poff[a], coff[a]
+        na, _ = chamfer_3D._host_offsets([v - n0 for v in poff[a:b + 1]], "noff")
+        ma, _ = chamfer_3D._host_offsets([v - m0 for v in coff[a:b + 1]], "moff")
+        rc = _lib.on_device_of(p, _lib.lib.genpc_uhd_ragged, b - a, ctypes.cast(na, ctypes.c_void_p), _lib.ptr(p[n0:poff[b]]),
+                               ctypes.cast(ma, ctypes.c_void_p), _lib.ptr(c[m0:coff[b]]), _lib.ptr(d2[a:b]), _lib.ptr(ij[a:b]))
+        if rc != 0:
+            raise RuntimeError("genpc_uhd_ragged failed (%d): %s" % (rc, _lib.last_error()))
+    hd = torch.sqrt(d2)
+    return (hd, ij) if return_witness else hd
+
+
+def score_uhd_folders(partial_dir, complete_dir):
+    """``UHD`` of every PLY of partial_dir against the PLY of the same name in complete_dir, all pairs in one ragged call:
+    (names, float64 [S] on the host, only_partial, only_complete).  Each file is read as ``UHD`` reads it -- a cloud of
+    >= 20000 points is FPS-subsampled to 10000 (partial) / 20000 (complete) -- so entry j is the float ``UHD`` returns for
+    pair j."""
+    pairs, only_partial, only_complete = match_cloud_files(partial_dir, complete_dir)
+    if not pairs:
+        return [], np.zeros((0,)), only_partial, only_complete
+    dev = torch.device("cuda", torch.cuda.current_device())
+    hd = uhd_ragged([_read_cloud(p, 20000, 10000, dev) for _, p, _ in pairs], [_read_cloud(c, 20000, 20000, dev) for _, _, c in pairs])
+    return [n for n, _, _ in pairs], hd.cpu().numpy(), only_partial, only_complete
+
+
 def cd_emd(pcdpath1, pcdpath2):
     """The reference's ``cd_emd`` (metric.py:135-148): both PLY clouds FPS-subsampled to 16384 points, then CD-L1 with
     gen = cloud 2, gt = cloud 1 and EMD (eps 0.005, 50 rounds) with p1 = cloud 2, p2 = cloud 1.  Returns the two 0-d
@@ -284,7 +365,22 @@ def main():
                     help="directed Hausdorff distance partial -> complete of two PLY clouds (the reference's UHD), printed x100")
     ap.add_argument("--clouds", nargs=2, metavar=("PRED_DIR", "GT_DIR"),
                     help="CD-L1 of every PLY of PRED_DIR against the PLY of the same name in GT_DIR, at the files' own sizes, printed x100")
+    ap.add_argument("--uhd-dirs", nargs=2, metavar=("PARTIAL_DIR", "COMPLETE_DIR"),
+                    help="UHD of every PLY of PARTIAL_DIR against the PLY of the same name in COMPLETE_DIR, all pairs in one call, and their mean, printed x100")
     args = ap.parse_args()
+    if args.uhd_dirs:
+        names, hds, only_partial, only_complete = score_uhd_folders(*args.uhd_dirs)
+        total = 0
+        for name, hd in zip(names, hds):
+            hd = float(hd)
+            print(f"{name} : {hd * 100:.2f}")
+            total += hd                                                               # metric.py:193
+        for side, lost in (("COMPLETE_DIR", only_partial), ("PARTIAL_DIR", only_complete)):
+            for name in lost:
+                print(f"{name} : no counterpart in {side}")
+        if names:
+            print(f"UHD: {total / len(names) * 100:.2f}")                             # metric.py:194-195
+        return
     if args.clouds:
         names, table, only_pred, only_gt = score_cloud_folders(*args.clouds)
         for name, (cd, _) in zip(names, table):

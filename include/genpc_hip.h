@@ -35,7 +35,8 @@ extern "C" {
 /* Library / device ------------------------------------------------------- */
 int genpc_abi_version(void);              /* bumps when a signature or a documented behaviour changes (25: genpc_nn_seeded_step added; 24: genpc_icp_plan added; 23: genpc_pose_loss_grad_batch added; 22: genpc_chamfer_backward_ragged added; 21: genpc_nm_distance_ragged added; 20: genpc_mesh_sample added; 19: genpc_uhd added; 18: genpc_knn_query added;
                                            * 17: genpc_fps_tune takes 0 or 256 only; 16: genpc_hpr_* asynchronous, counts -1 on an internal error;
-                                           * genpc_fps*: out_idx[0] -2 = failed the check) */
+                                           * genpc_fps*: out_idx[0] -2 = failed the check).
+                                           * Still 25 with genpc_uhd_ragged: a function added changes no signature and no documented behaviour. */
 const char *genpc_last_error(void);       /* last HIP error string, "" if none */
 int genpc_set_arith(int mode);            /* process default; returns the previous one */
 int genpc_set_arith_thread(int mode);     /* calling thread only, < 0: follow the default; returns the previous override */
@@ -574,6 +575,28 @@ int genpc_knn_query(int b, int nq, const float *xyz, int nt, const float *xyz2, 
  * null, or the problem is too large for one launch (B > 65535, N > 2^30, M > 65535 * 512).                            */
 int genpc_uhd(int b, int n, const float *xyz, int m, const float *xyz2,
               double *out_d2, int *out_ij, void *stream);
+
+/* Ragged UHD: c independent (queries, targets) pairs of any sizes in one call.  Pair j has the queries xyz[noff[j] .. noff[j+1])
+ * and the targets xyz2[moff[j] .. moff[j+1]); noff, moff: HOST arrays of c + 1 ascending ints, noff[0] = moff[0] = 0, copied
+ * before the call returns; xyz [noff[c],3], xyz2 [moff[c],3]: fp32, device, packed in pair order (as for
+ * genpc_nm_distance_ragged).  out_d2[j] (fp64) = max over pair j's queries of the minimum over its targets of
+ * s = ((dx*dx) + (dy*dy)) + (dz*dz), d = query - target, in fp64 on the widened coordinates, in that order, nothing fused:
+ * the bits of genpc_uhd(1, N_j, .., M_j, ..) on that pair alone.  out_ij[j] = (i*, j*), counted inside the pair's own slices:
+ * i* the lowest query that attains the maximum, j* the lowest target of the pair with s == out_d2[j] for query i*, or -1 if
+ * none has (on finite input that is genpc_uhd's witness).
+ * Non-finite coordinates, as for genpc_uhd: a pair of points whose s is NaN is skipped (the minimum is IEEE minNum), a query
+ * all of whose s are NaN has the minimum +inf; so out_d2 is never NaN, it is +inf where a query has no finite pair or an
+ * infinite minimum, i* is always a valid query index, and j* follows the rule above (the lowest target at s == +inf, -1 if
+ * every s of query i* is NaN).  One pair's non-finite input affects that pair only.  Finite input is the contract.
+ * The same bits on every run: the minima are folded with integer atomics on the bit pattern, no floating-point atomic.
+ * Asynchronous on `stream`: four launches whatever c is, the pair table in the kernel arguments, scratch from the library's
+ * workspace (8 bytes a query), no copy, no host read-back, no synchronisation (csrc/uhd_ragged.hip).  Returns 0 on success;
+ * 1 with nothing written if c == 0; -1 with genpc_last_error set, nothing enqueued and nothing written for c < 0, c > 384,
+ * null noff / moff, noff[0] != 0 or moff[0] != 0, descending offsets, noff[c] or moff[c] > 2^28, a pair with no queries or
+ * no targets (one empty on both sides too: the maximum or minimum of an empty set is undefined), a null device pointer, or
+ * a pair too large for one launch: every pair's M_j <= 65535 * 512 = 33553920 targets.                                 */
+int genpc_uhd_ragged(int c, const int *noff, const float *xyz, const int *moff, const float *xyz2,
+                     double *out_d2, int *out_ij, void *stream);
 
 /* Surface samples of a triangle mesh ----------------------------------------- *
  * count area-weighted samples of the mesh vertices[nv,3] (fp32) / faces[nf,3] (int32), uniform inside a face: the published
