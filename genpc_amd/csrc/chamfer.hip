@@ -691,12 +691,8 @@ __global__ __launch_bounds__(kGradBlock) void chamfer_grad_dir_kernel(int b, int
 }
 
 struct NNConfig {
-    int r;                // VALU path, queries per lane: 0 = pick, else 2 or 4
-    int blocks_per_cu;    // occupancy target used to pick the slice count
-    int mfma;             // 4: cell-sorted pruned search (opt-in: wins when most queries have a near target), 3: two-piece f16 MFMA filter (default), 1: fp32 MFMA filter (small problems), 0: VALU path (cross-check).  (2 was the bf16 filter, removed in round 3.)
-    int q;                // MFMA path, 32-query tiles per wave: 0 = pick, else 1 or 2
-    int u;                // MFMA path, tiles per bookkeeping unit: 0 = pick, else 1 or 2
-    bool env_path, env_wps;   // GENPC_NN_PATH / GENPC_NN_WPS were given
+    int family;           // GENPC_NN_PATH: 4 cell-sorted pruned search (opt-in: wins when most queries have a near target), 3 two-piece f16 MFMA filter (default), 1 fp32 MFMA filter (small problems), 0 VALU path (cross-check); -1: not given
+    int r, q, u, wps;     // GENPC_NN_R / _Q / _U / _WPS as given: nn_plan.h says which values count
     int dbg;              // GENPC_NN_DEBUG
 };
 
@@ -709,31 +705,38 @@ thread_local int t_tune_path = -1, t_tune_hooks = -1;      // (declared in commo
 static const NNConfig &nn_config()
 {
     static const NNConfig c = [] {
-        NNConfig k{0, 4, 3, 0, 0, false, false, 0};
+        NNConfig k{-1, 0, 0, 0, 0, 0};
         k.r = tune_env("GENPC_NN_R", 0, "VALU nearest-neighbour path: queries per lane (2 | 4, 0 = pick)");
         if (const char *e = tune_env_str("GENPC_NN_PATH", "nearest-neighbour kernel family: valu | mfma32 | f16 (default) | grid (opt-in)")) {
-            // (anything else used to fall through to the opt-in cell search -- e.g. 'bf16', a family removed in round 3)
-            if (e[0] == 'v') k.mfma = 0;
-            else if (e[0] == 'm') k.mfma = 1;
-            else if (e[0] == 'f') k.mfma = 3;
-            else if (e[0] == 'g') k.mfma = 4;
+            if (e[0] == 'v') k.family = kNNValu;
+            else if (e[0] == 'm') k.family = kNNMfma32;
+            else if (e[0] == 'f') k.family = kNNF16;
+            else if (e[0] == 'g') k.family = kNNGrid;
             else fprintf(stderr, "genpc_hip: GENPC_NN_PATH=%s is not one of valu | mfma32 | f16 | grid: keeping the default (f16)\n", e);
-            k.env_path = e[0] == 'v' || e[0] == 'm' || e[0] == 'f' || e[0] == 'g';
         }
         k.q = tune_env("GENPC_NN_Q", 0, "MFMA filter: 32-query tiles per wave (2 | 4, 0 = pick)");
         k.u = tune_env("GENPC_NN_U", 0, "MFMA filter: target tiles per bookkeeping unit (2 | 4, 0 = pick)");
-        if (k.q != 1 && k.q != 2 && k.q != 4) k.q = 0;
-        if (k.u != 1 && k.u != 2 && k.u != 4) k.u = 0;
-        {
-            const int w = tune_env("GENPC_NN_WPS", 0, "resident blocks per CU the nearest-neighbour planner assumes (0 = per kernel family)");
-            if (w > 0) { k.blocks_per_cu = w; k.env_wps = true; }
-        }
+        k.wps = tune_env("GENPC_NN_WPS", 0, "resident blocks per CU the nearest-neighbour planner assumes (0 = per kernel family)");
         k.dbg = tune_env("GENPC_NN_DEBUG", 0, "test hooks of the filtered nearest-neighbour paths (bit mask, see genpc_nn_tune)");
-        if (k.r != 2 && k.r != 4) k.r = 0;
-        if (k.blocks_per_cu < 1) k.blocks_per_cu = 1;
         return k;
     }();
     return c;
+}
+
+// What nn_plan may depend on beside the sizes: the device, the calling thread's family, the switches.
+static NNAsk nn_ask(int b, int cus)
+{
+    const NNConfig &cfg = nn_config();
+    NNAsk ask;
+    ask.b = b;
+    ask.cus = cus > 0 ? cus : num_cus();
+    ask.forced = t_tune_path;
+    ask.env_family = cfg.family;
+    ask.env_r = cfg.r;
+    ask.env_q = cfg.q;
+    ask.env_u = cfg.u;
+    ask.env_wps = cfg.wps;
+    return ask;
 }
 
 template <int Q, int U>
@@ -794,15 +797,11 @@ int nn_forward(int b, int ndir, const float *q0, int n0, const float *t0, int m0
                const float *q1, int n1, const float *t1, int m1, float *d1, int *i1, hipStream_t st,
                float radius2, const unsigned *dup0, const unsigned *dup1, int dup_shared)
 {
-    // A direction with no queries or no targets does nothing (the reference's
-    // loops do not execute, outputs keep the caller's zeros).
-    NNConfig cfg = nn_config();
-    if (t_tune_path >= 0) cfg.mfma = t_tune_path;
     NNArgs a{};
     a.b = b;
     a.fma = arith_mode() != 0 ? 1 : 0;
     a.radius2 = radius2;
-    a.debug = t_tune_hooks >= 0 ? t_tune_hooks : cfg.dbg;
+    a.debug = t_tune_hooks >= 0 ? t_tune_hooks : nn_config().dbg;
     if (a.debug & 512) {
         a.stats = (unsigned long long *)workspace(kWsNnStats, 256, nullptr, nullptr, 256);      // one block per device, shared by all streams
         if (!a.stats) return 0;
@@ -812,166 +811,41 @@ int nn_forward(int b, int ndir, const float *q0, int n0, const float *t0, int m0
     float *ds[2] = {d0, d1};
     int *is[2] = {i0, i1};
     const unsigned *dups[2] = {dup0, dup1};
-    int nqs[2] = {n0, n1}, nts[2] = {m0, m1};
-    int nd = 0;
-    int nt_max = 0;
+    const int nqs[2] = {n0, n1}, nts[2] = {m0, m1};
+    NNAsk ask = nn_ask(b, 0);
     for (int d = 0; d < ndir; d++) {
-        if (b <= 0 || nqs[d] <= 0 || nts[d] <= 0) continue;
-        NNDir &D = a.dir[nd++];
+        if (!ask.add(nqs[d], nts[d])) continue;
+        NNDir &D = a.dir[ask.ndir - 1];
         D.q = qs[d]; D.t = ts[d]; D.out_d = ds[d]; D.out_i = is[d];
         D.nq = nqs[d]; D.nt = nts[d];
         D.dupmask = dups[d];
         D.dup_shared = dups[d] ? dup_shared : 0;
-        if (D.nt > nt_max) nt_max = D.nt;
     }
-    a.ndir = nd;
+    const int nd = a.ndir = ask.ndir;
     if (nd == 0) return 1;
-    int path = cfg.mfma;
-    double pairs = 0.0;
-    for (int d = 0; d < nd; d++) pairs += (double)b * a.dir[d].nq * a.dir[d].nt;
-    // measured on MI355X (tools/nn_sweep.py): below ~6M pairs the single-launch fp32-MFMA
-    // kernel wins (1x1024^2 11.0 vs 13.5 us), from 2048^2 on the two-launch f16 filter
-    if (path == 3 && pairs < 6e6 && t_tune_path < 0 && !cfg.env_path) path = 1;
-    if (radius2 < __builtin_inff()) path = 4;      // only the cell search knows how to stop at a distance
-    if (path == 4) {
-        // three launches, O(N + M) work (nn_grid.hip); needs both directions to be each other's swap
-        if (nd == 1 || (a.dir[1].q == a.dir[0].t && a.dir[1].t == a.dir[0].q)) return launch_nn_grid(a, st);
-        path = 3;
-    }
-    if (path == 2) path = 3;                             // (the bf16 filter's number: gone)
-    const bool f16 = path == 3;
-    if (f16) path = 2;                                   // below, 2 = "filter + finish kernel" planning
-    if (path == 2 && nt_max >= (1 << 25)) path = 1;      // finish kernel packs tile indices in 21 bits
-    // R = 4 (fewer LDS reads per pair, more independent chains per lane) when the query
-    // blocks alone fill the chip; R = 2 otherwise: twice the blocks, half the per-wave
-    // epilogue (measured on MI355X: 1x16384^2 87 us vs 97 us, 13x16384^2 870 us vs 835 us).
-    long long want_blocks = (long long)num_cus() * cfg.blocks_per_cu;
-    int r = cfg.r;
-    if (!r) {
-        long long unsplit4 = 0;
-        for (int d = 0; d < nd; d++) unsplit4 += (long long)b * ceil_div(a.dir[d].nq, kBlock * 4);
-        r = unsplit4 >= num_cus() ? 4 : 2;
-    }
-    // MFMA path: a block covers 128*Q queries; Q = 2 halves the LDS reads and the blocks.
-    int q = cfg.q;
-    if (path && !q) {
-        long long unsplit2 = 0;
-        for (int d = 0; d < nd; d++) unsplit2 += (long long)b * ceil_div(a.dir[d].nq, 256);
-        // fp32 MFMA: Q = 2 measured slower at every size from 1x2048^2 to 13x16384^2
-        // f16 filter: 512-query blocks (Q = 4) once there is enough work to fill the chip with
-        // them (1x16384^2 37.8 vs 49.7 us), 256-query blocks below (1x8192^2 20.4 vs 21.6 us)
-        q = path == 2 ? (pairs >= 2e8 ? 4 : 2) : 1;
-        (void)unsplit2;
-    }
-    // f16 filter: at least two accumulator chains per wave (see the hazard note in nn_f16.hip)
-    if (path == 2 && q < 2) q = 2;
-    if (path == 2 && !cfg.env_wps) want_blocks = (long long)num_cus() * (q == 4 ? 2 : (q == 2 ? 3 : 4));   // resident blocks per CU (VGPRs)
-    const int qper = path ? 128 * q : kBlock * r;       // queries per block
-    const int gran = path == 2 ? 128 : (path ? 64 : kChunk);   // slice granularity: one bookkeeping unit
-    int pwords = path ? 3 : 1;                          // 8-byte words per (slice, query)
-    // One slice length for the whole launch, so that every block does the same amount
-    // of work, and per-direction slice counts S_d = ceil(nt_d / slice_len) (no empty
-    // slices when the two clouds differ in size).  slice_len is what makes the launch
-    // ~want_blocks blocks: sum_d b * qblocks_d * nt_d / want_blocks, but never below 8
-    // chunks, and not below 16 chunks (512 targets: below that the per-block staging /
-    // merge latency outweighs the parallelism; measured 1x8192^2 44 us vs 51 us) as long
-    // as two blocks per CU remain.
-    long long work = 0;          // blocks x targets if every block took one target
-    for (int d = 0; d < nd; d++) {
-        a.dir[d].qblocks = ceil_div(a.dir[d].nq, qper);
-        work += (long long)b * a.dir[d].qblocks * a.dir[d].nt;
-    }
-    auto blocks_at = [&](long long len) {
-        long long t = 0;
-        for (int d = 0; d < nd; d++) t += (long long)b * a.dir[d].qblocks * ceil_div64(a.dir[d].nt, len);
-        return t;
-    };
-    long long len = ceil_div64(ceil_div64(work, want_blocks), gran) * gran;
-    if (len < kChunk * 8) len = kChunk * 8;
-    if (len < kChunk * 16 && blocks_at(kChunk * 16) >= 2 * num_cus()) len = kChunk * 16;
-    if (len > nt_max) len = ceil_div64(nt_max, gran) * gran;
-    a.slice_len = (int)len;
-    // bookkeeping per 64 targets once a block has enough of them to amortise the coarser
-    // re-scan (measured: 1x2048^2 14.5 vs 16.0 us, 1x16384^2 63.6 vs 61.2, 13x16384^2 644 vs 590)
-    const int u = (cfg.u == 1 || cfg.u == 2) ? cfg.u : (len >= 2048 ? 2 : 1);
-    // filter path: the launch runs in rounds of `want_blocks` resident blocks, so the
-    // slice count is chosen to minimise rounds x (targets per block + a fixed per-block
-    // cost worth ~192 targets), over the slice counts that keep a query's candidate lists
-    // (slices x NL; NL = 2 lists per lane below three slices: a query is flagged only when THREE
-    // candidate units fall into one list) within kMaxLists = 16.
-    int nl = 1;
-    bool tight = false, wide = false;
-    if (path == 2) {
-        auto lists_of = [&](long long l, int &nl_out) {
-            int smin = 1 << 30, smax = 0;
-            for (int d = 0; d < nd; d++) {
-                const int sd = (int)ceil_div64(a.dir[d].nt, l);
-                smin = std::min(smin, sd);
-                smax = std::max(smax, sd);
-            }
-            nl_out = smin >= 3 ? 1 : 2;
-            return smax * nl_out;
-        };
-        // The f16 kernel's 512-query blocks (Q = 4) exist in two register budgets: 2 resident
-        // blocks per CU, or 3 (168 VGPRs, a little scratch: ~4 % faster per pair over many rounds,
-        // ~1 us slower when the launch is a single round).  All resident blocks share the VALU, so
-        // a round costs (resident blocks) x (targets per block + fixed part).
-        long long best_len = 0;
-        double best_cost = 0.0;
-        int best_res = 0;
-        const bool env_wps = cfg.env_wps;
-        for (int res = (f16 && q == 4 && !env_wps) ? 3 : 0; res != 1 && res >= 0; res = (res == 3 ? 2 : -1)) {
-            const long long slots = res ? (long long)num_cus() * res : want_blocks;
-            const double per_block = res == 3 ? 3.0 * 0.96 : (res == 2 ? 2.0 : 1.0);
-            for (int sc = 1; sc <= 16; sc++) {
-                const long long l = ceil_div64(ceil_div64(nt_max, sc), gran) * gran;
-                if (sc > 1 && l < 256) break;
-                int nl_c;
-                if (lists_of(l, nl_c) > 16) continue;
-                const long long rounds = ceil_div64(blocks_at(l), slots);
-                if (res == 3 && rounds < 3) continue;         // few rounds: the leaner kernel wins
-                const double cost = (double)rounds * (double)(std::min<long long>(l, nt_max) + 192) * per_block;
-                if (!best_len || cost < best_cost * 0.98) {      // prefer fewer slices unless clearly better
-                    best_len = l;
-                    best_cost = cost;
-                    best_res = res;
-                }
-            }
-        }
-        tight = best_res == 3;
-        len = best_len;
-        (void)lists_of(len, nl);
-        a.slice_len = (int)len;
-        // Single-round launches whose slice fits the kernel's 2048-target LDS tile: blocks of 8 waves / 1024 queries,
-        // one per CU -- the same two waves per SIMD, but a slice is read, split into f16 pieces and staged once per
-        // 1024 queries instead of once per 512 (the prologue was a third of a block's time: tools/nn_timeline.py).
-        if (f16 && q == 4 && !tight && len > 1024 && blocks_at(len) <= 2 * (long long)num_cus()) {
-            wide = true;
-            for (int d = 0; d < nd; d++) a.dir[d].qblocks = ceil_div(a.dir[d].nq, 2 * qper);
-        }
-        pwords = 2 * nl;        // (a1, c1) (codes of a2 | a3, c2) per list: list_enc in nn.h
-    }
-    long long tb = 0;
-    int units = 0;
-    size_t part = 0;
-    bool any_split = false;
-    for (int d = 0; d < nd; d++) {
-        NNDir &D = a.dir[d];
-        D.slices = ceil_div(D.nt, a.slice_len);
-        D.block_begin = (int)tb;
-        D.unit_begin = units;
-        tb += (long long)D.slices * b * D.qblocks;
-        units += b * D.qblocks;
-        if (D.slices > 1 || path == 2) {      // the filter always hands its lists to a second launch
-            part += (size_t)D.slices * b * D.nq * pwords;
-            any_split = true;
-        }
-    }
-    if (tb > 0x7fffffffLL) {
+    ask.swapped = nd == 2 && a.dir[1].q == a.dir[0].t && a.dir[1].t == a.dir[0].q;
+    ask.radius = radius2 < __builtin_inff();
+
+    const NNPlan plan = nn_plan(ask);
+    if (plan.family == kNNGrid) return launch_nn_grid(a, st);
+    if (plan.too_large) {
         set_error("chamfer: problem too large for one launch");
         return 0;
     }
-    if (any_split) {
+    a.slice_len = plan.slice_len;
+    a.hint_stride = plan.hint_stride;
+    bool any_partials = false;
+    for (int d = 0; d < nd; d++) {
+        NNDir &D = a.dir[d];
+        const NNPlanDir &P = plan.dir[d];
+        D.qblocks = P.qblocks;
+        D.slices = D.ntmax = P.slices;      // (ntmax: the f16 filter keeps one maximum per slice)
+        D.block_begin = P.block_begin;
+        D.unit_begin = P.unit_begin;
+        D.fin_begin = P.fin_begin;
+        any_partials = any_partials || P.partials;
+    }
+    if (any_partials) {
         // [arrival counters | per-slice partials]; counters are zeroed when the block is
         // (re)allocated and restored to zero by the merging block, so steady-state calls
         // need no memset.
@@ -980,22 +854,21 @@ int nn_forward(int b, int ndir, const float *q0, int n0, const float *t0, int m0
         // which earlier calls used for partials: it is cleared on the stream first (the kernels hand
         // every counter back as zero, so the 64 KiB invariant survives such a call).
         const size_t cnt_min = (size_t)1 << 16;
-        const size_t cnt_ints = std::max(cnt_min / sizeof(int), (size_t)units);
+        const size_t cnt_ints = std::max(cnt_min / sizeof(int), (size_t)plan.units);
         unsigned long long *wp;
         WsLayout L;
         L.add(a.arrive, cnt_ints);
-        L.add_tail(wp, part);          // (both directions' partials, handed out below)
+        L.add_tail(wp, (size_t)plan.part_words);          // (both directions' partials, handed out below)
         if (!ws_alloc(L, kWsNnForward, st, nullptr, cnt_min)) return 0;
         if (cnt_ints * sizeof(int) > cnt_min && !check(hipMemsetAsync(a.arrive, 0, (char *)wp - (char *)a.arrive, st), "hipMemsetAsync(arrival counters)")) return 0;
         size_t off = 0;
         for (int d = 0; d < nd; d++) {
-            if (a.dir[d].slices > 1 || path == 2) {
-                a.dir[d].part = wp + off;
-                off += (size_t)a.dir[d].slices * b * a.dir[d].nq * pwords;
-            }
+            if (!plan.dir[d].partials) continue;
+            a.dir[d].part = wp + off;
+            off += (size_t)a.dir[d].slices * b * a.dir[d].nq * plan.pwords;
         }
     }
-    if (path == 2) {
+    if (plan.family == kNNF16) {
         // exact duplicates among the targets (policy above nn_forward)
         const int force = (a.debug & 2048) ? 0 : ((a.debug & 4096) ? 1 : -1);
         DedupeHint *H = dedupe_hint();
@@ -1044,18 +917,16 @@ int nn_forward(int b, int ndir, const float *q0, int n0, const float *t0, int m0
             }
         }
         a.hint = H ? H->host : nullptr;
-        // bookkeeping unit: the finish kernel re-reads 16 targets per tile of every candidate unit --
-        // per QUERY, while the filter's work is per PAIR: short target clouds (many queries per
-        // pair) take 64-target units (half the re-read, +10 % filter VALU), long ones 128
-        const int fu = cfg.u == 2 || cfg.u == 4 ? cfg.u : (nt_max <= 8192 ? 2 : 4);
-        return launch_nn_f16(a, q, fu, nl, wide ? 2 : (tight ? 1 : 0), tb, st);
-    } else if (path) {
-        if (q == 2) { if (u == 2) launch_mfma<2, 2>(a, (int)tb, st); else launch_mfma<2, 1>(a, (int)tb, st); }
-        else        { if (u == 2) launch_mfma<1, 2>(a, (int)tb, st); else launch_mfma<1, 1>(a, (int)tb, st); }
-    } else if (r == 4) {
-        launch_r<4>(a, (int)tb, st);
+        return launch_nn_f16(a, plan, st);
+    }
+    const int blocks = (int)plan.blocks;
+    if (plan.family == kNNMfma32) {
+        if (plan.q == 2) { if (plan.unit == 2) launch_mfma<2, 2>(a, blocks, st); else launch_mfma<2, 1>(a, blocks, st); }
+        else             { if (plan.unit == 2) launch_mfma<1, 2>(a, blocks, st); else launch_mfma<1, 1>(a, blocks, st); }
+    } else if (plan.r == 4) {
+        launch_r<4>(a, blocks, st);
     } else {
-        launch_r<2>(a, (int)tb, st);
+        launch_r<2>(a, blocks, st);
     }
     return check(hipGetLastError(), "nn_forward_kernel launch") ? 1 : 0;
 }
@@ -1064,10 +935,28 @@ int nn_forward(int b, int ndir, const float *q0, int n0, const float *t0, int m0
 
 GENPC_API int genpc_nn_tune(int path, int hooks)
 {
-    const int prev = genpc::t_tune_path >= 0 ? genpc::t_tune_path : genpc::nn_config().mfma;
-    if (path >= 0 && path <= 4 && path != 2) genpc::t_tune_path = path;
+    const int env = genpc::nn_config().family;
+    const int prev = genpc::t_tune_path >= 0 ? genpc::t_tune_path : (env >= 0 ? env : (int)genpc::kNNF16);
+    if (path == genpc::kNNValu || path == genpc::kNNMfma32 || path == genpc::kNNF16 || path == genpc::kNNGrid) genpc::t_tune_path = path;
     if (hooks >= 0) genpc::t_tune_hooks = hooks;
     return prev;
+}
+
+GENPC_API int genpc_nn_plan(int b, int n, int m, int ndir, int cus, int out[16])
+{
+    using namespace genpc;
+    if (!out || ndir < 1 || ndir > 2) return -1;
+    // the shape as genpc_chamfer_forward (ndir 2) / genpc_nm_distance (ndir 1) bring it
+    NNAsk ask = nn_ask(b, cus);
+    ask.add(n, m);
+    if (ndir == 2) ask.add(m, n);
+    ask.swapped = ask.ndir == 2;
+    const NNPlan p = nn_plan(ask);
+    const int v[16] = {p.family, p.form, p.family == kNNValu ? p.r : p.q, p.unit, p.nl, p.slice_len, p.dir[0].slices, p.dir[1].slices,
+                       (int)std::min<long long>(p.blocks, 0x7fffffff), (int)std::min<long long>(p.fin_blocks, 0x7fffffff), p.early, p.too_large,
+                       p.dir[0].qblocks, p.dir[1].qblocks, p.hint_stride, ask.cus};
+    for (int i = 0; i < 16; i++) out[i] = v[i];
+    return 1;
 }
 
 GENPC_API int genpc_nn_stats(unsigned long long out[3], int reset, void *stream)

@@ -4,11 +4,10 @@
 #pragma once
 #include "common.h"
 #include "grid.h"
+#include "nn_plan.h"      // kChunk, kBlock, kMaxLists, kHTile, kFQ; NNPlan
 
 namespace genpc {
 
-constexpr int kChunk = 32;       // targets per min-only chunk (re-scan granularity)
-constexpr int kBlock = 256;      // 4 waves
 constexpr int kWavesPerBlock = kBlock / kWave;
 
 struct NNDir {
@@ -240,8 +239,6 @@ __device__ __forceinline__ float nn_tau(float a_best, float qq, float tmax2, dou
 }
 
 
-constexpr int kMaxLists = 16;          // slices x lists per lane, when sliced (planner: chamfer.hip)
-
 // Exact (reference arithmetic) minimum and first index over the 16 targets base + 16h ..
 // base + 16h + 15 of a 32-target tile: the rows whose approximate values lane half h of the
 // filter held (tile_row()).  A run that crosses the end of the cloud counts target nt - 1 for every position past it
@@ -319,8 +316,9 @@ __device__ __forceinline__ void rescan_half(const float *__restrict__ T, int nt,
     }
 }
 
-int launch_nn_f16(NNArgs &a, int q, int u, int nl, int tight, long long total_blocks, hipStream_t st);
-int launch_nn_finish(NNArgs &a, int nl, int upieces, float kqt, float ktt, float t2min, hipStream_t st);
+// the two launches of the f16 family, as the plan says (a: filled from the same plan by nn_forward; launch_nn_f16 adds the slice maxima's place)
+int launch_nn_f16(NNArgs &a, const NNPlan &plan, hipStream_t st);
+int launch_nn_finish(const NNArgs &a, const NNPlan &plan, float kqt, float ktt, float t2min, hipStream_t st);
 int launch_nn_grid(const NNArgs &a, hipStream_t st);
 size_t nn_dedupe_mask_words(int b, int n);
 int launch_nn_dedupe(int b, int nclouds, const float *const pts[2], const int n[2], unsigned *const masks[2], unsigned *hint,

@@ -39,7 +39,6 @@ __device__ unsigned long long g_timeline[4096 * 8];
 #else
 #define GENPC_TL(k) do {} while (0)
 #endif
-constexpr int kHTile = 1024;           // targets per LDS tile: 2 planes x 16 B = 32 KiB (template parameter HT: 1024 or 2048)
 constexpr double kQTh = 30.0, kTTh = 15.0;
 
 __device__ __forceinline__ unsigned f16_bits(float v) { return (unsigned)__builtin_bit_cast(unsigned short, (_Float16)v); }
@@ -361,7 +360,7 @@ __global__ __launch_bounds__(WV * kWave, W) void nn_f16_kernel(NNArgs a)
 }
 
 template <int Q, int NL>
-static void launch_main(const NNArgs &a, int blocks, int u, int tight, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr)
+static void launch_main(const NNArgs &a, const NNPlan &plan, hipStream_t st, hipEvent_t e0, hipEvent_t e1)
 {
     // (e0 / e1: genpc_nn_profile -- the events ride on the kernel's own dispatch, hipExtLaunchKernelGGL: they take the dispatch's
     //  start and end timestamps, what a rocprofv3 kernel trace reports, not the interval between two marker packets around it)
@@ -370,26 +369,20 @@ static void launch_main(const NNArgs &a, int blocks, int u, int tight, hipStream
         if (e0) hipExtLaunchKernelGGL(KERNEL, GRID, BLOCK, 0, st, e0, e1, 0, a);                                        \
         else hipLaunchKernelGGL(KERNEL, GRID, BLOCK, 0, st, a);                                                         \
     } while (0)
-    // tight 1: three waves per SIMD for the 512-query blocks (planner: launches of several rounds)
-    // tight 2 (planner: single round, Q = 4, slice_len > 1024): 8-wave blocks of 1024 queries, one per CU
-    // HT = 2048 (66 KiB of LDS per block; a slice of up to 2048 targets is resident) where two waves per SIMD are all the
-    // registers allow anyway: Q = 4, not tight, slice_len > 1024 (4 x 16384 x 8192, slices of 4096: 57.9 -> 54.7 us)
-    const bool big = Q == 4 && tight != 1 && a.slice_len > kHTile;
-    if (Q == 4 && tight == 2) {
-        if (u == 2) NN_F16_LAUNCH((nn_f16_kernel<4, 2, NL, 1, 2 * kHTile, 8>), dim3(blocks), dim3(8 * kWave));
+    // the forms of the 512-query blocks (nn_plan.h NNForm: waves per block, resident blocks per CU, LDS tile); 256-query
+    // blocks have the four-wave form alone.  plan.unit is 2 or 4.
+    const int blocks = (int)plan.blocks;
+    if (Q == 4 && plan.form == kNNWide) {
+        if (plan.unit == 2) NN_F16_LAUNCH((nn_f16_kernel<4, 2, NL, 1, 2 * kHTile, 8>), dim3(blocks), dim3(8 * kWave));
         else NN_F16_LAUNCH((nn_f16_kernel<4, 4, NL, 1, 2 * kHTile, 8>), dim3(blocks), dim3(8 * kWave));
-        return;
-    }
-    if (big) {
-        if (u == 2) NN_F16_LAUNCH((nn_f16_kernel<4, 2, NL, 2, 2 * kHTile, 4>), dim3(blocks), dim3(kBlock));
+    } else if (Q == 4 && plan.form == kNNTile2048) {
+        if (plan.unit == 2) NN_F16_LAUNCH((nn_f16_kernel<4, 2, NL, 2, 2 * kHTile, 4>), dim3(blocks), dim3(kBlock));
         else NN_F16_LAUNCH((nn_f16_kernel<4, 4, NL, 2, 2 * kHTile, 4>), dim3(blocks), dim3(kBlock));
-        return;
-    }
-    if (u == 2) {
-        if (tight) NN_F16_LAUNCH((nn_f16_kernel<Q, 2, NL, (Q == 4 ? 3 : 4), kHTile, 4>), dim3(blocks), dim3(kBlock));
-        else NN_F16_LAUNCH((nn_f16_kernel<Q, 2, NL, (Q == 4 ? 2 : 4), kHTile, 4>), dim3(blocks), dim3(kBlock));
+    } else if (Q == 4 && plan.form == kNNThreeWave) {
+        if (plan.unit == 2) NN_F16_LAUNCH((nn_f16_kernel<Q, 2, NL, (Q == 4 ? 3 : 4), kHTile, 4>), dim3(blocks), dim3(kBlock));
+        else NN_F16_LAUNCH((nn_f16_kernel<Q, 4, NL, (Q == 4 ? 3 : 4), kHTile, 4>), dim3(blocks), dim3(kBlock));
     } else {
-        if (tight) NN_F16_LAUNCH((nn_f16_kernel<Q, 4, NL, (Q == 4 ? 3 : 4), kHTile, 4>), dim3(blocks), dim3(kBlock));
+        if (plan.unit == 2) NN_F16_LAUNCH((nn_f16_kernel<Q, 2, NL, (Q == 4 ? 2 : 4), kHTile, 4>), dim3(blocks), dim3(kBlock));
         else NN_F16_LAUNCH((nn_f16_kernel<Q, 4, NL, (Q == 4 ? 2 : 4), kHTile, 4>), dim3(blocks), dim3(kBlock));
     }
 #undef NN_F16_LAUNCH
@@ -401,16 +394,12 @@ static void launch_main(const NNArgs &a, int blocks, int u, int tight, hipStream
 static thread_local bool g_prof_on = false;
 static thread_local hipEvent_t g_prof_e0 = nullptr, g_prof_e1 = nullptr;
 
-// Launches the filter and the finish kernel.  q / u / nl as chosen by the planner in chamfer.hip.
-int launch_nn_f16(NNArgs &a, int q, int u, int nl, int tight, long long total_blocks, hipStream_t st)
+// Launches the filter and the finish kernel: maps the plan to a template instance, decides nothing.
+int launch_nn_f16(NNArgs &a, const NNPlan &plan, hipStream_t st)
 {
     WsLayout L;
-    for (int d = 0; d < a.ndir; d++) {
-        a.dir[d].ntmax = a.dir[d].slices;
-        L.add(a.dir[d].tmaxp, (size_t)a.b * a.dir[d].ntmax);
-    }
+    for (int d = 0; d < a.ndir; d++) L.add(a.dir[d].tmaxp, (size_t)a.b * a.dir[d].ntmax);
     if (!ws_alloc(L, kWsNnTmax, st)) return 0;
-    const int blocks = (int)total_blocks;
     hipEvent_t pe0 = nullptr, pe1 = nullptr;
     if (g_prof_on) {
         if (!g_prof_e0) { (void)hipEventCreate(&g_prof_e0); (void)hipEventCreate(&g_prof_e1); }
@@ -418,15 +407,15 @@ int launch_nn_f16(NNArgs &a, int q, int u, int nl, int tight, long long total_bl
         pe1 = g_prof_e1;
     }
     // (256-target bookkeeping units, U = 8, in the wide form: filter -0.4 us, finish +1.7 us at 1 x 16384^2 -- not kept)
-    if (q == 4) {
-        if (nl == 2) launch_main<4, 2>(a, blocks, u, tight, st, pe0, pe1);
-        else launch_main<4, 1>(a, blocks, u, tight, st, pe0, pe1);
+    if (plan.q == 4) {
+        if (plan.nl == 2) launch_main<4, 2>(a, plan, st, pe0, pe1);
+        else launch_main<4, 1>(a, plan, st, pe0, pe1);
     } else {
-        if (nl == 2) launch_main<2, 2>(a, blocks, u, 0, st, pe0, pe1);
-        else launch_main<2, 1>(a, blocks, u, 0, st, pe0, pe1);
+        if (plan.nl == 2) launch_main<2, 2>(a, plan, st, pe0, pe1);
+        else launch_main<2, 1>(a, plan, st, pe0, pe1);
     }
     if (!check(hipGetLastError(), "nn_f16_kernel launch")) return 0;
-    return launch_nn_finish(a, nl, u, (float)kQTh, (float)kTTh, 0.0f, st);
+    return launch_nn_finish(a, plan, (float)kQTh, (float)kTTh, 0.0f, st);
 }
 
 }  // namespace genpc

@@ -27,7 +27,6 @@ __device__ unsigned long long g_timeline_fin[4096 * 8];
 #define GENPC_TLF(k) do {} while (0)
 #endif
 
-constexpr int kFQ = 64;                // queries per finish block
 constexpr int kFWork = 2048;           // work-item capacity (64 queries x 32 pieces)
 
 // EARLY: the form for launches whose blocks are all resident at once (at most two per CU: the headline step).  There a block's
@@ -265,24 +264,13 @@ __global__ __launch_bounds__(kBlock) void nn_finish_kernel(NNArgs a, int nl, int
     GENPC_TLF(5);
 }
 
-// Second launch of the filtered paths.  kqt / ktt: coefficients of the filter's error bound.
-int launch_nn_finish(NNArgs &a, int nl, int upieces, float kqt, float ktt, float t2min, hipStream_t st)
+// Second launch of the filtered paths, as the plan says.  kqt / ktt: coefficients of the filter's error bound.
+int launch_nn_finish(const NNArgs &a, const NNPlan &plan, float kqt, float ktt, float t2min, hipStream_t st)
 {
-    long long fb = 0;
-    for (int d = 0; d < a.ndir; d++) {
-        a.dir[d].fin_begin = (int)fb;
-        fb += (long long)a.b * ceil_div(a.dir[d].nq, kFQ);
-    }
-    if (fb > 0x7fffffffLL) {
-        set_error("chamfer: problem too large for one launch");
-        return 0;
-    }
-    a.hint_stride = (int)ceil_div64(fb, 16);
-    const bool early = fb <= 2 * (long long)num_cus();      // every block resident at once (see nn_finish_kernel)
 #define NN_FINISH_LAUNCH(FMA, EARLY) \
-    hipLaunchKernelGGL((nn_finish_kernel<FMA, EARLY>), dim3((unsigned)fb), dim3(kBlock), 0, st, a, nl, upieces, kqt, ktt, t2min)
-    if (a.fma) { if (early) NN_FINISH_LAUNCH(1, 1); else NN_FINISH_LAUNCH(1, 0); }
-    else { if (early) NN_FINISH_LAUNCH(0, 1); else NN_FINISH_LAUNCH(0, 0); }
+    hipLaunchKernelGGL((nn_finish_kernel<FMA, EARLY>), dim3((unsigned)plan.fin_blocks), dim3(kBlock), 0, st, a, plan.nl, plan.unit, kqt, ktt, t2min)
+    if (a.fma) { if (plan.early) NN_FINISH_LAUNCH(1, 1); else NN_FINISH_LAUNCH(1, 0); }
+    else { if (plan.early) NN_FINISH_LAUNCH(0, 1); else NN_FINISH_LAUNCH(0, 0); }
 #undef NN_FINISH_LAUNCH
     return check(hipGetLastError(), "nn_finish_kernel launch") ? 1 : 0;
 }

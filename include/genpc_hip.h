@@ -33,10 +33,10 @@ extern "C" {
 #define GENPC_ARITH_FMA 1
 
 /* Library / device ------------------------------------------------------- */
-int genpc_abi_version(void);              /* bumps when a signature or a documented behaviour changes (25: genpc_nn_seeded_step added; 24: genpc_icp_plan added; 23: genpc_pose_loss_grad_batch added; 22: genpc_chamfer_backward_ragged added; 21: genpc_nm_distance_ragged added; 20: genpc_mesh_sample added; 19: genpc_uhd added; 18: genpc_knn_query added;
+int genpc_abi_version(void);              /* bumps when a signature or a documented behaviour changes (26: genpc_nn_plan added; 25: genpc_nn_seeded_step added; 24: genpc_icp_plan added; 23: genpc_pose_loss_grad_batch added; 22: genpc_chamfer_backward_ragged added; 21: genpc_nm_distance_ragged added; 20: genpc_mesh_sample added; 19: genpc_uhd added; 18: genpc_knn_query added;
                                            * 17: genpc_fps_tune takes 0 or 256 only; 16: genpc_hpr_* asynchronous, counts -1 on an internal error;
                                            * genpc_fps*: out_idx[0] -2 = failed the check).
-                                           * Still 25 with genpc_uhd_ragged: a function added changes no signature and no documented behaviour. */
+                                           * genpc_uhd_ragged came without a bump. */
 const char *genpc_last_error(void);       /* last HIP error string, "" if none */
 int genpc_set_arith(int mode);            /* process default; returns the previous one */
 int genpc_set_arith_thread(int mode);     /* calling thread only, < 0: follow the default; returns the previous override */
@@ -70,6 +70,19 @@ int genpc_nn_tune(int path, int hooks);
  * pass (filter proof failed: exact ties, non-finite input), out[2] exact re-evaluations of
  * 16-/32-target pieces.  Synchronises `stream`; reset != 0 zeroes them afterwards.      */
 int genpc_nn_stats(unsigned long long out[3], int reset, void *stream);
+/* The plan (csrc/nn_plan.h) that genpc_chamfer_forward (ndir 2) or genpc_nm_distance (ndir 1) of [b, n, 3] against [b, m, 3]
+ * would get on the calling thread, its genpc_nn_tune family and the process's GENPC_NN_* switches in force, on a device of
+ * `cus` compute units; cus <= 0: the current device's, cus > 0: no GPU is touched.  Which kernel form a shape reaches depends
+ * on the device: tests ask here instead of assuming.
+ *   out[0] family (genpc_nn_tune's numbers)     out[1] form of the f16 filter's blocks: 0 four waves, 1 four waves at three
+ *   blocks per CU, 2 four waves with the 2048-target LDS tile, 3 eight waves ("wide")
+ *   out[2] 32-query tiles per wave Q (VALU family: queries per lane R)     out[3] target tiles per bookkeeping unit
+ *   out[4] lists per lane     out[5] targets per slice     out[6], out[7] slices of direction 0, 1
+ *   out[8] blocks of the first launch     out[9] blocks of the finish launch     out[10] 1: the finish kernel's EARLY form
+ *   out[11] 1: too large for one launch (the call would fail)     out[12], out[13] query blocks per slice of direction 0, 1
+ *   out[14] finish blocks per re-do report     out[15] the compute units planned for
+ * Fields that a family does not have are 0; the cell search (family 4) has none.  Returns 1, -1 for a bad argument.     */
+int genpc_nn_plan(int b, int n, int m, int ndir, int cus, int out[16]);
 /* Exact-duplicate pre-pass of the filtered nearest-neighbour path (csrc/nn_dedupe.hip): mask[e][k / 32] bit k % 32 is set
  * iff point k of cloud e has bit-identical coordinates to a point of lower index in the same cloud -- such a target can
  * never be reported by the reference's first-index-wins scan (chamfer3D.cu:30-71).  xyz [b, n, 3] float, mask

@@ -71,11 +71,19 @@ def test_config5_size_elementwise(gp, oracle, shape):
 @pytest.mark.parametrize("shape", [((1, 12001, 3), (1, 13003, 3)), ((4, 15403, 3), (4, 7855, 3)), ((2, 5000, 3), (2, 20011, 3)),
                                    ((1, 16384, 3), (1, 3001, 3)), ((3, 9000, 3), (3, 9000, 3))])
 def test_single_round_filter_forms_elementwise(gp, oracle, shape):
-    """Shapes whose launches are a single round with slices over 1024 targets: the filter's 2048-target LDS tiles
+    """Shapes chosen for launches of a single round with slices over 1024 targets: the filter's 2048-target LDS tiles
     (slice resident or not), the 8-wave blocks whose last block is partly empty (query counts that are no multiple of
-    1024), the alignment loop's four starts x (15403 vs 7855), and the finish kernel's best-unit speculation on all of them."""
+    1024), the alignment loop's four starts x (15403 vs 7855), and the finish kernel's best-unit speculation on all of them.
+    What they reach depends on the CU count (genpc_nn_plan, csrc/nn_plan.h).  On 256 CUs the first three are 8-wave launches
+    (slices of 1408, 3968 and 1792 targets); 1 x 16384 vs 3001 is a Q = 2 launch and 3 x 9000^2 a four-wave Q = 4 launch, both
+    with slices of exactly 1024, the latter in two rounds.  On 64 CUs none is a single round: three waves per SIMD for the
+    first, the second and the last, four waves with the 2048-target tile for the third, Q = 2 for the fourth.  The plan of the
+    device at hand goes into the failure message; tests/test_gpu_nn_forms.py reaches every form by search."""
+    import nn_forms
     a, b = gen_pair(sum(shape[0]) + sum(shape[1]), *shape)
-    assert_bits(run_hip(gp, a, b, 1), oracle.chamfer_forward(a, b, 1), str(shape))
+    p = nn_forms.plan(gp["lib"], None, shape[0][0], shape[0][1], shape[1][1])
+    assert p["family"] == nn_forms.F16 and not p["too_large"], p
+    assert_bits(run_hip(gp, a, b, 1), oracle.chamfer_forward(a, b, 1), "%s: %s" % (shape, nn_forms.describe(p)))
 
 
 def test_thirteen_real_scans_elementwise(gp, oracle, golden):

@@ -34,7 +34,7 @@ def _copies(targets):
 
 def test_what_the_kernel_constants_are():
     """The numbers the case module restates or the sizes rest on, read from the code."""
-    assert _constant("nn.h", "kBlock") // _constant("nn_seeded.hip", "kSLPQ") == C.QUERIES_PER_BLOCK
+    assert _constant("nn_plan.h", "kBlock") // _constant("nn_seeded.hip", "kSLPQ") == C.QUERIES_PER_BLOCK
     clamp = _constant("grid.h", "kCellGridMaxCells") * 3 // 4
     assert C.CAP_NM // 2 > clamp and C.CAP_NS // 2 > clamp           # build_seeded_grids: target(n) = n / 2, clamped
     rest, _, _, stat = C.case("cap", "loop")
