@@ -11,7 +11,7 @@ import torch  # noqa: F401  (loads torch's libamdhip64.so.7 first; ours binds to
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GENPC_LIB: an alternative build of the same library (kernel experiments only)
 LIB_PATH = os.environ.get("GENPC_LIB") or os.path.join(_HERE, "lib", "libgenpc_hip.so")
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -75,6 +75,10 @@ SIGNATURES = {
     "genpc_mfma_f16_probe": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
     "genpc_list_code_probe": (_i, [ctypes.c_longlong, _vp, _vp, _vp, _vp]),
     "genpc_fastdiv_probe": (_i, [ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "genpc_grid_build_probe": (_i, [_i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "genpc_grid_size_probe": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "genpc_grid_bound_probe": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i] + [_vp] * 9 + [_vp]),
+    "genpc_grid_range_probe": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "genpc_fps_multi": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
     "genpc_fps_defer": (_i, [_i]),
     "genpc_streams_prepare": (_i, [_vp]),

@@ -366,9 +366,9 @@ __global__ __launch_bounds__(kABlock, 4) void emd_auction_kernel(EmdAuction a)
                 const bool cull = !H.bad && (fabsf(x1) + fabsf(y1)) + fabsf(z1) < inf;
                 int bx0 = 0, bx1 = gx - 1, by0 = 0, by1 = gy - 1, bz0 = 0, bz1 = gz - 1;
                 auto set_box = [&](float R) {
-                    bx0 = grid_cell1((x1 - R) - sx, H.lo[0], H.inv, gx); bx1 = grid_cell1((x1 + R) + sx, H.lo[0], H.inv, gx);
-                    by0 = grid_cell1((y1 - R) - sy, H.lo[1], H.inv, gy); by1 = grid_cell1((y1 + R) + sy, H.lo[1], H.inv, gy);
-                    bz0 = grid_cell1((z1 - R) - sz, H.lo[2], H.inv, gz); bz1 = grid_cell1((z1 + R) + sz, H.lo[2], H.inv, gz);
+                    { const GridRange r = grid_cell_range(x1, R, sx, H.lo[0], H.inv, gx); bx0 = r.c0; bx1 = r.c1; }
+                    { const GridRange r = grid_cell_range(y1, R, sy, H.lo[1], H.inv, gy); by0 = r.c0; by1 = r.c1; }
+                    { const GridRange r = grid_cell_range(z1, R, sz, H.lo[2], H.inv, gz); bz0 = r.c0; bz1 = r.c1; }
                 };
                 if (cull) set_box(cb);
                 if (cull && (!seeded || (by1 - by0 + 1) * (bz1 - bz0 + 1) > kTwoPassRows)) {
@@ -417,8 +417,9 @@ __global__ __launch_bounds__(kABlock, 4) void emd_auction_kernel(EmdAuction a)
                                 keep = lb < c2;
                                 if (keep) {
                                     const float W = sqrtf(fmaxf(0.0f, __fmul_rn(c2, 1.000001f) - lb)) * 1.000001f;
-                                    cx0 = max(bx0, grid_cell1((x1 - W) - sx, H.lo[0], H.inv, gx));
-                                    cx1 = min(bx1, grid_cell1((x1 + W) + sx, H.lo[0], H.inv, gx));
+                                    const GridRange rw = grid_cell_range_in(x1, W, sx, H.lo[0], H.inv, gx, bx0, bx1);
+                                    cx0 = rw.c0;
+                                    cx1 = rw.c1;
                                 }
                             }
                             if (keep && cx0 <= cx1) {

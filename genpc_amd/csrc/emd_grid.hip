@@ -247,9 +247,9 @@ __global__ __launch_bounds__(kEBlock) __attribute__((amdgpu_waves_per_eu(4, 8)))
         // the box |p - x1| <= cb (cell function monotone: a point within cb of x1 on an axis lies in [cell(x1 - cb), cell(x1 + cb)])
         int bx0 = 0, bx1 = gx - 1, by0 = 0, by1 = gy - 1, bz0 = 0, bz1 = gz - 1;
         auto set_box = [&](float R) {
-            bx0 = grid_cell1((x1 - R) - sx, H.lo[0], H.inv, gx); bx1 = grid_cell1((x1 + R) + sx, H.lo[0], H.inv, gx);
-            by0 = grid_cell1((y1 - R) - sy, H.lo[1], H.inv, gy); by1 = grid_cell1((y1 + R) + sy, H.lo[1], H.inv, gy);
-            bz0 = grid_cell1((z1 - R) - sz, H.lo[2], H.inv, gz); bz1 = grid_cell1((z1 + R) + sz, H.lo[2], H.inv, gz);
+            { const GridRange r = grid_cell_range(x1, R, sx, H.lo[0], H.inv, gx); bx0 = r.c0; bx1 = r.c1; }
+            { const GridRange r = grid_cell_range(y1, R, sy, H.lo[1], H.inv, gy); by0 = r.c0; by1 = r.c1; }
+            { const GridRange r = grid_cell_range(z1, R, sz, H.lo[2], H.inv, gz); bz0 = r.c0; bz1 = r.c1; }
         };
         if (cull) set_box(cb);
         // A point without a seed (its first bid) or with a stale one (the prices of the two objects it knew have risen since
@@ -314,8 +314,9 @@ __global__ __launch_bounds__(kEBlock) __attribute__((amdgpu_waves_per_eu(4, 8)))
                     keep = lb < c2;                          // else nothing in this row can matter (prices >= 0)
                     if (keep) {
                         const float W = sqrtf(fmaxf(0.0f, __fmul_rn(c2, 1.000001f) - lb)) * 1.000001f;
-                        cx0 = max(bx0, grid_cell1((x1 - W) - sx, H.lo[0], H.inv, gx));
-                        cx1 = min(bx1, grid_cell1((x1 + W) + sx, H.lo[0], H.inv, gx));
+                        const GridRange rw = grid_cell_range_in(x1, W, sx, H.lo[0], H.inv, gx, bx0, bx1);
+                        cx0 = rw.c0;
+                        cx1 = rw.c1;
                     }
                 }
                 if (keep && cx0 <= cx1) {

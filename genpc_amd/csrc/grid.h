@@ -16,6 +16,10 @@
 // an association in its own copy has left the proof behind, which is why there are no copies -- but one: fps_grid.hip (gcell,
 // box_margin, 0.9999f) keeps a grid and margins of its own that nothing here proves.  On these helpers it returns the same
 // samples 0.8 - 2 % later, which is more than its own spread (DESIGN_NOTEBOOK.md, "icp_fused_kernel on grid.h; fps_grid.hip measured").
+// The bound in reverse -- the cells that can hold a point within R of q -- is grid_cell_range below, for the same reason in one place.
+// Tested by itself: csrc/probe.hip runs these helpers and grid.hip's builds on the inputs of tests/grid_cases.py (every fp32 wall and
+// its neighbours, far queries, 2^-60 / 2^60, lattices, degenerate clouds), tests/test_gpu_grid.py checks each gap against |p - q| in
+// exact arithmetic; the point that strays farthest outside its cell's fp32 walls uses 6 % of the slack (DESIGN_NOTEBOOK.md).
 #pragma once
 #include "common.h"
 #include "ragged_table.h"
@@ -36,7 +40,7 @@ struct GridFrame {          // what the helpers need of a grid; the headers of t
 __device__ __forceinline__ int grid_cell1(float p, float lo, float inv, int g)
 {
     const float t = __fmul_rn(__fsub_rn(p, lo), inv);
-    int c = (int)floorf(t);          // NaN -> 0 on gfx950 (v_cvt_i32_f32); clouds with non-finite coordinates are searched without culling
+    int c = (int)floorf(t);          // NaN -> 0, +inf -> g - 1, -inf -> 0 on gfx950 (v_cvt_i32_f32 saturates; tests/test_gpu_grid.py); clouds with non-finite coordinates are searched without culling
     c = c < 0 ? 0 : c;
     return c > g - 1 ? g - 1 : c;
 }
@@ -58,6 +62,26 @@ __device__ __forceinline__ float grid_gap(int c, int w, int g, float lo, float h
     const float wl = c > 0 ? __fadd_rn(lo, __fmul_rn((float)c, h)) : mn;
     const float wh = c + w < g ? __fadd_rn(lo, __fmul_rn((float)(c + w), h)) : mx;
     return grid_wall_gap(wl, wh, q, s);
+}
+
+// The Bound in reverse: the cells [c0, c1] of an axis that can hold a point p with |p_a - q_a| <= R (s = grid_slack of q on that
+// axis).  cell() is monotone and (q - R) - s <= p <= (q + R) + s with room for the two roundings, so the cell of p lies between
+// the cells of the two ends.  A NaN R gives [0, 0]: callers test R first.
+struct GridRange { int c0, c1; };
+__device__ __forceinline__ GridRange grid_cell_range(float q, float R, float s, float lo, float inv, int g)
+{
+    GridRange r;
+    r.c0 = grid_cell1((q - R) - s, lo, inv, g);
+    r.c1 = grid_cell1((q + R) + s, lo, inv, g);
+    return r;
+}
+// the same range inside [b0, b1], the range of a wider radius: each end is clipped as soon as it is known
+__device__ __forceinline__ GridRange grid_cell_range_in(float q, float R, float s, float lo, float inv, int g, int b0, int b1)
+{
+    GridRange r;
+    r.c0 = max(b0, grid_cell1((q - R) - s, lo, inv, g));
+    r.c1 = min(b1, grid_cell1((q + R) + s, lo, inv, g));
+    return r;
 }
 
 // Block-wide box: every thread brings the (mn, mx) of its own points and leaves with the block's.  s_red: 6 floats per wave.
@@ -107,7 +131,7 @@ __device__ __forceinline__ void grid_frame(const float mn[3], const int g[3], fl
 // Box (mn, mx) -> cubic cells of side h, about cells_target of them over the axes that are wider than h, at most
 // cells_max as the numbering counts them: COARSE (nn_grid.hip: 4 x 4 x 4 blocks, partial ones padded) 64 x the product of
 // (g + 3) / 4, else the product of g.  h grows by 1.26 (a doubling of the cell volume) up to REPS times to get there;
-// a box that still does not fit becomes one cell.  An axis without a finite coordinate gets lo = 0.
+// a box that still does not fit becomes one cell of side 1.  An axis without a finite coordinate gets lo = 0.
 template <int REPS, bool COARSE>
 __device__ __forceinline__ void grid_size(float mn[3], float mx[3], int cells_target, int cells_max, GridFrame &F)
 {
@@ -153,7 +177,7 @@ __device__ __forceinline__ void grid_size(float mn[3], float mx[3], int cells_ta
         }
         if (cells <= cells_max) break;
         h *= 1.26f;
-        if (rep == REPS - 1) { act[0] = act[1] = act[2] = false; }
+        if (rep == REPS - 1) { act[0] = act[1] = act[2] = false; h = 1.0f; }      // does not fit: one cell of side 1, as grid_frame's
     }
     for (int k = 0; k < 3; k++) if (!act[k]) g[k] = 1;
     grid_frame(mn, g, h, F);

@@ -131,9 +131,9 @@ __global__ __launch_bounds__(kBlock) void nn_seeded_kernel(SeededArgs a)
     int bx0 = 0, bx1 = gx - 1, by0 = 0, by1 = gy - 1, bz0 = 0, bz1 = gz - 1;
     if (rg2 == rg2 && rg2 < inf) {
         const float R = sqrtf(rg2) * 1.000001f;
-        bx0 = grid_cell1((gx_ - R) - sx, H.lo[0], H.inv, gx); bx1 = grid_cell1((gx_ + R) + sx, H.lo[0], H.inv, gx);
-        by0 = grid_cell1((gy_ - R) - sy, H.lo[1], H.inv, gy); by1 = grid_cell1((gy_ + R) + sy, H.lo[1], H.inv, gy);
-        bz0 = grid_cell1((gz_ - R) - sz, H.lo[2], H.inv, gz); bz1 = grid_cell1((gz_ + R) + sz, H.lo[2], H.inv, gz);
+        { const GridRange r = grid_cell_range(gx_, R, sx, H.lo[0], H.inv, gx); bx0 = r.c0; bx1 = r.c1; }
+        { const GridRange r = grid_cell_range(gy_, R, sy, H.lo[1], H.inv, gy); by0 = r.c0; by1 = r.c1; }
+        { const GridRange r = grid_cell_range(gz_, R, sz, H.lo[2], H.inv, gz); bz0 = r.c0; bz1 = r.c1; }
     }
     // Rows of the box, kSLPQ lanes striding over them four at a time: the extent of a row inside the box's x range is
     // fetched FIRST, for four rows at once -- a query with no target nearby (the back of the complete shape against a partial
@@ -164,8 +164,9 @@ __global__ __launch_bounds__(kBlock) void nn_seeded_kernel(SeededArgs a)
                 // (a best distance that overflowed to +inf ties with every target that far: the whole row -- inf - inf is a NaN, and
                 //  fmaxf made a width of 0 of it: tests/test_gpu_nn_seeded.py, log s = +50)
                 const float W = rg2 < inf ? sqrtf(fmaxf(0.0f, __fmul_rn(rg2, 1.000001f) - lb)) * 1.000001f : inf;
-                const int cx0 = max(bx0, grid_cell1((gx_ - W) - sx, H.lo[0], H.inv, gx));
-                const int cx1 = min(bx1, grid_cell1((gx_ + W) + sx, H.lo[0], H.inv, gx));
+                const GridRange rw = grid_cell_range_in(gx_, W, sx, H.lo[0], H.inv, gx, bx0, bx1);
+                const int cx0 = rw.c0;
+                const int cx1 = rw.c1;
                 if (cx0 > cx1) continue;
                 if (cx0 > bx0) p0 = ST[rowb[k] + cx0];
                 if (cx1 < bx1) p1 = ST[rowb[k] + cx1 + 1];

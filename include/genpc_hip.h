@@ -33,7 +33,7 @@ extern "C" {
 #define GENPC_ARITH_FMA 1
 
 /* Library / device ------------------------------------------------------- */
-int genpc_abi_version(void);              /* bumps when a signature or a documented behaviour changes (26: genpc_nn_plan added; 25: genpc_nn_seeded_step added; 24: genpc_icp_plan added; 23: genpc_pose_loss_grad_batch added; 22: genpc_chamfer_backward_ragged added; 21: genpc_nm_distance_ragged added; 20: genpc_mesh_sample added; 19: genpc_uhd added; 18: genpc_knn_query added;
+int genpc_abi_version(void);              /* bumps when a signature or a documented behaviour changes (27: genpc_grid_*_probe added; 26: genpc_nn_plan added; 25: genpc_nn_seeded_step added; 24: genpc_icp_plan added; 23: genpc_pose_loss_grad_batch added; 22: genpc_chamfer_backward_ragged added; 21: genpc_nm_distance_ragged added; 20: genpc_mesh_sample added; 19: genpc_uhd added; 18: genpc_knn_query added;
                                            * 17: genpc_fps_tune takes 0 or 256 only; 16: genpc_hpr_* asynchronous, counts -1 on an internal error;
                                            * genpc_fps*: out_idx[0] -2 = failed the check).
                                            * genpc_uhd_ragged came without a bump. */
@@ -509,6 +509,39 @@ int genpc_list_code_probe(long long n, const float *base, const float *v, float 
  * (tests/test_gpu_fastdiv.py).  All arrays device memory, n elements.                              */
 int genpc_fastdiv_probe(long long n, const float *num, const float *den, float *fast,
                         float *fast_packed, float *ieee, unsigned char *in_range, void *stream);
+
+/* Grid probes: csrc/grid.h's cell function, sizing, skip bound and cell range and csrc/grid.hip's two builds, run on the
+ * caller's inputs; the kernels behind them call those helpers themselves (tests/test_gpu_grid.py).  Device memory unless noted.
+ * A header is 13 words: lo[3], inv, h, slack[3] (float32), g[3], cells, bad (int32); a frame is its first 11.
+ *
+ * genpc_grid_build_probe, moff == null: the build of b clouds xyz[b][n][3] for cells_target and 1 <= cells_max <= 15360 cells:
+ * hdr[b], start[b][cells_max + 1], sorted[b][n][4] (x, y, z, bits of the index), pos_of[b][n] and orig_of[b][n] (either may be
+ * null).  moff != null (HOST, b + 1 offsets; noff likewise, null: moff): the ragged build of b clouds packed in xyz, each
+ * sized for itself; cloud j's cell table starts at start[moff[j] + 65 j], its points at sorted[moff[j]] with the index inside
+ * the cloud; a cloud with noff[j + 1] == noff[j] is not built and its pieces are not written; n, cells_*, pos_of, orig_of are
+ * not used.  Returns 0 when no cloud has a query.                                                         */
+int genpc_grid_build_probe(int b, int n, const float *xyz, const int *noff, const int *moff, int cells_target,
+                           int cells_max, void *hdr, int *start, float *sorted, int *pos_of, int *orig_of, void *stream);
+
+/* frames[i] = grid_size<16, false> (coarse == 0: the builds above) or grid_size<12, true> (nn_grid.hip's 4 x 4 x 4 numbering) of
+ * the box mn[i][3] .. mx[i][3] for cells_target[i], cells_max[i]; one thread per box.                            */
+int genpc_grid_size_probe(int nbox, int coarse, const float *mn, const float *mx, const int *cells_target,
+                          const int *cells_max, void *frames, void *stream);
+
+/* For one header, queries q[nq][3] and points p[n][3]: qcell[nq][3], pcell[n][3] = grid_cell1 per axis; qslack[nq][3] =
+ * grid_slack; per pair (j, i), at [j n + i]: gap1[..][3], gap4[..][3] = grid_gap per axis of the point's cell and of its aligned
+ * block of four cells; bound[..][3] = fma(gx,gx,fma(gy,gy,gz*gz)) * kGridShrink of gap1, fma(gy,gy,gz*gz) * kGridShrink of gap1,
+ * the first form of gap4; sq[..][2] = sqdist<0>, sqdist<1> of p - q.  slab[nq][3][gmax][2], for c < g of the axis: grid_gap(0, c)
+ * and grid_gap(c, g - c) of the shell walk; slab_bound the same shape: (m * m) * kGridShrink.  mn[3], mx[3] (both or neither):
+ * outer walls of the border cells, as icp.hip passes them.                                                 */
+int genpc_grid_bound_probe(const void *hdr, int nq, const float *q, int n, const float *p, const float *mn,
+                           const float *mx, int gmax, int *qcell, int *pcell, float *qslack, float *gap1, float *gap4,
+                           float *bound, float *sq, float *slab, float *slab_bound, void *stream);
+
+/* range[nq][3][2] = grid_cell_range of q[nq][3] with radius[nq][3] on each axis: the cells that can hold a point within the
+ * radius; clip[nq][3][2] != null: grid_cell_range_in, the range clipped to [clip[..][0], clip[..][1]].                */
+int genpc_grid_range_probe(const void *hdr, int nq, const float *q, const float *radius, const int *clip, int *range,
+                           void *stream);
 
 /* Farthest point sampling --------------------------------------------------- *
  * Deterministic counterpart of fpsample.fps_sampling as the reference uses it

@@ -44,7 +44,7 @@ def test_library_exports_every_declared_symbol():
         assert len(_lib.SIGNATURES[name][1]) == nargs, name
         assert fn is not None
     assert _lib.lib.genpc_abi_version() == _lib.ABI_VERSION
-    assert _lib.ABI_VERSION == 26                  # genpc_nn_plan added
+    assert _lib.ABI_VERSION == 27                  # the grid probes added
 
 
 def test_arith_mode_switch():
