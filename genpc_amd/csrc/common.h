@@ -68,6 +68,7 @@ enum Ws : int {
     kWsPoseLossGradBatch = 40, // pose.hip genpc_pose_loss_grad_batch: accumulators | states | posed clouds | neighbours | mask scratch
     kWsNnSeededStep = 41,     // pose.hip genpc_nn_seeded_step: both clouds' grids of one seeded step (nn_seeded.hip)
     kWsUhdRagged = 42,        // uhd_ragged.hip uhd_ragged: the bits of every query's minimum | per-item records
+    kWsKnnMeanRagged = 43,    // knn.hip knn_ragged: the clouds' grid headers | cell tables | sorted clouds | the means of a filter call that brought no mean_out
 };
 
 // The scratch pool: one grow-only block of device memory per (device, slot, stream); null on failure, the error recorded.

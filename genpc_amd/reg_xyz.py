@@ -401,3 +401,161 @@ def remove_noise_from_point_cloud(xyz, nb_neighbors=20, std_ratio=1.5):
     std = torch.sqrt(((m - mean) ** 2).sum() / (m.numel() - 1))
     keep = m < mean + std_ratio * std
     return xyz[keep], keep
+
+
+# ---------------------------------------------------------------------------
+# The ragged forms: S clouds of any sizes per library call (the batched scan pipeline's fusion tail).
+# ---------------------------------------------------------------------------
+OUTLIER_RAGGED_MAX_CLOUDS = 384          # include/genpc_hip.h: clouds per genpc_knn_mean_distance_ragged / genpc_outlier_filter_ragged call
+
+
+def _ragged_side(clouds, fn, name="clouds"):
+    """A ragged batch as (points [T,3] float32 contiguous, offsets: S + 1 Python ints): a list of [N_j,3] tensors or packed
+    (points, offsets), as pack_clouds of loss_functions/Chamfer3D/dist_chamfer_ragged.py reads them; errors name `fn`."""
+    from .loss_functions.Chamfer3D.dist_chamfer_ragged import _is_offsets, pack_clouds
+    if isinstance(clouds, tuple) and len(clouds) == 2 and torch.is_tensor(clouds[0]) and _is_offsets(clouds[1]):
+        points, off = clouds
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError("%s: packed %s must be [T,3], got %s" % (fn, name, tuple(points.shape)))
+        if torch.is_tensor(off) and off.is_cuda:
+            raise ValueError("%s: the offsets of %s live on the host (a device tensor would have to be read back)" % (fn, name))
+        if points.dtype != torch.float32:
+            raise TypeError("%s: packed %s must be torch.float32, got %s" % (fn, name, points.dtype))
+        return pack_clouds(clouds, name)
+    if not isinstance(clouds, (list, tuple)):
+        raise TypeError("%s: %s is a list of [N,3] tensors or a tuple (points, offsets)" % (fn, name))
+    for j, t in enumerate(clouds):
+        if not torch.is_tensor(t) or t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError("%s: %s[%d] must be an [N,3] tensor" % (fn, name, j))
+        if t.dtype != torch.float32:
+            raise TypeError("%s: %s[%d] must be torch.float32, got %s" % (fn, name, j, t.dtype))
+    return pack_clouds(clouds, name)
+
+
+def _ragged_chunks(off):
+    """(a, b, host offsets of clouds a..b counted from cloud a's first point) per library call."""
+    import ctypes
+    from . import chamfer_3D
+    for a in range(0, len(off) - 1, OUTLIER_RAGGED_MAX_CLOUDS):
+        b = min(a + OUTLIER_RAGGED_MAX_CLOUDS, len(off) - 1)
+        arr, _ = chamfer_3D._host_offsets([v - off[a] for v in off[a:b + 1]], "offsets")
+        yield a, b, ctypes.cast(arr, ctypes.c_void_p)
+
+
+def knn_mean_distance_ragged(clouds, k=20):
+    """``knn_mean_distance`` for S clouds of any sizes: a list of [N_j,3] float32 GPU tensors, or packed as (points [T,3],
+    offsets) with S + 1 host ints.  Returns a list of float32 [N_j] tensors, views of one packed result; cloud j's are the
+    bits of ``knn_mean_distance(clouds[j], k)``.  One library call per 384 clouds (genpc_knn_mean_distance_ragged: two
+    launches each), nothing waits for the result.  An empty cloud gives an empty tensor."""
+    pts, off = _ragged_side(clouds, "knn_mean_distance_ragged")
+    if int(k) not in (8, 16, 20, 32):
+        raise ValueError("knn_mean_distance_ragged: k must be 8, 16, 20 or 32")
+    if len(off) == 1:
+        return []
+    _lib.require_gpu(pts)
+    out = torch.empty(pts.shape[0], device=pts.device)
+    for a, b, arr in _ragged_chunks(off):
+        rc = _lib.on_device_of(pts, _L.genpc_knn_mean_distance_ragged, b - a, arr, _p(pts[off[a]:off[b]]), int(k), _p(out[off[a]:off[b]]))
+        if rc != 1:
+            raise RuntimeError("genpc_knn_mean_distance_ragged failed (%d): %s" % (rc, _lib.last_error()))
+    return [out[off[j]:off[j + 1]] for j in range(len(off) - 1)]
+
+
+def _outlier_filter_ragged(pts, off, nb_neighbors, std_ratio):
+    """keep (bool [T], packed), stats (float64 [S,3]: mean, std, threshold), kept (int32 [S]) of the packed clouds."""
+    s = len(off) - 1
+    keep = torch.empty(pts.shape[0], dtype=torch.uint8, device=pts.device)
+    # (a library call without a point enqueues nothing: its clouds are empty, and these are an empty cloud's words)
+    stats = torch.full((s, 3), float("nan"), dtype=torch.float64, device=pts.device)
+    kept = torch.zeros(s, dtype=torch.int32, device=pts.device)
+    for a, b, arr in _ragged_chunks(off):
+        rc = _lib.on_device_of(pts, _L.genpc_outlier_filter_ragged, b - a, arr, _p(pts[off[a]:off[b]]), int(nb_neighbors), float(std_ratio),
+                               None, _p(stats[a:b]), _p(keep[off[a]:off[b]]), _p(kept[a:b]))
+        if rc != 1:
+            raise RuntimeError("genpc_outlier_filter_ragged failed (%d): %s" % (rc, _lib.last_error()))
+    return keep.view(torch.bool), stats, kept
+
+
+def remove_noise_from_point_clouds(clouds, nb_neighbors=20, std_ratio=1.5, return_stats=False):
+    """``remove_noise_from_point_cloud`` for S clouds of any sizes (a list of [N_j,3] float32 GPU tensors, or packed as
+    (points, offsets)): returns (filtered: list of [K_j,3], keep: list of bool [N_j]); with return_stats also float64 [S,3]
+    = (mean, std, threshold) per cloud and int32 [S] = K_j, both on the device.  One library call per 384 clouds
+    (genpc_outlier_filter_ragged): means, statistics and mask are made on the device, the sums in the order
+    include/genpc_hip.h defines -- not torch's, so a point whose mean lies within rounding of the threshold (a relative 1e-15)
+    may fall on the other side than ``remove_noise_from_point_cloud`` puts it.  The host waits for the K_j, which size the
+    filtered tensors, and in the boolean index over the packed points: twice, whatever S is."""
+    pts, off = _ragged_side(clouds, "remove_noise_from_point_clouds")
+    if int(nb_neighbors) not in (8, 16, 20, 32):
+        raise ValueError("remove_noise_from_point_clouds: nb_neighbors must be 8, 16, 20 or 32")
+    s = len(off) - 1
+    if s == 0 and not pts.is_cuda:             # (an empty list has no device: the current one)
+        pts = pts.to(torch.device("cuda", torch.cuda.current_device()))
+    _lib.require_gpu(pts)
+    keep, stats, kept = _outlier_filter_ragged(pts, off, nb_neighbors, std_ratio)
+    sizes = kept.tolist()
+    filtered = list(torch.split(pts[keep], sizes)) if s else []
+    keeps = [keep[off[j]:off[j + 1]] for j in range(s)]
+    if return_stats:
+        return filtered, keeps, stats, kept
+    return filtered, keeps
+
+
+def fuse_scans(sources, targets, num_points=20000, distance_threshold=0.0001, std_ratio=2.5, source_cols=None, target_cols=None):
+    """``fuse`` for S scans at once: sources / targets are lists of [N_j,3] / [M_j,3] float32 GPU tensors or packed
+    (points, offsets); source_cols / target_cols, when both are given, lists of their colours.  One ``nm_distance_ragged``
+    call makes all the ``remove_close_points`` masks, one ``fps_sampling_multi`` samples the scans that exceed num_points,
+    one ``remove_noise_from_point_clouds`` filters them all (std_ratio None skips it).  Returns a list of fused clouds, or of
+    (fused, col) pairs; scan j's is what ``fuse(sources[j], targets[j], ...)`` returns, up to the caveat of
+    ``remove_noise_from_point_clouds``."""
+    from .fps import fps_sampling_multi
+    from .loss_functions.Chamfer3D.dist_chamfer_ragged import _one_way
+    sp, soff = _ragged_side(sources, "fuse_scans", "sources")
+    tp, toff = _ragged_side(targets, "fuse_scans", "targets")
+    if len(soff) != len(toff):
+        raise ValueError("fuse_scans: %d sources against %d targets" % (len(soff) - 1, len(toff) - 1))
+    s = len(soff) - 1
+    with_col = source_cols is not None and target_cols is not None
+    if with_col and (len(source_cols) != s or len(target_cols) != s):
+        raise ValueError("fuse_scans: one colour tensor per cloud (%d scans, %d source_cols, %d target_cols)" % (s, len(source_cols), len(target_cols)))
+    if s == 0:
+        return []
+    _lib.require_gpu(sp, tp)
+    if sp.device != tp.device:
+        raise ValueError("fuse_scans: sources and targets are on different devices")
+    if with_col:
+        for name, cols, off in (("source_cols", source_cols, soff), ("target_cols", target_cols, toff)):
+            for j, c in enumerate(cols):
+                if not torch.is_tensor(c) or tuple(c.shape) != (off[j + 1] - off[j], 3):
+                    raise ValueError("fuse_scans: %s[%d] must be [%d,3] like its cloud" % (name, j, off[j + 1] - off[j]))
+    # remove_close_points for every scan: the targets ask, the sources answer.  A scan with an empty side keeps its targets.
+    live = [j for j in range(s) if soff[j + 1] > soff[j] and toff[j + 1] > toff[j]]
+    keep_t = torch.ones(tp.shape[0], dtype=torch.bool, device=tp.device)
+    if len(live) == s:
+        d, _ = _one_way(tp, toff, sp, soff)
+        keep_t = ~(d < distance_threshold)
+    elif live:
+        q, qoff = _ragged_side([tp[toff[j]:toff[j + 1]] for j in live], "fuse_scans", "targets")
+        t, t_off = _ragged_side([sp[soff[j]:soff[j + 1]] for j in live], "fuse_scans", "sources")
+        d, _ = _one_way(q, qoff, t, t_off)
+        for i, j in enumerate(live):
+            keep_t[toff[j]:toff[j + 1]] = ~(d[qoff[i]:qoff[i + 1]] < distance_threshold)
+    bounds = torch.tensor(toff, device=tp.device)
+    csum = torch.cat([keep_t.new_zeros(1, dtype=torch.int64), torch.cumsum(keep_t, 0)])
+    sizes = (csum[bounds[1:]] - csum[bounds[:-1]]).tolist()                  # (the one host read of this step)
+    filtered = torch.split(tp[keep_t], sizes)
+    fused = [torch.cat([sp[soff[j]:soff[j + 1]], filtered[j]], dim=0) for j in range(s)]
+    cols = None
+    if with_col:
+        cols = [torch.cat([source_cols[j].float(), target_cols[j].float()[keep_t[toff[j]:toff[j + 1]]]], dim=0) for j in range(s)]
+    big = [j for j in range(s) if fused[j].shape[0] > num_points]
+    if big:
+        for j, idx in zip(big, fps_sampling_multi([fused[j] for j in big], [num_points] * len(big))):
+            idx = idx.long()
+            fused[j] = fused[j][idx]
+            if with_col:
+                cols[j] = cols[j][idx]
+    if std_ratio is not None:
+        fused, oks = remove_noise_from_point_clouds(fused, std_ratio=std_ratio)
+        if with_col:
+            cols = [cols[j][oks[j]] for j in range(s)]
+    return [(fused[j], cols[j]) for j in range(s)] if with_col else list(fused)

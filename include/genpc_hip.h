@@ -36,7 +36,9 @@ extern "C" {
 int genpc_abi_version(void);              /* bumps when a signature or a documented behaviour changes (27: genpc_grid_*_probe added; 26: genpc_nn_plan added; 25: genpc_nn_seeded_step added; 24: genpc_icp_plan added; 23: genpc_pose_loss_grad_batch added; 22: genpc_chamfer_backward_ragged added; 21: genpc_nm_distance_ragged added; 20: genpc_mesh_sample added; 19: genpc_uhd added; 18: genpc_knn_query added;
                                            * 17: genpc_fps_tune takes 0 or 256 only; 16: genpc_hpr_* asynchronous, counts -1 on an internal error;
                                            * genpc_fps*: out_idx[0] -2 = failed the check).
-                                           * genpc_uhd_ragged came without a bump. */
+                                           * genpc_uhd_ragged came without a bump.  From 27 on an addition that changes no existing signature and no
+                                           * documented behaviour no longer bumps the number: genpc_knn_mean_distance_ragged and
+                                           * genpc_outlier_filter_ragged came that way; a missing symbol is found when the binding loads. */
 const char *genpc_last_error(void);       /* last HIP error string, "" if none */
 int genpc_set_arith(int mode);            /* process default; returns the previous one */
 int genpc_set_arith_thread(int mode);     /* calling thread only, < 0: follow the default; returns the previous override */
@@ -591,6 +593,40 @@ int genpc_fps_stats(int c, int *rounds, void *stream);
  * it has without those points.                                                   */
 int genpc_knn_mean_distance(int n, const float *xyz, int k, float *mean_out,
                             void *stream);
+
+/* Ragged form: c clouds of any sizes in one call.  Cloud j is xyz[off[j] .. off[j+1]); off: a HOST array of c + 1 ascending
+ * ints, off[0] = 0, copied before the call returns (it travels in the kernel arguments); xyz [off[c],3]: fp32, device, packed
+ * in cloud order; k in {8, 16, 20, 32}.  mean_out[off[j] + i] holds the bits of genpc_knn_mean_distance(n_j, xyz + 3 off[j],
+ * k, ..)[i] on cloud j alone, in the call's arithmetic mode, NaN for NaN; a non-finite coordinate affects its own cloud only.
+ * An empty cloud is allowed and gets no work and no word of mean_out.
+ * Asynchronous on `stream`: two launches whatever c is (the ragged grid build, the search), scratch from the library's
+ * workspace, no copy, no host read-back, no synchronisation (csrc/knn.hip).  Returns 1 on success; -1 with genpc_last_error
+ * set, nothing enqueued and nothing written for c < 0, c > 384, a null off, off[0] != 0, descending offsets,
+ * off[c] > 2^28, a k outside the set, or (when there is work) a null xyz or mean_out; 1 at once with nothing enqueued
+ * if c == 0 or off[c] == 0.                                                                                            */
+int genpc_knn_mean_distance_ragged(int c, const int *off, const float *xyz, int k, float *mean_out,
+                                   void *stream);
+
+/* The whole statistical outlier filter for c clouds in one call (open3d's remove_statistical_outlier per cloud): clouds, off
+ * and k as above.  With m_i = (double) of cloud j's i-th mean and n its point count, every operation a separately rounded
+ * fp64 operation and NOTHING fused:
+ *   S(v)   the sum of n fp64 values in this order and no other: 1024 partial sums p[t], each starting at +0.0; p[t] adds
+ *          the elements i = t, t + 1024, t + 2048, ... in ascending i; then for w = 512, 256, ..., 1: p[t] = p[t] + p[t + w]
+ *          for t < w; S = p[0].  A function of n alone: not of c, of the cloud's place in the batch or of the launch shape;
+ *          no floating-point atomic.
+ *   mean = S(m) / n;   std = sqrt(S((m_i - mean) * (m_i - mean)) / (n - 1));   thr = mean + std_ratio * std
+ *   keep[off[j] + i] = m_i < thr ? 1 : 0;   kept[j] = the number of ones;   stats[j] = (mean, std, thr)
+ * So a one-point cloud has std = 0 / 0 = NaN and keeps nothing, a cloud with a NaN mean keeps nothing, and an empty cloud
+ * gets stats (NaN, NaN, NaN) and kept 0.  mean_out [off[c]] (fp32; null: the means stay in the workspace), stats [c,3]
+ * (fp64) and kept [c] (int32) may be null; keep [off[c]] (bytes) is required.  Every word of keep, stats and kept that belongs
+ * to the call is written.
+ * Asynchronous on `stream`: three launches whatever c is (the ragged grid build, the search, one workgroup per cloud for the
+ * statistics and the mask; no kernel spins or waits on another workgroup), scratch from the library's workspace, no copy,
+ * no host read-back, no synchronisation (csrc/knn.hip).  Returns as genpc_knn_mean_distance_ragged does; the null pointers
+ * refused are xyz and keep.                                                                                             */
+int genpc_outlier_filter_ragged(int c, const int *off, const float *xyz, int k, double std_ratio,
+                                float *mean_out, double *stats, unsigned char *keep, int *kept,
+                                void *stream);
 
 /* k nearest neighbours ------------------------------------------------------- *
  * For every query of xyz[B,NQ,3] its k nearest targets of xyz2[B,NT,3], 1 <= k <= 32: dist[B,NQ,k] (squared distances)
