@@ -90,6 +90,7 @@ SIGNATURES = {
     "genpc_knn_mean_distance_ragged": (_i, [_i, _vp, _vp, _i, _vp, _vp]),
     "genpc_outlier_filter_ragged": (_i, [_i, _vp, _vp, _i, _d, _vp, _vp, _vp, _vp, _vp]),
     "genpc_knn_query": (_i, [_i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "genpc_knn_query_ragged": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "genpc_uhd": (_i, [_i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "genpc_uhd_ragged": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "genpc_mesh_sample_bytes": (_i, [_i]),

@@ -69,6 +69,7 @@ enum Ws : int {
     kWsNnSeededStep = 41,     // pose.hip genpc_nn_seeded_step: both clouds' grids of one seeded step (nn_seeded.hip)
     kWsUhdRagged = 42,        // uhd_ragged.hip uhd_ragged: the bits of every query's minimum | per-item records
     kWsKnnMeanRagged = 43,    // knn.hip knn_ragged: the clouds' grid headers | cell tables | sorted clouds | the means of a filter call that brought no mean_out
+    kWsKnnQueryRagged = 44,   // knn_query.hip knn_query_ragged: the pairs' grid headers | cell tables | sorted targets | query order
 };
 
 // The scratch pool: one grow-only block of device memory per (device, slot, stream); null on failure, the error recorded.

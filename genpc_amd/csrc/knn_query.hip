@@ -17,7 +17,17 @@
 //     Only candidates with d < +inf are listed (NaN and infinite distances never enter); slots past the listed ones hold
 //     (+inf, -1).  A target cloud with a non-finite coordinate (CellGridHdr.bad) is searched without culling.
 // One path for every size: a tiny or degenerate cloud is a one-cell grid.
+//
+// The ragged form (genpc_knn_query_ragged): c (queries, targets) pairs of any sizes, packed, one call, three launches.
+//   * grid.hip's ragged build sorts every pair's targets into a grid of their own (ragged_table.h).  Its cells are sized for
+//     k <= 5 whatever k is; the search is exact on any grid, so a pair's rows are the bits of genpc_knn_query on it alone.
+//   * knn_query_order_ragged_kernel: one workgroup per pair, the same counting sort (knn_query_order_of, one body for both
+//     kernels); order[qoff[j] + .] holds query ids inside pair j.
+//   * knn_query_ragged_kernel: the same search (knn_query_of, one body for both kernels).  A workgroup serves up to 256 sorted
+//     queries of ONE pair: blockIdx.x is a work item of ragged_items.h's numbering with shift 8, the pair comes from a binary
+//     search of the table in the kernel arguments (uniform: scalar loads).
 #include "nn.h"
+#include "ragged_items.h"
 #include "../../include/genpc_hip.h"
 
 namespace genpc {
@@ -36,17 +46,12 @@ struct KnnQueryArgs {
     int nq, nt, k, cells_max, qblocks;
 };
 
-// order[batch][.] = the query ids of a batch element sorted by their cell in the element's target grid (a counting sort in LDS;
-// the order inside a cell is whatever the atomics give: every query writes its own results, so it reaches none of them)
-__global__ __launch_bounds__(kKQOBlock) void knn_query_order_kernel(int nq, const float *__restrict__ q, const CellGridHdr *__restrict__ hdr,
-                                                                    int *__restrict__ order, int cells_max)
+// THE ordering of one cloud's queries (knn_query_order_kernel, knn_query_order_ragged_kernel): O[.] = the ids of the nq
+// queries Q sorted by their cell in the target grid H (a counting sort in LDS; the order inside a cell is whatever the atomics
+// give: every query writes its own results, so it reaches none of them).  The whole workgroup calls it.
+__device__ __forceinline__ void knn_query_order_of(int nq, const float *__restrict__ Q, const CellGridHdr &H, int *__restrict__ O, int *s_cnt,
+                                                   int *s_w)
 {
-    extern __shared__ int s_cnt[];            // cells_max counters, then 2 ints per wave
-    int *s_w = s_cnt + cells_max;
-    const int batch = blockIdx.x;
-    const CellGridHdr H = hdr[batch];
-    const float *__restrict__ Q = q + (size_t)batch * nq * 3;
-    int *__restrict__ O = order + (size_t)batch * nq;
     for (int i = threadIdx.x; i < H.cells; i += kKQOBlock) s_cnt[i] = 0;
     __syncthreads();
     auto cell_of = [&](int j) {
@@ -60,21 +65,25 @@ __global__ __launch_bounds__(kKQOBlock) void knn_query_order_kernel(int nq, cons
     for (int j = threadIdx.x; j < nq; j += kKQOBlock) O[atomicAdd(&s_cnt[cell_of(j)], 1)] = j;
 }
 
-template <int CAP, int FMA>
-__global__ __launch_bounds__(kBlock) void knn_query_kernel(KnnQueryArgs a)
+// order[batch][.] = the query ids of a batch element sorted by their cell in the element's target grid
+__global__ __launch_bounds__(kKQOBlock) void knn_query_order_kernel(int nq, const float *__restrict__ q, const CellGridHdr *__restrict__ hdr,
+                                                                    int *__restrict__ order, int cells_max)
 {
-    const int batch = blockIdx.x / a.qblocks, pos = (blockIdx.x - batch * a.qblocks) * kBlock + threadIdx.x;
-    if (pos >= a.nq) return;
-    const int j = a.order[(size_t)batch * a.nq + pos];
-    const float *qp = a.q + ((size_t)batch * a.nq + j) * 3;
-    const float qx = qp[0], qy = qp[1], qz = qp[2];
-    const float4 *__restrict__ S = a.sorted + (size_t)batch * a.nt;
-    const int *__restrict__ ST = a.start + (size_t)batch * (a.cells_max + 1);
-    const CellGridHdr H = a.hdr[batch];
+    extern __shared__ int s_cnt[];            // cells_max counters, then 2 ints per wave
+    const int batch = blockIdx.x;
+    const CellGridHdr H = hdr[batch];
+    knn_query_order_of(nq, q + (size_t)batch * nq * 3, H, order + (size_t)batch * nq, s_cnt, s_cnt + cells_max);
+}
 
+// THE search of one query (knn_query_kernel, knn_query_ragged_kernel): the target cloud's grid (H, its cell table ST, its sorted
+// points S), the query and the k slots od / oi of its results.
+template <int CAP, int FMA>
+__device__ __forceinline__ void knn_query_of(const CellGridHdr &H, const float4 *__restrict__ S, const int *__restrict__ ST, const float qx,
+                                             const float qy, const float qz, const int k, float *__restrict__ od, int *__restrict__ oi)
+{
     unsigned long long L[CAP];           // ascending; L[0 .. CAP - k) pinned to 0, L[CAP - 1] is the k-th best
 #pragma unroll
-    for (int i = 0; i < CAP; i++) L[i] = i < CAP - a.k ? 0ull : kKQEmpty;
+    for (int i = 0; i < CAP; i++) L[i] = i < CAP - k ? 0ull : kKQEmpty;
     auto kth = [&]() { return __uint_as_float((unsigned)(L[CAP - 1] >> 32)); };      // +inf while fewer than k are listed
     auto run = [&](int p0, int p1) {     // the targets at positions [p0, p1) of the sorted cloud
         for (int p = p0; p < p1; p++) {
@@ -94,9 +103,7 @@ __global__ __launch_bounds__(kBlock) void knn_query_kernel(KnnQueryArgs a)
     };
 
     cell_grid_shell_walk(H, ST, qx, qy, qz, kth, run);
-    float *od = a.out_d + ((size_t)batch * a.nq + j) * a.k;
-    int *oi = a.out_i + ((size_t)batch * a.nq + j) * a.k;
-    const int skip = CAP - a.k;
+    const int skip = CAP - k;
 #pragma unroll
     for (int i = 0; i < CAP; i++) {
         if (i >= skip) {
@@ -104,6 +111,20 @@ __global__ __launch_bounds__(kBlock) void knn_query_kernel(KnnQueryArgs a)
             oi[i - skip] = (int)(unsigned)L[i];
         }
     }
+}
+
+template <int CAP, int FMA>
+__global__ __launch_bounds__(kBlock) void knn_query_kernel(KnnQueryArgs a)
+{
+    const int batch = blockIdx.x / a.qblocks, pos = (blockIdx.x - batch * a.qblocks) * kBlock + threadIdx.x;
+    if (pos >= a.nq) return;
+    const int j = a.order[(size_t)batch * a.nq + pos];
+    const float *qp = a.q + ((size_t)batch * a.nq + j) * 3;
+    const float qx = qp[0], qy = qp[1], qz = qp[2];
+    const float4 *__restrict__ S = a.sorted + (size_t)batch * a.nt;
+    const int *__restrict__ ST = a.start + (size_t)batch * (a.cells_max + 1);
+    const CellGridHdr H = a.hdr[batch];
+    knn_query_of<CAP, FMA>(H, S, ST, qx, qy, qz, a.k, a.out_d + ((size_t)batch * a.nq + j) * a.k, a.out_i + ((size_t)batch * a.nq + j) * a.k);
 }
 
 template <int CAP>
@@ -144,6 +165,104 @@ static int knn_query(int b, int nq, const float *xyz, int nt, const float *xyz2,
     return check(hipGetLastError(), "knn_query_kernel launch") ? 1 : 0;
 }
 
+// ---- the ragged form ----
+constexpr int kKQRShift = 8;                      // a work item: kBlock sorted queries of one pair
+static_assert((1 << kKQRShift) == kBlock, "a work item is what a workgroup of the search owns");
+
+struct KnnQueryRaggedArgs {
+    RaggedTable t;
+    const float *q;                // packed queries
+    const float4 *sorted;          // packed, every pair's targets in their own cell order: (x, y, z, index inside the pair's cloud)
+    const int *start;              // pair j's cell table at toff[j] + 65 j
+    const CellGridHdr *hdr;        // [c]
+    const int *order;              // packed like the queries: query ids INSIDE the pair, by cell of the pair's target grid
+    float *out_d;                  // [queries][k], packed like the queries
+    int *out_i;
+    int k;
+};
+static_assert(sizeof(KnnQueryRaggedArgs) <= 4096, "the pair table must fit the kernel arguments");
+
+// one workgroup per pair
+__global__ __launch_bounds__(kKQOBlock) void knn_query_order_ragged_kernel(RaggedTable t, const float *__restrict__ q,
+                                                                           const CellGridHdr *__restrict__ hdr, int *__restrict__ order,
+                                                                           int lds_cells)
+{
+    extern __shared__ int s_cnt[];            // lds_cells counters, then 2 ints per wave
+    const int pair = blockIdx.x;
+    const int q0 = t.qoff[pair], nq = t.qoff[pair + 1] - q0;
+    if (nq == 0) return;                      // nobody asks: no grid was built (the whole block leaves: no barrier is left waiting)
+    const CellGridHdr H = hdr[pair];
+    knn_query_order_of(nq, q + (size_t)q0 * 3, H, order + q0, s_cnt, s_cnt + lds_cells);
+}
+
+template <int CAP, int FMA>
+__global__ __launch_bounds__(kBlock) void knn_query_ragged_kernel(KnnQueryRaggedArgs a)
+{
+    const int item = blockIdx.x;
+    const int pair = ragged_pair_of_shift(a.t, item, kKQRShift);
+    const int q0 = a.t.qoff[pair], nq = a.t.qoff[pair + 1] - q0, t0 = a.t.toff[pair];
+    const long long pos = ragged_item_base_shift(a.t, pair, item, kKQRShift) + threadIdx.x;
+    if (pos >= nq) return;
+    const int j = a.order[(size_t)q0 + pos];
+    const float *qp = a.q + ((size_t)q0 + j) * 3;
+    const float qx = qp[0], qy = qp[1], qz = qp[2];
+    const float4 *__restrict__ S = a.sorted + t0;
+    const int *__restrict__ ST = a.start + ((size_t)t0 + (size_t)kRaggedStartPad * pair);
+    const CellGridHdr H = a.hdr[pair];
+    knn_query_of<CAP, FMA>(H, S, ST, qx, qy, qz, a.k, a.out_d + ((size_t)q0 + j) * a.k, a.out_i + ((size_t)q0 + j) * a.k);
+}
+
+template <int CAP>
+static void launch_knn_query_ragged_cap(const KnnQueryRaggedArgs &a, unsigned grid, int fma, hipStream_t st)
+{
+    if (fma) hipLaunchKernelGGL((knn_query_ragged_kernel<CAP, 1>), dim3(grid), dim3(kBlock), 0, st, a);
+    else hipLaunchKernelGGL((knn_query_ragged_kernel<CAP, 0>), dim3(grid), dim3(kBlock), 0, st, a);
+}
+
+static int knn_query_ragged(int c, const int *noff, const int *moff, const float *xyz, const float *xyz2, int k, float *dist, int *idx,
+                            hipStream_t st)
+{
+    char msg[160];
+    if (k < 1 || k > 32) {
+        set_error("genpc_knn_query_ragged: k must be 1 .. 32");
+        return -1;
+    }
+    KnnQueryRaggedArgs a{};
+    int max_targets = 0;
+    const char *err = nullptr;
+    const int rc = ragged_table_fill(c, noff, moff, a.t, &max_targets, &err);
+    if (rc < 0) {
+        snprintf(msg, sizeof msg, "genpc_knn_query_ragged: %s", err);
+        set_error(msg);
+        return -1;
+    }
+    if (rc == 0) return 1;
+    if (!xyz || !xyz2 || !dist || !idx) {
+        set_error("genpc_knn_query_ragged: null pointer");
+        return -1;
+    }
+    const int fma = arith_mode() != 0;
+    const int queries = a.t.qoff[c], targets = a.t.toff[c];
+    a.q = xyz; a.out_d = dist; a.out_i = idx; a.k = k;
+    WsLayout L;
+    L.add(a.hdr, c);
+    L.add(a.start, (size_t)ragged_start_len(targets, c));
+    L.add(a.sorted, (size_t)targets);
+    L.add(a.order, (size_t)queries);
+    if (!ws_alloc(L, kWsKnnQueryRagged, st)) return 0;
+    if (!launch_cell_grid_build_ragged(a.t, max_targets, xyz2, (CellGridHdr *)a.hdr, (int *)a.start, (float4 *)a.sorted, st)) return 0;
+    const int lds_cells = ragged_cells_max(max_targets);       // every built grid has at most this many cells
+    const size_t lds = ((size_t)lds_cells + 2 * (kKQOBlock / kWave)) * sizeof(int);
+    hipLaunchKernelGGL(knn_query_order_ragged_kernel, dim3(c), dim3(kKQOBlock), lds, st, a.t, xyz, a.hdr, (int *)a.order, lds_cells);
+    if (!check(hipGetLastError(), "knn_query_order_ragged_kernel launch")) return 0;
+    const unsigned grid = (unsigned)ragged_items_shift(queries, c, kKQRShift);
+    if (k <= 4) launch_knn_query_ragged_cap<4>(a, grid, fma, st);
+    else if (k <= 8) launch_knn_query_ragged_cap<8>(a, grid, fma, st);
+    else if (k <= 16) launch_knn_query_ragged_cap<16>(a, grid, fma, st);
+    else launch_knn_query_ragged_cap<32>(a, grid, fma, st);
+    return check(hipGetLastError(), "knn_query_ragged_kernel launch") ? 1 : 0;
+}
+
 }  // namespace genpc
 
 GENPC_API int genpc_knn_query(int b, int nq, const float *xyz, int nt, const float *xyz2, int k, float *dist, int *idx, void *stream)
@@ -163,4 +282,10 @@ GENPC_API int genpc_knn_query(int b, int nq, const float *xyz, int nt, const flo
         return -1;
     }
     return knn_query(b, nq, xyz, nt, xyz2, k, dist, idx, (hipStream_t)stream);
+}
+
+GENPC_API int genpc_knn_query_ragged(int c, const int *noff, const float *xyz, const int *moff, const float *xyz2, int k, float *dist, int *idx,
+                                     void *stream)
+{
+    return genpc::knn_query_ragged(c, noff, moff, xyz, xyz2, k, dist, idx, (hipStream_t)stream);
 }

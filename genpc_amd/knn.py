@@ -41,3 +41,44 @@ def knn_query(queries, targets, k):
     if rc != 1:
         raise RuntimeError("genpc_knn_query failed (%d): %s" % (rc, _lib.last_error()))
     return (dist[0], idx[0]) if single else (dist, idx)
+
+
+def knn_query_ragged(queries, targets, k):
+    """``knn_query`` for S (queries, targets) pairs of any sizes.  Each side is a list of [N_j,3] float32 GPU tensors, or
+    packed as (points [T,3], offsets) with S + 1 host ints (read as ``reg_xyz.knn_mean_distance_ragged`` reads its clouds).
+    Returns a list of S pairs ``(dist2 [N_j,k], idx [N_j,k])``, views of one packed result -- float32 squared distances and
+    int32 indices INSIDE pair j's own targets; pair j's are the bits of ``knn_query(queries[j], targets[j], k)``.  When the
+    QUERIES came packed the return value is ``(pairs, (dist2 [T,k], idx [T,k]))``: the same list and the packed result
+    it views, rows in the order of the packed queries.
+
+    One library call per 384 pairs (genpc_knn_query_ragged: three launches each), nothing waits for the result.  A pair
+    without queries gives empty tensors and may have no targets; a pair with queries and no targets is an error.  ``[]``
+    against ``[]`` gives ``[]``."""
+    from .loss_functions.Chamfer3D.dist_chamfer_ragged import _is_offsets
+    from .reg_xyz import _ragged_chunks, _ragged_side
+    k = int(k)
+    if k < 1 or k > MAX_K:
+        raise ValueError("knn_query_ragged: k must be 1 .. %d, got %d" % (MAX_K, k))
+    packed = isinstance(queries, tuple) and len(queries) == 2 and torch.is_tensor(queries[0]) and _is_offsets(queries[1])
+    q, qoff = _ragged_side(queries, "knn_query_ragged", "queries")
+    t, toff = _ragged_side(targets, "knn_query_ragged", "targets")
+    if len(qoff) != len(toff):
+        raise ValueError("knn_query_ragged: %d queries against %d targets" % (len(qoff) - 1, len(toff) - 1))
+    s = len(qoff) - 1
+    for j in range(s):
+        if qoff[j + 1] > qoff[j] and toff[j + 1] == toff[j]:
+            raise ValueError("knn_query_ragged: pair %d has %d queries and no targets" % (j, qoff[j + 1] - qoff[j]))
+    if s == 0:                                 # (no pair: nothing to ask the library)
+        return ([], (q.new_empty((0, k)), q.new_empty((0, k), dtype=torch.int32))) if packed else []
+    _lib.require_gpu(q, t)
+    if q.device != t.device:
+        raise ValueError("knn_query_ragged: queries and targets are on different devices")
+    dist = torch.empty((q.shape[0], k), dtype=torch.float32, device=q.device)
+    idx = torch.empty((q.shape[0], k), dtype=torch.int32, device=q.device)
+    for (a, b, narr), (_, _, marr) in zip(_ragged_chunks(qoff), _ragged_chunks(toff)):
+        rc = _lib.on_device_of(q, _L.genpc_knn_query_ragged, b - a, narr, _p(q[qoff[a]:qoff[b]]), marr, _p(t[toff[a]:toff[b]]), k,
+                               _p(dist[qoff[a]:qoff[b]]), _p(idx[qoff[a]:qoff[b]]))
+        if rc != 1:
+            raise RuntimeError("genpc_knn_query_ragged failed (%d): %s" % (rc, _lib.last_error()))
+    pairs = [(dist[qoff[j]:qoff[j + 1]], idx[qoff[j]:qoff[j + 1]]) for j in range(s)]
+    return (pairs, (dist, idx)) if packed else pairs

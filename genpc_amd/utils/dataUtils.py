@@ -235,6 +235,54 @@ def linear_interpolation(points, new_points, k=2):
     return (near * weights[:, :, None]).sum(dim=1)
 
 
+def linear_interpolation_clouds(clouds, new_points, k=2):
+    """``linear_interpolation`` for S scans at once: clouds[j] [M_j,3] and new_points[j] [N_j,3], lists of GPU tensors.  One
+    ``knn.knn_query_ragged`` names every scan's neighbours (indices inside the scan, plus the scan's offset: rows of the
+    packed clouds), then the reference's float64 lines run once on the packed gather.  Returns a list of float64 GPU tensors
+    [N_j,3]; scan j's is what ``linear_interpolation(clouds[j], new_points[j], k)`` returns for GPU tensors."""
+    import torch
+    from ..knn import knn_query_ragged
+    if not isinstance(clouds, (list, tuple)) or not isinstance(new_points, (list, tuple)):
+        raise TypeError("linear_interpolation_clouds: clouds and new_points are lists of [N,3] tensors")
+    if len(clouds) != len(new_points):
+        raise ValueError("linear_interpolation_clouds: %d clouds against %d sets of new points" % (len(clouds), len(new_points)))
+    for name, side in (("clouds", clouds), ("new_points", new_points)):
+        for j, t in enumerate(side):
+            if not torch.is_tensor(t) or t.dim() != 2 or t.shape[1] != 3:
+                raise ValueError("linear_interpolation_clouds: %s[%d] must be an [N,3] tensor" % (name, j))
+    for name, side in (("clouds", clouds), ("new_points", new_points)):
+        for j, t in enumerate(side):
+            if not t.is_cuda:
+                raise RuntimeError("genpc_amd: GPU tensors only (got a %s tensor for %s[%d]); the HIP path has no CPU fallback"
+                                   % (t.device, name, j))
+    for j, t in enumerate(clouds):
+        if t.shape[0] < k:
+            raise ValueError("linear_interpolation_clouds: k = %d neighbours of cloud %d of %d points" % (k, j, t.shape[0]))
+    if len(clouds) == 0:
+        return []
+    sizes = [t.shape[0] for t in new_points]
+    noff, moff = [0], [0]
+    for q, t in zip(new_points, clouds):
+        noff.append(noff[-1] + q.shape[0])
+        moff.append(moff[-1] + t.shape[0])
+    p64 = torch.cat([t.double() for t in clouds], dim=0)
+    q64 = torch.cat([t.double() for t in new_points], dim=0)
+    _, (_, idx) = knn_query_ragged((q64.float(), noff), (p64.float(), moff), k)      # idx [T,k], packed like the queries
+    missing = (idx < 0).any(dim=1)
+    if bool(missing.any()):
+        row = int(torch.nonzero(missing)[0, 0])
+        import bisect
+        pair = bisect.bisect_right(noff, row) - 1
+        raise ValueError("linear_interpolation_clouds: pair %d has a point without k neighbours at a finite distance "
+                         "(non-finite input)" % pair)
+    base = torch.repeat_interleave(torch.tensor(moff[:-1], device=idx.device), torch.tensor(sizes, device=idx.device), output_size=sum(sizes))
+    near = p64[idx.long() + base[:, None]]                             # [T, k, 3]
+    distances = ((near - q64[:, None, :]) ** 2).sum(dim=2).sqrt()
+    weights = 1 / (distances + 1e-8)
+    weights = weights / weights.sum(dim=1)[:, None]
+    return list(torch.split((near * weights[:, :, None]).sum(dim=1), sizes))
+
+
 def xyz2xyzrgb(partial_path, add_point_type='random', add_num_points=5000):
     """utils/dataUtils.py:137-155: the partial scan of a PLY file densified ('random': random_add_points; 'linear':
     add_num_points box samples interpolated with k = 5; anything else: as it is), with the reference's

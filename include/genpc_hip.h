@@ -38,7 +38,8 @@ int genpc_abi_version(void);              /* bumps when a signature or a documen
                                            * genpc_fps*: out_idx[0] -2 = failed the check).
                                            * genpc_uhd_ragged came without a bump.  From 27 on an addition that changes no existing signature and no
                                            * documented behaviour no longer bumps the number: genpc_knn_mean_distance_ragged and
-                                           * genpc_outlier_filter_ragged came that way; a missing symbol is found when the binding loads. */
+                                           * genpc_outlier_filter_ragged came that way, and so did genpc_knn_query_ragged (additive: the number
+                                           * stays 27); a missing symbol is found when the binding loads. */
 const char *genpc_last_error(void);       /* last HIP error string, "" if none */
 int genpc_set_arith(int mode);            /* process default; returns the previous one */
 int genpc_set_arith_thread(int mode);     /* calling thread only, < 0: follow the default; returns the previous override */
@@ -640,6 +641,27 @@ int genpc_outlier_filter_ragged(int c, const int *off, const float *xyz, int k, 
  * NT < 1 with NQ > 0; 1 at once for NQ == 0 or B == 0.                                                                */
 int genpc_knn_query(int b, int nq, const float *xyz, int nt, const float *xyz2, int k,
                     float *dist, int *idx, void *stream);
+
+/* Ragged form: c independent (queries, targets) pairs of any sizes in one call.  Pair j has the queries xyz[noff[j] .. noff[j+1])
+ * and the targets xyz2[moff[j] .. moff[j+1]); noff, moff: HOST arrays of c + 1 ascending ints, noff[0] = moff[0] = 0, copied
+ * before the call returns (the table travels in the kernel arguments); xyz [noff[c],3], xyz2 [moff[c],3]: fp32, device, packed
+ * in pair order (as for genpc_nm_distance_ragged); 1 <= k <= 32.  dist [noff[c],k] (fp32 squared distances) and idx [noff[c],k]
+ * (int32, counted INSIDE the pair's own target cloud) are packed in pair order: pair j's rows are bit for bit what
+ * genpc_knn_query(1, N_j, xyz + 3 noff[j], M_j, xyz2 + 3 moff[j], k, ..) returns for that pair alone, in the call's arithmetic
+ * mode -- the same key order distance bits << 32 | index, the same rule for the k-th place, the same non-finite rules: only
+ * targets at d < +inf are listed, the slots past them hold (+inf, -1), a target cloud with a non-finite coordinate is searched
+ * without culling.  M_j < k is legal and fills the tail with (+inf, -1).  A pair's non-finite input affects that pair only.
+ * Every output word that belongs to a pair with queries is written; a pair with N_j == 0 writes nothing and its targets, if
+ * any, are not looked at.  The result does not depend on where a pair stands in the call or on the other pairs: every pair's
+ * targets get a grid of their own, sized otherwise than the single call's, and the search is exact on any grid.
+ * Asynchronous on `stream`: three launches whatever c is (the ragged grid build, one workgroup per pair ordering its queries,
+ * the search; no kernel spins or waits on another workgroup), scratch from the library's workspace, no copy, no host
+ * read-back, no synchronisation (csrc/knn_query.hip).  Returns 1 on success; 1 at once with nothing enqueued if c == 0 or
+ * noff[c] == 0 (after the offsets have been checked); -1 with genpc_last_error set, nothing enqueued and nothing written for
+ * k < 1, k > 32, c < 0, c > 384, a null table, offsets that do not start at 0 or descend, more than 2^28 points on a side, a
+ * pair with queries and no targets, or (when there is work) a null xyz, xyz2, dist or idx; 0 on a HIP error.             */
+int genpc_knn_query_ragged(int c, const int *noff, const float *xyz, const int *moff, const float *xyz2, int k,
+                           float *dist, int *idx, void *stream);
 
 /* Directed Hausdorff distance (UHD) ------------------------------------------ *
  * From the queries xyz[B,N,3] to the targets xyz2[B,M,3] (fp32, device), exact in fp64: the coordinates are widened and
