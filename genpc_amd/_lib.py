@@ -47,6 +47,8 @@ SIGNATURES = {
     "genpc_emd_contended": (_i, []),
     "genpc_emd_calc_dist": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
     "genpc_emd_backward": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "genpc_emd_forward_ragged": (_i, [_i, _vp] + [_vp] * 10 + [_f, _i, _vp]),
+    "genpc_emd_backward_ragged": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "genpc_get_uvs": (_i, [_i, _i, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp]),
     "genpc_uv_to_pixels": (_i, [_i, _vp, _f, _i, _vp, _vp]),
     "genpc_paint_pixels": (_i, [_i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),

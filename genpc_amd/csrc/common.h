@@ -70,6 +70,7 @@ enum Ws : int {
     kWsUhdRagged = 42,        // uhd_ragged.hip uhd_ragged: the bits of every query's minimum | per-item records
     kWsKnnMeanRagged = 43,    // knn.hip knn_ragged: the clouds' grid headers | cell tables | sorted clouds | the means of a filter call that brought no mean_out
     kWsKnnQueryRagged = 44,   // knn_query.hip knn_query_ragged: the pairs' grid headers | cell tables | sorted targets | query order
+    kWsEmdRagged = 45,        // emd_ragged.hip genpc_emd_forward_ragged: two bidder lists | filter seeds | two counts per pair
 };
 
 // The scratch pool: one grow-only block of device memory per (device, slot, stream); null on failure, the error recorded.

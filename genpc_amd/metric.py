@@ -29,6 +29,10 @@ float64 bits per pair; ``score_uhd_folders`` reads two folders of PLY files unde
 at once.
 
     python -m genpc_amd.metric --uhd-dirs PARTIAL_DIR COMPLETE_DIR
+
+``evaluate_scans_ragged`` is ``evaluate_scans`` -- CD-L1, CD-L2 and EMD -- for S scans of different sizes, scan j with the
+same N_j points (a multiple of 256) on both sides: ``evaluate_clouds``' two columns plus one ragged auction call
+(csrc/emd_ragged.hip) for all scans.
 """
 import argparse
 import ctypes
@@ -71,6 +75,27 @@ def evaluate_clouds(preds, gts):
     a1, a2 = seg_means(d1, off1)
     b1, b2 = seg_means(d2, off2)
     return torch.stack([(a1 + b1) / 2, a2 + b2], dim=1)
+
+
+def evaluate_scans_ragged(preds, gts, eps=0.005, iters=50):
+    """``evaluate_scans`` for S scans of different sizes: preds, gts as ``evaluate_clouds`` takes them, scan j with N_j points
+    on BOTH sides, N_j % 256 == 0 (the auction's rule).  Returns float64 [S,3] on the device: columns 0-1 are
+    ``evaluate_clouds``'s CD-L1 and CD-L2, column 2 the EMD of ``evaluate_scans`` (eps, iters) from ONE ragged auction call
+    (csrc/emd_ragged.hip) -- the float64 mean of the float64 square roots of the scan's fp32 dist.  Forward only."""
+    from .loss_functions.Chamfer3D.dist_chamfer_ragged import pack_clouds
+    from .loss_functions.emd.emd_ragged import check_pairs, forward_packed
+    p1, off1 = pack_clouds(preds, "preds")
+    p2, off2 = pack_clouds(gts, "gts")
+    check_pairs(off1, off2, "evaluate_scans_ragged")
+    _lib.require_gpu(p1, p2)
+    cd = evaluate_clouds((p1, off1), (p2, off2))
+    s = len(off1) - 1
+    with torch.no_grad():
+        dist = forward_packed(p1.detach(), p2.detach(), off1, eps, iters)["dist"]
+    counts = torch.tensor([b - a for a, b in zip(off1, off1[1:])], dtype=torch.int64).to(dist.device)
+    seg = torch.repeat_interleave(torch.arange(s, device=dist.device), counts, output_size=dist.numel())
+    emd = torch.zeros(s, dtype=torch.float64, device=dist.device).index_add_(0, seg, torch.sqrt(dist.double())) / counts.double()
+    return torch.cat([cd, emd[:, None]], dim=1)
 
 
 def match_cloud_files(pred_dir, gt_dir):

@@ -10,6 +10,7 @@ import torch
 
 from ..loss_functions import chamfer_3DDist, emdModule
 from ..loss_functions.Chamfer3D.dist_chamfer_ragged import chamfer_raggedDist
+from ..loss_functions.emd.emd_ragged import emd_raggedDist
 
 
 class Completionloss:
@@ -75,3 +76,18 @@ def chamfer_ragged_loss(clouds1, clouds2, kind="l1"):
         return torch.zeros(c, dtype=torch.float64, device=d.device).index_add(0, seg, v.double()) / counts.double()
     a, b = seg_mean(d1, off1), seg_mean(d2, off2)
     return ((a + b) / 2 if kind == "l1" else a + b).float()
+
+
+def emd_ragged_loss(clouds1, clouds2, eps=0.005, iters=50):
+    """Completionloss.emd_loss (utils/loss_util.py:45-49) for c pairs of clouds of different sizes at once: clouds1, clouds2 as
+    emd_raggedDist takes them (lists of [N_j,3] float32 GPU tensors, or (points, offsets); pair j has N_j points on both
+    sides, N_j % 256 == 0).  One auction call for all pairs; returns a [c] float32 tensor, pair j's loss sqrt(dist).mean() --
+    the fp32 reduction emd_loss applies to that pair alone, so the same bits.  A pair without points scores NaN.
+    Differentiable in clouds1; not part of the reference's facade."""
+    dist, _ = emd_raggedDist()(clouds1, clouds2, eps, iters)
+    if torch.is_tensor(dist):
+        off = [int(v) for v in clouds1[1]]
+        if len(off) == 1:
+            return dist.new_empty((0,))
+        dist = [dist[a:b] for a, b in zip(off, off[1:])]
+    return torch.stack([torch.sqrt(d.view(1, -1)).mean(1).mean() for d in dist])

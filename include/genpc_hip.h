@@ -39,7 +39,8 @@ int genpc_abi_version(void);              /* bumps when a signature or a documen
                                            * genpc_uhd_ragged came without a bump.  From 27 on an addition that changes no existing signature and no
                                            * documented behaviour no longer bumps the number: genpc_knn_mean_distance_ragged and
                                            * genpc_outlier_filter_ragged came that way, and so did genpc_knn_query_ragged (additive: the number
-                                           * stays 27); a missing symbol is found when the binding loads. */
+                                           * stays 27) and genpc_emd_forward_ragged / genpc_emd_backward_ragged (additive as well: still 27);
+                                           * a missing symbol is found when the binding loads. */
 const char *genpc_last_error(void);       /* last HIP error string, "" if none */
 int genpc_set_arith(int mode);            /* process default; returns the previous one */
 int genpc_set_arith_thread(int mode);     /* calling thread only, < 0: follow the default; returns the previous override */
@@ -224,6 +225,34 @@ int genpc_emd_calc_dist(int b, int n, const float *xyz1, const float *xyz2, cons
 int genpc_emd_backward(int b, int n, const float *xyz1, const float *xyz2,
                        float *gradxyz, const float *graddist, const int *idx,
                        void *stream);
+
+/* The auction over a RAGGED batch (csrc/emd_ragged.hip): c independent pairs, pair j of N_j points against N_j objects, in one
+ * call.  off is a HOST array of c + 1 ints, ascending from 0, copied before return (it rides in the kernel arguments); one
+ * table serves both clouds because the auction needs equal sizes inside a pair.  Every N_j is a multiple of 256, or 0.
+ * Every device array is packed in pair order and off[c] long (x 3 for the points).  assignment and bid index inside the pair's
+ * own objects, assignment_inv and max_idx inside its own points.  The outputs may arrive uninitialised: the call's first
+ * launch writes every pair's initial state (emd_module.alloc_state's values) and the call's own scratch, so a second call on
+ * the same buffers returns the same bits.
+ * Contract: pair j's dist, assignment, assignment_inv, bid and bid_increments are bit for bit what
+ * genpc_emd_forward(1, N_j, N_j, ...) returns on that pair alone from alloc_state's initial values, in the call's arithmetic
+ * mode, for any eps (negative included) and any iters >= 0 (0: dist 0, assignment -1).  price is exact except after a forced
+ * last round with several bidders on one object (the order of the additions there is a race in the reference too).  A point
+ * whose own coordinates are not finite bids on object -1 in the reference and in genpc_emd_forward (an out-of-bounds write);
+ * here it bids on object 0 of its pair.
+ * Launches: at most 3 * iters + 2 whatever c is (as built: 2 * iters + 2 -- initial state, a bid and a resolve launch per
+ * round, CalcDist); no host read-back, no synchronisation, no copy; no kernel waits for another workgroup.
+ * Returns 1 when done or when there is nothing to do (c == 0, or no pair has points; a pair with N_j == 0 is legal and writes
+ * nothing); 0 on a HIP error; -1 with genpc_last_error() set and nothing enqueued -- decided before the GPU is touched -- for
+ * c < 0 or c > 384, a null off with c > 0, off[0] != 0 or descending offsets, an N_j that is not a multiple of 256,
+ * off[c] > 2^28, iters < 0, or a null device pointer with work to do. */
+int genpc_emd_forward_ragged(int c, const int *off, const float *xyz1, const float *xyz2,
+                             float *dist, int *assignment, float *price, int *assignment_inv,
+                             int *bid, float *bid_increments, float *max_increments, int *max_idx,
+                             float eps, int iters, void *stream);
+/* genpc_emd_backward per pair: gradxyz[off[c],3] (caller-zeroed) += 2 * graddist * (xyz1 - xyz2[idx]), idx inside the pair's
+ * objects (an index outside them adds nothing).  The gradient goes to xyz1 only.  One launch; the same refusals. */
+int genpc_emd_backward_ragged(int c, const int *off, const float *xyz1, const float *xyz2,
+                              float *gradxyz, const float *graddist, const int *idx, void *stream);
 
 /* Depth prompting: projection, splat, colour gather ------------------------ *
  * Replaces DepthPrompting.getUvs (DepthPrompting.py:239-271) for the cameras the
