@@ -1,8 +1,12 @@
-// emd.h -- device helpers shared by the auction kernels (emd.hip: tiled bid, settle / resolve; emd_grid.hip: the
-// cell-sorted culled bid; emd_auction.hip: all rounds in one launch).  The objects' spatial index is grid.h's.
+// emd.h -- device helpers shared by the auction kernels (emd.hip: tiled bid, settle / resolve; emd_ragged.hip: the same over
+// a ragged batch; emd_grid.hip: the cell-sorted culled bid; emd_auction.hip: all rounds in one launch): the bit-exact rules
+// of the bid, its ties and the election, each stated once.  emd_steps.h builds a round's steps on ONE cloud from them for
+// emd.hip and emd_ragged.hip.  The objects' spatial index is grid.h's.
 #pragma once
 #include "common.h"
 #include "grid.h"
+
+#include <type_traits>
 
 namespace genpc {
 
@@ -41,10 +45,14 @@ __device__ __forceinline__ void atomic_max_float(float *addr, float val)
 // Folds (ob, obb, oi, obi) into (b, bb, bi, bbi): best / second-best values with the
 // index of an object attaining each.  Value-symmetric; on a tie for first place the
 // lower index is kept as `bi` (the reference's order is restored by the tie path).
-__device__ __forceinline__ void merge_top2(float &b, float &bb, int &bi, int &bbi, float ob, float obb, int oi, int obi)
+// I: int, an object index, or long long, position << 32 | object index (emd_auction.hip: ties keep the lower POSITION -- any
+// choice does: an exact tie for first place is settled by the tie path, the second's identity only seeds the next search).
+template <class I>
+__device__ __forceinline__ void merge_top2(float &b, float &bb, I &bi, I &bbi, float ob, float obb, I oi, I obi)
 {
+    typedef std::make_unsigned_t<I> UI;
     float nb2;
-    int nbi;
+    I nbi;
     if (b > ob) {
         nb2 = fmaxf(bb, ob);
         nbi = ob > bb ? oi : bbi;
@@ -53,13 +61,53 @@ __device__ __forceinline__ void merge_top2(float &b, float &bb, int &bi, int &bb
         nbi = b > obb ? bi : obi;
     } else {                       // equal first places: the other one is the second
         nb2 = b;
-        nbi = ((unsigned)oi < (unsigned)bi) ? bi : oi;
+        nbi = ((UI)oi < (UI)bi) ? bi : oi;
     }
-    const bool take = ob > b || (ob == b && (unsigned)oi < (unsigned)bi);
+    const bool take = ob > b || (ob == b && (UI)oi < (UI)bi);
     bi = take ? oi : bi;
     b = fmaxf(b, ob);
     bb = nb2;
     bbi = nbi;
+}
+
+// One candidate of value d and index kk into a lane's own top-2 (v_max + v_med3): strictly greater wins, so of equal values
+// the one met first is kept (I as for merge_top2).
+template <class I>
+__device__ __forceinline__ void insert_top2(float &best, float &better, I &best_i, I &better_i, float d, I kk)
+{
+    const bool gt = d > best;
+    const bool gt2 = !gt && d > better;
+    better_i = gt ? best_i : (gt2 ? kk : better_i);
+    better = __builtin_amdgcn_fmed3f(d, best, better);
+    best = fmaxf(best, d);
+    best_i = gt ? kk : best_i;
+}
+
+// The reference's partition of a cloud of n objects with U bidders left (emd_cuda.cu:108-118): threads of a block that share
+// one bidder.  Needed only to order exactly tied candidates.
+__device__ __forceinline__ int ref_thread_per_unass(int n, int U)
+{
+    const int block_cnt = n / 256;
+    const int unass_per_block = (U + block_cnt - 1) / block_cnt;
+    return 256 / unass_per_block;
+}
+
+// Key of object k among the objects tied for a bidder's first place: (reference thread, index), thread-major as the
+// reference's scan meets them (emd_cuda.cu:136-139,165-173) -- the smallest key is the object it reports.
+__device__ __forceinline__ unsigned long long ref_tie_key(int k, int n, int thread_per_unass)
+{
+    const int kt = k & 2047;                       // position in the reference's 2048-tile
+    const int tile0 = k - kt;
+    const int end_k = min(n, tile0 + 2048) - tile0;
+    const int delta = (end_k + thread_per_unass - 1) / thread_per_unass;
+    return ((unsigned long long)(kt / delta) << 32) | (unsigned)k;
+}
+
+// GetMax's window (emd_cuda.cu:188): a bidder stands for election when its increment is within 1e-6 of the object's largest
+__device__ __forceinline__ bool in_election_window(float bid_increment, float max_increment)
+{
+    const double bid_inc = (double)bid_increment, max_inc = (double)max_increment;
+    return bid_inc - 1e-6 <= max_inc && max_inc <= bid_inc + 1e-6;
 }
 
 // Threshold of the bid pre-filter for m = max(better, seed): a candidate with squared distance sq
@@ -72,6 +120,17 @@ __device__ __forceinline__ void merge_top2(float &b, float &bb, int &bi, int &bb
 __device__ __forceinline__ float filter_cb(float m)
 {
     return __fadd_rn(__fsub_rn(3.0f, m), __fmul_rn(2e-6f, __fadd_rn(1.0f, fabsf(m))));
+}
+
+// Seed of the pre-filter from two distinct objects sa, sc of the cloud (X2, PR: its objects and prices), re-valued at
+// today's prices: the second-best value over ALL objects is at least the smaller of any two distinct objects' values, so
+// a candidate provably not above the seed can be neither best nor strictly second.
+template <int FMA>
+__device__ __forceinline__ float seed_of_two(float x1, float y1, float z1, const float *__restrict__ X2, const float *__restrict__ PR, int sa, int sc)
+{
+    const float da = bid_value<FMA>(x1, y1, z1, X2[(size_t)sa * 3 + 0], X2[(size_t)sa * 3 + 1], X2[(size_t)sa * 3 + 2], PR[sa]);
+    const float dc = bid_value<FMA>(x1, y1, z1, X2[(size_t)sc * 3 + 0], X2[(size_t)sc * 3 + 1], X2[(size_t)sc * 3 + 2], PR[sc]);
+    return fminf(da, dc);
 }
 
 // lanes-per-bidder for U bidders on a grid of G blocks per batch element

@@ -32,7 +32,7 @@
 // equal (a tie for first place) the bidder's lanes re-scan and select the tied
 // object with the smallest (reference-thread, index) key, so assignments agree
 // with the oracle even on clouds with duplicated points.
-#include "emd.h"
+#include "emd_steps.h"
 #include "../../include/genpc_hip.h"
 
 #include <stdlib.h>
@@ -76,9 +76,7 @@ __global__ __launch_bounds__(kEBlock) void emd_bid_kernel(int n, const float *__
                                                           int *__restrict__ chain_cnt)
 {
     constexpr int kTile = TILE, kLoadsPerThread = TILE / 256;
-    // one tile of objects as four planes (x, y, z, price): a 16-byte read delivers four consecutive objects' x as two
-    // register pairs for the packed fp32 filter below
-    __shared__ __attribute__((aligned(16))) float sX[kTile], sY[kTile], sZ[kTile], sP[kTile];
+    __shared__ BidTile<TILE> tile;
     // 1-D grid of G * nb blocks.  The blocks of a cloud run on ONE XCD (blocks go to the XCDs round-robin by linear id), for
     // the largest multiple of 8 clouds: every block of a cloud re-reads the cloud's objects and prices tile by tile, and with
     // its blocks on all eight XCDs every 4 MB L2 held every cloud (8 x 32768: 4.2 MB; 14.9 -> 13.9 ms, 64 x 2048 1.74 -> 1.54).
@@ -105,15 +103,14 @@ __global__ __launch_bounds__(kEBlock) void emd_bid_kernel(int n, const float *__
     const int p = lane & (P - 1);
     const int g = lane / P;
 
-    const float *__restrict__ X1 = xyz1 + (size_t)batch * n * 3;
-    const float *__restrict__ X2 = xyz2 + (size_t)batch * n * 3;
-    const float *__restrict__ PR = price + (size_t)batch * n;
-    const int *__restrict__ L = list + (size_t)batch * n;
-
-    // reference partition, needed only to order exactly tied candidates
-    const int block_cnt = n / 256;
-    const int unass_per_block = (U + block_cnt - 1) / block_cnt;
-    const int thread_per_unass = 256 / unass_per_block;
+    const size_t base = (size_t)batch * n;
+    const float *__restrict__ X1 = xyz1 + base * 3;
+    const int *__restrict__ L = list + base;
+    EmdBidCloud c;
+    c.n = n; c.U = U; c.eps = eps;
+    c.X2 = xyz2 + base * 3; c.PR = price + base;
+    c.bid = bid + base; c.second = second != nullptr ? second + base : nullptr;
+    c.bid_increments = bid_increments + base; c.max_increments = max_increments + base;
 
     // Work units.  NB blocks cover the U bidders at P lanes each.  When even the
     // finest split (P = 64) leaves most of the grid idle -- the late rounds, where a
@@ -150,15 +147,7 @@ __global__ __launch_bounds__(kEBlock) void emd_bid_kernel(int n, const float *__
         // fetch), 4 in the late rounds of a few clouds, where a unit is a chain -- fetch, stage, a four-trip scan, fetch
         // ... -- and each tile's fetch latency was exposed (tools: ~2.9 k ticks per 1024-object tile of a unit's 27 k).
         float4 pre[AHEAD][kLoadsPerThread];
-        auto fetch = [&](auto slot_c, int k2) {
-            constexpr int slot = decltype(slot_c)::value;
-#pragma unroll
-            for (int i = 0; i < kLoadsPerThread; i++) {
-                const int k = k2 + threadIdx.x + i * kEBlock;
-                const int kk = k < n ? k : n - 1;
-                pre[slot][i] = make_float4(X2[(size_t)kk * 3 + 0], X2[(size_t)kk * 3 + 1], X2[(size_t)kk * 3 + 2], PR[kk]);
-            }
-        };
+        auto fetch = [&](auto slot_c, int k2) { bid_fetch<TILE>(pre[decltype(slot_c)::value], c, k2); };
         if (k_lo < k_hi) fetch(std::integral_constant<int, 0>{}, k_lo);
         if (AHEAD > 1 && k_lo + kTile < k_hi) fetch(std::integral_constant<int, (AHEAD > 1 ? 1 : 0)>{}, k_lo + kTile);
         if (AHEAD > 2 && k_lo + 2 * kTile < k_hi) fetch(std::integral_constant<int, (AHEAD > 2 ? 2 : 0)>{}, k_lo + 2 * kTile);
@@ -167,96 +156,20 @@ __global__ __launch_bounds__(kEBlock) void emd_bid_kernel(int n, const float *__
         const bool active = u < U;
         const int j = L[active ? u : U - 1];
         const float x1 = X1[(size_t)j * 3 + 0], y1 = X1[(size_t)j * 3 + 1], z1 = X1[(size_t)j * 3 + 2];
-        float best = -1e9f, better = -1e9f;
-        int best_i = -1, better_i = -1;
         // Seed of the pre-filter: the objects this point ranked first and second the
-        // last time it bid, re-valued at today's prices.  The second-best value over ALL
-        // objects is at least the smaller of any two distinct objects' values, so a
-        // candidate provably not above `seed` can be neither best nor strictly second.
+        // last time it bid, re-valued at today's prices (seed_of_two).
         // The filter is thereby selective from the first object on, whatever the length
         // of a lane's sequence (without it, late rounds with 64 lanes per bidder
         // evaluated every pair exactly).
         float seed = -1e9f;
         if (second != nullptr) {
-            const int sa = bid[(size_t)batch * n + j], sc = second[(size_t)batch * n + j];
-            if (sc >= 0 && sa != sc && (unsigned)sa < (unsigned)n) {
-                const float da = bid_value<FMA>(x1, y1, z1, X2[(size_t)sa * 3 + 0], X2[(size_t)sa * 3 + 1],
-                                                X2[(size_t)sa * 3 + 2], PR[sa]);
-                const float dc = bid_value<FMA>(x1, y1, z1, X2[(size_t)sc * 3 + 0], X2[(size_t)sc * 3 + 1],
-                                                X2[(size_t)sc * 3 + 2], PR[sc]);
-                seed = fminf(da, dc);
-            }
+            const int sa = c.bid[j], sc = c.second[j];
+            if (sc >= 0 && sa != sc && (unsigned)sa < (unsigned)n) seed = seed_of_two<FMA>(x1, y1, z1, c.X2, c.PR, sa, sc);
         }
-        float cb = filter_cb(fmaxf(better, seed));
-
+        const BidPoint pt = {x1, y1, z1, seed};
+        BidLane s = bid_lane(seed);
         auto tile_step = [&](auto slot_c, int k2) {
-            constexpr int slot = decltype(slot_c)::value;
-            const int end_k = min(n, k2 + kTile) - k2;
-            __syncthreads();                               // the previous tile has been scanned
-#pragma unroll
-            for (int i = 0; i < kLoadsPerThread; i++) {
-                const int t = threadIdx.x + i * kEBlock;
-                if (t < end_k) { sX[t] = pre[slot][i].x; sY[t] = pre[slot][i].y; sZ[t] = pre[slot][i].z; sP[t] = pre[slot][i].w; }
-            }
-            __syncthreads();
-            if (k2 + AHEAD * kTile < k_hi) fetch(slot_c, k2 + AHEAD * kTile);
-            // Pre-filter.  A candidate can change this lane's (best, better) only if its
-            // value exceeds `better`, i.e. only if sqrt(s) < 3 - price - better.  That is
-            // tested conservatively in squared space with fp32 and no sqrt / fp64:
-            // cb = (3 - better) + 2e-6 (1 + |better|) absorbs every rounding of the test itself at
-            // ANY magnitude of the clouds (filter_cb: the slack needed is u (21 + 9 |better|),
-            // u = 2^-24, the slack given 33 u (1 + |better|)), so a candidate that fails the
-            // test provably evaluates to d <= better and the exact update would be a
-            // no-op.  The exact path (double-precision expression of emd_cuda.cu:146)
-            // runs for the whole wave when any lane passes; for lanes that did not pass
-            // it is that same no-op.  Results are therefore bit-identical with and
-            // without the filter.
-            // Four CONSECUTIVE objects per lane and iteration (4*P divides every tile length: n % 256 == 0,
-            // P <= 64), evaluated two per instruction (packed fp32: same operations, same roundings as
-            // sqdist and filter_cb's test); a lane's verdicts stay in SGPRs (one ballot per object), so a
-            // group none of whose members can matter costs 16 packed operations, 4 compares and one scalar branch
-            // (28 instead of 51 instructions per four objects; in-run A/B with the 1024-object tiles: 13 x 16384 7.68 ->
-            // 7.31 ms, 8 x 32768 16.05 -> 15.05 -- with 2048-object tiles and half the resident waves it LOST 6 %;
-            // issuing the next group's LDS reads early costs registers and residency: 7.23 -> 8.6 ms).
-            const v2f x1v = {x1, x1}, y1v = {y1, y1}, z1v = {z1, z1};
-            for (int t = 4 * p; t < end_k; t += 4 * P) {
-                const float4 X4 = *(const float4 *)&sX[t], Y4 = *(const float4 *)&sY[t], Z4 = *(const float4 *)&sZ[t],
-                             W4 = *(const float4 *)&sP[t];
-                const v2f cbv = {cb, cb};
-                v2f sqv[2];
-                unsigned long long pass[4];
-#pragma unroll
-                for (int h = 0; h < 2; h++) {
-                    const v2f dx = (h ? (v2f){X4.z, X4.w} : (v2f){X4.x, X4.y}) - x1v;
-                    const v2f dy = (h ? (v2f){Y4.z, Y4.w} : (v2f){Y4.x, Y4.y}) - y1v;
-                    const v2f dz = (h ? (v2f){Z4.z, Z4.w} : (v2f){Z4.x, Z4.y}) - z1v;
-                    if (FMA) sqv[h] = __builtin_elementwise_fma(dz, dz, __builtin_elementwise_fma(dx, dx, dy * dy));
-                    else sqv[h] = (dx * dx + dy * dy) + dz * dz;
-                    const v2f tt = cbv - (h ? (v2f){W4.z, W4.w} : (v2f){W4.x, W4.y});
-                    const v2f t2 = tt * tt;
-                    pass[2 * h] = __ballot(sqv[h].x < t2.x);
-                    pass[2 * h + 1] = __ballot(sqv[h].y < t2.y);
-                }
-                if ((pass[0] | pass[1] | pass[2] | pass[3]) != 0ull) {
-                    const float sq[4] = {sqv[0].x, sqv[0].y, sqv[1].x, sqv[1].y};
-                    const float pr[4] = {W4.x, W4.y, W4.z, W4.w};
-#pragma unroll
-                    for (int i = 0; i < 4; i++) {
-                        if (pass[i] != 0ull) {
-                            const float r = sqrtf(sq[i]);
-                            const float d = (float)((3.0 - (double)r) - (double)pr[i]);
-                            const bool gt = d > best;
-                            const bool gt2 = !gt && d > better;
-                            const int kk = k2 + t + i;
-                            better_i = gt ? best_i : (gt2 ? kk : better_i);
-                            better = __builtin_amdgcn_fmed3f(d, best, better);
-                            best = fmaxf(best, d);
-                            best_i = gt ? kk : best_i;
-                        }
-                    }
-                    cb = filter_cb(fmaxf(better, seed));
-                }
-            }
+            bid_tile_step<FMA, TILE>(tile, pre[decltype(slot_c)::value], c, pt, s, p, P, k2, k2 + AHEAD * kTile, k_hi);
         };
         for (int k2 = k_lo; k2 < k_hi; k2 += AHEAD * kTile) {          // block-uniform trip tests
             tile_step(std::integral_constant<int, 0>{}, k2);
@@ -264,14 +177,7 @@ __global__ __launch_bounds__(kEBlock) void emd_bid_kernel(int n, const float *__
             if (AHEAD > 2 && k2 + 2 * kTile < k_hi) tile_step(std::integral_constant<int, (AHEAD > 2 ? 2 : 0)>{}, k2 + 2 * kTile);
             if (AHEAD > 3 && k2 + 3 * kTile < k_hi) tile_step(std::integral_constant<int, (AHEAD > 3 ? 3 : 0)>{}, k2 + 3 * kTile);
         }
-        // merge the P partial top-2s of a bidder (value-symmetric)
-        for (int off = 1; off < P; off <<= 1) {
-            const float ob = __shfl_xor(best, off, kWave);
-            const float obb = __shfl_xor(better, off, kWave);
-            const int oi = __shfl_xor(best_i, off, kWave);
-            const int obi = __shfl_xor(better_i, off, kWave);
-            merge_top2(best, better, best_i, better_i, ob, obb, oi, obi);
-        }
+        bid_merge_lanes(s, P);
         if (Z > 1) {
             // publish this slice's top-2 per bidder, then let the last slice to arrive
             // fold all Z of them (top-2 merging is associative and symmetric)
@@ -282,15 +188,15 @@ __global__ __launch_bounds__(kEBlock) void emd_bid_kernel(int n, const float *__
             unsigned long long *slot =
                 (unsigned long long *)(parts + ((size_t)batch * kSplitMaxBidders + (active ? u : 0)) * kZMax);
             if (active && p == 0) {
-                __hip_atomic_store(slot + 2 * zs, ((unsigned long long)__float_as_uint(best) << 32) | __float_as_uint(better),
+                __hip_atomic_store(slot + 2 * zs, ((unsigned long long)__float_as_uint(s.best) << 32) | __float_as_uint(s.better),
                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(slot + 2 * zs + 1, ((unsigned long long)(unsigned)best_i << 32) | (unsigned)better_i,
+                __hip_atomic_store(slot + 2 * zs + 1, ((unsigned long long)(unsigned)s.best_i << 32) | (unsigned)s.better_i,
                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             int *cntp = arrive + (size_t)batch * kArrivePerBatch + grp;
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();                       // also: every lane is done with the tile
-            int *s_ticket = (int *)sX;
+            int *s_ticket = (int *)tile.x;
             if (threadIdx.x == 0)
                 *s_ticket = __hip_atomic_fetch_add(cntp, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __syncthreads();
@@ -310,55 +216,28 @@ __global__ __launch_bounds__(kEBlock) void emd_bid_kernel(int n, const float *__
             }
             // hand the merged result to all P lanes of the bidder (the tie path below is cooperative)
             const int src_lane = lane & ~(P - 1);
-            best = __shfl(mb, src_lane, kWave);
-            better = __shfl(mbb, src_lane, kWave);
-            best_i = __shfl(mi, src_lane, kWave);
-            better_i = __shfl(mbi, src_lane, kWave);
+            s.best = __shfl(mb, src_lane, kWave);
+            s.better = __shfl(mbb, src_lane, kWave);
+            s.best_i = __shfl(mi, src_lane, kWave);
+            s.better_i = __shfl(mbi, src_lane, kWave);
         }
-        // exact tie for first place: pick the candidate the reference's scan meets first
-        const bool tie = active && (best == better);
-        if (__any(tie)) {
-            unsigned long long key = ~0ull;
-            if (tie) {
-                for (int k = p; k < n; k += P) {
-                    const float d = bid_value<FMA>(x1, y1, z1, X2[(size_t)k * 3 + 0], X2[(size_t)k * 3 + 1],
-                                                   X2[(size_t)k * 3 + 2], PR[k]);
-                    if (d == best) {
-                        const int kt = k & 2047;                       // position in the reference's 2048-tile
-                        const int tile0 = k - kt;
-                        const int end_k = min(n, tile0 + 2048) - tile0;
-                        const int delta = (end_k + thread_per_unass - 1) / thread_per_unass;
-                        const unsigned long long kk = ((unsigned long long)(kt / delta) << 32) | (unsigned)k;
-                        key = kk < key ? kk : key;
-                    }
-                }
-            }
-            for (int off = 1; off < P; off <<= 1) {
-                const unsigned long long o = __shfl_xor(key, off, kWave);
-                key = o < key ? o : key;
-            }
-            if (tie) best_i = (int)(key & 0xffffffffu);
-        }
+        bid_break_tie<FMA>(c, pt, s, active, p, P);
         if (active && p == 0) {
-            const float inc = __fadd_rn(__fsub_rn(best, better), eps);
-            bid[(size_t)batch * n + j] = best_i;
-            if (second != nullptr) second[(size_t)batch * n + j] = better_i;
-            bid_increments[(size_t)batch * n + j] = inc;
-            atomic_max_float(&max_increments[(size_t)batch * n + best_i], inc);
+            int best_i;
+            const float inc = bid_write<false>(c, s, j, best_i);
             // the round's bidders of an object as a chain through the object's head word (emd_settle_kernel): a record is
             // (increment bits << 32) | (stamp << 24) | bidder, the head holds the latest bidder's, next[j] what j displaced.
             // The bidder field is 24 bits: the chain is only built for n <= 2^24 (`settle` in genpc_emd_forward)
             if (chain_head != nullptr) {
                 const unsigned long long mine = ((unsigned long long)(unsigned)__float_as_int(inc) << 32) | (stamp << 24) | (unsigned)j;
-                chain_next[(size_t)batch * n + j] = atomicExch(&chain_head[(size_t)batch * n + best_i], mine);
-                atomicAdd(&chain_cnt[(size_t)batch * n + best_i], 1);       // how many bid for it this round (no value returned: nothing waits)
+                chain_next[base + j] = atomicExch(&chain_head[base + best_i], mine);
+                atomicAdd(&chain_cnt[base + best_i], 1);       // how many bid for it this round (no value returned: nothing waits)
             }
         }
     }
 }
 
-// emd_cuda.cu:181-194.  In the forced last round every bidder is "assigned", and
-// the owner recorded in assignment_inv is the last writer: elect the highest j.
+// emd_cuda.cu:181-194
 __global__ __launch_bounds__(kEBlock) void emd_getmax_kernel(int n, const int *__restrict__ list,
                                                              const int *__restrict__ cnt, const int *__restrict__ bid,
                                                              const float *__restrict__ bid_increments,
@@ -367,14 +246,24 @@ __global__ __launch_bounds__(kEBlock) void emd_getmax_kernel(int n, const int *_
 {
     const int batch = blockIdx.y;
     const int U = cnt[batch];
-    for (int u = blockIdx.x * kEBlock + threadIdx.x; u < U; u += gridDim.x * kEBlock) {
-        const int j = list[(size_t)batch * n + u];
-        const int bid_id = bid[(size_t)batch * n + j];
-        const double bid_inc = (double)bid_increments[(size_t)batch * n + j];
-        const double max_inc = (double)max_increments[(size_t)batch * n + bid_id];
-        if (last || (bid_inc - 1e-6 <= max_inc && max_inc <= bid_inc + 1e-6))
-            atomicMax(&max_idx[(size_t)batch * n + bid_id], j);
-    }
+    const size_t base = (size_t)batch * n;
+    for (int u = blockIdx.x * kEBlock + threadIdx.x; u < U; u += gridDim.x * kEBlock)
+        elect_bidder(bid + base, bid_increments + base, max_increments + base, max_idx + base, list[base + u], last);
+}
+
+// batch element `batch` of the call's arrays as a cloud (emd_steps.h); pos_of / price_s are null for the tiled bid
+__device__ __forceinline__ EmdRoundCloud round_cloud(int batch, int n, const int *list, int *list_next, int *cnt_next, int *assignment,
+                                                     int *assignment_inv, float *price, const int *bid, const float *bid_increments,
+                                                     float *max_increments, int *max_idx, const int *pos_of, float *price_s)
+{
+    const size_t base = (size_t)batch * n;
+    EmdRoundCloud c;
+    c.list = list + base; c.list_next = list_next + base; c.cnt_next = cnt_next + batch;
+    c.assignment = assignment + base; c.assignment_inv = assignment_inv + base; c.max_idx = max_idx + base;
+    c.bid = bid + base; c.bid_increments = bid_increments + base;
+    c.price = price + base; c.max_increments = max_increments + base;
+    c.pos_of = price_s ? pos_of + base : nullptr; c.price_s = price_s ? price_s + 4 * base : nullptr;
+    return c;
 }
 
 // emd_cuda.cu:196-215 plus construction of the next round's bidder list.
@@ -390,40 +279,12 @@ __global__ __launch_bounds__(kEBlock) void emd_assign_kernel(int n, const int *_
 {
     const int batch = blockIdx.y;
     const int U = cnt[batch];
-    const size_t base = (size_t)batch * n;
+    const EmdRoundCloud c = round_cloud(batch, n, list, list_next, cnt_next, assignment, assignment_inv, price, bid, bid_increments,
+                                        max_increments, max_idx, pos_of, price_s);
     for (int u = blockIdx.x * kEBlock + threadIdx.x; u < U; u += gridDim.x * kEBlock) {
-        const int j = list[base + u];
-        const int bid_id = bid[base + j];
-        const bool elected = max_idx[base + bid_id] == j;
-        if (last) {
-            // every remaining bidder takes its object (not a bijection, :201)
-            assignment[base + j] = bid_id;
-            atomicAdd(&price[base + bid_id], bid_increments[base + j]);
-            if (elected) {
-                assignment_inv[base + bid_id] = j;
-                max_increments[base + bid_id] = -1e9f;
-                max_idx[base + bid_id] = -1;
-            }
-        } else if (elected) {
-            const int prev = assignment_inv[base + bid_id];
-            if (prev != -1) {
-                assignment[base + prev] = -1;
-                const int pos = atomicAdd(&cnt_next[batch], 1);
-                list_next[base + pos] = prev;
-            }
-            assignment_inv[base + bid_id] = j;
-            assignment[base + j] = bid_id;
-            const float np_ = __fadd_rn(price[base + bid_id], bid_increments[base + j]);
-            price[base + bid_id] = np_;
-            if (price_s) price_s[4 * (base + pos_of[base + bid_id])] = np_;
-            max_increments[base + bid_id] = -1e9f;
-            // elections are per round; only this thread's own comparison above
-            // needed the value, every other bidder of the object compares != j
-            max_idx[base + bid_id] = -1;
-        } else {
-            const int pos = atomicAdd(&cnt_next[batch], 1);
-            list_next[base + pos] = j;
-        }
+        const int j = c.list[u];
+        const int bid_id = c.bid[j];
+        assign_bidder(c, j, bid_id, c.max_idx[bid_id] == j, last);
     }
 }
 
@@ -491,8 +352,7 @@ __global__ __launch_bounds__(kEBlock) void emd_settle_kernel(int n, const int *_
         const float old_price = price[base + bid_id];
         if (C > kChainWalkMax) {
             const float my_inc = bid_increments[base + j];
-            const double bid_inc = (double)my_inc, max_inc = (double)max_increments[base + bid_id];
-            const bool inwin = last || (bid_inc - 1e-6 <= max_inc && max_inc <= bid_inc + 1e-6);
+            const bool inwin = last || in_election_window(my_inc, max_increments[base + bid_id]);
             if (last) {
                 assignment[base + j] = bid_id;                       // every remaining bidder takes its object (:201)
                 atomicAdd(&price[base + bid_id], my_inc);
@@ -537,14 +397,12 @@ __global__ __launch_bounds__(kEBlock) void emd_settle_kernel(int n, const int *_
             }
             winner = -1;
             for (unsigned long long r = head; live(r); r = chain_next[base + who(r)]) {
-                const double bid_inc = (double)inc_of(r), max_inc = (double)mx;
-                if ((last || (bid_inc - 1e-6 <= max_inc && max_inc <= bid_inc + 1e-6)) && who(r) > winner) winner = who(r);
+                if ((last || in_election_window(inc_of(r), mx)) && who(r) > winner) winner = who(r);
             }
         }
         const bool elected = winner == j;
         if (last) {
-            // every remaining bidder takes its object (not a bijection, :201)
-            assignment[base + j] = bid_id;
+            assignment[base + j] = bid_id;                           // every remaining bidder takes its object (:201)
             atomicAdd(&price[base + bid_id], my_inc);
             if (elected) {
                 assignment_inv[base + bid_id] = j;
@@ -566,7 +424,7 @@ __global__ __launch_bounds__(kEBlock) void emd_settle_kernel(int n, const int *_
 // GetMax and Assign of one round in ONE launch, one 1024-thread block per batch element: used from
 // the round on in which few bidders are left (the two list-walking launches are then pure latency:
 // 4.7 + 5.1 us plus a launch boundary per round at 1 x 16384).  Phase 1 elects (atomicMax, performed in
-// L2), the block barrier separates it from phase 2, which reads the elections with L1-bypassing loads.
+// L2), the block barrier separates it from phase 2, which reads the elections with L1-bypassing loads (resolve_round).
 constexpr int kResolveBlock = 1024;
 __global__ __launch_bounds__(kResolveBlock) void emd_resolve_kernel(int n, const int *__restrict__ list,
                                                                     const int *__restrict__ cnt, int *__restrict__ list_next,
@@ -579,48 +437,8 @@ __global__ __launch_bounds__(kResolveBlock) void emd_resolve_kernel(int n, const
                                                                     const int *__restrict__ pos_of, float *__restrict__ price_s)
 {
     const int batch = blockIdx.x;
-    const int U = cnt[batch];
-    const size_t base = (size_t)batch * n;
-    for (int u = threadIdx.x; u < U; u += kResolveBlock) {
-        const int j = list[base + u];
-        const int bid_id = bid[base + j];
-        const double bid_inc = (double)bid_increments[base + j];
-        const double max_inc = (double)max_increments[base + bid_id];
-        if (last || (bid_inc - 1e-6 <= max_inc && max_inc <= bid_inc + 1e-6)) atomicMax(&max_idx[base + bid_id], j);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    for (int u = threadIdx.x; u < U; u += kResolveBlock) {
-        const int j = list[base + u];
-        const int bid_id = bid[base + j];
-        const bool elected = __hip_atomic_load(&max_idx[base + bid_id], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == j;
-        if (last) {
-            assignment[base + j] = bid_id;
-            atomicAdd(&price[base + bid_id], bid_increments[base + j]);
-            if (elected) {
-                assignment_inv[base + bid_id] = j;
-                max_increments[base + bid_id] = -1e9f;
-                max_idx[base + bid_id] = -1;
-            }
-        } else if (elected) {
-            const int prev = assignment_inv[base + bid_id];
-            if (prev != -1) {
-                assignment[base + prev] = -1;
-                const int pos = atomicAdd(&cnt_next[batch], 1);
-                list_next[base + pos] = prev;
-            }
-            assignment_inv[base + bid_id] = j;
-            assignment[base + j] = bid_id;
-            const float np_ = __fadd_rn(price[base + bid_id], bid_increments[base + j]);
-            price[base + bid_id] = np_;
-            if (price_s) price_s[4 * (base + pos_of[base + bid_id])] = np_;
-            max_increments[base + bid_id] = -1e9f;
-            max_idx[base + bid_id] = -1;
-        } else {
-            const int pos = atomicAdd(&cnt_next[batch], 1);
-            list_next[base + pos] = j;
-        }
-    }
+    resolve_round<kResolveBlock>(round_cloud(batch, n, list, list_next, cnt_next, assignment, assignment_inv, price, bid, bid_increments,
+                                             max_increments, max_idx, pos_of, price_s), cnt[batch], last);
 }
 
 // emd_cuda.cu:217-226
@@ -638,9 +456,7 @@ __global__ __launch_bounds__(kEBlock) void emd_calc_dist_kernel(long long total,
         dist[t] = 0.0f;
         return;
     }
-    const float *p1 = xyz1 + t * 3;
-    const float *p2 = xyz2 + (i * n + k) * 3;
-    dist[t] = sqdist<FMA>(p1[0] - p2[0], p1[1] - p2[1], p1[2] - p2[2]);
+    dist[t] = calc_dist_point<FMA>(xyz1 + t * 3, xyz2 + (i * n + k) * 3);
 }
 
 // emd_cuda.cu:284-300
@@ -652,13 +468,7 @@ __global__ __launch_bounds__(kEBlock) void emd_grad_kernel(long long total, int 
     const long long t = (long long)blockIdx.x * kEBlock + threadIdx.x;
     if (t >= total) return;
     const long long i = t / n;
-    const float *p1 = xyz1 + t * 3;
-    const float *p2 = xyz2 + (i * n + idx[t]) * 3;
-    const float g = __fmul_rn(grad_dist[t], 2.0f);
-    float *o = grad_xyz + t * 3;
-    o[0] = __fadd_rn(o[0], __fmul_rn(g, p1[0] - p2[0]));
-    o[1] = __fadd_rn(o[1], __fmul_rn(g, p1[1] - p2[1]));
-    o[2] = __fadd_rn(o[2], __fmul_rn(g, p1[2] - p2[2]));
+    grad_point(xyz1 + t * 3, xyz2 + (i * n + idx[t]) * 3, grad_xyz + t * 3, grad_dist[t]);
 }
 
 }  // namespace genpc
@@ -844,7 +654,7 @@ GENPC_API int genpc_emd_forward(int b, int n, int m, const float *xyz1, const fl
             // 95 us against 166 us at 32 lanes), even when that needs more units than blocks.  With
             // many clouds in flight (b >= 32) fewer bidders per staged tile cost more than that (+2 %).
             const int force_p = it > 0 && b < 32 ? 64 : 0;
-            // 1024-object tiles (16 KiB of LDS; the default filter variant is 78 VGPRs = six waves per SIMD, the unfiltered one
+            // 1024-object tiles (16 KiB of LDS; the default filter variant is 76 VGPRs = six waves per SIMD, the unfiltered one
             // 72 = eight: tools/kmeta.sh emd) wherever
             // the bid is throughput-bound; a single small cloud is latency-bound and pays for the extra barrier pairs
             // (in-run A/B: 13 x 16384 8.28 -> 7.65 ms, 64 x 2048 1.99 -> 1.80, 1 x 16384 =, 1 x 2048 0.69 -> 0.76;

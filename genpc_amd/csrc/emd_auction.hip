@@ -55,29 +55,6 @@ constexpr int kCtrlWords = 18 * 16;
 template <class T> __device__ __forceinline__ T ald(const T *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 template <class T> __device__ __forceinline__ void ast(T *p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// merge_top2 (emd.h) for indices that carry a payload: position << 32 | object index; ties keep the lower POSITION (any
-// choice does: an exact tie for first place is settled by the tie path, the second's identity only seeds the next search)
-__device__ __forceinline__ void merge_top2_64(float &b, float &bb, long long &bi, long long &bbi, float ob, float obb, long long oi, long long obi)
-{
-    float nb2;
-    long long nbi;
-    if (b > ob) {
-        nb2 = fmaxf(bb, ob);
-        nbi = ob > bb ? oi : bbi;
-    } else if (ob > b) {
-        nb2 = fmaxf(obb, b);
-        nbi = b > obb ? bi : obi;
-    } else {
-        nb2 = b;
-        nbi = ((unsigned long long)oi < (unsigned long long)bi) ? bi : oi;
-    }
-    const bool take = ob > b || (ob == b && (unsigned long long)oi < (unsigned long long)bi);
-    bi = take ? oi : bi;
-    b = fmaxf(b, ob);
-    bb = nb2;
-    bbi = nbi;
-}
-
 struct __attribute__((aligned(16))) F3A { float x, y, z; };      // the coordinates of a sorted entry as one 12-byte load
 
 struct EmdAuction {
@@ -173,7 +150,6 @@ __global__ __launch_bounds__(kABlock, 4) void emd_auction_kernel(EmdAuction a)
     const CellGridHdr H = a.hdr[batch];
     const int gx = H.g[0], gy = H.g[1], gz = H.g[2];
     const float h = H.h, inf = __builtin_inff();
-    const int block_cnt = n / 256;
     // per point, in LDS (slot of the owner lane): [1], [2] the sorted positions of the objects ranked first and second at its
     // last bid (the seeds of its next one), and what Settle needs of this round's bid
     s_out[threadIdx.x][1] = -1; s_out[threadIdx.x][2] = -1;
@@ -213,8 +189,7 @@ __global__ __launch_bounds__(kABlock, 4) void emd_auction_kernel(EmdAuction a)
             LPB = LPB < 8 ? 8 : (LPB > 64 ? 64 : LPB);
             const int per_wave = kWave / LPB;
             const int sub = lane & (LPB - 1), grp = lane / LPB;
-            const int unass_per_block = (U + block_cnt - 1) / block_cnt;
-            const int thread_per_unass = 256 / unass_per_block;
+            const int thread_per_unass = ref_thread_per_unass(n, U);
             for (int k0 = 0; k0 < nbid; k0 += per_wave) {
                 const int kq = k0 + grp;
                 const bool active = kq < nbid;
@@ -255,22 +230,11 @@ __global__ __launch_bounds__(kABlock, 4) void emd_auction_kernel(EmdAuction a)
                         const float4 o = S[ps];
                         const float d = bid_value<FMA>(x1, y1, z1, o.x, o.y, o.z, w);
                         if (mode == 0) {
-                            const bool gt = d > best;
-                            const bool gt2 = !gt && d > better;
-                            const long long pk = ((long long)ps << 32) | (unsigned)__float_as_int(o.w);
-                            better_p = gt ? best_p : (gt2 ? pk : better_p);
-                            better = __builtin_amdgcn_fmed3f(d, best, better);
-                            best = fmaxf(best, d);
-                            best_p = gt ? pk : best_p;
+                            insert_top2(best, better, best_p, better_p, d, ((long long)ps << 32) | (unsigned)__float_as_int(o.w));
                         } else if (d == best) {
                             // an object that ties for first place: its key in the reference's thread-major scan order
                             // (emd_cuda.cu:108-118,136-139,165-173: the candidate the scan meets first is reported)
-                            const int k = __float_as_int(o.w);
-                            const int kt = k & 2047;
-                            const int tile0 = k - kt;
-                            const int end_k = min(n, tile0 + 2048) - tile0;
-                            const int delta = (end_k + thread_per_unass - 1) / thread_per_unass;
-                            const unsigned long long kk = ((unsigned long long)(kt / delta) << 32) | (unsigned)k;
+                            const unsigned long long kk = ref_tie_key(__float_as_int(o.w), n, thread_per_unass);
                             tie_key = kk < tie_key ? kk : tie_key;
                         }
                     }
@@ -436,7 +400,7 @@ __global__ __launch_bounds__(kABlock, 4) void emd_auction_kernel(EmdAuction a)
                 for (int off = 1; off < LPB; off <<= 1) {
                     const float ob = __shfl_xor(best, off, kWave), obb = __shfl_xor(better, off, kWave);
                     const long long oi = __shfl_xor(best_p, off, kWave), obi = __shfl_xor(better_p, off, kWave);
-                    merge_top2_64(best, better, best_p, better_p, ob, obb, oi, obi);
+                    merge_top2(best, better, best_p, better_p, ob, obb, oi, obi);
                 }
                 int best_i = best_p >= 0 ? (int)(best_p & 0xffffffffll) : -1;
                 const bool tie = active && (best == better);
@@ -500,8 +464,8 @@ __global__ __launch_bounds__(kABlock, 4) void emd_auction_kernel(EmdAuction a)
             const float old_price = ald(&a.price[base + bid_id]);
             if (C > 4) {
                 const float my_inc = r_inc;
-                const double bid_inc = (double)my_inc, max_inc = (double)ald(&a.max_increments[base + bid_id]);
-                const bool inwin = last || (bid_inc - 1e-6 <= max_inc && max_inc <= bid_inc + 1e-6);
+                const float max_inc = ald(&a.max_increments[base + bid_id]);
+                const bool inwin = last || in_election_window(my_inc, max_inc);
                 if (last) {
                     ast(&a.assignment[base + j], bid_id);
                     atomicAdd(&a.price[base + bid_id], my_inc);
@@ -530,8 +494,7 @@ __global__ __launch_bounds__(kABlock, 4) void emd_auction_kernel(EmdAuction a)
                     }
                     winner = -1;
                     for (unsigned long long r = head; live(r); r = ald(&a.chain_next[base + who(r)])) {
-                        const double bid_inc = (double)inc_of(r), max_inc = (double)mx;
-                        if ((last || (bid_inc - 1e-6 <= max_inc && max_inc <= bid_inc + 1e-6)) && who(r) > winner) winner = who(r);
+                        if ((last || in_election_window(inc_of(r), mx)) && who(r) > winner) winner = who(r);
                     }
                 }
                 const bool elected = winner == j;

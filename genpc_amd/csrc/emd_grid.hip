@@ -84,9 +84,7 @@ __global__ __launch_bounds__(kEBlock) __attribute__((amdgpu_waves_per_eu(4, 8)))
     const int gx = H.g[0], gy = H.g[1], gz = H.g[2];
     const float h = H.h, inf = __builtin_inff();
     // reference partition, needed only to order exactly tied candidates
-    const int block_cnt = n / 256;
-    const int unass_per_block = (U + block_cnt - 1) / block_cnt;
-    const int thread_per_unass = 256 / unass_per_block;
+    const int thread_per_unass = ref_thread_per_unass(n, U);
 
     const int units = (U + per_block - 1) / per_block;
     for (int unit = bx; unit < units; unit += G) {
@@ -106,9 +104,7 @@ __global__ __launch_bounds__(kEBlock) __attribute__((amdgpu_waves_per_eu(4, 8)))
         {
             const int sa = a.bid[base + j], sc = a.second[base + j];
             if (sc >= 0 && sa != sc && (unsigned)sa < (unsigned)n) {
-                const float da = bid_value<FMA>(x1, y1, z1, X2[(size_t)sa * 3 + 0], X2[(size_t)sa * 3 + 1], X2[(size_t)sa * 3 + 2], PR[sa]);
-                const float dc = bid_value<FMA>(x1, y1, z1, X2[(size_t)sc * 3 + 0], X2[(size_t)sc * 3 + 1], X2[(size_t)sc * 3 + 2], PR[sc]);
-                seed = fminf(da, dc);
+                seed = seed_of_two<FMA>(x1, y1, z1, X2, PR, sa, sc);
                 seeded = true;
             }
         }
@@ -135,22 +131,11 @@ __global__ __launch_bounds__(kEBlock) __attribute__((amdgpu_waves_per_eu(4, 8)))
                 st_pass++;
                 const float d = bid_value<FMA>(x1, y1, z1, o.x, o.y, o.z, o.w);
                 if (mode == 0) {
-                    const bool gt = d > best;
-                    const bool gt2 = !gt && d > better;
-                    const int kk = OF[ps];
-                    better_i = gt ? best_i : (gt2 ? kk : better_i);
-                    better = __builtin_amdgcn_fmed3f(d, best, better);
-                    best = fmaxf(best, d);
-                    best_i = gt ? kk : best_i;
+                    insert_top2(best, better, best_i, better_i, d, OF[ps]);
                 } else if (d == best) {
                     // an object that ties for first place: its key in the reference's thread-major scan order
                     // (emd_cuda.cu:108-118,136-139,165-173: the candidate the scan meets first is reported)
-                    const int k = OF[ps];
-                    const int kt = k & 2047;                       // position in the reference's 2048-tile
-                    const int tile0 = k - kt;
-                    const int end_k = min(n, tile0 + 2048) - tile0;
-                    const int delta = (end_k + thread_per_unass - 1) / thread_per_unass;
-                    const unsigned long long kk = ((unsigned long long)(kt / delta) << 32) | (unsigned)k;
+                    const unsigned long long kk = ref_tie_key(OF[ps], n, thread_per_unass);
                     tie_key = kk < tie_key ? kk : tie_key;
                 }
             }

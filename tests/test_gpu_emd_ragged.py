@@ -244,6 +244,23 @@ def test_8_non_finite_coordinates(gp, oracle, mode):
         np.testing.assert_array_equal(got[name][off[1]:off[2]].view(np.uint32), d[name].view(np.uint32), err_msg=name)
 
 
+@pytest.mark.parametrize("mode", [0, 1])
+def test_8a_non_finite_bidder(gp, oracle, mode):
+    """A BIDDER with a NaN coordinate, in the middle pair: none of its candidates compares above -1e9, and it bids on object 0
+    of its own pair (csrc/emd_ragged.hip; the reference's object -1 would be a slot of the pair in front).  Its neighbours keep
+    the oracle's bits, and every index the pair holds stays inside the pair."""
+    pairs = make_pairs([256, 256, 256], 850)
+    bad = pairs[1][0].copy()
+    bad[97, 2] = np.nan
+    pairs[1] = (bad, pairs[1][1])
+    got, off = run_ragged(gp, pairs, 0.005, 3, mode)
+    check_against_oracle(oracle, got, off, pairs, "t8a", 0.005, 3, mode, skip=(1,))
+    assert got["bid"][off[1] + 97] == 0
+    for name in ("bid", "assignment", "assignment_inv"):
+        v = got[name][off[1]:off[2]]
+        assert ((v >= -1) & (v < 256)).all(), name
+
+
 def test_9_repeat_on_the_same_output_buffers(gp):
     pairs = make_pairs([768, 0, 2304, 256], 900)
     s = garbage_state(gp, offsets(pairs)[-1])
