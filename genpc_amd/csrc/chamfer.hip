@@ -54,22 +54,33 @@ __global__ __launch_bounds__(kBlock) void nn_forward_kernel(NNArgs a)
     __shared__ float4 tile[kTile / 4 * 3 + 3];      // + one spare group for the pipeline's last prefetch
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = threadIdx.x >> 6;
-    int bid = blockIdx.x;
-    const int d = (a.ndir > 1 && bid >= a.dir[1].block_begin) ? 1 : 0;
-    const NNDir &D = a.dir[d];
-    bid -= D.block_begin;
-    // bid = (slice * b + batch) * qblocks + qblock
-    const int qb = bid % D.qblocks;
-    const int rest = bid / D.qblocks;
-    const int batch = rest % a.b;
-    const int slice = rest / a.b;
+    // every kernel argument the block uses, in one round (nn.h, above NN_ARG); the decode divides by multiplying (nn_decode.h)
+    int ndir = a.ndir, nbatch = a.b, slice_len = a.slice_len, debug = a.debug;
+    NNDiv by_b = a.by_b;
+    NN_GLOBAL(int) arrive_g = (NN_GLOBAL(int))a.arrive;
+    NN_ARG(int, begin, block_begin); NN_ARG(int, qblocks, qblocks); NN_ARG(NNDiv, by_q, by_qblocks);
+    NN_ARG(int, nq, nq); NN_ARG(int, nt, nt); NN_ARG(int, slices, slices); NN_ARG(int, ubegin, unit_begin);
+    NN_ARG_PTR(const float, q, q); NN_ARG_PTR(const float, t, t);
+    NN_ARG_PTR(float, out_d, out_d); NN_ARG_PTR(int, out_i, out_i); NN_ARG_PTR(unsigned long long, part, part);
+    asm volatile("" : "+s"(ndir), "+s"(nbatch), "+s"(slice_len), "+s"(debug), "+s"(by_b.mul), "+s"(by_b.shift), "+s"(arrive_g),
+                 NN_HELD(begin), NN_HELD(qblocks), "+s"(by_q_0.mul), "+s"(by_q_0.shift), "+s"(by_q_1.mul), "+s"(by_q_1.shift), NN_HELD(nq), NN_HELD(nt),
+                 NN_HELD(slices), NN_HELD(ubegin), NN_HELD(q), NN_HELD(t), NN_HELD(out_d), NN_HELD(out_i), NN_HELD(part));
+    int *const arrive = (int *)arrive_g;
+    const int d = (ndir > 1 && (int)blockIdx.x >= begin_1) ? 1 : 0;
+    const int qblocks = NN_OF_DIR(qblocks), nq = NN_OF_DIR(nq), nt = NN_OF_DIR(nt), slices = NN_OF_DIR(slices), unit_begin = NN_OF_DIR(ubegin);
+    const float *const q_dir = (const float *)NN_OF_DIR(q), *const t_dir = (const float *)NN_OF_DIR(t);
+    float *const out_d_dir = (float *)NN_OF_DIR(out_d);
+    int *const out_i_dir = (int *)NN_OF_DIR(out_i);
+    unsigned long long *const part_dir = (unsigned long long *)NN_OF_DIR(part);
+    // block id within the direction = (slice * b + batch) * qblocks + qblock
+    const NNBlockId id = nn_decode_block((int)blockIdx.x - NN_OF_DIR(begin), qblocks, NNDiv{NN_OF_DIR(by_q).mul, NN_OF_DIR(by_q).shift}, nbatch, by_b);
+    const int qb = id.qb, batch = id.batch, slice = id.slice;
 
-    const int nq = D.nq, nt = D.nt;
-    const float *__restrict__ Q = D.q + (size_t)batch * nq * 3;
-    const float *__restrict__ T = D.t + (size_t)batch * nt * 3;
+    const float *__restrict__ Q = q_dir + (size_t)batch * nq * 3;
+    const float *__restrict__ T = t_dir + (size_t)batch * nt * 3;
 
-    const int k_begin = slice * a.slice_len;
-    int k_end = k_begin + a.slice_len;
+    const int k_begin = slice * slice_len;
+    int k_end = k_begin + slice_len;
     if (k_end > nt) k_end = nt;
 
     float qx[R], qy[R], qz[R], best[R];
@@ -90,7 +101,7 @@ __global__ __launch_bounds__(kBlock) void nn_forward_kernel(NNArgs a)
     // so that every byte a ds_read_b128 fetches is used (12 B per target).
     float *tile_f = (float *)tile;
     float nf = 0.0f;      // NaN once a target of the slice had a non-finite coordinate
-    for (int t0 = k_begin; t0 < k_end && !(a.debug & 4); t0 += kTile) {
+    for (int t0 = k_begin; t0 < k_end && !(debug & 4); t0 += kTile) {
         const int tn = min(kTile, k_end - t0);
         const int tn_pad = (tn + kChunk - 1) / kChunk * kChunk;
         __syncthreads();                       // readers of the previous tile are done
@@ -148,8 +159,9 @@ __global__ __launch_bounds__(kBlock) void nn_forward_kernel(NNArgs a)
     // Non-finite input: the minimum-of-chunks scan silently skips NaN distances, the reference's
     // tiled scan does not always (nn_exhaustive, nn.h).  A slice that saw a non-finite target marks
     // its partials; queries of such a cloud, and non-finite queries, are answered exhaustively.
-    int bad = __syncthreads_or(nf != nf);
-    if (D.slices > 1) {
+    int *s_or = (int *)tile + 12;              // block_or's four words: beside the exhaustive pass's, which use the tile below
+    int bad = block_or(nf != nf, s_or);
+    if (slices > 1) {
         // Publish this slice's (minimum, chunk) per query; the last block to arrive for
         // this (direction, batch, query block) folds all S slices in slice order with
         // strict '<' (earlier slice == lower index wins) and carries on alone.
@@ -157,8 +169,8 @@ __global__ __launch_bounds__(kBlock) void nn_forward_kernel(NNArgs a)
         // with agent-scope atomics (write-through `sc1` stores, L1-bypassing loads): with
         // 8-byte agent atomics on both sides no release / acquire fence is needed -- a
         // release would write back the whole XCD's dirty L2 lines.
-        const size_t bnq = (size_t)a.b * nq;
-        unsigned long long *P = D.part + (size_t)batch * nq;
+        const size_t bnq = (size_t)nbatch * nq;
+        unsigned long long *P = part_dir + (size_t)batch * nq;
 #pragma unroll
         for (int r = 0; r < R; r++) {
             const int j = q0 + r * kWave;
@@ -167,15 +179,15 @@ __global__ __launch_bounds__(kBlock) void nn_forward_kernel(NNArgs a)
                 __hip_atomic_store(P + (size_t)slice * bnq + j, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
-        if (a.debug & 2) return;
-        int *cnt = a.arrive + D.unit_begin + batch * D.qblocks + qb;
+        if (debug & 2) return;
+        int *cnt = arrive + unit_begin + batch * qblocks + qb;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         int *s_ticket = (int *)tile;      // the tile is dead after the barrier above (one LDS object)
         if (threadIdx.x == 0)
             *s_ticket = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __syncthreads();
-        if (*s_ticket != D.slices - 1) return;
+        if (*s_ticket != slices - 1) return;
         if (threadIdx.x == 0) __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
 #pragma unroll
         for (int r = 0; r < R; r++) {
@@ -186,7 +198,7 @@ __global__ __launch_bounds__(kBlock) void nn_forward_kernel(NNArgs a)
             float bv = __uint_as_float((unsigned)(v >> 32));
             int bc = (int)(unsigned)v;
             if (v == ~0ull) { bv = __builtin_inff(); bc = 0; }      // marked slice: no chunk to recover (the query goes exhaustive)
-            for (int s2 = 1; s2 < D.slices; s2++) {
+            for (int s2 = 1; s2 < slices; s2++) {
                 v = __hip_atomic_load(P + (size_t)s2 * bnq + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 bad |= v == ~0ull;
                 const float vv = __uint_as_float((unsigned)(v >> 32));
@@ -207,8 +219,8 @@ __global__ __launch_bounds__(kBlock) void nn_forward_kernel(NNArgs a)
     // next slice.  Either can only match at a HIGHER position than the true first
     // index, which lies inside the slice, and the lowest match wins.
     typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
-    float *__restrict__ od = D.out_d + (size_t)batch * nq;
-    int *__restrict__ oi = D.out_i + (size_t)batch * nq;
+    float *__restrict__ od = out_d_dir + (size_t)batch * nq;
+    int *__restrict__ oi = out_i_dir + (size_t)batch * nq;
     // the target tile is dead: its LDS holds the list of queries for the exhaustive pass
     __syncthreads();
     int *s_nflag = (int *)tile;
@@ -216,12 +228,12 @@ __global__ __launch_bounds__(kBlock) void nn_forward_kernel(NNArgs a)
     float *s_xred = (float *)(s_nflag + 8);
     int *s_flag = s_nflag + 16;                  // up to kBlock * R entries
     if (threadIdx.x == 0) *s_nflag = 0;
-    bad = __syncthreads_or(bad);                 // merged partials: every lane read the same marks
+    bad = block_or(bad, s_or);                   // merged partials: every lane read the same marks
 #pragma unroll
     for (int r = 0; r < R; r++) {
         const int base = bchunk[r];
         int first = 0;
-        if (!(a.debug & 1)) {
+        if (!(debug & 1)) {
             if (base + kChunk <= nt) {
                 const f4u *tp = (const f4u *)(T + (size_t)base * 3);
 #pragma unroll
@@ -333,22 +345,36 @@ __global__ __launch_bounds__(kBlock) void nn_mfma_kernel(NNArgs a)
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = threadIdx.x >> 6;
     const int half = lane >> 5, col = lane & 31;
-    int bid = blockIdx.x;
-    const int d = (a.ndir > 1 && bid >= a.dir[1].block_begin) ? 1 : 0;
-    const NNDir &D = a.dir[d];
-    bid -= D.block_begin;
-    const int qb = bid % D.qblocks;
-    const int rest = bid / D.qblocks;
-    const int batch = rest % a.b;
-    const int slice = rest / a.b;
+    // every kernel argument the block uses, in one round (nn.h, above NN_ARG); the decode divides by multiplying (nn_decode.h)
+    int ndir = a.ndir, nbatch = a.b, slice_len = a.slice_len, debug = a.debug;
+    NNDiv by_b = a.by_b;
+    NN_GLOBAL(int) arrive_g = (NN_GLOBAL(int))a.arrive;
+    NN_GLOBAL(unsigned long long) stats_g = (NN_GLOBAL(unsigned long long))a.stats;
+    NN_ARG(int, begin, block_begin); NN_ARG(int, qblocks, qblocks); NN_ARG(NNDiv, by_q, by_qblocks);
+    NN_ARG(int, nq, nq); NN_ARG(int, nt, nt); NN_ARG(int, slices, slices); NN_ARG(int, ubegin, unit_begin);
+    NN_ARG_PTR(const float, q, q); NN_ARG_PTR(const float, t, t);
+    NN_ARG_PTR(float, out_d, out_d); NN_ARG_PTR(int, out_i, out_i); NN_ARG_PTR(unsigned long long, part, part);
+    asm volatile("" : "+s"(ndir), "+s"(nbatch), "+s"(slice_len), "+s"(debug), "+s"(by_b.mul), "+s"(by_b.shift), "+s"(arrive_g), "+s"(stats_g),
+                 NN_HELD(begin), NN_HELD(qblocks), "+s"(by_q_0.mul), "+s"(by_q_0.shift), "+s"(by_q_1.mul), "+s"(by_q_1.shift), NN_HELD(nq), NN_HELD(nt),
+                 NN_HELD(slices), NN_HELD(ubegin), NN_HELD(q), NN_HELD(t), NN_HELD(out_d), NN_HELD(out_i), NN_HELD(part));
+    int *const arrive = (int *)arrive_g;
+    unsigned long long *const stats = (unsigned long long *)stats_g;
+    const int d = (ndir > 1 && (int)blockIdx.x >= begin_1) ? 1 : 0;
+    const int qblocks = NN_OF_DIR(qblocks), nq = NN_OF_DIR(nq), nt = NN_OF_DIR(nt), slices = NN_OF_DIR(slices), unit_begin = NN_OF_DIR(ubegin);
+    const float *const q_dir = (const float *)NN_OF_DIR(q), *const t_dir = (const float *)NN_OF_DIR(t);
+    float *const out_d_dir = (float *)NN_OF_DIR(out_d);
+    int *const out_i_dir = (int *)NN_OF_DIR(out_i);
+    unsigned long long *const part_dir = (unsigned long long *)NN_OF_DIR(part);
+    // block id within the direction = (slice * b + batch) * qblocks + qblock
+    const NNBlockId id = nn_decode_block((int)blockIdx.x - NN_OF_DIR(begin), qblocks, NNDiv{NN_OF_DIR(by_q).mul, NN_OF_DIR(by_q).shift}, nbatch, by_b);
+    const int qb = id.qb, batch = id.batch, slice = id.slice;
 
-    const int nq = D.nq, nt = D.nt;
-    const float *__restrict__ Qp = D.q + (size_t)batch * nq * 3;
-    const float *__restrict__ T = D.t + (size_t)batch * nt * 3;
-    const float cx = T[0], cy = T[1], cz = T[2];
+    const float *__restrict__ Qp = q_dir + (size_t)batch * nq * 3;
+    const float *__restrict__ T = t_dir + (size_t)batch * nt * 3;
+    const float cx = NN_CONST(T)[0], cy = NN_CONST(T)[1], cz = NN_CONST(T)[2];
 
-    const int k_begin = slice * a.slice_len;
-    int k_end = k_begin + a.slice_len;
+    const int k_begin = slice * slice_len;
+    int k_end = k_begin + slice_len;
     if (k_end > nt) k_end = nt;
 
     float qx[Q], qy[Q], qz[Q], b0[Q], b1[Q], qq[Q];
@@ -408,7 +434,7 @@ __global__ __launch_bounds__(kBlock) void nn_mfma_kernel(NNArgs a)
 
     float tmax2 = 0.0f;
     float nf = 0.0f;      // NaN once a target of the slice had a non-finite coordinate
-    for (int t0 = k_begin; t0 < k_end && !(a.debug & 4); t0 += kMTile) {
+    for (int t0 = k_begin; t0 < k_end && !(debug & 4); t0 += kMTile) {
         const int tn = min(kMTile, k_end - t0);
         const int tn_pad = (tn + 2 * kC - 1) / (2 * kC) * (2 * kC);
         __syncthreads();
@@ -467,12 +493,12 @@ __global__ __launch_bounds__(kBlock) void nn_mfma_kernel(NNArgs a)
     __syncthreads();
     tmax2 = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
 
-    if (D.slices > 1) {
+    if (slices > 1) {
         // Per query and slice three 8-byte words (a1,c1) (a2,c2) (a3,tmax2), agent-scope
         // atomic stores / loads on both sides (see the VALU kernel); the last block to
         // arrive folds the slices in slice order.
-        const size_t bnq = (size_t)a.b * nq;
-        unsigned long long *P = D.part + (size_t)batch * nq;
+        const size_t bnq = (size_t)nbatch * nq;
+        unsigned long long *P = part_dir + (size_t)batch * nq;
         if (!half) {
 #pragma unroll
             for (int r = 0; r < Q; r++) {
@@ -489,14 +515,14 @@ __global__ __launch_bounds__(kBlock) void nn_mfma_kernel(NNArgs a)
                 }
             }
         }
-        if (a.debug & 2) return;
-        int *cnt = a.arrive + D.unit_begin + batch * D.qblocks + qb;
+        if (debug & 2) return;
+        int *cnt = arrive + unit_begin + batch * qblocks + qb;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (threadIdx.x == 0)
             s_misc[0] = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __syncthreads();
-        if (s_misc[0] != D.slices - 1) return;
+        if (s_misc[0] != slices - 1) return;
         if (threadIdx.x == 0) __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
         for (int r = 0; r < Q; r++) {
@@ -505,7 +531,7 @@ __global__ __launch_bounds__(kBlock) void nn_mfma_kernel(NNArgs a)
             Top3 f;
             top3_init(f);
             float tm = 0.0f;
-            for (int s2 = 0; s2 < D.slices; s2++) {
+            for (int s2 = 0; s2 < slices; s2++) {
                 const unsigned long long *p = P + (size_t)s2 * 3 * bnq + j;
                 const unsigned long long w0 = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 const unsigned long long w1 = __hip_atomic_load(p + bnq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -521,8 +547,8 @@ __global__ __launch_bounds__(kBlock) void nn_mfma_kernel(NNArgs a)
     }
 
     // Decide, re-scan the listed tile(s) exactly, or flag the query for the exhaustive pass.
-    float *__restrict__ od = D.out_d + (size_t)batch * nq;
-    int *__restrict__ oi = D.out_i + (size_t)batch * nq;
+    float *__restrict__ od = out_d_dir + (size_t)batch * nq;
+    int *__restrict__ oi = out_i_dir + (size_t)batch * nq;
     __syncthreads();
     if (threadIdx.x == 0) s_misc[1] = 0;
     __syncthreads();
@@ -530,11 +556,11 @@ __global__ __launch_bounds__(kBlock) void nn_mfma_kernel(NNArgs a)
     for (int r = 0; r < Q; r++) {
         const Top3 &f = st[r];
         bool two = false, flag = false;
-        if (!nn_safe(f.a1, f.a2, qq[r], tmax2) || (a.debug & 16)) {
+        if (!nn_safe(f.a1, f.a2, qq[r], tmax2) || (debug & 16)) {
             two = true;
             if (!nn_safe(f.a1, f.a3, qq[r], tmax2) || f.c2 < 0) flag = true;
         }
-        if (f.c1 < 0 || (a.debug & 8)) flag = true;
+        if (f.c1 < 0 || (debug & 8)) flag = true;
         if (!(tmax2 < __builtin_inff()) || !(qq[r] < __builtin_inff())) flag = true;      // non-finite input
         const int j = q0 + r * 32;
         if (flag) {
@@ -545,7 +571,7 @@ __global__ __launch_bounds__(kBlock) void nn_mfma_kernel(NNArgs a)
         const int base = half ? f.c2 : f.c1;
         float bd = __builtin_inff();
         int bi = 0;
-        if ((!half || (two && f.c2 != f.c1)) && !(a.debug & 1)) rescan_chunk<FMA, kC>(T, nt, base, qx[r], qy[r], qz[r], bd, bi);
+        if ((!half || (two && f.c2 != f.c1)) && !(debug & 1)) rescan_chunk<FMA, kC>(T, nt, base, qx[r], qy[r], qz[r], bd, bi);
         const float obd = __shfl_xor(bd, 32);
         const int obi = __shfl_xor(bi, 32);
         if (!half && j < nq) {
@@ -556,9 +582,9 @@ __global__ __launch_bounds__(kBlock) void nn_mfma_kernel(NNArgs a)
     }
     __syncthreads();
     const int nflag = s_misc[1];
-    if (a.stats && threadIdx.x == 0) {
-        atomicAdd(&a.stats[0], (unsigned long long)min(128 * Q, nq - qb * 128 * Q));
-        atomicAdd(&a.stats[1], (unsigned long long)nflag);
+    if (stats && threadIdx.x == 0) {
+        atomicAdd(&stats[0], (unsigned long long)min(128 * Q, nq - qb * 128 * Q));
+        atomicAdd(&stats[1], (unsigned long long)nflag);
     }
     for (int fidx = 0; fidx < nflag; fidx++) nn_exhaustive<FMA>(Qp, T, nt, s_flag[fidx], od, oi, s_red, s_fi);
 }
@@ -834,11 +860,13 @@ int nn_forward(int b, int ndir, const float *q0, int n0, const float *t0, int m0
     }
     a.slice_len = plan.slice_len;
     a.hint_stride = plan.hint_stride;
+    a.by_b = nn_div_make(b);
     bool any_partials = false;
     for (int d = 0; d < nd; d++) {
         NNDir &D = a.dir[d];
         const NNPlanDir &P = plan.dir[d];
         D.qblocks = P.qblocks;
+        D.by_qblocks = nn_div_make(P.qblocks);
         D.slices = D.ntmax = P.slices;      // (ntmax: the f16 filter keeps one maximum per slice)
         D.block_begin = P.block_begin;
         D.unit_begin = P.unit_begin;

@@ -5,44 +5,74 @@
 #include "common.h"
 #include "grid.h"
 #include "nn_plan.h"      // kChunk, kBlock, kMaxLists, kHTile, kFQ; NNPlan
+#include "nn_decode.h"    // NNDiv; which (query block, batch element, slice) a block is
 
 namespace genpc {
 
 constexpr int kWavesPerBlock = kBlock / kWave;
 
+// (The fields stand in the order in which the kernels read them at entry -- what one kernel uses is adjacent, so that its
+// round of argument loads is a few wide ones: the filter reads dupmask .. t and block_begin .. slices, the finish step
+// tmaxp .. out_i and nq .. ntmax, the single-launch kernels part .. out_i and block_begin .. slices.)
 struct NNDir {
+    const unsigned *dupmask;   // [B][ceil(nt / 32)]: targets that are later copies of a bit-identical target (nn_dedupe.hip), or null
+    // split-f16 path (nn_f16.hip / nn_finish.hip)
+    float *tmaxp;           // partial maxima of |t'|^2 [B][ntmax] (per slice, or per split block)
+    unsigned long long *part;   // per-slice partials [S, B*nq] (S > 1): distance bits << 32 | chunk
     const float *q;    // queries  [B, nq, 3]
     const float *t;    // targets  [B, nt, 3]
     float *out_d;      // final    [B, nq]
     int *out_i;
-    unsigned long long *part;   // per-slice partials [S, B*nq] (S > 1): distance bits << 32 | chunk
-    int nq, nt;
-    // split-f16 path (nn_f16.hip / nn_finish.hip)
-    float *tmaxp;           // partial maxima of |t'|^2 [B][ntmax] (per slice, or per split block)
     const uint4 *arec;      // pre-split targets [B][4 planes][ntp] x 16 B
-    int ntp, ntmax;         // nt rounded up to 128; entries of tmaxp per batch element
-    int fin_begin;          // first nn_finish_kernel block of this direction
-    const unsigned *dupmask;   // [B][ceil(nt / 32)]: targets that are later copies of a bit-identical target (nn_dedupe.hip), or null
-    int dup_shared;            // the mask is [1][ceil(nt / 32)] and serves every batch element (scaled / replicated copies of one cloud)
-    int qblocks;       // ceil(nq / (256*R))
-    int slices;        // S for this direction: ceil(nt / slice_len)
     int block_begin;   // first block id of this direction
+    int dup_shared;            // the mask is [1][ceil(nt / 32)] and serves every batch element (scaled / replicated copies of one cloud)
+    NNDiv by_qblocks;  // the block decode's divisors as multiplier and shift (nn_decode.h); filled where the plan is copied in
+    int qblocks;       // ceil(nq / (256*R))
+    int nq, nt;
+    int slices;        // S for this direction: ceil(nt / slice_len)
+    int fin_begin;          // first nn_finish_kernel block of this direction
+    NNDiv by_fblocks;  // ... by the finish blocks per batch element, nn_fin_blocks(nq)
+    int ntmax;         // entries of tmaxp per batch element
     int unit_begin;    // first arrival counter of this direction
+    int ntp;           // nt rounded up to 128
 };
 
 struct NNArgs {
     NNDir dir[2];
+    int slice_len;     // targets per slice (all blocks of a launch do equal work), multiple of kChunk
+    NNDiv by_b;        // nn_decode.h: division by b
     int ndir;
     int b;
-    int slice_len;     // targets per slice (all blocks of a launch do equal work), multiple of kChunk
-    int *arrive;       // [sum_d b*qblocks] arrival counters, zero between launches
     int debug;         // experiment switches (GENPC_NN_DEBUG): 1 skip index recovery, 2 skip merge, 4 skip main loop
+    int hint_stride;   // every hint_stride-th finish block reports to `hint` (scaled up)
+    NNDiv by_hint;     // ... and the division by it
     int fma;           // arithmetic mode of this call (read once at the entry point; host side only)
     unsigned long long *stats;   // hook 512: [0] queries, [1] exhaustive re-dos, [2] exact pieces; else null
-    int hint_stride;   // every hint_stride-th finish block reports to `hint` (scaled up)
     unsigned *hint;    // host-visible word: exhaustive re-dos of the filtered path are added to it (dedupe policy, chamfer.hip), or null
+    int *arrive;       // [sum_d b*qblocks] arrival counters, zero between launches
     float radius2;     // grid path only: search limit (squared); +inf = none.  Queries with no target within it get (+inf, -1)
 };
+
+// Kernel arguments are read ONCE, at kernel entry, in one round of scalar loads with compile-time offsets: the scalar cache is
+// cold at the start of every launch and all blocks start together, so every further round is a miss for every block at once.
+// The compiler left to itself loads an argument next to its first use (behind barriers and vector loads), and turns
+// `d ? a.dir[1].f : a.dir[0].f` into a load from a selected ADDRESS, which waits for d.  So each of the four kernels copies
+// what it uses -- of BOTH directions -- into locals and names them all in ONE empty asm that claims to modify them: every
+// load stands in front of it, and the direction's fields are selected from values.  (One asm per value was tried first: the
+// scheduler put the first of them between the loads -- two rounds again in some instantiations.)  Pointers go through the asm
+// as what every pointer in NNArgs is, pointers to global memory: a generic one would come out without its address space
+// (flat_load instead of global_load, and the centre no longer through the scalar cache).  Pointers out of the arguments are
+// dereferenced where they were: a second round, which overlaps the vector loads.
+#define NN_GLOBAL(T) __attribute__((address_space(1))) T *
+// An input cloud is not written while a launch that reads it runs: a block's common centre -- the same three words for every
+// lane -- comes through the scalar cache into SGPRs, as it did when the compiler could see that the pointer was a
+// `const __restrict__` argument.  The same contract as then: a caller that lets an OUTPUT of the call alias an input cloud
+// gets stale centres from the scalar cache, silently (the cache is invalidated at the start of a kernel, not during it).
+#define NN_CONST(p) ((const __attribute__((address_space(4))) float *)(p))
+#define NN_ARG(T, name, field) T name##_0 = a.dir[0].field, name##_1 = a.dir[1].field
+#define NN_ARG_PTR(T, name, field) NN_GLOBAL(T) name##_0 = (NN_GLOBAL(T))a.dir[0].field; NN_GLOBAL(T) name##_1 = (NN_GLOBAL(T))a.dir[1].field
+#define NN_HELD(name) "+s"(name##_0), "+s"(name##_1)
+#define NN_OF_DIR(name) (d ? name##_1 : name##_0)
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -148,6 +178,23 @@ __device__ __forceinline__ int tile_row(int w) { return 8 * ((w >> 2) & 3) + 4 *
 // and is never replaced.  A NaN elsewhere only drops that target; with nothing below +inf
 // the first target stays.  Must be called by all threads of the block.
 constexpr int kRefTile = 512;    // chamfer3D.cu:13 `const int batch=512`
+
+// Is v non-zero in any thread of the block?  Through s, one word per wave; must be called by all threads.  (Not
+// __syncthreads_or: the device library's reduction reads the workgroup size from the implicit kernel arguments -- a scalar
+// load of its own, late in the kernel, and a miss for every block.)  For blocks of kBlock threads: s holds kWavesPerBlock
+// words (the filter's eight-wave form does not call it).
+__device__ __forceinline__ int block_or(int v, int *s)
+{
+    static_assert(kWavesPerBlock * kWave == kBlock, "block_or folds one word per wave of a kBlock-thread block");
+    const int any = __ballot(v != 0) != 0ull;
+    __syncthreads();                     // whoever read s before is done
+    if ((threadIdx.x & (kWave - 1)) == 0) s[threadIdx.x >> 6] = any;
+    __syncthreads();
+    int r = 0;
+#pragma unroll
+    for (int w = 0; w < kWavesPerBlock; w++) r |= s[w];
+    return r;
+}
 template <int FMA>
 __device__ __forceinline__ void nn_exhaustive(const float *__restrict__ Qp, const float *__restrict__ T, int nt, int j,
                                               float *__restrict__ od, int *__restrict__ oi, float *s_red, int *s_fi)
@@ -161,7 +208,7 @@ __device__ __forceinline__ void nn_exhaustive(const float *__restrict__ Qp, cons
         const float hd = sqdist<FMA>(tp[0] - x, tp[1] - y, tp[2] - z);
         dead |= hd != hd;
     }
-    dead = __syncthreads_or(dead);
+    dead = block_or(dead, s_fi);      // (s_fi is written again behind the barrier below)
     float bd = __builtin_inff();
     int bi = 0x7fffffff;
     if (!dead) {

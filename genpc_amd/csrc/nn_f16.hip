@@ -33,9 +33,12 @@ typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
 // tools/nn_timeline.py builds a private copy of the library with -DGENPC_NN_TIMELINE: thread 0 of every block stamps the
 // shader clock at the phase boundaries of nn_f16_kernel (nothing of this exists in the shipped library)
 #ifdef GENPC_NN_TIMELINE
-__device__ unsigned long long g_timeline[4096 * 8];
-#define GENPC_TL(k) do { if (threadIdx.x == 0 && blockIdx.x < 4096) { g_timeline[blockIdx.x * 8 + (k)] = __builtin_readcyclecounter(); \
-    if ((k) == 0) g_timeline[blockIdx.x * 8 + 6] = wall_clock64(); if ((k) == 5) g_timeline[blockIdx.x * 8 + 7] = wall_clock64(); } } while (0)
+// (rows of kTimelineRow words: 0-5 the phase boundaries, 6-7 the wall clock at a block's start and end, 8 the moment before the
+// block's first vector load is issued -- everything in front of it is kernel arguments and the block decode)
+constexpr int kTimelineRow = 16;
+__device__ unsigned long long g_timeline[4096 * kTimelineRow];
+#define GENPC_TL(k) do { if (threadIdx.x == 0 && blockIdx.x < 4096) { g_timeline[blockIdx.x * kTimelineRow + (k)] = __builtin_readcyclecounter(); \
+    if ((k) == 0) g_timeline[blockIdx.x * kTimelineRow + 6] = wall_clock64(); if ((k) == 5) g_timeline[blockIdx.x * kTimelineRow + 7] = wall_clock64(); } } while (0)
 #else
 #define GENPC_TL(k) do {} while (0)
 #endif
@@ -91,24 +94,35 @@ __global__ __launch_bounds__(WV * kWave, W) void nn_f16_kernel(NNArgs a)
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = threadIdx.x >> 6;
     const int half = lane >> 5, col = lane & 31;
-    int bid = blockIdx.x;
-    const int d = (a.ndir > 1 && bid >= a.dir[1].block_begin) ? 1 : 0;
-    const NNDir &D = a.dir[d];
-    bid -= D.block_begin;
-    const int qb = bid % D.qblocks;
-    const int rest = bid / D.qblocks;
-    const int batch = rest % a.b;
-    const int slice = rest / a.b;
+    // every kernel argument the block uses, in one round (nn.h, above NN_ARG); the decode divides by multiplying (nn_decode.h)
+    int ndir = a.ndir, nbatch = a.b, slice_len = a.slice_len, debug = a.debug;
+    NNDiv by_b = a.by_b;
+    NN_ARG(int, begin, block_begin); NN_ARG(int, qblocks, qblocks); NN_ARG(NNDiv, by_q, by_qblocks);
+    NN_ARG(int, nq, nq); NN_ARG(int, nt, nt); NN_ARG(int, slices, slices); NN_ARG(int, dupsh, dup_shared);
+    NN_ARG_PTR(const float, q, q); NN_ARG_PTR(const float, t, t); NN_ARG_PTR(const unsigned, dup, dupmask);
+    NN_ARG_PTR(float, tmaxp, tmaxp); NN_ARG_PTR(unsigned long long, part, part);
+    asm volatile("" : "+s"(ndir), "+s"(nbatch), "+s"(slice_len), "+s"(debug), "+s"(by_b.mul), "+s"(by_b.shift), NN_HELD(begin), NN_HELD(qblocks),
+                 "+s"(by_q_0.mul), "+s"(by_q_0.shift), "+s"(by_q_1.mul), "+s"(by_q_1.shift), NN_HELD(nq), NN_HELD(nt), NN_HELD(slices), NN_HELD(dupsh),
+                 NN_HELD(q), NN_HELD(t), NN_HELD(dup), NN_HELD(tmaxp), NN_HELD(part));
+    const int d = (ndir > 1 && (int)blockIdx.x >= begin_1) ? 1 : 0;
+    const int qblocks = NN_OF_DIR(qblocks), nq = NN_OF_DIR(nq), nt = NN_OF_DIR(nt), slices = NN_OF_DIR(slices), dup_shared = NN_OF_DIR(dupsh);
+    const float *const q_dir = (const float *)NN_OF_DIR(q), *const t_dir = (const float *)NN_OF_DIR(t);
+    const float *const t_dir0 = (const float *)t_0;
+    const int nt_dir0 = nt_0;
+    const unsigned *const dup_dir = (const unsigned *)NN_OF_DIR(dup);
+    float *const tmaxp_dir = (float *)NN_OF_DIR(tmaxp);
+    unsigned long long *const part_dir = (unsigned long long *)NN_OF_DIR(part);
+    const NNBlockId id = nn_decode_block((int)blockIdx.x - NN_OF_DIR(begin), qblocks, NNDiv{NN_OF_DIR(by_q).mul, NN_OF_DIR(by_q).shift}, nbatch, by_b);
+    const int qb = id.qb, batch = id.batch, slice = id.slice;
 
-    const int nq = D.nq, nt = D.nt;
-    const float *__restrict__ Qp = D.q + (size_t)batch * nq * 3;
-    const float *__restrict__ T = D.t + (size_t)batch * nt * 3;
+    const float *__restrict__ Qp = q_dir + (size_t)batch * nq * 3;
+    const float *__restrict__ T = t_dir + (size_t)batch * nt * 3;
     // both clouds are centred on the first point of the direction-0 target cloud
-    const float *cptr = a.dir[0].t + (size_t)batch * a.dir[0].nt * 3;
+    const auto cptr = NN_CONST(t_dir0 + (size_t)batch * nt_dir0 * 3);
     const float cx = cptr[0], cy = cptr[1], cz = cptr[2];
 
-    const int k_begin = slice * a.slice_len;
-    int k_end = k_begin + a.slice_len;
+    const int k_begin = slice * slice_len;
+    int k_end = k_begin + slice_len;
     if (k_end > nt) k_end = nt;
 
     // Prologue loads: this lane's queries and -- when the slice fits one LDS tile -- the block's whole slice are
@@ -119,6 +133,7 @@ __global__ __launch_bounds__(WV * kWave, W) void nn_f16_kernel(NNArgs a)
     // a load that every lane issues needs no branch, and a branch would hold its own wait)
     float raw0[Q], raw1[Q];
     const int q0 = (qb * WV + wave) * (32 * Q) + col;
+    GENPC_TL(8);
 #pragma unroll
     for (int r = 0; r < Q; r++) {
         int j = q0 + r * 32;
@@ -138,7 +153,7 @@ __global__ __launch_bounds__(WV * kWave, W) void nn_f16_kernel(NNArgs a)
     float pre[kPer][3];
     // later copies of a bit-identical target (nn_dedupe.hip; bit i: this thread's i-th target of the tile) are staged like
     // padding: the first copy answers for them, and three equal minima in one list would send the query to the exhaustive pass
-    const unsigned *__restrict__ dupm = D.dupmask ? D.dupmask + (D.dup_shared ? (size_t)0 : (size_t)batch * ((nt + 31) >> 5)) : nullptr;
+    const unsigned *__restrict__ dupm = dup_dir ? dup_dir + (dup_shared ? (size_t)0 : (size_t)batch * ((nt + 31) >> 5)) : nullptr;
     unsigned predup = 0u;
     auto prefetch = [&](int t0) {
         predup = 0u;
@@ -242,7 +257,7 @@ __global__ __launch_bounds__(WV * kWave, W) void nn_f16_kernel(NNArgs a)
     float tmax2 = 0.0f;
     float nf = 0.0f;      // NaN once a target of the slice had a non-finite coordinate
     if (!resident && k_begin < k_end) prefetch(k_begin);
-    for (int t0 = k_begin; t0 < k_end && !(a.debug & 4); t0 += HT) {
+    for (int t0 = k_begin; t0 < k_end && !(debug & 4); t0 += HT) {
         const int tn = min(HT, k_end - t0);
         const int tn_pad = (tn + kC - 1) / kC * kC;
         __syncthreads();                 // every wave is done reading the previous tile
@@ -324,13 +339,13 @@ __global__ __launch_bounds__(WV * kWave, W) void nn_f16_kernel(NNArgs a)
         float tm = s_red[0];
 #pragma unroll
         for (int w2 = 1; w2 < WV; w2++) tm = fmaxf(tm, s_red[w2]);
-        if (threadIdx.x == 0) D.tmaxp[(size_t)batch * D.slices + slice] = tm;
+        if (threadIdx.x == 0) tmaxp_dir[(size_t)batch * slices + slice] = tm;
     }
 
     // Publish the lists: the two lane halves folded, NL lists of two 8-byte words per query and slice
     // (a1, c1) (codes of a2 and a3, c2): list_enc in nn.h.
-    const size_t bnq = (size_t)a.b * nq;
-    unsigned long long *P = D.part + (size_t)batch * nq;
+    const size_t bnq = (size_t)nbatch * nq;
+    unsigned long long *P = part_dir + (size_t)batch * nq;
 #pragma unroll
     for (int r = 0; r < Q; r++) {
 #pragma unroll
@@ -423,7 +438,7 @@ int launch_nn_f16(NNArgs &a, const NNPlan &plan, hipStream_t st)
 #ifdef GENPC_NN_TIMELINE
 extern "C" __attribute__((visibility("default"))) int genpc_nn_timeline_read(unsigned long long *out)
 {
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(genpc::g_timeline), sizeof(unsigned long long) * 4096 * 8) == hipSuccess;
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(genpc::g_timeline), sizeof(unsigned long long) * 4096 * genpc::kTimelineRow) == hipSuccess;
 }
 #endif
 

@@ -21,8 +21,9 @@
 namespace genpc {
 
 #ifdef GENPC_NN_TIMELINE       // tools/nn_timeline.py (see nn_f16.hip)
-__device__ unsigned long long g_timeline_fin[4096 * 8];
-#define GENPC_TLF(k) do { if (threadIdx.x == 0 && blockIdx.x < 4096) g_timeline_fin[blockIdx.x * 8 + (k)] = __builtin_readcyclecounter(); } while (0)
+constexpr int kTimelineRowFin = 16;      // 0-5 the phase boundaries, 8 the moment before the first vector load is issued
+__device__ unsigned long long g_timeline_fin[4096 * kTimelineRowFin];
+#define GENPC_TLF(k) do { if (threadIdx.x == 0 && blockIdx.x < 4096) g_timeline_fin[blockIdx.x * kTimelineRowFin + (k)] = __builtin_readcyclecounter(); } while (0)
 #else
 #define GENPC_TLF(k) do {} while (0)
 #endif
@@ -49,20 +50,38 @@ __global__ __launch_bounds__(kBlock) void nn_finish_kernel(NNArgs a, int nl, int
     __shared__ int s_misc[3];                    // work items, flagged queries, pieces evaluated (stats hook)
     GENPC_TLF(0);
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-    int bid = blockIdx.x;
-    const int d = (a.ndir > 1 && bid >= a.dir[1].fin_begin) ? 1 : 0;
-    const NNDir &D = a.dir[d];
-    bid -= D.fin_begin;
-    const int nq = D.nq, nt = D.nt;
-    const int fblocks = (nq + kFQ - 1) / kFQ;
-    const int batch = bid / fblocks, fb = bid % fblocks;
-    const float *__restrict__ Qp = D.q + (size_t)batch * nq * 3;
-    const float *__restrict__ T = D.t + (size_t)batch * nt * 3;
-    float *__restrict__ od = D.out_d + (size_t)batch * nq;
-    int *__restrict__ oi = D.out_i + (size_t)batch * nq;
-    const size_t bnq = (size_t)a.b * nq;
-    const unsigned long long *P = D.part + (size_t)batch * nq;
-    const int nlists = D.slices * nl;
+    // every kernel argument the block uses, in one round (nn.h, above NN_ARG); the decode divides by multiplying (nn_decode.h)
+    int ndir = a.ndir, nbatch = a.b, debug = a.debug, hint_stride = a.hint_stride;
+    NNDiv by_hint = a.by_hint;
+    NN_GLOBAL(unsigned long long) stats_g = (NN_GLOBAL(unsigned long long))a.stats;
+    NN_GLOBAL(unsigned) hint_g = (NN_GLOBAL(unsigned))a.hint;
+    NN_ARG(int, begin, fin_begin); NN_ARG(NNDiv, by_f, by_fblocks);
+    NN_ARG(int, nq, nq); NN_ARG(int, nt, nt); NN_ARG(int, slices, slices); NN_ARG(int, ntmax, ntmax);
+    NN_ARG_PTR(const float, q, q); NN_ARG_PTR(const float, t, t); NN_ARG_PTR(const float, tmaxp, tmaxp);
+    NN_ARG_PTR(float, out_d, out_d); NN_ARG_PTR(int, out_i, out_i); NN_ARG_PTR(const unsigned long long, part, part);
+    asm volatile("" : "+s"(ndir), "+s"(nbatch), "+s"(debug), "+s"(hint_stride), "+s"(by_hint.mul), "+s"(by_hint.shift), "+s"(stats_g), "+s"(hint_g),
+                 "+s"(nl), "+s"(upieces), "+s"(kqt), "+s"(ktt), "+s"(t2min), NN_HELD(begin),
+                 "+s"(by_f_0.mul), "+s"(by_f_0.shift), "+s"(by_f_1.mul), "+s"(by_f_1.shift), NN_HELD(nq), NN_HELD(nt), NN_HELD(slices), NN_HELD(ntmax),
+                 NN_HELD(q), NN_HELD(t), NN_HELD(tmaxp), NN_HELD(out_d), NN_HELD(out_i), NN_HELD(part));
+    unsigned long long *const stats = (unsigned long long *)stats_g;
+    unsigned *const hint = (unsigned *)hint_g;
+    const int d = (ndir > 1 && (int)blockIdx.x >= begin_1) ? 1 : 0;
+    const int nq = NN_OF_DIR(nq), nt = NN_OF_DIR(nt), fblocks = nn_fin_blocks(nq), slices = NN_OF_DIR(slices), ntmax = NN_OF_DIR(ntmax);
+    const float *const q_dir = (const float *)NN_OF_DIR(q), *const t_dir = (const float *)NN_OF_DIR(t), *const tmaxp_dir = (const float *)NN_OF_DIR(tmaxp);
+    const float *const t_dir0 = (const float *)t_0;
+    const int nt_dir0 = nt_0;
+    float *const out_d_dir = (float *)NN_OF_DIR(out_d);
+    int *const out_i_dir = (int *)NN_OF_DIR(out_i);
+    const unsigned long long *const part_dir = (const unsigned long long *)NN_OF_DIR(part);
+    const NNFinId id = nn_decode_fin((int)blockIdx.x - NN_OF_DIR(begin), fblocks, NNDiv{NN_OF_DIR(by_f).mul, NN_OF_DIR(by_f).shift});
+    const int batch = id.batch, fb = id.fb;
+    const float *__restrict__ Qp = q_dir + (size_t)batch * nq * 3;
+    const float *__restrict__ T = t_dir + (size_t)batch * nt * 3;
+    float *__restrict__ od = out_d_dir + (size_t)batch * nq;
+    int *__restrict__ oi = out_i_dir + (size_t)batch * nq;
+    const size_t bnq = (size_t)nbatch * nq;
+    const unsigned long long *P = part_dir + (size_t)batch * nq;
+    const int nlists = slices * nl;
 
     const int ql = threadIdx.x & (kFQ - 1), part = threadIdx.x >> 6;     // part == wave
     int j = fb * kFQ + ql;
@@ -75,15 +94,15 @@ __global__ __launch_bounds__(kBlock) void nn_finish_kernel(NNArgs a, int nl, int
     // each value was first needed they made four round trips in a row -- DESIGN_NOTEBOOK.md, "prologue loads").
     // The query goes FIRST: it is the one that is not in L2 any more (the lists and maxima were written a moment ago), and
     // with the lists ahead of it the block was no faster than before (measured).
-    const float *cptr = a.dir[0].t + (size_t)batch * a.dir[0].nt * 3;      // common centre of the filter
+    const auto cptr = NN_CONST(t_dir0 + (size_t)batch * nt_dir0 * 3);      // common centre of the filter
     const float ccx = cptr[0], ccy = cptr[1], ccz = cptr[2];
     // EARLY: every thread of a query holds the query itself (s_q serves the work-list phase, where items change hands);
     // otherwise wave 0 loads it for the block
     float4 qv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    GENPC_TLF(8);
     if (EARLY || part == 0) qv = make_float4(Qp[(size_t)j * 3 + 0], Qp[(size_t)j * 3 + 1], Qp[(size_t)j * 3 + 2], 0.0f);
     // per-slice maxima of |t'|^2 (filter kernel): the first trip of the loop below, peeled (ntmax >= 1; index clamped)
-    const int ntmax = D.ntmax;
-    const float *tmp = D.tmaxp + (size_t)batch * ntmax;
+    const float *tmp = tmaxp_dir + (size_t)batch * ntmax;
     const bool tm_mine = (int)threadIdx.x < ntmax;
     const float tm0 = tmp[tm_mine ? (int)threadIdx.x : 0];
     // this thread's lists: li = part + 4k
@@ -144,7 +163,7 @@ __global__ __launch_bounds__(kBlock) void nn_finish_kernel(NNArgs a, int nl, int
     int pieces = 0;
     bool has_piece = false;
     HalfPiece piece;
-    if (cb >= 0 && live && !(a.debug & 1)) {
+    if (cb >= 0 && live && !(debug & 1)) {
         const int left = (nt - (cb & ~1) + 31) >> 5;
         has_piece = part < (left < upieces ? left : upieces);
     }
@@ -163,7 +182,7 @@ __global__ __launch_bounds__(kBlock) void nn_finish_kernel(NNArgs a, int nl, int
         // non-finite targets anywhere in the cloud (the filter publishes +inf) or a non-finite query:
         // the reference's result depends on its 512-target tiling, only nn_exhaustive reproduces it
         if (!(tmax2 < __builtin_inff()) || !(qq < __builtin_inff())) tau = __builtin_nanf("");
-        if (a.debug & 16) tau = __builtin_inff();          // test hook: every listed tile is evaluated
+        if (debug & 16) tau = __builtin_inff();          // test hook: every listed tile is evaluated
         // (the compiler sinks the arithmetic to the threshold's first use, behind the piece, unless it is held here)
         if (EARLY) asm volatile("" : "+v"(tau));
     }
@@ -178,7 +197,7 @@ __global__ __launch_bounds__(kBlock) void nn_finish_kernel(NNArgs a, int nl, int
     }
     if (mine != ~0ull) atomicMin(&s_best[ql], mine);
     GENPC_TLF(2);
-    bool flag = (a.debug & 8) != 0 || !(tau == tau);   // test hook / non-finite input: exhaustive pass
+    bool flag = (debug & 8) != 0 || !(tau == tau);   // test hook / non-finite input: exhaustive pass
     int ncand = 0;
     // any OTHER listed unit whose minimum is not provably out becomes work items of 16 targets for the block
     auto consider = [&](float av, int c, bool is_best) {
@@ -210,7 +229,7 @@ __global__ __launch_bounds__(kBlock) void nn_finish_kernel(NNArgs a, int nl, int
         consider(a2, (int)(unsigned)w1[k], false);
     }
     if (flag && live) s_qflag[ql] = 1;
-    if (a.debug & 32) {      // diagnostics: approximate minimum and candidate count instead of the result
+    if (debug & 32) {      // diagnostics: approximate minimum and candidate count instead of the result
         __syncthreads();
         if (part == 0) s_a[0][ql] = 0.0f;
         __syncthreads();
@@ -222,7 +241,7 @@ __global__ __launch_bounds__(kBlock) void nn_finish_kernel(NNArgs a, int nl, int
     __syncthreads();
     GENPC_TLF(3);
     const int nwork = min(s_misc[0], kFWork);
-    if (nwork > 0 && !(a.debug & 1)) {               // block-uniform
+    if (nwork > 0 && !(debug & 1)) {               // block-uniform
         for (int w = threadIdx.x; w < nwork; w += kBlock) {
             const unsigned it = s_work[w];
             const int slot = (int)(it >> 22);
@@ -235,7 +254,7 @@ __global__ __launch_bounds__(kBlock) void nn_finish_kernel(NNArgs a, int nl, int
         }
         __syncthreads();
     }
-    if (a.stats && pieces) atomicAdd(&s_misc[2], pieces);
+    if (stats && pieces) atomicAdd(&s_misc[2], pieces);
     __syncthreads();
     GENPC_TLF(4);
     if (part == 0 && live) {
@@ -253,20 +272,24 @@ __global__ __launch_bounds__(kBlock) void nn_finish_kernel(NNArgs a, int nl, int
     // without such queries -- all of them on ordinary input -- do nothing
     // (sampled: every hint_stride-th block, scaled up -- at most 16 atomics on host memory per launch; they cost ~0.3 us
     // each and the kernel does not end before the last one has landed)
-    if (nflag && a.hint && threadIdx.x == 0 && blockIdx.x % a.hint_stride == 0 && !(tmax2 != tmax2) && tmax2 < __builtin_inff())
-        __hip_atomic_fetch_add(a.hint, (unsigned)(nflag * a.hint_stride), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    if (a.stats && threadIdx.x == 0) {
-        atomicAdd(&a.stats[0], (unsigned long long)min(kFQ, nq - fb * kFQ));
-        atomicAdd(&a.stats[1], (unsigned long long)nflag);
-        atomicAdd(&a.stats[2], (unsigned long long)s_misc[2]);
+    if (nflag && hint && threadIdx.x == 0 && nn_is_multiple((int)blockIdx.x, hint_stride, by_hint) && !(tmax2 != tmax2) && tmax2 < __builtin_inff())
+        __hip_atomic_fetch_add(hint, (unsigned)(nflag * hint_stride), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (stats && threadIdx.x == 0) {
+        atomicAdd(&stats[0], (unsigned long long)min(kFQ, nq - fb * kFQ));
+        atomicAdd(&stats[1], (unsigned long long)nflag);
+        atomicAdd(&stats[2], (unsigned long long)s_misc[2]);
     }
     for (int fidx = 0; fidx < nflag; fidx++) nn_exhaustive<FMA>(Qp, T, nt, s_flagged[fidx], od, oi, s_red, s_fi);
     GENPC_TLF(5);
 }
 
 // Second launch of the filtered paths, as the plan says.  kqt / ktt: coefficients of the filter's error bound.
-int launch_nn_finish(const NNArgs &a, const NNPlan &plan, float kqt, float ktt, float t2min, hipStream_t st)
+int launch_nn_finish(const NNArgs &args, const NNPlan &plan, float kqt, float ktt, float t2min, hipStream_t st)
 {
+    // the finish blocks' decode (nn_decode.h)
+    NNArgs a = args;
+    for (int d = 0; d < a.ndir; d++) a.dir[d].by_fblocks = nn_div_make(nn_fin_blocks(a.dir[d].nq));
+    a.by_hint = nn_div_make(a.hint_stride);
 #define NN_FINISH_LAUNCH(FMA, EARLY) \
     hipLaunchKernelGGL((nn_finish_kernel<FMA, EARLY>), dim3((unsigned)plan.fin_blocks), dim3(kBlock), 0, st, a, plan.nl, plan.unit, kqt, ktt, t2min)
     if (a.fma) { if (plan.early) NN_FINISH_LAUNCH(1, 1); else NN_FINISH_LAUNCH(1, 0); }
@@ -280,6 +303,6 @@ int launch_nn_finish(const NNArgs &a, const NNPlan &plan, float kqt, float ktt, 
 #ifdef GENPC_NN_TIMELINE
 extern "C" __attribute__((visibility("default"))) int genpc_nn_timeline_read_finish(unsigned long long *out)
 {
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(genpc::g_timeline_fin), sizeof(unsigned long long) * 4096 * 8) == hipSuccess;
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(genpc::g_timeline_fin), sizeof(unsigned long long) * 4096 * genpc::kTimelineRowFin) == hipSuccess;
 }
 #endif

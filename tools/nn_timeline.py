@@ -45,9 +45,10 @@ torch.cuda.synchronize()
 L = ctypes.CDLL(_lib.LIB_PATH)
 if not hasattr(L, "genpc_nn_timeline_read"):
     sys.exit("this library was not built with -DGENPC_NN_TIMELINE (python tools/nn_timeline.py --build, then GENPC_LIB=...)")
-buf = (ctypes.c_ulonglong * (4096 * 8))()
+ROW = 16      # words per block: 0-5 phase boundaries, 6-7 wall clock at start and end, 8 before the first vector load
+buf = (ctypes.c_ulonglong * (4096 * ROW))()
 assert L.genpc_nn_timeline_read(buf)
-t = np.frombuffer(buf, dtype=np.uint64).reshape(4096, 8).astype(np.int64)
+t = np.frombuffer(buf, dtype=np.uint64).reshape(4096, ROW).astype(np.int64)
 if os.environ.get("NN_TIMELINE_BLOCKS"):
     # per XCD (block id % 8): start and end of every block relative to the XCD's first start, in block order
     # slots 6, 7: the 100 MHz wall clock (one for the chip) at a block's start and end, in 10 ns units from the first start
@@ -60,6 +61,13 @@ if os.environ.get("NN_TIMELINE_BLOCKS"):
         print(" ".join("%d:%d-%d" % (i, t[i, 6] - w0, t[i, 7] - w0) for i in sel))
 t = t[t[:, 0] > 0]
 print("%d blocks stamped (shader-clock ticks; per-block differences only -- the counter is per XCD)" % len(t))
+# ticks per microsecond: a block's shader-clock ticks over its 100 MHz wall-clock interval
+rate = (t[:, 5] - t[:, 0]) / np.maximum(t[:, 7] - t[:, 6], 1) * 100.0
+print("   tick rate: median %.0f ticks per us (min %.0f max %.0f)" % (np.median(rate), rate.min(), rate.max()))
+v = t[:, 8] - t[:, 0]
+print("   %-52s min %7d median %7d max %7d" % ("entry -> first vector load issued", v.min(), np.median(v), v.max()))
+v = t[:, 2] - t[:, 0]
+print("   %-52s min %7d median %7d max %7d" % ("start -> first MFMA", v.min(), np.median(v), v.max()))
 names = {1: "scale known (queries + slice read, maximum reduced)", 2: "first LDS tile staged", 3: "second LDS tile staged",
          4: "MFMA loop done", 5: "lists published"}
 prev = 0
@@ -73,9 +81,11 @@ for k in (1, 2, 3, 4, 5):
 v = t[:, 5] - t[:, 0]
 print("   %-52s min %7d median %7d max %7d" % ("whole block", v.min(), np.median(v), v.max()))
 assert L.genpc_nn_timeline_read_finish(buf)
-t = np.frombuffer(buf, dtype=np.uint64).reshape(4096, 8).astype(np.int64)
+t = np.frombuffer(buf, dtype=np.uint64).reshape(4096, ROW).astype(np.int64)
 t = t[t[:, 0] > 0]
 print("finish kernel, %d blocks stamped" % len(t))
+v = t[:, 8] - t[:, 0]
+print("   %-52s min %7d median %7d max %7d" % ("entry -> first vector load issued", v.min(), np.median(v), v.max()))
 names = {1: "lists, query, |t|max loaded", 2: "best unit evaluated, threshold", 3: "further candidates listed", 4: "further candidates evaluated", 5: "results written"}
 prev = 0
 for k in (1, 2, 3, 4, 5):
