@@ -18,7 +18,7 @@ struct NNDir {
     const unsigned *dupmask;   // [B][ceil(nt / 32)]: targets that are later copies of a bit-identical target (nn_dedupe.hip), or null
     // split-f16 path (nn_f16.hip / nn_finish.hip)
     float *tmaxp;           // partial maxima of |t'|^2 [B][ntmax] (per slice, or per split block)
-    unsigned long long *part;   // per-slice partials [S, B*nq] (S > 1): distance bits << 32 | chunk
+    unsigned long long *part;   // per-slice partials [S, B*nq] (S > 1): distance bits << 32 | chunk; f16 family: ListRec records (below)
     const float *q;    // queries  [B, nq, 3]
     const float *t;    // targets  [B, nt, 3]
     float *out_d;      // final    [B, nq]
@@ -108,6 +108,11 @@ __device__ __forceinline__ void top3_insert(Top3 &s, float m, int id)
 
 // Hand-off of a list from the filter (nn_f16.hip) to the finish step (nn_finish.hip): two 8-byte words per query
 //     (a1, c1)   (code2 : code3, c2)
+// side by side in ONE 16-byte record, ListRec, at [slice * NL + n][batch * nq + j] of the direction's area (list_rec): a lane
+// stores or loads a list with one 16-byte instruction, and the 32 lanes of a query tile cover 512 contiguous bytes.  (Until the
+// records the two words lay in two planes B * nq words apart: two 8-byte stores and two 8-byte loads per list.)  The area starts
+// 16-byte aligned: the workspace piece does, and direction 1 begins slices * B * nq * pwords words behind direction 0, pwords even.
+// The filter and the finish step are the area's only writer and reader; the fp32-MFMA and VALU kernels keep their own format in it.
 // a1 exact (the acceptance threshold is derived from it); a2 and a3 travel as 16-bit codes of LOWER bounds --
 // a2' = fl(a1 + dec(code2)) <= a2, a3' = fl(a2' + dec(code3)) <= a3 -- which is all the finish step needs of them: a
 // unit is evaluated exactly when a2' <= tau (a superset), a query is re-done exhaustively when a3' <= tau (a superset).
@@ -124,6 +129,15 @@ __device__ __forceinline__ unsigned list_enc(float base, float v)
     return (__float_as_uint(d) >> 15) & 0xffffu;
 }
 __device__ __forceinline__ float list_dec(float base, unsigned code) { return base + __uint_as_float(code << 15); }
+
+typedef unsigned long long ListRec __attribute__((ext_vector_type(2)));      // .x = (a1, c1), .y = (code2 : code3, c2)
+// record of list `list` (slice * NL + n) of query j of batch element `batch`; bnq = B * nq
+template <typename P>
+__device__ __forceinline__ auto list_rec(P *part, int list, size_t bnq, int batch, int nq, int j)
+{
+    typedef typename std::conditional<std::is_const<P>::value, const ListRec, ListRec>::type R;
+    return (R *)part + ((size_t)list * bnq + (size_t)batch * nq + j);
+}
 
 template <int FMA, int LEN>
 __device__ __forceinline__ void rescan_chunk(const float *__restrict__ T, int nt, int base, float qx, float qy,

@@ -34,13 +34,17 @@ typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
 // shader clock at the phase boundaries of nn_f16_kernel (nothing of this exists in the shipped library)
 #ifdef GENPC_NN_TIMELINE
 // (rows of kTimelineRow words: 0-5 the phase boundaries, 6-7 the wall clock at a block's start and end, 8 the moment before the
-// block's first vector load is issued -- everything in front of it is kernel arguments and the block decode)
+// block's first vector load is issued -- everything in front of it is kernel arguments and the block decode; 9-11 the partner
+// wave: lane 0 of wave 4, which shares wave 0's SIMD in the wide form, at its MFMA loop's start, its end and "lists published" --
+// word 4 is wave 0's loop end, and the two waves of a block read the same counter)
 constexpr int kTimelineRow = 16;
 __device__ unsigned long long g_timeline[4096 * kTimelineRow];
 #define GENPC_TL(k) do { if (threadIdx.x == 0 && blockIdx.x < 4096) { g_timeline[blockIdx.x * kTimelineRow + (k)] = __builtin_readcyclecounter(); \
     if ((k) == 0) g_timeline[blockIdx.x * kTimelineRow + 6] = wall_clock64(); if ((k) == 5) g_timeline[blockIdx.x * kTimelineRow + 7] = wall_clock64(); } } while (0)
+#define GENPC_TL_PARTNER(k) do { if (WV == 8 && threadIdx.x == 4 * kWave && blockIdx.x < 4096) g_timeline[blockIdx.x * kTimelineRow + (k)] = __builtin_readcyclecounter(); } while (0)
 #else
 #define GENPC_TL(k) do {} while (0)
+#define GENPC_TL_PARTNER(k) do {} while (0)
 #endif
 constexpr double kQTh = 30.0, kTTh = 15.0;
 
@@ -289,7 +293,7 @@ __global__ __launch_bounds__(WV * kWave, W) void nn_f16_kernel(NNArgs a)
         }
         if (t0 + HT < k_end) prefetch(t0 + HT);
         __syncthreads();
-        if (t0 == k_begin) GENPC_TL(2); else GENPC_TL(3);
+        if (t0 == k_begin) { GENPC_TL(2); GENPC_TL_PARTNER(9); } else GENPC_TL(3);
         // prologue of the LDS tile: target tile 0, rows of tiles 0 and 1
         fetch(0, 0);
         fetch(1, 32);
@@ -325,6 +329,7 @@ __global__ __launch_bounds__(WV * kWave, W) void nn_f16_kernel(NNArgs a)
     }
 
     GENPC_TL(4);
+    GENPC_TL_PARTNER(10);
     // max |t'|^2 of the slice, for the bound of the finish step: every query block sees the same targets, the
     // first one publishes
     if (qb == 0) {
@@ -342,10 +347,10 @@ __global__ __launch_bounds__(WV * kWave, W) void nn_f16_kernel(NNArgs a)
         if (threadIdx.x == 0) tmaxp_dir[(size_t)batch * slices + slice] = tm;
     }
 
-    // Publish the lists: the two lane halves folded, NL lists of two 8-byte words per query and slice
-    // (a1, c1) (codes of a2 and a3, c2): list_enc in nn.h.
+    // Publish the lists: the two lane halves folded, NL lists of one 16-byte record per query and slice
+    // (a1, c1) (codes of a2 and a3, c2): list_enc and ListRec in nn.h.  One 16-byte store per list: the 32 lanes that store
+    // write 512 contiguous bytes.
     const size_t bnq = (size_t)nbatch * nq;
-    unsigned long long *P = part_dir + (size_t)batch * nq;
 #pragma unroll
     for (int r = 0; r < Q; r++) {
 #pragma unroll
@@ -363,15 +368,23 @@ __global__ __launch_bounds__(WV * kWave, W) void nn_f16_kernel(NNArgs a)
             top3_insert(f, o3, -1);
             const int j = q0 + r * 32;
             if (!half && j < nq) {
-                unsigned long long *p = P + (size_t)(slice * NL + n) * 2 * bnq + j;
                 const unsigned code2 = list_enc(f.a1, f.a2);
                 const unsigned code3 = list_enc(list_dec(f.a1, code2), f.a3);
-                p[0] = ((unsigned long long)__float_as_uint(f.a1) << 32) | (unsigned)f.c1;
-                p[bnq] = ((unsigned long long)((code2 << 16) | code3) << 32) | (unsigned)f.c2;
+                ListRec rec;
+                rec.x = ((unsigned long long)__float_as_uint(f.a1) << 32) | (unsigned)f.c1;
+                rec.y = ((unsigned long long)((code2 << 16) | code3) << 32) | (unsigned)f.c2;
+                ListRec *p = list_rec(part_dir, slice * NL + n, bnq, batch, nq, j);
+                // written through (sc1): a block's 16 KB of lists are on their way to memory when they are stored, not when the
+                // kernel's end finds them dirty in the L2 -- and the finish blocks read them from other XCDs in any case.
+                // (The filter's trace duration minus its last block's end, 1 x 16384^2: plain 3.0 us, non-temporal 2.8,
+                // written through 2.2, the finish kernel unchanged; DESIGN_NOTEBOOK.md, "list records".)  Written as the
+                // instruction: a plain 16-byte store cannot carry the bit; the s_nop keeps the next instruction off the data registers.
+                asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"((NN_GLOBAL(ListRec))p), "v"(rec) : "memory");
             }
         }
     }
     GENPC_TL(5);
+    GENPC_TL_PARTNER(11);
 }
 
 template <int Q, int NL>

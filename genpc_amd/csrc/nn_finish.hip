@@ -80,7 +80,6 @@ __global__ __launch_bounds__(kBlock) void nn_finish_kernel(NNArgs a, int nl, int
     float *__restrict__ od = out_d_dir + (size_t)batch * nq;
     int *__restrict__ oi = out_i_dir + (size_t)batch * nq;
     const size_t bnq = (size_t)nbatch * nq;
-    const unsigned long long *P = part_dir + (size_t)batch * nq;
     const int nlists = slices * nl;
 
     const int ql = threadIdx.x & (kFQ - 1), part = threadIdx.x >> 6;     // part == wave
@@ -106,19 +105,19 @@ __global__ __launch_bounds__(kBlock) void nn_finish_kernel(NNArgs a, int nl, int
     const bool tm_mine = (int)threadIdx.x < ntmax;
     const float tm0 = tmp[tm_mine ? (int)threadIdx.x : 0];
     // this thread's lists: li = part + 4k
-    unsigned long long w0[kMaxLists / 4], w1[kMaxLists / 4];      // (a1, c1), (codes of a2 | a3, c2): list_enc in nn.h
+    // one 16-byte load per list (ListRec in nn.h).  The records stay whole until every load is out: taken apart inside the
+    // branch, the first one was waited for there -- a round trip in front of the other loads.
+    ListRec w[kMaxLists / 4];
     float amin = __builtin_inff();
 #pragma unroll
     for (int k = 0; k < kMaxLists / 4; k++) {
         const int li = part + 4 * k;
-        w0[k] = 0x7f800000ull << 32;      // (+inf, 0)
-        w1[k] = 0xff00ff00ull << 32;      // a2, a3 = +inf
-        if (li < nlists) {
-            const unsigned long long *p = P + (size_t)li * 2 * bnq + j;
-            w0[k] = p[0];
-            w1[k] = p[bnq];
-        }
+        w[k] = ListRec{0x7f800000ull << 32, 0xff00ff00ull << 32};      // (+inf, 0); a2, a3 = +inf
+        if (li < nlists) w[k] = *list_rec(part_dir, li, bnq, batch, nq, j);
     }
+    unsigned long long w0[kMaxLists / 4], w1[kMaxLists / 4];      // (a1, c1), (codes of a2 | a3, c2): list_enc in nn.h
+#pragma unroll
+    for (int k = 0; k < kMaxLists / 4; k++) { w0[k] = w[k].x; w1[k] = w[k].y; }
     int cmin = -1, kmin = -1;               // unit of this thread's smallest first minimum
 #pragma unroll
     for (int k = 0; k < kMaxLists / 4; k++) {

@@ -45,7 +45,8 @@ torch.cuda.synchronize()
 L = ctypes.CDLL(_lib.LIB_PATH)
 if not hasattr(L, "genpc_nn_timeline_read"):
     sys.exit("this library was not built with -DGENPC_NN_TIMELINE (python tools/nn_timeline.py --build, then GENPC_LIB=...)")
-ROW = 16      # words per block: 0-5 phase boundaries, 6-7 wall clock at start and end, 8 before the first vector load
+ROW = 16      # words per block: 0-5 phase boundaries, 6-7 wall clock at start and end, 8 before the first vector load,
+              # 9-11 wave 4 (wide form: wave 0's SIMD partner) at its MFMA loop's start, its end and "lists published"
 buf = (ctypes.c_ulonglong * (4096 * ROW))()
 assert L.genpc_nn_timeline_read(buf)
 t = np.frombuffer(buf, dtype=np.uint64).reshape(4096, ROW).astype(np.int64)
@@ -80,6 +81,15 @@ for k in (1, 2, 3, 4, 5):
     prev = k
 v = t[:, 5] - t[:, 0]
 print("   %-52s min %7d median %7d max %7d" % ("whole block", v.min(), np.median(v), v.max()))
+# the two waves of a SIMD (wide form only: wave 4 shares wave 0's SIMD; words 9-11 are its loop start, loop end and publish)
+pw = t[t[:, 10] > 0]
+if len(pw):
+    e0, e4 = pw[:, 4] - pw[:, 0], pw[:, 10] - pw[:, 0]
+    print("   a SIMD's two waves, ticks from the block's start, medians over %d blocks:" % len(pw))
+    print("   %-52s wave 0 %7d  wave 4 %7d" % ("MFMA loop entered", np.median(pw[:, 2] - pw[:, 0]), np.median(pw[:, 9] - pw[:, 0])))
+    print("   %-52s wave 0 %7d  wave 4 %7d  wave 4 - wave 0 %7d" % ("MFMA loop left", np.median(e0), np.median(e4), np.median(e4 - e0)))
+    print("   %-52s wave 0 %7d  wave 4 %7d" % ("lists published", np.median(pw[:, 5] - pw[:, 0]), np.median(pw[:, 11] - pw[:, 0])))
+    print("   %-52s %.2f us" % ("last block end after the first block start (wall)", (t[:, 7].max() - t[:, 6].min()) / 100.0))
 assert L.genpc_nn_timeline_read_finish(buf)
 t = np.frombuffer(buf, dtype=np.uint64).reshape(4096, ROW).astype(np.int64)
 t = t[t[:, 0] > 0]
