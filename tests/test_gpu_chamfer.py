@@ -121,8 +121,10 @@ def test_backward_vs_oracle(gp, oracle):
 def test_backward_large_call_forms(gp, oracle):
     """From 262144 points per call the backward is one pass per direction: each term goes to the query's own row by plain
     read-modify-write and to the target's row through an LDS tile that owns its output rows (csrc/chamfer.hip:
-    chamfer_grad_dir_kernel) -- against the oracle, ragged sizes (a last tile of 904 rows, a cloud smaller than a tile),
-    indices that pile up on few targets."""
+    chamfer_grad_dir_kernel) -- against the oracle, a cloud smaller than a tile, indices that pile up on few targets.  (Cloud
+    1 has a last tile of 904 rows, but every idx2 is below 40: that tile and the one before it are launched and flush zeros,
+    no term lands past the first tile.  tests/test_chamfer_grad_cases.py says what else this call does not reach;
+    tests/test_gpu_chamfer_backward.py is where every path of the kernel is run.)"""
     torch = gp["torch"]
     rng = np.random.default_rng(77)
     bsz, n, m = 24, 9096, 3000            # 24 x (9096 + 3000) = 290 k points
