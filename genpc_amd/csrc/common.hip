@@ -150,7 +150,7 @@ bool ws_alloc(WsLayout &L, Ws slot, hipStream_t stream, bool *fresh, size_t zero
 
 }  // namespace genpc
 
-GENPC_API int genpc_abi_version(void) { return 27; }
+GENPC_API int genpc_abi_version(void) { return 28; }
 
 GENPC_API const char *genpc_last_error(void)
 {

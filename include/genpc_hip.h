@@ -33,7 +33,7 @@ extern "C" {
 #define GENPC_ARITH_FMA 1
 
 /* Library / device ------------------------------------------------------- */
-int genpc_abi_version(void);              /* bumps when a signature or a documented behaviour changes (27: genpc_grid_*_probe added; 26: genpc_nn_plan added; 25: genpc_nn_seeded_step added; 24: genpc_icp_plan added; 23: genpc_pose_loss_grad_batch added; 22: genpc_chamfer_backward_ragged added; 21: genpc_nm_distance_ragged added; 20: genpc_mesh_sample added; 19: genpc_uhd added; 18: genpc_knn_query added;
+int genpc_abi_version(void);              /* bumps when a signature or a documented behaviour changes (28: genpc_hpr_plan added, GENPC_HPR_NOCULL keeps bits 128 and 512 only; 27: genpc_grid_*_probe added; 26: genpc_nn_plan added; 25: genpc_nn_seeded_step added; 24: genpc_icp_plan added; 23: genpc_pose_loss_grad_batch added; 22: genpc_chamfer_backward_ragged added; 21: genpc_nm_distance_ragged added; 20: genpc_mesh_sample added; 19: genpc_uhd added; 18: genpc_knn_query added;
                                            * 17: genpc_fps_tune takes 0 or 256 only; 16: genpc_hpr_* asynchronous, counts -1 on an internal error;
                                            * genpc_fps*: out_idx[0] -2 = failed the check).
                                            * genpc_uhd_ragged came without a bump.  From 27 on an addition that changes no existing signature and no
@@ -317,6 +317,19 @@ int genpc_hpr_visibility(int c, int n, const float *points, const double *eyes,
 int genpc_hpr_best_view_counts(int c, int n, const float *points, const double *eyes, double radius,
                                unsigned char *visible, int *counts, unsigned char *exact,
                                int *second_pass_points, void *stream);
+
+/* The plan of a hidden-point-removal call of c views x n points (csrc/hpr_plan.h; best_only: the call is
+ * genpc_hpr_best_view_counts) on a device of `cus` compute units (<= 0: the current device's), with the process's
+ * GENPC_HPR_* switches; no GPU work.  out[24]:
+ *   out[0] 1: too large (the call would fail)     out[1] tiles per view     out[2] two-kernel form     out[3] views are pruned
+ *   out[4] key bits of the view sort     out[5] clips before a polygon is handed over     out[6], out[7] home tiles, chunks
+ *   out[8] candidates marked at a time     out[9], out[10] hand-over of a block's last points: from batch, at most lanes
+ *   out[11] parked points the polygon store holds     out[12] 1: the first try has a kernel of its own
+ *   out[13], out[14] 256-thread blocks over the points, capped     out[15] over the views
+ *   out[16] .. out[19] one-wave blocks: first try, walk, large polygons, global polygons     out[20] vertices per global buffer
+ *   out[21], out[22] MiB of the polygon store, of the global buffers (rounded down)     out[23] the compute units planned for
+ * Returns 1, -1 for a bad argument.     */
+int genpc_hpr_plan(int c, int n, int best_only, int cus, int out[24]);
 
 /* A cheaper visibility for viewpoint ranking.  NOT the reference's operator (that is
  * genpc_hpr_visibility above): a z-buffer test -- a point is visible from camera c

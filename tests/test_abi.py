@@ -30,6 +30,7 @@ def test_header_has_the_path():
     assert p["genpc_pose_loss_grad_batch"] == 17   # b, nc, v, vert_col, center, params, np, partial, partial_col, 3 weights, radius, size, 2 outputs + stream
     assert p["genpc_pose_loss_grad"] == 20         # (unchanged beside it: the single-element evaluation with the caller's neighbours)
     assert p["genpc_nn_plan"] == 6                 # b, n, m, ndir, cus, out
+    assert p["genpc_hpr_plan"] == 5                # c, n, best_only, cus, out
     assert p["genpc_nn_seeded_step"] == 14         # b, nm, rest, center, params, ns, stat, posed, d1, i1, d2, i2, sample + stream
 
 
@@ -44,7 +45,7 @@ def test_library_exports_every_declared_symbol():
         assert len(_lib.SIGNATURES[name][1]) == nargs, name
         assert fn is not None
     assert _lib.lib.genpc_abi_version() == _lib.ABI_VERSION
-    assert _lib.ABI_VERSION == 27                  # the grid probes added
+    assert _lib.ABI_VERSION == 28                  # genpc_hpr_plan added
 
 
 def test_arith_mode_switch():

@@ -34,9 +34,9 @@ def test_the_symbol_is_declared_bound_and_exported(K):
     assert getattr(_lib.lib, "genpc_knn_query_ragged") is not None
 
 
-def test_abi_version_is_27_in_library_and_binding(K):
+def test_abi_version_is_28_in_library_and_binding(K):          # (this addition kept 27; 28: genpc_hpr_plan)
     from genpc_amd import _lib
-    assert _lib.ABI_VERSION == 27 and _lib.lib.genpc_abi_version() == 27
+    assert _lib.ABI_VERSION == 28 and _lib.lib.genpc_abi_version() == 28
 
 
 def test_cpu_tensors_raise(K, D):

@@ -35,9 +35,9 @@ def test_both_symbols_are_declared_bound_and_exported(R):
         assert getattr(_lib.lib, name) is not None
 
 
-def test_abi_version_is_27_in_library_and_binding(R):
+def test_abi_version_is_28_in_library_and_binding(R):          # (this addition kept 27; 28: genpc_hpr_plan)
     from genpc_amd import _lib
-    assert _lib.ABI_VERSION == 27 and _lib.lib.genpc_abi_version() == 27
+    assert _lib.ABI_VERSION == 28 and _lib.lib.genpc_abi_version() == 28
 
 
 def test_cpu_tensors_raise(R):

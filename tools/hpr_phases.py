@@ -1,6 +1,6 @@
 """Where hpr_kernel spends its time (shader-clock ticks per phase, trip counts of the clip loop).
 
-    python tools/hpr_phases.py --build      # here: csrc/hpr.hip with -DGENPC_HPR_PROF into tools/_hprprof/libgenpc_hip.so
+    python tools/hpr_phases.py --build      # here: csrc/hpr*.hip with -DGENPC_HPR_PROF into tools/_hprprof/libgenpc_hip.so
     GENPC_LIB=$PWD/tools/_hprprof/libgenpc_hip.so python tools/hpr_phases.py          # on the GPU box
 """
 import ctypes, os, subprocess, sys
@@ -12,10 +12,16 @@ if "--build" in sys.argv:
     B.build(verbose=False)
     os.makedirs(OUT, exist_ok=True)
     cflags = [f for f in B.FLAGS if f != "-shared"]
-    obj = os.path.join(OUT, "hpr.o")
-    subprocess.check_call([B.HIPCC] + cflags + ["-DGENPC_HPR_PROF", "-c", os.path.join(B.CSRC, "hpr.hip"), "-o", obj])
-    objs = [os.path.join(B.LIBDIR, "obj", os.path.basename(s)[:-4] + ".o") for s in B.sources() if not s.endswith("/hpr.hip")]
-    subprocess.check_call([B.HIPCC, "--offload-arch=" + B.ARCH, "-shared", "-fPIC", "-fno-gpu-rdc"] + objs + [obj, "-o", os.path.join(OUT, "libgenpc_hip.so")])
+    # every hpr*.hip with the define (hpr_first.hip and hpr_wave.hip each hold an array of counters, hpr.hip adds them)
+    objs = []
+    for s in B.sources():
+        base = os.path.basename(s)[:-4]
+        if base.startswith("hpr"):
+            objs.append(os.path.join(OUT, base + ".o"))
+            subprocess.check_call([B.HIPCC] + cflags + ["-DGENPC_HPR_PROF", "-c", s, "-o", objs[-1]])
+        else:
+            objs.append(os.path.join(B.LIBDIR, "obj", base + ".o"))
+    subprocess.check_call([B.HIPCC, "--offload-arch=" + B.ARCH, "-shared", "-fPIC", "-fno-gpu-rdc"] + objs + ["-o", os.path.join(OUT, "libgenpc_hip.so")])
     print(os.path.join(OUT, "libgenpc_hip.so"))
     sys.exit(0)
 import numpy as np, torch
