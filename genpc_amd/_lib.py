@@ -71,10 +71,13 @@ SIGNATURES = {
     "genpc_pose_optimize_cd_batch": (_i, [_i, _i, _vp, _i, _vp, _f, _i, _i, _vp, _vp, _vp, _vp]),
     "genpc_icp_batch": (_i, [_i, _i, _vp, _i, _vp, _d, _vp, _i, _d, _d, _vp, _vp, _vp]),
     "genpc_icp_plan": (_i, [_i, _vp]),
+    "genpc_icp_batch_ragged": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _d, _vp, _i, _d, _d, _vp, _vp, _vp]),
+    "genpc_icp_ragged_plan": (_i, [_i, _vp, _vp]),
     "genpc_nn_plan": (_i, [_i, _i, _i, _i, _i, _vp]),
     "genpc_hpr_plan": (_i, [_i, _i, _i, _i, _vp]),
     "genpc_scale_search_scores": (_i, [_i, _i, _vp, _i, _vp, _vp, _f, _vp, _vp]),
     "genpc_voxel_down_sample": (_i, [_i, _vp, _vp, _d, _vp, _vp, _vp, _vp]),
+    "genpc_voxel_down_sample_ragged": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "genpc_mfma_f16_probe": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
     "genpc_list_code_probe": (_i, [ctypes.c_longlong, _vp, _vp, _vp, _vp]),
     "genpc_fastdiv_probe": (_i, [ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -20,7 +20,9 @@
 // Numerics follow oracle/genpc_oracle_geom.c (oracle_icp): same fp32 NN, sums in
 // double; sums are reduced in a different order (1e-12 relative).
 #include "nn.h"
-#include "icp_plan.h"
+#include "ragged_table.h"
+#define GENPC_ICP_PLAN_HD GENPC_RAGGED_HD          // icp_plan() on the device too: icp_fused_ragged_kernel
+#include "icp_ragged_plan.h"
 #include "../../include/genpc_hip.h"
 
 #include <math.h>
@@ -391,18 +393,20 @@ __device__ unsigned long long g_icp_tl[2 + 3 * 64];
 #define ICP_STAMP(i) do { } while (0)
 #endif
 
+// The solve of candidate `cand` by the calling workgroup: init, out_T and stats are the call's arrays, indexed by cand; the clouds
+// are the candidate's own.  The one statement of the arithmetic: icp_fused_kernel and icp_fused_ragged_kernel are this and nothing else.
 template <int FMA>
-__global__ __launch_bounds__(kFT) void icp_fused_kernel(int ns, const float *__restrict__ source, int nt, const float *__restrict__ target,
-                                                        float md2, double max_dist, const double *__restrict__ init, int max_iter,
-                                                        double rel_fitness, double rel_rmse, int cells_cap, double *__restrict__ out_T,
-                                                        double *__restrict__ stats)
+__device__ __forceinline__ void icp_fused_solve(int cand, int ns, const float *__restrict__ source, int nt, const float *__restrict__ target,
+                                                float md2, double max_dist, const double *__restrict__ init, int max_iter,
+                                                double rel_fitness, double rel_rmse, int cells_cap, double *__restrict__ out_T,
+                                                double *__restrict__ stats)
 {
     extern __shared__ __align__(16) unsigned char icp_lds[];
     __shared__ GridFrame F;
     __shared__ float s_mx[3];                  // the cloud's maximum (its minimum is F.lo): the outer walls of the border cells
     __shared__ IcpState s_state;
     __shared__ float s_red[6 * kFWaves];       // the box reduction's, then the scan's
-    const int cand = blockIdx.x, tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
     const int ntp = (nt + 3) & ~3;
     float4 *P = (float4 *)icp_lds;                                   // [ntp] targets in cell order: x, y, z, index
     unsigned *cend = (unsigned *)(P + ntp);                          // [cells_cap] end of each cell's run in P
@@ -613,6 +617,50 @@ __global__ __launch_bounds__(kFT) void icp_fused_kernel(int ns, const float *__r
     if (tid < 16) out_T[(size_t)cand * 16 + tid] = s_T[tid];
 }
 
+template <int FMA>
+__global__ __launch_bounds__(kFT) void icp_fused_kernel(int ns, const float *__restrict__ source, int nt, const float *__restrict__ target,
+                                                        float md2, double max_dist, const double *__restrict__ init, int max_iter,
+                                                        double rel_fitness, double rel_rmse, int cells_cap, double *__restrict__ out_T,
+                                                        double *__restrict__ stats)
+{
+    icp_fused_solve<FMA>(blockIdx.x, ns, source, nt, target, md2, max_dist, init, max_iter, rel_fitness, rel_rmse, cells_cap, out_T, stats);
+}
+
+// genpc_icp_batch_ragged's one launch: workgroup blockIdx.x solves candidate blockIdx.x of the call.  Its pair -- the largest j
+// with koff[j] <= candidate, a uniform binary search of the table in the kernel arguments (scalar loads) -- gives it its own
+// ns, nt, clouds and, through icp_plan(nt), its own cell budget, by which icp_fused_solve carves the LDS (ntp, cells_cap): the
+// launch's dynamic LDS is the largest of the pairs' (icp_ragged_plan.h).  A candidate of a multi-launch pair leaves at once.
+struct IcpRaggedArgs {
+    int c;
+    int soff[kIcpRaggedMaxPairs + 1];          // source of pair j: [soff[j], soff[j + 1])
+    int toff[kIcpRaggedMaxPairs + 1];          // its target
+    int koff[kIcpRaggedMaxPairs + 1];          // its candidates
+    const float *source, *target;              // packed
+    const double *init;                        // [K,16]
+    double *out_T, *stats;                     // [K,16], [K,3]
+    double max_dist, rel_fitness, rel_rmse;
+    float md2;
+    int max_iter;
+};
+static_assert(sizeof(IcpRaggedArgs) <= 4096, "the pair table must fit the kernel arguments");
+
+template <int FMA>
+__global__ __launch_bounds__(kFT) void icp_fused_ragged_kernel(IcpRaggedArgs a)
+{
+    const int cand = blockIdx.x;
+    int lo = 0, hi = a.c - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (a.koff[mid] <= cand) lo = mid; else hi = mid - 1;
+    }
+    const int s0 = a.soff[lo], t0 = a.toff[lo];
+    const int ns = a.soff[lo + 1] - s0, nt = a.toff[lo + 1] - t0;
+    const IcpPlan plan = icp_plan(nt);
+    if (!plan.one_workgroup) return;                  // (uniform: the whole workgroup leaves)
+    icp_fused_solve<FMA>(cand, ns, a.source + (size_t)s0 * 3, nt, a.target + (size_t)t0 * 3, a.md2, a.max_dist, a.init, a.max_iter,
+                         a.rel_fitness, a.rel_rmse, plan.cells, a.out_T, a.stats);
+}
+
 static int gx(int n)          // (not pose_plan.h's lin_grid: the same block of 256, but at most 64 blocks per row where that one allows 1024)
 {
     int g = ceil_div(n, kIBlock);
@@ -696,6 +744,116 @@ GENPC_API int genpc_icp_plan(int nt, int out[3])
     const genpc::IcpPlan p = genpc::icp_plan(nt);
     out[0] = p.one_workgroup;
     out[1] = p.cells;
+    out[2] = p.lds_bytes;
+    return 1;
+}
+
+namespace genpc {
+
+static int icp_ragged_refuse(const char *fn, const char *what)
+{
+    char msg[192];
+    snprintf(msg, sizeof msg, "%s: %s", fn, what);
+    set_error(msg);
+    return -1;
+}
+
+// one offset table of a ragged ICP call: null when it starts at 0 and ascends, else what is wrong with it
+static const char *icp_ragged_table_fault(int c, const int *off)
+{
+    if (off[0] != 0) return "offsets must start at 0";
+    for (int j = 0; j < c; j++)
+        if (off[j + 1] < off[j]) return "offsets must ascend";
+    return nullptr;
+}
+
+}  // namespace genpc
+
+GENPC_API int genpc_icp_batch_ragged(int c, const int *soff, const int *toff, const int *koff, const float *source, const float *target,
+                                     double max_dist, const double *init, int max_iter, double rel_fitness, double rel_rmse,
+                                     double *out_T, double *stats, void *stream)
+{
+    using namespace genpc;
+    const char *fn = "genpc_icp_batch_ragged";
+    // every refusal is decided here, before anything touches a device
+    if (c < 0) return icp_ragged_refuse(fn, "negative number of pairs");
+    if (max_iter < 0) return icp_ragged_refuse(fn, "negative number of iterations");
+    if (c == 0) return 1;
+    if (c > kIcpRaggedMaxPairs) return icp_ragged_refuse(fn, "more than 256 pairs in one call");
+    static_assert(kIcpRaggedMaxPairs == 256, "the message above names the bound");
+    if (!soff || !toff || !koff) return icp_ragged_refuse(fn, "null offset table");
+    for (const int *off : {soff, toff, koff}) {
+        const char *fault = icp_ragged_table_fault(c, off);
+        if (fault) return icp_ragged_refuse(fn, fault);
+    }
+    if (soff[c] > kIcpRaggedMaxPoints || toff[c] > kIcpRaggedMaxPoints) return icp_ragged_refuse(fn, "more than 2^28 points on one side");
+    if (koff[c] > kIcpRaggedMaxCandidates) return icp_ragged_refuse(fn, "more than 2^20 candidates");
+    for (int j = 0; j < c; j++) {
+        if (koff[j + 1] == koff[j]) continue;          // a pair without candidates is skipped, whatever its clouds
+        if (soff[j + 1] == soff[j] || toff[j + 1] == toff[j]) {
+            char what[96];
+            snprintf(what, sizeof what, "pair %d has candidates and an empty %s", j, soff[j + 1] == soff[j] ? "source" : "target");
+            return icp_ragged_refuse(fn, what);
+        }
+    }
+    const int k = koff[c];
+    if (k == 0) return 1;
+    if (!source || !target || !init || !out_T || !stats) return icp_ragged_refuse(fn, "null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    const IcpRaggedPlan plan = icp_ragged_plan(c, toff);
+    if (plan.fused_pairs) {
+        const size_t lds = (size_t)plan.lds_bytes;
+        const int fma = arith_mode() != 0 ? 1 : 0;
+        static size_t set_bytes[2] = {0, 0};
+        if (lds > set_bytes[fma]) {
+            const hipError_t e = fma ? hipFuncSetAttribute((const void *)icp_fused_ragged_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
+                                     : hipFuncSetAttribute((const void *)icp_fused_ragged_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (!check(e, "hipFuncSetAttribute(icp_fused_ragged_kernel)")) return 0;
+            set_bytes[fma] = lds;
+        }
+        IcpRaggedArgs a{};
+        a.c = c;
+        for (int j = 0; j <= kIcpRaggedMaxPairs; j++) {
+            const int i = j < c ? j : c;
+            a.soff[j] = soff[i]; a.toff[j] = toff[i]; a.koff[j] = koff[i];
+        }
+        a.source = source; a.target = target; a.init = init; a.out_T = out_T; a.stats = stats;
+        a.max_dist = max_dist; a.rel_fitness = rel_fitness; a.rel_rmse = rel_rmse;
+        a.md2 = (float)(max_dist * max_dist);
+        a.max_iter = max_iter;
+        // one workgroup per candidate of the call; those of a multi-launch pair leave at once
+        if (fma) hipLaunchKernelGGL((icp_fused_ragged_kernel<1>), dim3(k), dim3(kFT), lds, st, a);
+        else hipLaunchKernelGGL((icp_fused_ragged_kernel<0>), dim3(k), dim3(kFT), lds, st, a);
+        if (!check(hipGetLastError(), "icp (ragged, one workgroup) launch")) return 0;
+    }
+    if (plan.loop_pairs) {
+        for (int j = 0; j < c; j++) {
+            const int kj = koff[j + 1] - koff[j], nt = toff[j + 1] - toff[j];
+            if (kj == 0 || icp_plan(nt).one_workgroup) continue;
+            const int rc = genpc_icp_batch(kj, soff[j + 1] - soff[j], source + (size_t)soff[j] * 3, nt, target + (size_t)toff[j] * 3, max_dist,
+                                           init + (size_t)koff[j] * 16, max_iter, rel_fitness, rel_rmse, out_T + (size_t)koff[j] * 16,
+                                           stats + (size_t)koff[j] * 3, stream);
+            if (rc != 1) return rc < 0 ? 0 : rc;
+        }
+    }
+    return 1;
+}
+
+GENPC_API int genpc_icp_ragged_plan(int c, const int *toff, int out[3])
+{
+    using namespace genpc;
+    const char *fn = "genpc_icp_ragged_plan";
+    if (!out) return icp_ragged_refuse(fn, "null pointer");
+    out[0] = out[1] = out[2] = 0;
+    if (c < 0) return icp_ragged_refuse(fn, "negative number of pairs");
+    if (c == 0) return 1;
+    if (c > kIcpRaggedMaxPairs) return icp_ragged_refuse(fn, "more than 256 pairs in one call");
+    if (!toff) return icp_ragged_refuse(fn, "null offset table");
+    const char *fault = icp_ragged_table_fault(c, toff);
+    if (fault) return icp_ragged_refuse(fn, fault);
+    const IcpRaggedPlan p = icp_ragged_plan(c, toff);
+    out[0] = p.fused_pairs;
+    out[1] = p.loop_pairs;
     out[2] = p.lds_bytes;
     return 1;
 }

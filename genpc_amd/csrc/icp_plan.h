@@ -7,6 +7,12 @@
 #pragma once
 #include <stddef.h>
 
+// icp.hip defines this as ragged_table.h's GENPC_RAGGED_HD before it includes the header: the one-launch kernel of
+// genpc_icp_batch_ragged asks the plan of its own pair on the device.  Everywhere else it is nothing, and the header plain C++.
+#ifndef GENPC_ICP_PLAN_HD
+#define GENPC_ICP_PLAN_HD
+#endif
+
 namespace genpc {
 
 constexpr int kFT = 1024;                    // threads of the one-workgroup solve
@@ -21,7 +27,7 @@ constexpr int kFCellsMax = 8192, kFCellsMin = 1024;     // the grid's cell budge
 constexpr int kFIndexLimit = 65536;                     // a key holds the target's position in 16 bits
 
 // LDS of the one-workgroup solve for nt targets with `cells` grid cells: the cloud as float4, padded to a multiple of four
-inline size_t icp_fused_lds(int nt, int cells) { return ((size_t)nt + 3) / 4 * 4 * 16 + (size_t)cells * 4 + kFFixed; }
+GENPC_ICP_PLAN_HD inline size_t icp_fused_lds(int nt, int cells) { return ((size_t)nt + 3) / 4 * 4 * 16 + (size_t)cells * 4 + kFFixed; }
 
 struct IcpPlan {
     int one_workgroup;      // 1: icp_fused_kernel, one launch per call; 0: the multi-launch loop
@@ -29,7 +35,7 @@ struct IcpPlan {
     int lds_bytes;          // dynamic LDS of the launch (0 for the loop)
 };
 
-inline IcpPlan icp_plan(int nt)
+GENPC_ICP_PLAN_HD inline IcpPlan icp_plan(int nt)
 {
     IcpPlan p{0, 0, 0};
     if (nt <= 0 || nt >= kFIndexLimit) return p;

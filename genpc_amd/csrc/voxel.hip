@@ -14,7 +14,7 @@
 //   voxel_head_kernel     run heads; rocprim inclusive scan gives every run its output slot
 //   voxel_mean_kernel     the head of a run sums it in that order, in double: the same additions in
 //                         the same order as a CPU loop over the points -> bit-identical means
-#include "common.h"
+#include "voxel.h"
 #include "../../include/genpc_hip.h"
 
 #include <string.h>
@@ -22,18 +22,6 @@
 #include <rocprim/device/device_scan.hpp>
 
 namespace genpc {
-
-constexpr int kVBlock = 256;
-
-__device__ __forceinline__ unsigned f2ord(float f)      // order-preserving map float -> uint
-{
-    const unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(unsigned o)
-{
-    return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
 
 // bounds[0..2] = min, [3..5] = max as ordered uints (initialised to 0xffffffff / 0)
 __global__ __launch_bounds__(kVBlock) void voxel_bounds_kernel(int n, const float *__restrict__ xyz, unsigned *bounds)
@@ -78,15 +66,9 @@ __global__ __launch_bounds__(kVBlock) void voxel_key_kernel(int n, const float *
 {
     const int i = blockIdx.x * kVBlock + threadIdx.x;
     if (i >= n) return;
-    unsigned long long key = 0ull;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const double origin = (double)ord2f(bounds[k]) - voxel * 0.5;
-        const double c = floor(((double)xyz[(size_t)i * 3 + k] - origin) / voxel);
-        // 21 bits per axis; a non-finite coordinate or a grid finer than 2^21 cells per axis is an error
-        if (!(c >= 0.0 && c < 2097152.0)) { *err = 1; key = ~0ull; break; }
-        key = (key << 21) | (unsigned long long)c;
-    }
+    // 21 bits per axis; a non-finite coordinate or a grid finer than 2^21 cells per axis is an error
+    unsigned long long key;
+    if (!voxel_point_key(xyz + (size_t)i * 3, voxel, bounds, key)) *err = 1;
     keys[i] = key;
     idx[i] = i;
 }

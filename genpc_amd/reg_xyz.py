@@ -559,3 +559,182 @@ def fuse_scans(sources, targets, num_points=20000, distance_threshold=0.0001, st
         if with_col:
             cols = [cols[j][oks[j]] for j in range(s)]
     return [(fused[j], cols[j]) for j in range(s)] if with_col else list(fused)
+
+
+# ---------------------------------------------------------------------------
+# The stage between the pose initialisation and the fusion tail, for S scans per library call: the voxel grids and the
+# coarse ICP sweep of reg() (reg_xyz.py:146-173).
+# ---------------------------------------------------------------------------
+VOXEL_RAGGED_MAX_CLOUDS = 256            # include/genpc_hip.h: GENPC_VOXEL_RAGGED_MAX_CLOUDS
+ICP_RAGGED_MAX_PAIRS = 256               # include/genpc_hip.h: GENPC_ICP_RAGGED_MAX_PAIRS
+
+
+def _host_ints(values):
+    import ctypes
+    from . import chamfer_3D
+    arr, _ = chamfer_3D._host_offsets(values, "offsets")
+    return ctypes.cast(arr, ctypes.c_void_p), arr
+
+
+def voxel_down_sample_clouds(clouds, voxel_size, colors=None):
+    """``voxel_down_sample`` for S clouds of any sizes: a list of [N_j,3] float32 GPU tensors, or packed as (points [T,3],
+    offsets) with S + 1 host ints.  voxel_size: one float for all, or one per cloud (reg mixes 0.02, 0.03 and 0.04); colors,
+    when given, are packed or listed like the clouds.  Returns a list of [K_j,3] tensors -- with colours (list, list) -- each a
+    view of one packed result; cloud j's are the bits of ``voxel_down_sample(clouds[j], voxel_size[j])``.  One library call per
+    256 clouds (genpc_voxel_down_sample_ragged: a fixed number of launches) and ONE read-back, of all the counts, whatever S
+    is.  A cloud with a non-finite coordinate or more than 2^21 voxels along an axis raises ValueError naming it."""
+    import ctypes
+    fn = "voxel_down_sample_clouds"
+    pts, off = _ragged_side(clouds, fn)
+    s = len(off) - 1
+    sizes = [float(voxel_size)] * s if np.ndim(voxel_size) == 0 else [float(v) for v in voxel_size]
+    if len(sizes) != s:
+        raise ValueError("%s: %d voxel sizes for %d clouds" % (fn, len(sizes), s))
+    for j, v in enumerate(sizes):
+        if not v > 0:
+            raise ValueError("%s: the voxel size of cloud %d must be positive" % (fn, j))
+    col = None
+    if colors is not None:
+        col, coff = _ragged_side(colors, fn, "colors")
+        if coff != off:
+            raise ValueError("%s: colors must be [N_j,3] like their clouds" % fn)
+    if s == 0:
+        return [] if col is None else ([], [])
+    _lib.require_gpu(pts)
+    if col is not None:
+        _lib.require_gpu(col)
+        if col.device != pts.device:
+            raise ValueError("%s: clouds and colors are on different devices" % fn)
+    out = torch.empty_like(pts)
+    outc = torch.empty_like(col) if col is not None else None
+    counts = torch.empty(s, dtype=torch.int32, device=pts.device)
+    for a in range(0, s, VOXEL_RAGGED_MAX_CLOUDS):
+        b = min(a + VOXEL_RAGGED_MAX_CLOUDS, s)
+        arr, _keep = _host_ints([v - off[a] for v in off[a:b + 1]])
+        vs = (ctypes.c_double * (b - a))(*sizes[a:b])
+        rc = _lib.on_device_of(pts, _L.genpc_voxel_down_sample_ragged, b - a, arr, _p(pts[off[a]:off[b]]),
+                               _p(None if col is None else col[off[a]:off[b]]), ctypes.cast(vs, ctypes.c_void_p), _p(out[off[a]:off[b]]),
+                               _p(None if outc is None else outc[off[a]:off[b]]), _p(counts[a:b]))
+        if rc != 1:
+            raise RuntimeError("genpc_voxel_down_sample_ragged failed (%d): %s" % (rc, _lib.last_error()))
+    got = counts.tolist()                     # (the one host read)
+    for j, k in enumerate(got):
+        if k < 0:
+            raise ValueError("%s: cloud %d has a non-finite coordinate, or more than 2^21 voxels along an axis" % (fn, j))
+    down = [out[off[j]:off[j] + got[j]] for j in range(s)]
+    if col is None:
+        return down
+    return down, [outc[off[j]:off[j] + got[j]] for j in range(s)]
+
+
+def registration_icp_ragged(sources, targets, max_correspondence_distance, inits, max_iteration=30, relative_fitness=1e-6,
+                            relative_rmse=1e-6):
+    """``registration_icp`` for S (source, target) pairs of any sizes at once: sources / targets are lists of [N_j,3] / [M_j,3]
+    float32 GPU tensors or packed (points, offsets); inits a list of S arrays, [K_j,4,4] or [4,4] float64 (K_j = 0 skips the
+    pair).  Returns a list of (transformation [K_j,4,4] float64 numpy, fitness [K_j], inlier_rmse [K_j], iters [K_j]) -- a
+    [4,4] init gives unbatched values, as registration_icp does.  One library call per 256 pairs (genpc_icp_batch_ragged: the
+    pairs whose target fits the one-workgroup solve share ONE launch and get the bits of registration_icp on the pair alone)
+    and one copy back per call of this function."""
+    fn = "registration_icp_ragged"
+    sp, soff = _ragged_side(sources, fn, "sources")
+    tp, toff = _ragged_side(targets, fn, "targets")
+    if len(soff) != len(toff):
+        raise ValueError("%s: %d sources against %d targets" % (fn, len(soff) - 1, len(toff) - 1))
+    s = len(soff) - 1
+    if not isinstance(inits, (list, tuple)) or len(inits) != s:
+        raise ValueError("%s: inits is a list of one [K,4,4] or [4,4] array per pair (%d pairs)" % (fn, s))
+    arrs, koff = [], [0]
+    for j, init in enumerate(inits):
+        a = np.asarray(init.detach().cpu() if torch.is_tensor(init) else init, np.float64)
+        if a.shape != (4, 4) and (a.ndim != 3 or a.shape[1:] != (4, 4)):
+            raise ValueError("%s: inits[%d] must be [K,4,4] or [4,4], got %s" % (fn, j, a.shape))
+        arrs.append(a.reshape(-1, 4, 4))
+        koff.append(koff[-1] + arrs[-1].shape[0])
+        if arrs[-1].shape[0] and (soff[j + 1] == soff[j] or toff[j + 1] == toff[j]):
+            raise ValueError("%s: pair %d has candidates and an empty %s" % (fn, j, "source" if soff[j + 1] == soff[j] else "target"))
+    if s == 0:
+        return []
+    _lib.require_gpu(sp, tp)
+    if sp.device != tp.device:
+        raise ValueError("%s: sources and targets are on different devices" % fn)
+    k = koff[-1]
+    dev = sp.device
+    init_t = torch.as_tensor(np.concatenate(arrs, axis=0).reshape(k, 16)).contiguous().to(dev)
+    buf = torch.empty(k * 19, dtype=torch.float64, device=dev)           # transforms and statistics: one copy back
+    out_T, stats = buf[:k * 16].view(k, 16), buf[k * 16:].view(k, 3)
+    for a in range(0, s, ICP_RAGGED_MAX_PAIRS):
+        b = min(a + ICP_RAGGED_MAX_PAIRS, s)
+        sa, _k1 = _host_ints([v - soff[a] for v in soff[a:b + 1]])
+        ta, _k2 = _host_ints([v - toff[a] for v in toff[a:b + 1]])
+        ka, _k3 = _host_ints([v - koff[a] for v in koff[a:b + 1]])
+        rc = _lib.on_device_of(sp, _L.genpc_icp_batch_ragged, b - a, sa, ta, ka, _p(sp[soff[a]:soff[b]]), _p(tp[toff[a]:toff[b]]),
+                               float(max_correspondence_distance), _p(init_t[koff[a]:koff[b]]), int(max_iteration),
+                               float(relative_fitness), float(relative_rmse), _p(out_T[koff[a]:koff[b]]), _p(stats[koff[a]:koff[b]]))
+        if rc != 1:
+            raise RuntimeError("genpc_icp_batch_ragged failed (rc=%d): %s" % (rc, _lib.last_error()))
+    host = buf.cpu().numpy()
+    T = host[:k * 16].reshape(k, 4, 4)
+    st = host[k * 16:].reshape(k, 3)
+    res = []
+    for j in range(s):
+        a, b = koff[j], koff[j + 1]
+        if np.ndim(inits[j]) == 2:
+            res.append((T[a], float(st[a, 0]), float(st[a, 1]), int(st[a, 2])))
+        else:
+            res.append((T[a:b], st[a:b, 0], st[a:b, 1], st[a:b, 2].astype(int)))
+    return res
+
+
+def coarse_scale_sweeps(sources_down, targets_down, cd_inv_weight=0.5, scales=None, max_correspondence_distance=0.075,
+                        return_all=False):
+    """``coarse_scale_sweep`` for S scans at once (lists of [N_j,3] / [M_j,3] float32 GPU tensors, or packed): returns a list of
+    (best_scale, best_loss, coarse_transformation), with return_all also every candidate's transform [K,4,4] and score [K].
+    Two ``registration_icp_ragged`` calls -- one candidate per scan from the identity, then len(scales) per scan from
+    T1_j @ diag(scale) -- and the S * len(scales) (source, inverse-transformed target) pairs scored through ``chamfer_ragged``;
+    the first minimum wins, as the reference's strict '<'.  The host reads back three times whatever S is."""
+    from .loss_functions.Chamfer3D.dist_chamfer_ragged import chamfer_ragged
+    fn = "coarse_scale_sweeps"
+    sp, soff = _ragged_side(sources_down, fn, "sources_down")
+    tp, toff = _ragged_side(targets_down, fn, "targets_down")
+    if len(soff) != len(toff):
+        raise ValueError("%s: %d sources against %d targets" % (fn, len(soff) - 1, len(toff) - 1))
+    s = len(soff) - 1
+    if s == 0:
+        return []
+    if scales is None:
+        scales = np.linspace(1.5, 0.8, 11)
+    scales = np.atleast_1d(np.asarray(scales, np.float64))
+    k = len(scales)
+    md = max_correspondence_distance
+    first = registration_icp_ragged((sp, soff), (tp, toff), md, [np.eye(4)] * s)
+    inits = []
+    for j in range(s):                                       # icp_with_scaling: ICP again from result @ diag(scale)
+        cand = []
+        for sc in scales:
+            S = np.eye(4)
+            S[:3, :3] *= sc
+            cand.append(first[j][0] @ S)
+        inits.append(np.stack(cand))
+    T = [r[0] for r in registration_icp_ragged((sp, soff), (tp, toff), md, inits)]          # S x [K,4,4]
+    src_k, tgt_k, o1, o2 = [], [], [0], [0]
+    for j in range(s):                                       # :161-162, per scan as coarse_scale_sweep writes it
+        inv = torch.as_tensor(np.linalg.inv(T[j]), device=tp.device)
+        tgt = tp[toff[j]:toff[j + 1]].double()
+        tgt_k.append((tgt @ inv[:, :3, :3].transpose(1, 2) + inv[:, None, :3, 3]).float().reshape(-1, 3))
+        src_k.append(sp[soff[j]:soff[j + 1]].repeat(k, 1))
+        for _ in range(k):
+            o1.append(o1[-1] + soff[j + 1] - soff[j])
+            o2.append(o2[-1] + toff[j + 1] - toff[j])
+    # (chamfer_ragged takes as many library calls as its pair limit asks for)
+    d1, d2, _, _, _, _ = chamfer_ragged((torch.cat(src_k).contiguous(), o1), (torch.cat(tgt_k).contiguous(), o2))
+    scores = []
+    for j in range(s):
+        a1, a2 = d1[o1[j * k]:o1[(j + 1) * k]].view(k, -1), d2[o2[j * k]:o2[(j + 1) * k]].view(k, -1)
+        scores.append(torch.sqrt(a1).mean(1) + torch.sqrt(a2).mean(1) * cd_inv_weight)
+    cd = torch.stack(scores).cpu().numpy()                   # [S,K]: one copy back
+    out = []
+    for j in range(s):
+        best = int(np.argmin(cd[j]))                         # the first minimum == strict '<'
+        r = (float(scales[best]), float(cd[j, best]), T[j][best])
+        out.append(r + (T[j], cd[j].copy()) if return_all else r)
+    return out

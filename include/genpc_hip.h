@@ -40,6 +40,7 @@ int genpc_abi_version(void);              /* bumps when a signature or a documen
                                            * documented behaviour no longer bumps the number: genpc_knn_mean_distance_ragged and
                                            * genpc_outlier_filter_ragged came that way, and so did genpc_knn_query_ragged (additive: the number
                                            * stays 27) and genpc_emd_forward_ragged / genpc_emd_backward_ragged (additive as well: still 27);
+                                           * genpc_voxel_down_sample_ragged, genpc_icp_batch_ragged and genpc_icp_ragged_plan likewise: still 28;
                                            * a missing symbol is found when the binding loads. */
 const char *genpc_last_error(void);       /* last HIP error string, "" if none */
 int genpc_set_arith(int mode);            /* process default; returns the previous one */
@@ -507,6 +508,26 @@ int genpc_pose_optimize_batch(int b, int nc, const float *complete, const float 
 int genpc_voxel_down_sample(int n, const float *xyz, const float *colors, double voxel_size,
                             float *out, float *out_colors, int *out_count, void *stream);
 
+/* genpc_voxel_down_sample over a ragged batch: c clouds of any sizes, each with its own voxel size, one call
+ * (csrc/voxel_ragged.hip).  off[c + 1] and voxel_sizes[c] are HOST arrays: cloud j is xyz[off[j] .. off[j + 1]) of the packed
+ * [off[c],3] device points (colors: packed like xyz, or NULL) and is down-sampled at voxel_sizes[j].  out / out_colors have
+ * off[c] rows: cloud j's voxels are written to rows off[j] .. off[j] + out_counts[j]; out_counts[c] is a DEVICE array.
+ * Per cloud the rows and the count are the bits of genpc_voxel_down_sample on that cloud alone: the grid anchored at the
+ * cloud's OWN min_bound - voxel / 2, ascending (i, j, k), means in double in ascending point index.  out_counts[j] = -1 when
+ * a coordinate of cloud j is not finite or its grid exceeds 2^21 cells on an axis (its rows are then unspecified, every other
+ * cloud is unaffected); an empty cloud gives 0.
+ * Asynchronous on `stream`: a fixed number of launches whatever c is (bounds, keys, two stable radix sorts -- by key, then by
+ * cloud number --, run heads, one scan, means and counts, the error fold); the offsets and sizes travel by value in the kernel
+ * arguments, so nothing of the host arrays is read after return and no copy is enqueued -- which bounds c.
+ * Returns 1 on success (also for c == 0: nothing written), 0 on a HIP error; -1 with genpc_last_error set
+ * ("genpc_voxel_down_sample_ragged: ...") and nothing enqueued for c < 0, c > GENPC_VOXEL_RAGGED_MAX_CLOUDS, a null table,
+ * off[0] != 0, descending offsets, more than 2^28 points, a voxel size that is not > 0 (the message names the cloud), or a
+ * null device pointer with work to do.                                                                                  */
+#define GENPC_VOXEL_RAGGED_MAX_CLOUDS 256
+int genpc_voxel_down_sample_ragged(int c, const int *off, const float *xyz, const float *colors,
+                                   const double *voxel_sizes, float *out, float *out_colors,
+                                   int *out_counts, void *stream);
+
 /* ICP + scale search --------------------------------------------------------- *
  * Batched point-to-point ICP with the semantics of open3d's registration_icp as
  * reg_xyz.py calls it (:18-20,28-37: TransformationEstimationPointToPoint, default
@@ -525,6 +546,30 @@ int genpc_icp_batch(int k, int ns, const float *source, int nt, const float *tar
  * (five launches per pass); out[1] = the grid's cell budget (8192, 4096, 2048 or 1024; 0 for the
  * loop); out[2] = the launch's dynamic LDS in bytes (0 for the loop).  Returns -1 for out == NULL. */
 int genpc_icp_plan(int nt, int out[3]);
+
+/* genpc_icp_batch over a ragged batch: c (source, target) pairs of any sizes, each with its own candidates, one call.
+ * soff / toff / koff [c + 1] are HOST arrays (by value in the kernel arguments: nothing is read after return, which bounds c):
+ * pair j is source[soff[j] .. soff[j + 1]) against target[toff[j] .. toff[j + 1]) of the packed device clouds, its candidates
+ * are the rows koff[j] .. koff[j + 1] of init[K,16] (K = koff[c]; row-major 4x4, DOUBLE, device); out_T[K,16] and stats[K,3]
+ * as in genpc_icp_batch.  The pairs whose target count gets the one-workgroup plan (genpc_icp_plan) are ALL solved by one
+ * launch, a workgroup per (pair, candidate) with its own pair's cell budget: each of their candidates gets the BITS of
+ * genpc_icp_batch on that pair alone, in both arithmetic modes.  The others run, one pair after the other inside the call,
+ * through genpc_icp_batch's multi-launch loop and get what it gives them.  A pair without candidates is skipped.
+ * Returns 1 on success (also when there is no candidate: nothing written), 0 on a HIP error; -1 with genpc_last_error set
+ * ("genpc_icp_batch_ragged: ...") and nothing enqueued for c < 0, max_iter < 0, c > GENPC_ICP_RAGGED_MAX_PAIRS, a null table,
+ * a table that does not start at 0 or descends, more than 2^28 points on a side, more than 2^20 candidates, a pair that has
+ * candidates and an empty source or target (the message names it), or a null device pointer with work to do.            */
+#define GENPC_ICP_RAGGED_MAX_PAIRS 256
+int genpc_icp_batch_ragged(int c, const int *soff, const int *toff, const int *koff,
+                           const float *source, const float *target, double max_dist,
+                           const double *init, int max_iter, double rel_fitness, double rel_rmse,
+                           double *out_T, double *stats, void *stream);
+
+/* How a genpc_icp_batch_ragged call with these target offsets is split (csrc/icp_ragged_plan.h; no GPU is touched):
+ * out[0] = the pairs solved by the one launch, out[1] = the pairs sent to the multi-launch loop (a pair without targets is
+ * on neither side), out[2] = the launch's dynamic LDS in bytes, the largest of its pairs' genpc_icp_plan.  Returns 1; -1
+ * with genpc_last_error set for out == NULL, c < 0, c > GENPC_ICP_RAGGED_MAX_PAIRS, a null or ill-formed toff.          */
+int genpc_icp_ragged_plan(int c, const int *toff, int out[3]);
 
 /* Scores of iterative_scale_search (reg_xyz.py:60-96) for K anisotropic scale
  * candidates scales[K,3] in one batched NN launch:
