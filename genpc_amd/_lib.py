@@ -73,6 +73,8 @@ SIGNATURES = {
     "genpc_icp_plan": (_i, [_i, _vp]),
     "genpc_icp_batch_ragged": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _d, _vp, _i, _d, _d, _vp, _vp, _vp]),
     "genpc_icp_ragged_plan": (_i, [_i, _vp, _vp]),
+    "genpc_scale_search_scores_ragged": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp]),
+    "genpc_scale_search_ragged_plan": (_i, [_i, _vp, _vp]),
     "genpc_nn_plan": (_i, [_i, _i, _i, _i, _i, _vp]),
     "genpc_hpr_plan": (_i, [_i, _i, _i, _i, _vp]),
     "genpc_scale_search_scores": (_i, [_i, _i, _vp, _i, _vp, _vp, _f, _vp, _vp]),

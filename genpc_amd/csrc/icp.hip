@@ -23,6 +23,7 @@
 #include "ragged_table.h"
 #define GENPC_ICP_PLAN_HD GENPC_RAGGED_HD          // icp_plan() on the device too: icp_fused_ragged_kernel
 #include "icp_ragged_plan.h"
+#include "cd_score.h"                              // kIBlock, and the score's sums in their one order
 #include "../../include/genpc_hip.h"
 
 #include <math.h>
@@ -33,8 +34,6 @@ extern "C" int genpc_chamfer_forward(int b, int n, const float *xyz1, int m, con
                                      int *idx1, float *dist2, int *idx2, void *stream);
 
 namespace genpc {
-
-constexpr int kIBlock = 256;
 
 struct IcpState {
     double prev_fitness, prev_rmse;
@@ -309,29 +308,9 @@ __global__ __launch_bounds__(kIBlock) void cd_score_kernel(int n1, const float *
 {
     __shared__ double red[2][kIBlock / kWave];
     const int c = blockIdx.x;
-    double a = 0.0, b = 0.0;
-    for (int j = threadIdx.x; j < n1; j += kIBlock) a += (double)sqrtf(d1[(size_t)c * n1 + j]);
-    for (int j = threadIdx.x; j < n2; j += kIBlock) b += (double)sqrtf(d2[(size_t)c * n2 + j]);
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        a += __shfl_xor(a, off, kWave);
-        b += __shfl_xor(b, off, kWave);
-    }
-    if (lane == 0) {
-        red[0][wave] = a;
-        red[1][wave] = b;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double x = 0.0, y = 0.0;
-        for (int q = 0; q < kIBlock / kWave; q++) {
-            x += red[0][q];
-            y += red[1][q];
-        }
-        const float m1 = (float)(x / n1), m2 = (float)(y / n2);
-        scores[c] = m1 + m2 * w;
-    }
+    const double a = cd_score_thread_sum(n1, [&](int j) { return d1[(size_t)c * n1 + j]; });
+    const double b = cd_score_thread_sum(n2, [&](int j) { return d2[(size_t)c * n2 + j]; });
+    cd_score_reduce(a, b, n1, n2, w, &red[0][0], scores + c);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

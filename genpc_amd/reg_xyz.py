@@ -738,3 +738,122 @@ def coarse_scale_sweeps(sources_down, targets_down, cd_inv_weight=0.5, scales=No
         r = (float(scales[best]), float(cd[j, best]), T[j][best])
         out.append(r + (T[j], cd[j].copy()) if return_all else r)
     return out
+
+
+# ---------------------------------------------------------------------------
+# The fine xyz scale search of reg() (reg_xyz.py:60-96, :176-199) for S scans per library call.
+# ---------------------------------------------------------------------------
+SCALE_SEARCH_RAGGED_MAX_PAIRS = 256      # include/genpc_hip.h: GENPC_SCALE_SEARCH_RAGGED_MAX_PAIRS
+
+
+def _scale_search_scores_packed(sources, targets, scales, cd_inv_weight, fn):
+    """(scores [K] float32 on the device -- None without a scan --, koff: S + 1 Python ints) of scale_search_scores_ragged."""
+    sp, soff = _ragged_side(sources, fn, "sources")
+    tp, toff = _ragged_side(targets, fn, "targets")
+    if len(soff) != len(toff):
+        raise ValueError("%s: %d sources against %d targets" % (fn, len(soff) - 1, len(toff) - 1))
+    s = len(soff) - 1
+    if not isinstance(scales, (list, tuple)) or len(scales) != s:
+        raise ValueError("%s: scales is a list of one [K,3] array per pair (%d pairs)" % (fn, s))
+    rows, koff = [], [0]
+    for j, sc in enumerate(scales):
+        a = sc.detach().float() if torch.is_tensor(sc) else torch.from_numpy(np.asarray(sc).astype(np.float32))
+        if a.numel() == 0 and a.dim() == 1:
+            a = a.reshape(0, 3)
+        if a.dim() != 2 or a.shape[1] != 3:
+            raise ValueError("%s: scales[%d] must be [K,3], got %s" % (fn, j, tuple(a.shape)))
+        rows.append(a)
+        koff.append(koff[-1] + a.shape[0])
+        if a.shape[0] and (soff[j + 1] == soff[j] or toff[j + 1] == toff[j]):
+            raise ValueError("%s: pair %d has candidates and an empty %s" % (fn, j, "source" if soff[j + 1] == soff[j] else "target"))
+    if s == 0:
+        return None, koff
+    _lib.require_gpu(sp, tp)
+    if sp.device != tp.device:
+        raise ValueError("%s: sources and targets are on different devices" % fn)
+    dev = sp.device
+    if all(not r.is_cuda for r in rows):
+        scales_t = torch.cat(rows).contiguous().to(dev)              # host candidates: one upload
+    else:
+        scales_t = torch.cat([r.to(dev) for r in rows]).contiguous()
+    scores = torch.empty(koff[-1], device=dev)
+    for a in range(0, s, SCALE_SEARCH_RAGGED_MAX_PAIRS):
+        b = min(a + SCALE_SEARCH_RAGGED_MAX_PAIRS, s)
+        sa, _k1 = _host_ints([v - soff[a] for v in soff[a:b + 1]])
+        ta, _k2 = _host_ints([v - toff[a] for v in toff[a:b + 1]])
+        ka, _k3 = _host_ints([v - koff[a] for v in koff[a:b + 1]])
+        rc = _lib.on_device_of(sp, _L.genpc_scale_search_scores_ragged, b - a, sa, ta, ka, _p(sp[soff[a]:soff[b]]), _p(tp[toff[a]:toff[b]]),
+                               _p(scales_t[koff[a]:koff[b]]), float(cd_inv_weight), _p(scores[koff[a]:koff[b]]))
+        if rc != 1:
+            raise RuntimeError("genpc_scale_search_scores_ragged failed (rc=%d): %s" % (rc, _lib.last_error()))
+    return scores, koff
+
+
+def scale_search_scores_ragged(sources, targets, scales, cd_inv_weight=0):
+    """The scores of ``iterative_scale_search`` for S (source, target) pairs of any sizes at once: sources / targets are lists of
+    [N_j,3] / [M_j,3] float32 GPU tensors or packed (points, offsets); scales a list of S arrays or tensors [K_j,3] (K_j = 0
+    skips the pair).  Returns a list of float32 [K_j] device tensors, views of one packed result: candidate k of pair j gets
+    mean sqrt(NN(source_j * scales_j[k] -> target_j)) + cd_inv_weight * mean sqrt(NN(target_j -> source_j * scales_j[k])), the
+    bits of genpc_scale_search_scores on the pair alone.  One library call per 256 pairs (genpc_scale_search_scores_ragged: two
+    launches each, no copy of a cloud per candidate); nothing waits for the result."""
+    scores, koff = _scale_search_scores_packed(sources, targets, scales, cd_inv_weight, "scale_search_scores_ragged")
+    if scores is None:
+        return []
+    return [scores[koff[j]:koff[j + 1]] for j in range(len(koff) - 1)]
+
+
+def iterative_scale_searches(sources, targets, scale_ranges, scale_steps, init_transforms=None, cd_inv_weight=0):
+    """``iterative_scale_search`` for S scans at once (lists of [N_j,3] / [M_j,3] float32 GPU tensors, or packed): scale_ranges is
+    three (lo, hi) pairs for all scans or a list of S such triples; init_transforms None or a list of S [4,4] arrays (None: the
+    identity).  Returns a list of (best_scales_transformation [4,4], best_loss, best_transformation [4,4]); scan j's is what
+    ``iterative_scale_search(sources[j], targets[j], ...)`` returns -- the scores and the winner bit for bit, the winner's ICP
+    bit for bit where its target gets the one-workgroup ICP plan (``registration_icp_ragged``).  Candidate order z (outer), x,
+    y (inner); the first minimum wins.  One ``scale_search_scores_ragged``, ONE read-back of all scores and one
+    ``registration_icp_ragged`` over the winners, whatever S is.  A scan whose scores hold a NaN raises ValueError naming it."""
+    fn = "iterative_scale_searches"
+    sp, soff = _ragged_side(sources, fn, "sources")
+    tp, toff = _ragged_side(targets, fn, "targets")
+    if len(soff) != len(toff):
+        raise ValueError("%s: %d sources against %d targets" % (fn, len(soff) - 1, len(toff) - 1))
+    s = len(soff) - 1
+    shape = np.shape(scale_ranges)
+    if shape == (3, 2):
+        ranges = [scale_ranges] * s
+    elif shape == (s, 3, 2):
+        ranges = list(scale_ranges)
+    else:
+        raise ValueError("%s: scale_ranges is three (lo, hi) pairs, or one such triple per scan (%d scans)" % (fn, s))
+    if init_transforms is not None and (not isinstance(init_transforms, (list, tuple)) or len(init_transforms) != s):
+        raise ValueError("%s: init_transforms is None or a list of one [4,4] array per scan (%d scans)" % (fn, s))
+    inits = []
+    for j in range(s):
+        T = np.eye(4) if init_transforms is None or init_transforms[j] is None else np.asarray(init_transforms[j], np.float64)
+        if T.shape != (4, 4):
+            raise ValueError("%s: init_transforms[%d] must be [4,4], got %s" % (fn, j, T.shape))
+        inits.append(T)
+    cands = []
+    for r in ranges:
+        xs = np.linspace(r[0][0], r[0][1], scale_steps)
+        ys = np.linspace(r[1][0], r[1][1], scale_steps)
+        zs = np.linspace(r[2][0], r[2][1], scale_steps)
+        gz, gx, gy = np.meshgrid(zs, xs, ys, indexing="ij")          # candidate order z (outer), x, y (inner)
+        cands.append(np.stack([gx.ravel(), gy.ravel(), gz.ravel()], axis=1).astype(np.float64))
+    scores, koff = _scale_search_scores_packed((sp, soff), (tp, toff), cands, cd_inv_weight, fn)
+    if s == 0:
+        return []
+    sc = scores.cpu().numpy()                                        # (the one read-back of the scores)
+    best, scaled = [], []
+    for j in range(s):
+        sj = sc[koff[j]:koff[j + 1]]
+        if np.isnan(sj).any():
+            raise ValueError("%s: scan %d has a NaN score (a non-finite coordinate, or a scaled one that overflows)" % (fn, j))
+        best.append(int(np.argmin(sj)))                              # the first minimum == strict '<'
+        sv = torch.as_tensor(cands[j][best[j]], device=sp.device)
+        scaled.append((sp[soff[j]:soff[j + 1]].double() * sv).float())   # icp_with_scaling_xyz's statement
+    icp = registration_icp_ragged(scaled, (tp, toff), 0.075, inits)
+    out = []
+    for j in range(s):
+        S = np.eye(4)
+        S[0, 0], S[1, 1], S[2, 2] = cands[j][best[j]]
+        out.append((S, float(sc[koff[j] + best[j]]), icp[j][0]))
+    return out

@@ -41,6 +41,7 @@ int genpc_abi_version(void);              /* bumps when a signature or a documen
                                            * genpc_outlier_filter_ragged came that way, and so did genpc_knn_query_ragged (additive: the number
                                            * stays 27) and genpc_emd_forward_ragged / genpc_emd_backward_ragged (additive as well: still 27);
                                            * genpc_voxel_down_sample_ragged, genpc_icp_batch_ragged and genpc_icp_ragged_plan likewise: still 28;
+                                           * genpc_scale_search_scores_ragged and genpc_scale_search_ragged_plan too: still 28;
                                            * a missing symbol is found when the binding loads. */
 const char *genpc_last_error(void);       /* last HIP error string, "" if none */
 int genpc_set_arith(int mode);            /* process default; returns the previous one */
@@ -578,6 +579,35 @@ int genpc_icp_ragged_plan(int c, const int *toff, int out[3]);
 int genpc_scale_search_scores(int k, int ns, const float *source, int nt,
                               const float *target, const float *scales,
                               float cd_inv_weight, float *scores, void *stream);
+
+/* genpc_scale_search_scores over a ragged batch: c (source, target) pairs of any sizes, each with its own candidates, one call.
+ * soff / toff / koff [c + 1] are HOST arrays (by value in the kernel arguments: nothing is read after return, which bounds c):
+ * pair j is source[soff[j] .. soff[j + 1]) against target[toff[j] .. toff[j + 1]) of the packed device clouds, its candidates
+ * are the rows koff[j] .. koff[j + 1] of scales[K,3] (K = koff[c]; float32, device); scores[K] is device float32:
+ *   scores[k] = float(mean64 sqrtf(NN(s_k o source -> target))) + float(mean64 sqrtf(NN(target -> s_k o source))) * cd_inv_weight
+ * with s_k o p = (float)((double)p * (double)s) per axis.  Two launches whatever c and K are: one grid per pair's target, then
+ * one workgroup per candidate, which keeps the scaled source and its own grid in LDS and adds the distances where it finds
+ * them; no copy of either cloud and no distance array is written, no floating-point atomic is used.
+ * On finite input every candidate's score is the BITS of genpc_scale_search_scores on its pair alone, in both arithmetic
+ * modes, wherever the pair stands in the batch.  A pair whose source does not fit a compute unit's LDS
+ * (genpc_scale_search_ragged_plan) is scored inside the call by genpc_scale_search_scores on its slices.  A pair without
+ * candidates is skipped.  Not finite: a pair whose target holds a non-finite coordinate gets NaN for all its scores, a
+ * candidate whose scaled source holds one (a non-finite scale, a product that overflows) gets NaN, the others do not notice
+ * (for the pairs of the one launch; what genpc_scale_search_scores returns on such input is not defined).
+ * Returns 1 on success (also when there is no candidate: nothing written), 0 on a HIP error; -1 with genpc_last_error set
+ * ("genpc_scale_search_scores_ragged: ...") and nothing enqueued for c < 0, c > GENPC_SCALE_SEARCH_RAGGED_MAX_PAIRS, a null
+ * table, a table that does not start at 0 or descends, more than 2^28 points on a side, more than 2^20 candidates, a pair that
+ * has candidates and an empty source or target (the message names it), or a null device pointer with work to do.        */
+#define GENPC_SCALE_SEARCH_RAGGED_MAX_PAIRS 256
+int genpc_scale_search_scores_ragged(int c, const int *soff, const int *toff, const int *koff,
+                                     const float *source, const float *target, const float *scales,
+                                     float cd_inv_weight, float *scores, void *stream);
+
+/* How a genpc_scale_search_scores_ragged call with these source offsets is split (csrc/scale_search_ragged_plan.h; no GPU is
+ * touched): out[0] = the pairs scored by the one launch, out[1] = the pairs sent to genpc_scale_search_scores (a pair without
+ * source points is on neither side), out[2] = the launch's dynamic LDS in bytes, the largest of its pairs'.  Returns 1; -1
+ * with genpc_last_error set for out == NULL, c < 0, c > GENPC_SCALE_SEARCH_RAGGED_MAX_PAIRS, a null or ill-formed soff. */
+int genpc_scale_search_ragged_plan(int c, const int *soff, int out[3]);
 
 /* Hardware-premise probe ------------------------------------------------------ *
  * D[p] = A[p] B[p] + C[p] for `problems` independent 32x16 * 16x32 + 32x32 products computed by ONE

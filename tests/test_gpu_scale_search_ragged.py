@@ -1,0 +1,273 @@
+"""genpc_scale_search_scores_ragged and reg_xyz.iterative_scale_searches on the GPU (csrc/scale_search_ragged.hip).
+
+Bars.  Against genpc_scale_search_scores on each pair alone: the BITS, in both arithmetic modes -- the nearest distance is a
+minimum over sqdist values and does not depend on how it is found, and both kernels add the square roots in csrc/cd_score.h's one
+order.  Against the definition (the CPU oracle's exhaustive Chamfer on the scaled source, float32(mean64(sqrt32(d)))): one fp32
+ulp, as tests/test_gpu_icp_paths.py::test_scale_search_scores_with_duplicates derives it (the double sums differ only by their
+order, so the rounding can flip only at a tie).  The clouds are icp_pass_ref.shape's, a few to 3000 points, so that every test
+takes a few seconds; the two sizes at the plan's boundary come from genpc_scale_search_ragged_plan."""
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+
+import icp_pass_ref as R
+from test_gpu_icp_paths import library_modes
+
+pytestmark = pytest.mark.gpu
+
+W = np.float32(0.5)
+SENTINEL = 0x7FC12345          # (a NaN with a payload: no score has these bits)
+
+
+@pytest.fixture(scope="module")
+def rg():
+    import torch
+    assert torch.cuda.is_available(), "-m gpu tests need a GPU"
+    from genpc_amd import _lib, reg_xyz
+    return dict(torch=torch, R=reg_xyz, lib=_lib.lib, L=_lib)
+
+
+def grid27():
+    xs = np.linspace(0.8, 1.2, 3)
+    return np.array([[x, y, z] for z in xs for x in xs for y in xs]).astype(np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def pairs():
+    """[(name, source [ns,3], target [nt,3], candidates [K,3])]: the cases of the issue, in the order of the call."""
+    out = []
+    seed = 100
+    for i, ns in enumerate((1, 63, 64, 65, 255, 256, 257, 700)):
+        for j, nt in enumerate((1, 300, 3000)):
+            seed += 1
+            src = (R.shape(seed, ns).astype(np.float64) * 0.97 + 0.01).astype(np.float32)
+            cand = grid27() if (i + j) % 2 == 0 else np.array([[1.05, 0.9, 1.1]], np.float32)
+            out.append(("ns%d_nt%d" % (ns, nt), src, R.shape(seed + 500, nt), cand))
+    out.insert(5, ("skipped", np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32)))
+    # the existing test's construction: duplicates on both sides, 200 source points one ulp beside others that collapse under some scales
+    rng = np.random.default_rng(77)
+    src = R.shape(11, 700)[np.arange(2048) % 700]
+    near = src[rng.integers(0, 2048, 200)].copy()
+    near[:, 0] = np.nextafter(near[:, 0], np.float32(np.inf))
+    src = np.ascontiguousarray(np.concatenate([src, near]))
+    out.append(("duplicates", src, np.ascontiguousarray(R.shape(12, 1800)[rng.integers(0, 1800, 3000)]), grid27()))
+    out.append(("all_equal_source", np.ascontiguousarray(np.repeat(R.shape(13, 1), 300, axis=0)), R.shape(14, 300), grid27()))
+    flat_s, flat_t = R.shape(15, 257).copy(), R.shape(16, 300).copy()
+    flat_s[:, 2] = 0.0
+    flat_t[:, 2] = 0.0
+    out.append(("coplanar", flat_s, flat_t, grid27()))
+    far = np.array([[1e-3, 1e-3, 1e-3], [50, 50, 50], [-1, -1, -1], [1e-3, 50, 1], [1, 1, 1]], np.float32)
+    out.append(("far_scales", R.shape(17, 700), R.shape(18, 300), far))
+    for _, s, t, c in out:
+        for a in (s, t, c):
+            a.setflags(write=False)
+    return tuple(out)
+
+
+def single(rg, src, tgt, cand, w=W):
+    """genpc_scale_search_scores on one pair alone -> float32 [K]."""
+    torch = rg["torch"]
+    S_, T_, C_ = (torch.from_numpy(np.array(a, np.float32)).cuda() for a in (src, tgt, cand))
+    scores = torch.empty(len(cand), device="cuda")
+    rc = rg["L"].on_device_of(S_, rg["lib"].genpc_scale_search_scores, len(cand), src.shape[0], rg["L"].ptr(S_), tgt.shape[0],
+                              rg["L"].ptr(T_), rg["L"].ptr(C_), float(w), rg["L"].ptr(scores))
+    assert rc == 1, rg["L"].last_error()
+    return scores.cpu().numpy()
+
+
+def ragged(rg, cases, w=W, packed=False):
+    """reg_xyz.scale_search_scores_ragged over `cases` -> list of float32 [K_j] numpy arrays."""
+    torch = rg["torch"]
+    src = [torch.from_numpy(np.array(c[1], np.float32)).cuda() for c in cases]
+    tgt = [torch.from_numpy(np.array(c[2], np.float32)).cuda() for c in cases]
+    if packed:
+        so, to = np.cumsum([0] + [len(s) for s in src]).tolist(), np.cumsum([0] + [len(t) for t in tgt]).tolist()
+        src, tgt = (torch.cat(src).contiguous(), so), (torch.cat(tgt).contiguous(), to)
+    got = rg["R"].scale_search_scores_ragged(src, tgt, [c[3] for c in cases], cd_inv_weight=float(w))
+    torch.cuda.synchronize()
+    return [g.cpu().numpy() for g in got]
+
+
+_CACHE = {}
+
+
+def batch(rg, mode):
+    """(the one ragged call over pairs(), each pair alone), computed once per arithmetic mode."""
+    if mode not in _CACHE:
+        with library_modes(rg, mode):
+            got = ragged(rg, pairs())
+            alone = [single(rg, s, t, c) if len(c) else np.zeros(0, np.float32) for _, s, t, c in pairs()]
+        _CACHE[mode] = (got, alone)
+    return _CACHE[mode]
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_bits_per_pair(rg, mode):
+    """One call over every case: each pair's scores are the bits of genpc_scale_search_scores on the pair alone."""
+    got, alone = batch(rg, mode)
+    assert len(got) == len(pairs())
+    for (name, _, _, cand), g, a in zip(pairs(), got, alone):
+        assert g.shape == (len(cand),) and g.dtype == np.float32, name
+        assert np.isfinite(a).all(), name
+        assert np.array_equal(bits(g), bits(a)), (name, mode, g, a)
+
+
+@functools.lru_cache(maxsize=None)
+def definition(mode):
+    """The scores of pairs() from the oracle's exhaustive Chamfer, as test_scale_search_scores_with_duplicates writes them."""
+    from oracle import oracle
+    oracle.build()
+    out = []
+    for _, src, tgt, cand in pairs():
+        exp = []
+        for c in cand:
+            sc = (src.astype(np.float64) * c.astype(np.float64)).astype(np.float32)
+            d1, d2, _, _ = oracle.chamfer_forward(sc[None], np.ascontiguousarray(tgt)[None], mode)
+            m1 = np.float32(np.sqrt(d1[0]).astype(np.float64).mean())
+            m2 = np.float32(np.sqrt(d2[0]).astype(np.float64).mean())
+            exp.append(np.float32(m1 + np.float32(m2 * W)))
+        out.append(np.array(exp, np.float32))
+    return out
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_against_the_definition(rg, oracle, mode):
+    got, _ = batch(rg, mode)
+    worst = 0.0
+    for (name, _, _, _), g, e in zip(pairs(), got, definition(mode)):
+        if not len(e):
+            continue
+        ulp = np.spacing(e)
+        worst = max(worst, float((np.abs(g.astype(np.float64) - e.astype(np.float64)) / ulp).max()))
+        assert (np.abs(g.astype(np.float64) - e.astype(np.float64)) <= ulp).all(), (name, mode, g, e)
+    print("mode %d: largest difference to the definition %.3g ulp" % (mode, worst))
+
+
+def plan(rg, sizes):
+    soff = (ctypes.c_int * (len(sizes) + 1))(*np.cumsum([0] + list(sizes)).tolist())
+    out = (ctypes.c_int * 3)(-1, -1, -1)
+    assert rg["lib"].genpc_scale_search_ragged_plan(len(sizes), ctypes.cast(soff, ctypes.c_void_p), ctypes.cast(out, ctypes.c_void_p)) == 1
+    return tuple(out)
+
+
+@functools.lru_cache(maxsize=None)
+def last_fused(rg_lib):
+    lo, hi = 1, 1 << 20
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        soff = (ctypes.c_int * 2)(0, mid)
+        out = (ctypes.c_int * 3)()
+        assert rg_lib.genpc_scale_search_ragged_plan(1, ctypes.cast(soff, ctypes.c_void_p), ctypes.cast(out, ctypes.c_void_p)) == 1
+        lo, hi = (mid, hi) if out[0] == 1 else (lo, mid - 1)
+    return lo
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_plan_boundary(rg, mode):
+    """The largest source of the one launch and the smallest of the single call, a small pair between them, in one call."""
+    last = last_fused(rg["lib"])
+    assert plan(rg, [last])[:2] == (1, 0) and plan(rg, [last + 1])[:2] == (0, 1)
+    two = np.array([[0.9, 1.1, 1.0], [1.15, 0.85, 1.05]], np.float32)
+    cases = [("last", R.shape(31, last), R.shape(32, 300), two), ("small", R.shape(33, 65), R.shape(34, 300), two),
+             ("first_beyond", R.shape(35, last + 1), R.shape(36, 300), two)]
+    fused, loop, lds = plan(rg, [len(c[1]) for c in cases])
+    assert (fused, loop) == (2, 1) and lds == plan(rg, [last])[2]
+    with library_modes(rg, mode):
+        got = ragged(rg, cases)
+        for (name, s, t, c), g in zip(cases, got):
+            a = single(rg, s, t, c)
+            assert np.array_equal(bits(g), bits(a)), (name, mode, g, a)
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_position_independence_and_repeatability(rg, mode):
+    got, _ = batch(rg, mode)
+    with library_modes(rg, mode):
+        again = ragged(rg, pairs())
+        rev = ragged(rg, pairs()[::-1])[::-1]
+        packed = ragged(rg, pairs(), packed=True)
+    for (name, _, _, _), g, a, r, p in zip(pairs(), got, again, rev, packed):
+        assert np.array_equal(bits(g), bits(a)), (name, "the same call twice")
+        assert np.array_equal(bits(g), bits(r)), (name, "reversed order")
+        assert np.array_equal(bits(g), bits(p)), (name, "packed input")
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_nothing_else_is_written(rg, mode):
+    """The C entry point on a scores buffer with sentinel words in front and behind: those stay, and the words between are the
+    scores (the skipped pair has no word: its neighbours' ranges touch)."""
+    torch = rg["torch"]
+    names = [p[0] for p in pairs()]
+    cases = [pairs()[names.index(n)] for n in ("ns65_nt300", "skipped", "ns257_nt1", "coplanar")]
+    src = torch.from_numpy(np.concatenate([c[1] for c in cases])).cuda()
+    tgt = torch.from_numpy(np.concatenate([c[2] for c in cases])).cuda()
+    cand = torch.from_numpy(np.concatenate([c[3] for c in cases])).cuda()
+    tabs = [(ctypes.c_int * 5)(*np.cumsum([0] + [len(c[i]) for c in cases]).tolist()) for i in (1, 2, 3)]
+    k, pad = tabs[2][4], 64
+    buf = torch.full((k + 2 * pad,), SENTINEL, dtype=torch.int32, device="cuda")
+    with library_modes(rg, mode):
+        rc = rg["L"].on_device_of(src, rg["lib"].genpc_scale_search_scores_ragged, 4, *[ctypes.cast(t, ctypes.c_void_p) for t in tabs],
+                                  rg["L"].ptr(src), rg["L"].ptr(tgt), rg["L"].ptr(cand), float(W), rg["L"].ptr(buf[pad:]))
+        torch.cuda.synchronize()
+    assert rc == 1, rg["L"].last_error()
+    host = buf.cpu().numpy().view(np.uint32)
+    assert (host[:pad] == SENTINEL).all() and (host[pad + k:] == SENTINEL).all()
+    got, _ = batch(rg, mode)
+    want = np.concatenate([bits(got[names.index(c[0])]) for c in cases])
+    assert np.array_equal(host[pad:pad + k], want)
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_not_finite(rg, mode):
+    """A NaN in one pair's target: all its scores NaN.  An inf scale in one candidate of another pair: that score alone.  Every
+    other score has the bits of the clean call."""
+    names = [p[0] for p in pairs()]
+    cases = [list(pairs()[names.index(n)]) for n in ("ns700_nt300", "ns64_nt3000", "coplanar", "ns256_nt300")]
+    got, _ = batch(rg, mode)
+    clean = [got[names.index(c[0])] for c in cases]
+    tgt = cases[0][2].copy()
+    tgt[123, 1] = np.nan
+    cases[0][2] = tgt
+    cand = cases[2][3].copy()
+    cand[5, 2] = np.inf
+    cases[2][3] = cand
+    with library_modes(rg, mode):
+        dirty = ragged(rg, cases)
+    assert np.isnan(dirty[0]).all() and len(dirty[0]) == 27
+    assert np.isnan(dirty[2][5])
+    keep = np.arange(27) != 5
+    assert np.array_equal(bits(dirty[2][keep]), bits(clean[2][keep]))
+    assert np.array_equal(bits(dirty[1]), bits(clean[1])) and np.array_equal(bits(dirty[3]), bits(clean[3]))
+
+
+def test_the_python_layer(rg):
+    """iterative_scale_searches over three scans of different sizes: every triple is iterative_scale_search's on the scan alone
+    (the targets get the one-workgroup ICP plan: bit for bit); a scan with a NaN raises and is named."""
+    torch = rg["torch"]
+    sizes = ((300, 450), (1100, 2000), (2000, 800))
+    init1 = np.eye(4)
+    init1[:3, :3] = R.rot([0.1, 0.3, 1.0], 2.0)
+    init1[:3, 3] = [0.004, -0.003, 0.002]
+    src = [torch.from_numpy((R.shape(41 + j, ns).astype(np.float64) * (0.9 + 0.08 * j)).astype(np.float32)).cuda() for j, (ns, _) in enumerate(sizes)]
+    tgt = [torch.from_numpy(R.shape(51 + j, nt)).cuda() for j, (_, nt) in enumerate(sizes)]
+    assert all(R.plan(nt)[0] == 1 for _, nt in sizes)
+    ranges, inits = [(0.8, 1.2)] * 3, [None, init1, None]
+    got = rg["R"].iterative_scale_searches(src, tgt, ranges, 3, init_transforms=inits, cd_inv_weight=0.5)
+    assert len(got) == 3
+    for j in range(3):
+        S, loss, T = rg["R"].iterative_scale_search(src[j], tgt[j], ranges, 3, init_transform=inits[j], cd_inv_weight=0.5)
+        assert np.array_equal(got[j][0], S) and got[j][1] == loss and np.array_equal(got[j][2], T), j
+    # per-scan ranges give the same as the shared triple
+    per_scan = rg["R"].iterative_scale_searches(src, tgt, [ranges] * 3, 3, init_transforms=inits, cd_inv_weight=0.5)
+    for a, b in zip(got, per_scan):
+        assert np.array_equal(a[0], b[0]) and a[1] == b[1] and np.array_equal(a[2], b[2])
+    bad = tgt[1].clone()
+    bad[7, 0] = float("nan")
+    with pytest.raises(ValueError, match="scan 1 "):
+        rg["R"].iterative_scale_searches(src, [tgt[0], bad, tgt[2]], ranges, 3, cd_inv_weight=0.5)
