@@ -103,6 +103,7 @@ SIGNATURES = {
     "genpc_uhd_ragged": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "genpc_mesh_sample_bytes": (_i, [_i]),
     "genpc_mesh_sample": (_i, [_i, _vp, _vp, _i, _vp, _i, ctypes.c_ulonglong, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "genpc_mesh_sample_ragged": (_i, [_i] + [_vp] * 13),
 }
 
 

@@ -73,6 +73,7 @@ enum Ws : int {
     kWsEmdRagged = 45,        // emd_ragged.hip genpc_emd_forward_ragged: two bidder lists | filter seeds | two counts per pair
     kWsVoxelRagged = 46,      // voxel_ragged.hip genpc_voxel_down_sample_ragged: per-cloud bounds and error words | keys | clouds | orders | heads | ranks | sort / scan scratch
     kWsScaleSearchRagged = 47, // scale_search_ragged.hip genpc_scale_search_scores_ragged: the targets' grid headers | cell tables | sorted targets (nothing per candidate)
+    kWsMeshSampleRagged = 48, // mesh_sample_ragged.hip genpc_mesh_sample_ragged: per-mesh headers | per-face local cumulative weights | per-chunk sums
 };
 
 // The scratch pool: one grow-only block of device memory per (device, slot, stream); null on failure, the error recorded.

@@ -857,3 +857,209 @@ def iterative_scale_searches(sources, targets, scale_ranges, scale_steps, init_t
         S[0, 0], S[1, 1], S[2, 2] = cands[j][best[j]]
         out.append((S, float(sc[koff[j] + best[j]]), icp[j][0]))
     return out
+
+
+# ---------------------------------------------------------------------------
+# reg() over S scans: every stage of stage 2 but the pose initialisation's alignment loop is one pass for all of them.
+# ---------------------------------------------------------------------------
+def _scan_list(x, s, fn, name):
+    """None, or a list of s entries (each a tensor or None) -> a list of s entries."""
+    if x is None:
+        return [None] * s
+    if not isinstance(x, (list, tuple)) or len(x) != s:
+        raise ValueError("%s: %s is None or a list of one entry per scan (%d scans)" % (fn, name, s))
+    return list(x)
+
+
+def _voxel_grids(clouds, voxel_size, cols=None):
+    """voxel_down_sample_clouds over clouds of which only some bring colours (cols[j] None): the coloured ones in one call, the
+    others in another -> (down: list, down_cols: list with None where none was given)."""
+    s = len(clouds)
+    cols = [None] * s if cols is None else cols
+    with_c = [j for j in range(s) if cols[j] is not None]
+    without = [j for j in range(s) if cols[j] is None]
+    down, dcol = [None] * s, [None] * s
+    if with_c:
+        d, c = voxel_down_sample_clouds([clouds[j] for j in with_c], voxel_size, colors=[cols[j] for j in with_c])
+        for i, j in enumerate(with_c):
+            down[j], dcol[j] = d[i], c[i]
+    if without:
+        for i, d in zip(without, voxel_down_sample_clouds([clouds[j] for j in without], voxel_size)):
+            down[i] = d
+    return down, dcol
+
+
+def reg_tensors_scans(partials, completes, generative_model="trellis", dataset="redwood", cd_inv_weight=0.5, diff_init=True,
+                      reg_fine_xyz=False, pose_voxel=0.02, cd_only_pose=False, partial_cols=None, complete_cols=None,
+                      diff_transforms=None):
+    """``reg_tensors`` for S scans at once: partials / completes are lists of [N_j,3] / [M_j,3] GPU tensors, partial_cols /
+    complete_cols / diff_transforms None or lists with one entry per scan (an entry may be None); the other arguments are
+    ``reg_tensors``' and hold for every scan.  Returns a list of ``reg_tensors``' dicts, same keys.  The stages:
+      pose         the grids at `pose_voxel` of all clouds that need one through ``voxel_down_sample_clouds`` (with colours where
+                   given); ``object_pose_optimization`` then runs PER SCAN, unchanged -- its alignment loop is the one stage of
+                   stage 2 without a ragged form.  Entries of diff_transforms that are given are used as they are.
+      glue         ``_apply``, ``normalize_numpy`` and the instantmesh rotation are ``reg_tensors``' own statements per scan, so
+                   every ragged stage receives the bits ``reg_tensors`` feeds its single-scan stage.
+      instantmesh  ``remove_noise_from_point_clouds`` over all sources (its documented caveat: a point whose k-NN mean lies within
+                   rounding of the threshold may fall on the other side than ``remove_noise_from_point_cloud`` puts it).
+      coarse       the 0.03 grids of all 2 S clouds in one ``voxel_down_sample_clouds`` call, then ``coarse_scale_sweeps``.
+      fine         (reg_fine_xyz) the grids in one call -- 0.03 and 0.03, none and 0.04 for pcn / kitti -- then
+                   ``iterative_scale_searches`` with [(0.8, 1.2)] * 3, 10.
+    Scan j's entry is what ``reg_tensors`` returns on that scan alone, up to the caveats of the ragged stages it goes through
+    (coarse_loss: ``coarse_scale_sweeps``' score, a relative few ulp; the ICP bit for bit where the down-sampled target gets
+    the one-workgroup plan)."""
+    from .optim_registration.diff_obj_pose import object_pose_optimization
+    fn = "reg_tensors_scans"
+    if not isinstance(partials, (list, tuple)) or not isinstance(completes, (list, tuple)):
+        raise TypeError("%s: partials and completes are lists of [N,3] tensors" % fn)
+    s = len(partials)
+    if len(completes) != s:
+        raise ValueError("%s: %d partials against %d completes" % (fn, s, len(completes)))
+    scols = _scan_list(partial_cols, s, fn, "partial_cols")
+    tcols = _scan_list(complete_cols, s, fn, "complete_cols")
+    diffs = _scan_list(diff_transforms, s, fn, "diff_transforms")
+    for name, clouds in (("partials", partials), ("completes", completes)):
+        for j, t in enumerate(clouds):
+            if not torch.is_tensor(t) or t.dim() != 2 or t.shape[1] != 3:
+                raise ValueError("%s: %s[%d] must be an [N,3] tensor" % (fn, name, j))
+    _lib.require_gpu(*partials, *completes)
+    if s == 0:
+        return []
+    sources = [t.contiguous().float() for t in partials]
+    targets = [t.contiguous().float() for t in completes]
+    scols = [None if c is None else c.contiguous().float() for c in scols]
+    tcols = [None if c is None else c.contiguous().float() for c in tcols]
+    outs = [{} for _ in range(s)]
+    if not diff_init:
+        diffs = [np.eye(4) for _ in range(s)]
+    else:                                                               # :109-122
+        need = [j for j in range(s) if diffs[j] is None]
+        if need:
+            down, dcol = _voxel_grids([targets[j] for j in need] + [sources[j] for j in need], pose_voxel,
+                                      [tcols[j] for j in need] + [scols[j] for j in need])
+            for i, j in enumerate(need):
+                k = len(need) + i
+                # (the loop gets tensors of its own, as voxel_down_sample would hand it: the grids are views of one packed result)
+                T = object_pose_optimization(down[i].clone(), down[k].clone(), radius=0.02, lr=0.01, iters=200, render_size=224, cd_only=cd_only_pose,
+                                             complete_col=None if dcol[i] is None else dcol[i].clone(),
+                                             partial_col=None if dcol[k] is None else dcol[k].clone())
+                diffs[j] = np.linalg.inv(T.astype(np.float64))
+    for j in range(s):
+        outs[j]["diff_transform"] = diffs[j]
+        sources[j] = _apply(diffs[j], sources[j])                       # :126
+        targets[j], _, _ = normalize_numpy(targets[j], range=0.5)       # :130
+    if generative_model in ("instantmesh",):                            # :132-137
+        sources, keeps = remove_noise_from_point_clouds(sources)
+        for j in range(s):
+            if scols[j] is not None:
+                scols[j] = scols[j][keeps[j]]
+            dev = targets[j].device
+            targets[j] = (targets[j].double() @ torch.as_tensor(get_rotate_matrix("x", 90).T, device=dev)
+                          @ torch.as_tensor(get_rotate_matrix("y", 90).T, device=dev)).float()
+    down = voxel_down_sample_clouds(list(sources) + list(targets), 0.03)
+    sweeps = coarse_scale_sweeps(down[:s], down[s:], cd_inv_weight=cd_inv_weight)              # :146-173
+    coarse = []
+    for j in range(s):
+        best_scale, best_loss, T = sweeps[j]
+        coarse.append(T)
+        outs[j].update(best_scale=best_scale, coarse_loss=best_loss, coarse_transformation=T)
+    if reg_fine_xyz:                                                    # :176-199
+        sources = [_apply(coarse[j], sources[j]) for j in range(s)]
+        if dataset in ("pcn", "kitti"):
+            src_s, tgt_s = sources, voxel_down_sample_clouds(list(targets), 0.04)
+        else:
+            down = voxel_down_sample_clouds(list(sources) + list(targets), 0.03)
+            src_s, tgt_s = down[:s], down[s:]
+        fine = iterative_scale_searches(list(src_s), list(tgt_s), [(0.8, 1.2)] * 3, 10, cd_inv_weight=cd_inv_weight)
+        for j in range(s):
+            S, loss_xyz, T_xyz = fine[j]
+            outs[j].update(best_scales_transformation=S, xyz_loss=loss_xyz, best_transformation_xyz=T_xyz)
+            targets[j] = _apply(np.linalg.inv(S), targets[j])
+            targets[j] = _apply(np.linalg.inv(T_xyz), targets[j])
+            sources[j] = _apply(np.linalg.inv(coarse[j]), sources[j])
+    for j in range(s):
+        target = _apply(np.linalg.inv(coarse[j]), targets[j])           # :201-205
+        target = _apply(np.linalg.inv(diffs[j]), target)
+        source = _apply(np.linalg.inv(diffs[j]), sources[j])
+        outs[j].update(source=source, target=target, source_col=scols[j], target_col=tcols[j])
+    return outs
+
+
+def reg_scans(cfg, flags, cd_inv_weight=0.5, diff_init=True, reg_fine_xyz=False, seed=None, **kwargs):
+    """The file form of ``reg`` for a list of flags: returns a list of ``reg``'s dicts and writes every ``{flag}_fused.ply`` WITH
+    COLOURS.  Every flag's two input files are checked first: a missing one raises FileNotFoundError naming it before any work.
+    With an int ``seed`` ONE draw of 163 840 samples per mesh serves both of ``reg``'s samplings, all meshes in one
+    ``sample_surfaces_gpu`` call: sample i does not depend on the count, so the first 120 000 samples, voxel-down-sampled at 0.02
+    with their colours (one ``voxel_down_sample_clouds`` call for all meshes), ARE the cloud ``object_pose_optimization``'s file
+    form builds.  The partial cloud of the pose comes through ``load_point_cloud`` and the pose runs in tensor form on those
+    tensors, per flag: its alignment loop is the one per-scan stage.  With ``seed=None`` the host sampler runs per flag, as in
+    ``reg`` (``rng=`` included).  Then ``reg_tensors_scans`` and ``fuse_scans`` with ``reg``'s parameters.  The pose's
+    debugging files in the working directory (``partial.png``, ``partial_mask.png``, ``final_transform.npy``) are NOT written.
+    kwargs: ``cd_only_pose`` and ``rng``, as in ``reg``; anything else raises."""
+    import os
+    from .optim_registration.diff_obj_pose import load_point_cloud, object_pose_optimization
+    from .utils.dataUtils import read_ply, save_ply_xyzrgb
+    from .utils.mesh_io import glb2point, load_glb, sample_surfaces_gpu
+    unknown = set(kwargs) - {"cd_only_pose", "rng"}
+    if unknown:
+        raise TypeError("reg_scans(cfg, flags, ...): unexpected keyword argument(s) %s (it takes cd_only_pose, rng, seed)" % sorted(unknown))
+    if seed is not None:
+        if kwargs.get("rng") is not None:
+            raise TypeError("reg_scans(cfg, flags, ...): seed (the device sampler) and rng (the host sampler) exclude each other")
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+            raise TypeError("reg_scans(cfg, flags, ...): seed must be an int or None, got %r" % (seed,))
+    if isinstance(flags, str) or not isinstance(flags, (list, tuple)):
+        raise TypeError("reg_scans(cfg, flags, ...): flags is a list of flags")
+    path = cfg.output_path
+    plys = [f"{path}/{flag}/color_point.ply" for flag in flags]
+    glbs = [f"{path}/{flag}/{flag}_{cfg.generative_model}.glb" for flag in flags]
+    for f in [x for pair in zip(plys, glbs) for x in pair]:
+        if not os.path.exists(f):
+            print(f"Path {f} does not exist.")
+            raise FileNotFoundError(f"Path {f} does not exist.")
+    s = len(flags)
+    if s == 0:
+        return []
+    dev = torch.device(getattr(cfg, "device", "cuda"))
+    if seed is not None:
+        meshes = []
+        for g in glbs:
+            V, F, C = load_glb(g)
+            meshes.append((V, F, np.full(V.shape, 0.5) if C is None else C))     # (a colourless file: 0.5 grey, as glb2point_gpu)
+        drawn = sample_surfaces_gpu(meshes, 163840, int(seed), device=dev)
+        txyz, tcol = [d[0] for d in drawn], [d[2] for d in drawn]
+    else:
+        txyz, tcol = [], []
+    diffs = [None] * s
+    if diff_init:                                                       # :109-122
+        if seed is not None:
+            cxyz, ccol = voxel_down_sample_clouds([t[:120000] for t in txyz], 0.02, colors=[c[:120000] for c in tcol])
+        for j in range(s):
+            pxyz, pcol = load_point_cloud(plys[j], dev, radius=0.02, num_points=8000)
+            if seed is not None:
+                cx, cc = cxyz[j].clone(), ccol[j].clone()
+            else:
+                cx, cc = load_point_cloud(glbs[j], dev, radius=0.02, num_points=120000)
+            T = object_pose_optimization(cx, pxyz, radius=0.02, lr=0.01, iters=200, render_size=224, vis=True,
+                                         cd_only=kwargs.get("cd_only_pose", False), complete_col=cc, partial_col=pcol)
+            diffs[j] = np.linalg.inv(T.astype(np.float64))
+    sxyz, scol = [], []
+    for j in range(s):
+        xyz, col = read_ply(plys[j])                                    # :124 o3d.io.read_point_cloud
+        if seed is None:
+            t, c = glb2point(glbs[j], num_points=163840, rng=kwargs.get("rng"))                # :125
+            txyz.append(torch.as_tensor(t, dtype=torch.float32, device=dev))
+            tcol.append(torch.as_tensor(c, dtype=torch.float32, device=dev))
+        if col is None:
+            col = np.zeros_like(xyz)                                    # an open3d cloud without colours: fused file stays valid
+        sxyz.append(torch.as_tensor(xyz, dtype=torch.float32, device=dev))
+        scol.append(torch.as_tensor(col, dtype=torch.float32, device=dev))
+    outs = reg_tensors_scans(sxyz, txyz, generative_model=cfg.generative_model, dataset=getattr(cfg, "dataset", "redwood"),
+                             cd_inv_weight=cd_inv_weight, diff_init=diff_init, reg_fine_xyz=reg_fine_xyz, partial_cols=scol,
+                             complete_cols=tcol, diff_transforms=diffs if diff_init else None)
+    fused = fuse_scans([o["source"] for o in outs], [o["target"] for o in outs], num_points=20000, distance_threshold=0.0001,
+                       std_ratio=2.5, source_cols=[o["source_col"] for o in outs], target_cols=[o["target_col"] for o in outs])   # :207-217
+    for j, flag in enumerate(flags):
+        outs[j].update(fused=fused[j][0], fused_col=fused[j][1], fused_path=f"{path}/{flag}/{flag}_fused.ply")
+        save_ply_xyzrgb(fused[j][0].double().cpu().numpy(), fused[j][1].double().cpu().numpy(), outs[j]["fused_path"])     # :221
+    return outs

@@ -21,6 +21,9 @@ the "complete" cloud that reg() aligns.  Host-side format code, numpy only.
                random numbers and integer face weights, so sample i is a function of (mesh, seed, i) alone and the
                cloud is reproducible from an integer seed on every machine (include/genpc_hip.h: genpc_mesh_sample).
                The host functions above are untouched by it.
+``sample_surfaces_gpu`` / ``glb2points_gpu``  the same for a list of meshes of any sizes, each with its own seed and count, in
+               one library call per 128 meshes (csrc/mesh_sample_ragged.hip: genpc_mesh_sample_ragged): per mesh the bits of
+               the single-mesh functions.
 """
 import base64
 import io
@@ -349,3 +352,167 @@ def glb2point_gpu(glb_path, down_sample=None, num_points=16384, seed=0, device=N
         from ..reg_xyz import voxel_down_sample
         pts, col = voxel_down_sample(pts, down_sample, colors=col)
     return pts, col
+
+
+# ---------------------------------------------------------------------------
+# The ragged device path: genpc_mesh_sample_ragged (csrc/mesh_sample_ragged.hip), S meshes per library call.
+# ---------------------------------------------------------------------------
+MESH_SAMPLE_RAGGED_MAX_MESHES = 128      # include/genpc_hip.h: GENPC_MESH_SAMPLE_RAGGED_MAX_MESHES
+
+
+def _per_mesh_ints(value, s, fn, name, lo, hi):
+    """`value` -- one int for all meshes or one per mesh -- as a list of s Python ints in [lo, hi)."""
+    vals = [value] * s if np.ndim(value) == 0 else list(value)
+    if len(vals) != s:
+        raise ValueError("%s: %d %s for %d meshes" % (fn, len(vals), name, s))
+    for v in vals:
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError("%s: %s must be ints, got %r" % (fn, name, v))
+        if not lo <= int(v) < hi:
+            raise ValueError("%s: %s must be in [%d, %d), got %d" % (fn, name, lo, hi, int(v)))
+    return [int(v) for v in vals]
+
+
+def _shape(a):
+    return tuple(a.shape) if hasattr(a, "shape") else tuple(np.shape(a))
+
+
+def _pack_kind(arrays, dtype, device, name):
+    """One packed device tensor of the rows of `arrays`: host arrays are concatenated on the host and uploaded ONCE, device
+    tensors concatenated on the device."""
+    import torch
+    if not any(torch.is_tensor(a) for a in arrays):
+        np_dtype = np.float32 if dtype == torch.float32 else np.int32
+        host = np.concatenate([np.ascontiguousarray(np.asarray(a), np_dtype).reshape(-1, 3) for a in arrays])
+        return torch.from_numpy(host).to(device)
+    return torch.cat([_device_array(a, dtype, device, name) for a in arrays]).contiguous()
+
+
+def _mesh_sample_ragged(meshes, counts, seeds, want_bary=False, device=None, fn="sample_surfaces_gpu"):
+    """The library calls of sample_surfaces_gpu -> dict(points [T,3], face [T], colors [T,3] or None, bary [T,3] or None,
+    status int32 [S] (device, not read), soff: S + 1 Python ints); every argument error is raised before a device is touched."""
+    import ctypes
+    import torch
+    if not isinstance(meshes, (list, tuple)):
+        raise TypeError("%s: meshes is a list of (vertices, faces) or (vertices, faces, colors)" % fn)
+    s = len(meshes)
+    for j, m in enumerate(meshes):
+        if not isinstance(m, (list, tuple)) or len(m) not in (2, 3):
+            raise TypeError("%s: meshes[%d] must be (vertices, faces) or (vertices, faces, colors)" % (fn, j))
+        for t in m:
+            if torch.is_tensor(t) and not t.is_cuda:
+                raise RuntimeError("genpc_amd: GPU tensors only (got a %s tensor in meshes[%d]); the HIP path has no CPU fallback -- "
+                                   "pass numpy arrays to have them uploaded" % (t.device, j))
+    counts = _per_mesh_ints(counts, s, fn, "counts", 0, 1 << 28)
+    seeds = _per_mesh_ints(seeds, s, fn, "seeds", 0, 1 << 64)
+    nv, nf, with_col = [], [], []
+    for j, m in enumerate(meshes):
+        vs, fs = _shape(m[0]), _shape(m[1])
+        if len(vs) != 2 or vs[1] != 3 or len(fs) != 2 or fs[1] != 3:
+            raise ValueError("%s: meshes[%d] needs vertices [nv,3] and faces [nf,3]" % (fn, j))
+        if vs[0] < 1 or not 1 <= fs[0] <= 1 << 24:
+            raise ValueError("%s: meshes[%d] needs nv >= 1 and 1 <= nf <= 2^24 (nv %d, nf %d)" % (fn, j, vs[0], fs[0]))
+        c = m[2] if len(m) == 3 else None
+        if c is not None and _shape(c) != vs:
+            raise ValueError("%s: the colors of meshes[%d] must be [nv,3] like its vertices" % (fn, j))
+        nv.append(vs[0])
+        nf.append(fs[0])
+        with_col.append(c is not None)
+    soff = [0]
+    for k in counts:
+        soff.append(soff[-1] + k)
+    if s == 0:
+        return dict(points=None, face=None, colors=None, bary=None, status=None, soff=soff)
+    given = [t for m in meshes for t in m if torch.is_tensor(t)]
+    if device is None:
+        device = given[0].device if given else torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    if any(t.device != device for t in given):
+        raise ValueError("%s: the meshes are on different devices" % fn)
+    V = _pack_kind([m[0] for m in meshes], torch.float32, device, "vertices")
+    F = _pack_kind([m[1] for m in meshes], torch.int32, device, "faces")
+    C = None
+    if any(with_col):          # a colourless mesh beside coloured ones: constant 0.5, which interpolates to exactly 0.5
+        C = _pack_kind([m[2] if with_col[j] else np.full((nv[j], 3), 0.5, np.float32) for j, m in enumerate(meshes)],
+                       torch.float32, device, "colors")
+    voff, foff = [0], [0]
+    for j in range(s):
+        voff.append(voff[-1] + nv[j])
+        foff.append(foff[-1] + nf[j])
+    total = soff[-1]
+    pts = torch.empty(total, 3, device=device)
+    fi = torch.empty(total, dtype=torch.int32, device=device)
+    col = torch.empty(total, 3, device=device) if C is not None else None
+    bary = torch.empty(total, 3, device=device) if want_bary else None
+    status = torch.empty(s, dtype=torch.int32, device=device)
+    from .. import _lib
+    L, p = _lib.lib, _lib.ptr
+    for a in range(0, s, MESH_SAMPLE_RAGGED_MAX_MESHES):
+        b = min(a + MESH_SAMPLE_RAGGED_MAX_MESHES, s)
+        tabs = [(ctypes.c_int * (b - a + 1))(*[v - off[a] for v in off[a:b + 1]]) for off in (voff, foff, soff)]
+        sd = (ctypes.c_ulonglong * (b - a))(*seeds[a:b])
+        vp = [ctypes.cast(t, ctypes.c_void_p) for t in tabs] + [ctypes.cast(sd, ctypes.c_void_p)]
+        sl = slice(soff[a], soff[b])
+        rc = _lib.on_device_of(V, L.genpc_mesh_sample_ragged, b - a, vp[0], vp[1], vp[2], vp[3], p(V[voff[a]:voff[b]]),
+                               p(None if C is None else C[voff[a]:voff[b]]), p(F[foff[a]:foff[b]]), p(pts[sl]),
+                               p(None if col is None else col[sl]), p(fi[sl]), p(None if bary is None else bary[sl]), p(status[a:b]))
+        if rc != 1:
+            raise RuntimeError("genpc_mesh_sample_ragged failed (%d): %s" % (rc, _lib.last_error()))
+    return dict(points=pts, face=fi, colors=col, bary=bary, status=status, soff=soff)
+
+
+def _raise_bad_meshes(status, fn):
+    for j, st in enumerate(status.tolist()):              # (the one read-back)
+        if st != 1:
+            raise ValueError("%s: mesh %d cannot be sampled -- a face index outside [0, nv), a non-finite vertex of a face, or all "
+                             "face weights zero (every face degenerate)" % (fn, j))
+
+
+def sample_surfaces_gpu(meshes, counts, seeds, return_bary=False, device=None):
+    """``sample_surface_gpu`` for S meshes of any sizes at once.  meshes: a list of (vertices, faces) or (vertices, faces,
+    colors), numpy arrays (packed on the host, ONE upload per array kind) or GPU tensors; counts and seeds: one int for all
+    meshes or one per mesh (a count may be 0).  Returns a list of the tuples ``sample_surface_gpu`` returns -- (points,
+    face_index[, colors][, bary]) -- each a view of one packed result; mesh j's are the bits of ``sample_surface_gpu`` on that
+    mesh alone with counts[j] and seeds[j] (include/genpc_hip.h: genpc_mesh_sample_ragged).  The colours are there when ANY
+    mesh of the batch brings some: a mesh without gets constant 0.5 vertex colours, whose interpolation is exactly 0.5 (what
+    ``glb2point_gpu`` returns for a colourless file).  One library call per 128 meshes and ONE read-back, of all the status
+    words, whatever S is: ValueError naming the first mesh that cannot be sampled.  A CPU tensor raises."""
+    r = _mesh_sample_ragged(meshes, counts, seeds, return_bary, device)
+    soff = r["soff"]
+    if len(soff) == 1:
+        return []
+    _raise_bad_meshes(r["status"], "sample_surfaces_gpu")
+    out = []
+    for j in range(len(soff) - 1):
+        sl = slice(soff[j], soff[j + 1])
+        t = (r["points"][sl], r["face"][sl])
+        if r["colors"] is not None:
+            t += (r["colors"][sl],)
+        if return_bary:
+            t += (r["bary"][sl],)
+        out.append(t)
+    return out
+
+
+def glb2points_gpu(glb_paths, down_sample=None, num_points=16384, seed=0, device=None):
+    """``glb2point_gpu`` for a list of files: load_glb per file on the host, one upload per array kind, ONE ragged draw
+    (``sample_surfaces_gpu``: num_points and seed are one int for all files or one per file) and -- with down_sample -- one
+    ``voxel_down_sample_clouds`` over all the clouds.  Returns a list of (points float32 [n,3], colours float32 [n,3]) device
+    tensors; entry j has the bits of ``glb2point_gpu(glb_paths[j], ...)``, 0.5 grey for a file without colours."""
+    import torch
+    fn = "glb2points_gpu"
+    loaded = [load_glb(g) for g in glb_paths]
+    r = _mesh_sample_ragged([(V, F) if C is None else (V, F, C) for V, F, C in loaded], num_points, seed, False, device, fn)
+    soff = r["soff"]
+    if len(soff) == 1:
+        return []
+    _raise_bad_meshes(r["status"], fn)
+    pts = r["points"]
+    col = r["colors"] if r["colors"] is not None else torch.full_like(pts, 0.5)
+    if down_sample:
+        from ..reg_xyz import voxel_down_sample_clouds
+        dp, dc = voxel_down_sample_clouds((pts, soff), down_sample, colors=(col, soff))
+        return list(zip(dp, dc))
+    return [(pts[soff[j]:soff[j + 1]], col[soff[j]:soff[j + 1]]) for j in range(len(soff) - 1)]

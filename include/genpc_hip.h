@@ -856,6 +856,33 @@ int genpc_mesh_sample(int nv, const float *vertices, const float *vertex_colors,
                       float *out_colors, int *out_face, float *out_bary, int *out_status,
                       void *workspace, void *stream);
 
+/* Ragged surface sampling: c meshes of any sizes in one call, each with its own seed and sample count.  Mesh j has the vertices
+ * vertices[voff[j] .. voff[j+1]) (and vertex_colors, packed the same way, optional), the faces faces[foff[j] .. foff[j+1]) --
+ * int32 indices counted inside the mesh's OWN vertices -- and the output rows [soff[j] .. soff[j+1]); voff, foff, soff: HOST
+ * arrays of c + 1 ascending ints starting at 0, seeds: a HOST array of c words; all four are copied before the call returns.
+ * Mesh j's rows of out_xyz [soff[c],3] and of the optional out_colors [soff[c],3], out_face [soff[c]] (an index inside the
+ * mesh's own faces) and out_bary [soff[c],3] are the bits of genpc_mesh_sample on that mesh alone with count = soff[j+1] -
+ * soff[j] and seed = seeds[j]: the definition above holds per mesh -- Amax, the weight shift and the cumulative weights are the
+ * mesh's own, sample i of a mesh uses Philox counter i (the index inside the mesh) and key seeds[j] -- and so does the prefix
+ * property: a sample does not depend on its mesh's count, on the other meshes or on the mesh's place in the batch.
+ * out_status[j] (device ints, c of them): 1 or -1 by genpc_mesh_sample's rules judged on mesh j alone; a face index >= nv_j is
+ * bad even where the packed array has a vertex there, and is checked before anything is loaded through it.  A mesh with -1
+ * has every word of its outputs written as the single call writes them and changes no bit of any other mesh.  A count of 0
+ * is allowed: the mesh's status is still written.
+ * Asynchronous on `stream`: a memset and FOUR launches whatever c is, the tables in the kernel arguments, scratch from the
+ * library's workspace (16 bytes a mesh, 8 bytes a face, 8 bytes per chunk of 1024 faces and per mesh), integer atomics only
+ * (the same bits on every run), no copy, no host read-back, no synchronisation (csrc/mesh_sample_ragged.hip).  Returns 1 (c == 0
+ * too, with nothing done); -1 with genpc_last_error set ("genpc_mesh_sample_ragged: ...") and nothing enqueued for c < 0,
+ * c > GENPC_MESH_SAMPLE_RAGGED_MAX_MESHES (the tables travel in 4 KiB of kernel arguments), a null table, tables that do not
+ * start at 0 or descend, a mesh with nf_j outside [1, 2^24] or nv_j = 0, more than 2^28 vertices, faces or samples in all,
+ * out_colors without vertex_colors, or a null required pointer (vertices, faces, out_status; out_xyz unless soff[c] == 0).  */
+#define GENPC_MESH_SAMPLE_RAGGED_MAX_MESHES 128
+int genpc_mesh_sample_ragged(int c, const int *voff, const int *foff, const int *soff,
+                             const unsigned long long *seeds, const float *vertices,
+                             const float *vertex_colors, const int *faces, float *out_xyz,
+                             float *out_colors, int *out_face, float *out_bary, int *out_status,
+                             void *stream);
+
 #ifdef __cplusplus
 }
 #endif
