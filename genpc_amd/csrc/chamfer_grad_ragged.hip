@@ -37,17 +37,6 @@ struct ChamferRaggedGradArgs {
 };
 static_assert(sizeof(ChamferRaggedGradArgs) <= 4096, "the pair table must fit the kernel arguments");
 
-// ragged_pair_of (ragged_table.h) over either column of the table: the largest j with (off[j] >> 6) + j <= item
-__device__ __forceinline__ int ragged_pair_of_column(const int *off, int c, int item)
-{
-    int lo = 0, hi = c - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if ((off[mid] >> 6) + mid <= item) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 // The row a lane serves.  side 0: row `at` of xyz1, whose index points into the pair's other[0 .. nother) of xyz2; side 1 the converse.
 struct RaggedRow {
     int side, at, other0, nother;
@@ -59,7 +48,7 @@ __device__ __forceinline__ RaggedRow ragged_row(const ChamferRaggedGradArgs &a)
     r.side = (int)blockIdx.x >= a.items1;
     const int item = (int)blockIdx.x - (r.side ? a.items1 : 0);
     const int *mine = r.side ? a.t.toff : a.t.qoff, *theirs = r.side ? a.t.qoff : a.t.toff;
-    const int pair = ragged_pair_of_column(mine, a.t.c, item);
+    const int pair = ragged_item_owner(mine, a.t.c, item, 6);          // (ragged_pair_of over either column of the table)
     const int r0 = mine[pair], nr = mine[pair + 1] - r0;
     const int i = (item - ((r0 >> 6) + pair)) * kRaggedLanes + (int)threadIdx.x;
     r.live = i < nr;

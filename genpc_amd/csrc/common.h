@@ -27,6 +27,8 @@ const char *tune_env_str(const char *name, const char *what);     // string-valu
 // does (chamfer3D.cu:147, emd_cuda.cu:278); returns false on error.
 bool check(hipError_t e, const char *what);
 void set_error(const char *msg);
+// A ragged entry point refuses a call: records "<fn>: <what>" and returns -1.
+int ragged_refuse(const char *fn, const char *what);
 
 // The slots of the scratch pool.  Two users of one slot on one stream overwrite each other: a new user takes a NEW enumerator
 // (10, 11, 19, 21, 23 and 32 are retired) unless sharing is the point, and then the comment says so.  The values are map keys only.

@@ -44,6 +44,14 @@ void set_error(const char *msg)
     g_err = msg;
 }
 
+int ragged_refuse(const char *fn, const char *what)
+{
+    char msg[192];
+    snprintf(msg, sizeof msg, "%s: %s", fn, what);
+    set_error(msg);
+    return -1;
+}
+
 bool check(hipError_t e, const char *what)
 {
     if (e == hipSuccess) return true;

@@ -189,11 +189,7 @@ static int emd_ragged_check(const char *who, int c, const int *off)
     const char *err = nullptr;
     char msg[160];
     const int rc = ragged_table_fill(c, off, off, rt, &max_targets, &err);
-    if (rc < 0) {
-        snprintf(msg, sizeof msg, "%s: %s", who, err);
-        set_error(msg);
-        return -1;
-    }
+    if (rc < 0) return ragged_refuse(who, err);
     for (int j = 0; j < c; j++) {
         if ((off[j + 1] - off[j]) % 256 != 0) {
             snprintf(msg, sizeof msg, "%s: pair %d has %d points, not a multiple of 256", who, j, off[j + 1] - off[j]);

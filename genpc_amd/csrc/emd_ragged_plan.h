@@ -9,12 +9,7 @@
 //   * The grid is at most 384 * 1024 workgroups: far below 2^31.
 // Host code only, no HIP: tests/emd_ragged_plan_check.cpp includes it under the sanitizers.
 #pragma once
-
-#if defined(__HIPCC__)
-#define GENPC_EMD_PLAN_HD __host__ __device__
-#else
-#define GENPC_EMD_PLAN_HD
-#endif
+#include "ragged_offsets.h"
 
 namespace genpc {
 
@@ -30,7 +25,7 @@ struct EmdRaggedTable {
 };
 
 // the most workgroups pair of n points can use: one bidder per wave, everybody bidding
-GENPC_EMD_PLAN_HD inline int emd_ragged_block_cap(int n)
+GENPC_RAGGED_HD inline int emd_ragged_block_cap(int n)
 {
     const long long cap = ((long long)n * 64 + kEmdRaggedBlock - 1) / kEmdRaggedBlock;
     return cap > kEmdRaggedMaxBlocks ? kEmdRaggedMaxBlocks : (int)cap;
@@ -55,35 +50,19 @@ inline int emd_ragged_plan(int c, const int *off, int cus, EmdRaggedTable &t)
     t.c = c;
     const long long total = off[c];
     int at = 0;
+    ragged_pad_copy(t.off, off, c);
     for (int j = 0; j < c; j++) {
-        t.off[j] = off[j];
         t.first[j] = at;
         at += emd_ragged_blocks_of(off[j + 1] - off[j], total, cus);
     }
-    for (int j = c; j <= kEmdRaggedMaxPairs; j++) { t.off[j] = off[c]; t.first[j] = at; }
+    for (int j = c; j <= kEmdRaggedMaxPairs; j++) t.first[j] = at;
     return at;
 }
 
 // the pair that owns workgroup `block` of the bid launch (0 <= block < first[c]): the largest j with first[j] <= block
-GENPC_EMD_PLAN_HD inline int emd_ragged_pair_of_block(const EmdRaggedTable &t, int block)
-{
-    int lo = 0, hi = t.c - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (t.first[mid] <= block) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
+GENPC_RAGGED_HD inline int emd_ragged_pair_of_block(const EmdRaggedTable &t, int block) { return ragged_owner(t.first, t.c, block); }
 
 // the pair that owns point (or object) `pos` of the packed arrays (0 <= pos < off[c]): the largest j with off[j] <= pos
-GENPC_EMD_PLAN_HD inline int emd_ragged_pair_of_point(const EmdRaggedTable &t, int pos)
-{
-    int lo = 0, hi = t.c - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (t.off[mid] <= pos) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
+GENPC_RAGGED_HD inline int emd_ragged_pair_of_point(const EmdRaggedTable &t, int pos) { return ragged_owner(t.off, t.c, pos); }
 
 }  // namespace genpc

@@ -23,6 +23,7 @@
 #include "ragged_table.h"
 #define GENPC_ICP_PLAN_HD GENPC_RAGGED_HD          // icp_plan() on the device too: icp_fused_ragged_kernel
 #include "icp_ragged_plan.h"
+#include "ragged_cand.h"
 #include "cd_score.h"                              // kIBlock, and the score's sums in their one order
 #include "../../include/genpc_hip.h"
 
@@ -606,14 +607,11 @@ __global__ __launch_bounds__(kFT) void icp_fused_kernel(int ns, const float *__r
 }
 
 // genpc_icp_batch_ragged's one launch: workgroup blockIdx.x solves candidate blockIdx.x of the call.  Its pair -- the largest j
-// with koff[j] <= candidate, a uniform binary search of the table in the kernel arguments (scalar loads) -- gives it its own
+// with koff[j] <= candidate, ragged_cand.h's uniform search of the table in the kernel arguments (scalar loads) -- gives it its own
 // ns, nt, clouds and, through icp_plan(nt), its own cell budget, by which icp_fused_solve carves the LDS (ntp, cells_cap): the
 // launch's dynamic LDS is the largest of the pairs' (icp_ragged_plan.h).  A candidate of a multi-launch pair leaves at once.
 struct IcpRaggedArgs {
-    int c;
-    int soff[kIcpRaggedMaxPairs + 1];          // source of pair j: [soff[j], soff[j + 1])
-    int toff[kIcpRaggedMaxPairs + 1];          // its target
-    int koff[kIcpRaggedMaxPairs + 1];          // its candidates
+    RaggedCandTable t;                         // (first: the layout of the kernel arguments)
     const float *source, *target;              // packed
     const double *init;                        // [K,16]
     double *out_T, *stats;                     // [K,16], [K,3]
@@ -622,18 +620,15 @@ struct IcpRaggedArgs {
     int max_iter;
 };
 static_assert(sizeof(IcpRaggedArgs) <= 4096, "the pair table must fit the kernel arguments");
+static_assert(kIcpRaggedMaxPairs == kRaggedCandMaxPairs && kIcpRaggedMaxPoints == kRaggedCandMaxPoints &&
+              kIcpRaggedMaxCandidates == kRaggedCandMaxCandidates, "ragged_cand.h checks and carries the table");
 
 template <int FMA>
 __global__ __launch_bounds__(kFT) void icp_fused_ragged_kernel(IcpRaggedArgs a)
 {
-    const int cand = blockIdx.x;
-    int lo = 0, hi = a.c - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (a.koff[mid] <= cand) lo = mid; else hi = mid - 1;
-    }
-    const int s0 = a.soff[lo], t0 = a.toff[lo];
-    const int ns = a.soff[lo + 1] - s0, nt = a.toff[lo + 1] - t0;
+    const int cand = blockIdx.x, pair = ragged_cand_pair_of(a.t, cand);
+    const int s0 = a.t.soff[pair], t0 = a.t.toff[pair];
+    const int ns = a.t.soff[pair + 1] - s0, nt = a.t.toff[pair + 1] - t0;
     const IcpPlan plan = icp_plan(nt);
     if (!plan.one_workgroup) return;                  // (uniform: the whole workgroup leaves)
     icp_fused_solve<FMA>(cand, ns, a.source + (size_t)s0 * 3, nt, a.target + (size_t)t0 * 3, a.md2, a.max_dist, a.init, a.max_iter,
@@ -727,57 +722,21 @@ GENPC_API int genpc_icp_plan(int nt, int out[3])
     return 1;
 }
 
-namespace genpc {
-
-static int icp_ragged_refuse(const char *fn, const char *what)
-{
-    char msg[192];
-    snprintf(msg, sizeof msg, "%s: %s", fn, what);
-    set_error(msg);
-    return -1;
-}
-
-// one offset table of a ragged ICP call: null when it starts at 0 and ascends, else what is wrong with it
-static const char *icp_ragged_table_fault(int c, const int *off)
-{
-    if (off[0] != 0) return "offsets must start at 0";
-    for (int j = 0; j < c; j++)
-        if (off[j + 1] < off[j]) return "offsets must ascend";
-    return nullptr;
-}
-
-}  // namespace genpc
-
 GENPC_API int genpc_icp_batch_ragged(int c, const int *soff, const int *toff, const int *koff, const float *source, const float *target,
                                      double max_dist, const double *init, int max_iter, double rel_fitness, double rel_rmse,
                                      double *out_T, double *stats, void *stream)
 {
     using namespace genpc;
     const char *fn = "genpc_icp_batch_ragged";
-    // every refusal is decided here, before anything touches a device
-    if (c < 0) return icp_ragged_refuse(fn, "negative number of pairs");
-    if (max_iter < 0) return icp_ragged_refuse(fn, "negative number of iterations");
-    if (c == 0) return 1;
-    if (c > kIcpRaggedMaxPairs) return icp_ragged_refuse(fn, "more than 256 pairs in one call");
-    static_assert(kIcpRaggedMaxPairs == 256, "the message above names the bound");
-    if (!soff || !toff || !koff) return icp_ragged_refuse(fn, "null offset table");
-    for (const int *off : {soff, toff, koff}) {
-        const char *fault = icp_ragged_table_fault(c, off);
-        if (fault) return icp_ragged_refuse(fn, fault);
-    }
-    if (soff[c] > kIcpRaggedMaxPoints || toff[c] > kIcpRaggedMaxPoints) return icp_ragged_refuse(fn, "more than 2^28 points on one side");
-    if (koff[c] > kIcpRaggedMaxCandidates) return icp_ragged_refuse(fn, "more than 2^20 candidates");
-    for (int j = 0; j < c; j++) {
-        if (koff[j + 1] == koff[j]) continue;          // a pair without candidates is skipped, whatever its clouds
-        if (soff[j + 1] == soff[j] || toff[j + 1] == toff[j]) {
-            char what[96];
-            snprintf(what, sizeof what, "pair %d has candidates and an empty %s", j, soff[j + 1] == soff[j] ? "source" : "target");
-            return icp_ragged_refuse(fn, what);
-        }
-    }
+    // every refusal is decided here, before anything touches a device: ragged_cand.h's about the table, and a negative number
+    // of iterations, which ranks behind a negative number of pairs alone
+    if (c >= 0 && max_iter < 0) return ragged_refuse(fn, "negative number of iterations");
+    const char *what = nullptr;
+    char buf[96];
+    const int work = ragged_cand_check(c, soff, toff, koff, &what, buf);
+    if (work <= 0) return work < 0 ? ragged_refuse(fn, what) : 1;
     const int k = koff[c];
-    if (k == 0) return 1;
-    if (!source || !target || !init || !out_T || !stats) return icp_ragged_refuse(fn, "null pointer");
+    if (!source || !target || !init || !out_T || !stats) return ragged_refuse(fn, "null pointer");
     hipStream_t st = (hipStream_t)stream;
     const IcpRaggedPlan plan = icp_ragged_plan(c, toff);
     if (plan.fused_pairs) {
@@ -791,11 +750,7 @@ GENPC_API int genpc_icp_batch_ragged(int c, const int *soff, const int *toff, co
             set_bytes[fma] = lds;
         }
         IcpRaggedArgs a{};
-        a.c = c;
-        for (int j = 0; j <= kIcpRaggedMaxPairs; j++) {
-            const int i = j < c ? j : c;
-            a.soff[j] = soff[i]; a.toff[j] = toff[i]; a.koff[j] = koff[i];
-        }
+        ragged_cand_fill(a.t, c, soff, toff, koff);
         a.source = source; a.target = target; a.init = init; a.out_T = out_T; a.stats = stats;
         a.max_dist = max_dist; a.rel_fitness = rel_fitness; a.rel_rmse = rel_rmse;
         a.md2 = (float)(max_dist * max_dist);
@@ -822,14 +777,13 @@ GENPC_API int genpc_icp_ragged_plan(int c, const int *toff, int out[3])
 {
     using namespace genpc;
     const char *fn = "genpc_icp_ragged_plan";
-    if (!out) return icp_ragged_refuse(fn, "null pointer");
+    if (!out) return ragged_refuse(fn, "null pointer");
     out[0] = out[1] = out[2] = 0;
-    if (c < 0) return icp_ragged_refuse(fn, "negative number of pairs");
-    if (c == 0) return 1;
-    if (c > kIcpRaggedMaxPairs) return icp_ragged_refuse(fn, "more than 256 pairs in one call");
-    if (!toff) return icp_ragged_refuse(fn, "null offset table");
-    const char *fault = icp_ragged_table_fault(c, toff);
-    if (fault) return icp_ragged_refuse(fn, fault);
+    const char *what = nullptr;
+    const int some = ragged_cand_count(c, &what);
+    if (some <= 0) return some < 0 ? ragged_refuse(fn, what) : 1;
+    if (!toff) return ragged_refuse(fn, "null offset table");
+    if ((what = ragged_offsets_fault(c, toff))) return ragged_refuse(fn, what);
     const IcpRaggedPlan p = icp_ragged_plan(c, toff);
     out[0] = p.fused_pairs;
     out[1] = p.loop_pairs;

@@ -7,7 +7,7 @@
 #pragma once
 #include <stddef.h>
 
-// icp.hip defines this as ragged_table.h's GENPC_RAGGED_HD before it includes the header: the one-launch kernel of
+// icp.hip defines this as ragged_offsets.h's GENPC_RAGGED_HD before it includes the header: the one-launch kernel of
 // genpc_icp_batch_ragged asks the plan of its own pair on the device.  Everywhere else it is nothing, and the header plain C++.
 #ifndef GENPC_ICP_PLAN_HD
 #define GENPC_ICP_PLAN_HD

@@ -204,27 +204,14 @@ static int launch_knn_ragged(const KnnRaggedArgs &a, hipStream_t st)
 static int knn_ragged(const char *who, int c, const int *off, const float *xyz, int k, bool filter, double std_ratio, float *mean_out,
                       double *stats, unsigned char *keep, int *kept, hipStream_t st)
 {
-    char msg[160];
     KnnRaggedArgs a{};
     int max_points = 0;
     const char *err = nullptr;
     const int rc = ragged_table_fill(c, off, off, a.t, &max_points, &err);
-    if (rc < 0) {
-        snprintf(msg, sizeof msg, "%s: %s", who, err);
-        set_error(msg);
-        return -1;
-    }
-    if (k != 8 && k != 16 && k != 20 && k != 32) {
-        snprintf(msg, sizeof msg, "%s: k must be 8, 16, 20 or 32", who);
-        set_error(msg);
-        return -1;
-    }
+    if (rc < 0) return ragged_refuse(who, err);
+    if (k != 8 && k != 16 && k != 20 && k != 32) return ragged_refuse(who, "k must be 8, 16, 20 or 32");
     if (rc == 0) return 1;
-    if (!xyz || (filter ? !keep : !mean_out)) {
-        snprintf(msg, sizeof msg, "%s: null pointer", who);
-        set_error(msg);
-        return -1;
-    }
+    if (!xyz || (filter ? !keep : !mean_out)) return ragged_refuse(who, "null pointer");
     const int total = a.t.qoff[c];
     a.std_ratio = std_ratio; a.stats = stats; a.keep = keep; a.kept = kept; a.mean = mean_out;
     WsLayout L;

@@ -222,7 +222,6 @@ static void launch_knn_query_ragged_cap(const KnnQueryRaggedArgs &a, unsigned gr
 static int knn_query_ragged(int c, const int *noff, const int *moff, const float *xyz, const float *xyz2, int k, float *dist, int *idx,
                             hipStream_t st)
 {
-    char msg[160];
     if (k < 1 || k > 32) {
         set_error("genpc_knn_query_ragged: k must be 1 .. 32");
         return -1;
@@ -231,11 +230,7 @@ static int knn_query_ragged(int c, const int *noff, const int *moff, const float
     int max_targets = 0;
     const char *err = nullptr;
     const int rc = ragged_table_fill(c, noff, moff, a.t, &max_targets, &err);
-    if (rc < 0) {
-        snprintf(msg, sizeof msg, "genpc_knn_query_ragged: %s", err);
-        set_error(msg);
-        return -1;
-    }
+    if (rc < 0) return ragged_refuse("genpc_knn_query_ragged", err);
     if (rc == 0) return 1;
     if (!xyz || !xyz2 || !dist || !idx) {
         set_error("genpc_knn_query_ragged: null pointer");

@@ -108,14 +108,6 @@ __global__ __launch_bounds__(kMsBlock) void mesh_ragged_sample_kernel(MsRaggedTa
     }
 }
 
-static int ms_ragged_refuse(const char *what)
-{
-    char msg[160];
-    snprintf(msg, sizeof msg, "genpc_mesh_sample_ragged: %s", what);
-    set_error(msg);
-    return -1;
-}
-
 }  // namespace genpc
 
 GENPC_API int genpc_mesh_sample_ragged(int c, const int *voff, const int *foff, const int *soff, const unsigned long long *seeds,
@@ -123,14 +115,15 @@ GENPC_API int genpc_mesh_sample_ragged(int c, const int *voff, const int *foff, 
                                        float *out_colors, int *out_face, float *out_bary, int *out_status, void *stream)
 {
     using namespace genpc;
+    const char *fn = "genpc_mesh_sample_ragged";
     // every refusal is decided here, before anything touches a device
     MsRaggedTable t;
     const char *err = nullptr;
     const int work = ms_ragged_fill(c, voff, foff, soff, seeds, t, &err);
-    if (work < 0) return ms_ragged_refuse(err);
+    if (work < 0) return ragged_refuse(fn, err);
     if (work == 0) return 1;
-    if (out_colors && !vertex_colors) return ms_ragged_refuse("out_colors without vertex_colors");
-    if (!vertices || !faces || !out_status || (t.soff[c] > 0 && !out_xyz)) return ms_ragged_refuse("null pointer");
+    if (out_colors && !vertex_colors) return ragged_refuse(fn, "out_colors without vertex_colors");
+    if (!vertices || !faces || !out_status || (t.soff[c] > 0 && !out_xyz)) return ragged_refuse(fn, "null pointer");
     hipStream_t st = (hipStream_t)stream;
     WsLayout L;
     MsRaggedScratch s;

@@ -14,13 +14,8 @@
 //   * samples, shift 8: item = the 256 samples a workgroup of the sampling launch draws, all of one mesh.
 // Host code only, no HIP: tests/mesh_sample_ragged_plan_check.cpp includes it under the sanitizers.
 #pragma once
+#include "ragged_offsets.h"
 #include "ws_layout.h"
-
-#if defined(__HIPCC__)
-#define GENPC_MS_RAGGED_HD __host__ __device__
-#else
-#define GENPC_MS_RAGGED_HD
-#endif
 
 namespace genpc {
 
@@ -45,21 +40,13 @@ struct MsRaggedHeader {                           // = mesh_sample.h's MsHeader 
 };
 
 // the number of the first work item of mesh j   (0 <= j <= c; j == c: the number of items of the launch)
-GENPC_MS_RAGGED_HD inline int ms_ragged_first_item(const int *off, int j, int shift) { return (off[j] >> shift) + j; }
+GENPC_RAGGED_HD inline int ms_ragged_first_item(const int *off, int j, int shift) { return (off[j] >> shift) + j; }
 
 // the mesh a work item serves: the largest j with (off[j] >> shift) + j <= item   (0 <= item < ms_ragged_first_item(off, c, shift))
-GENPC_MS_RAGGED_HD inline int ms_ragged_mesh_of(const int *off, int c, int item, int shift)
-{
-    int lo = 0, hi = c - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if ((off[mid] >> shift) + mid <= item) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
+GENPC_RAGGED_HD inline int ms_ragged_mesh_of(const int *off, int c, int item, int shift) { return ragged_item_owner(off, c, item, shift); }
 
 // the first element of a work item, counted inside its mesh; at or beyond the mesh's size: the item is idle
-GENPC_MS_RAGGED_HD inline int ms_ragged_item_base(const int *off, int mesh, int item, int shift)
+GENPC_RAGGED_HD inline int ms_ragged_item_base(const int *off, int mesh, int item, int shift)
 {
     return (item - ms_ragged_first_item(off, mesh, shift)) << shift;
 }
@@ -74,9 +61,7 @@ inline int ms_ragged_fill(int c, const int *voff, const int *foff, const int *so
     if (c > kMsRaggedMaxMeshes) { *err = "more than 128 meshes in one call"; return -1; }
     static_assert(kMsRaggedMaxMeshes == 128, "the message above names the bound");
     if (!voff || !foff || !soff || !seeds) { *err = "null offset or seed table"; return -1; }
-    if (voff[0] != 0 || foff[0] != 0 || soff[0] != 0) { *err = "offsets must start at 0"; return -1; }
-    for (int j = 0; j < c; j++)
-        if (voff[j + 1] < voff[j] || foff[j + 1] < foff[j] || soff[j + 1] < soff[j]) { *err = "offsets must ascend"; return -1; }
+    if ((*err = ragged_offsets_fault(c, {voff, foff, soff}))) return -1;
     if (voff[c] > kMsRaggedMaxTotal || foff[c] > kMsRaggedMaxTotal || soff[c] > kMsRaggedMaxTotal) {
         *err = "more than 2^28 vertices, faces or samples in one call";
         return -1;
@@ -87,11 +72,9 @@ inline int ms_ragged_fill(int c, const int *voff, const int *foff, const int *so
         if (voff[j + 1] == voff[j]) { *err = "every mesh needs nv >= 1 vertices"; return -1; }
     }
     t.c = c;
-    for (int j = 0; j <= kMsRaggedMaxMeshes; j++) {
-        t.voff[j] = voff[j < c ? j : c];
-        t.foff[j] = foff[j < c ? j : c];
-        t.soff[j] = soff[j < c ? j : c];
-    }
+    ragged_pad_copy(t.voff, voff, c);
+    ragged_pad_copy(t.foff, foff, c);
+    ragged_pad_copy(t.soff, soff, c);
     for (int j = 0; j < kMsRaggedMaxMeshes; j++) t.seed[j] = j < c ? seeds[j] : 0;
     return 1;
 }

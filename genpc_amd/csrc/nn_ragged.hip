@@ -96,12 +96,7 @@ GENPC_API int genpc_nm_distance_ragged(int c, const int *noff, const float *xyz,
     int max_targets = 0;
     const char *err = nullptr;
     const int rc = ragged_table_fill(c, noff, moff, t, &max_targets, &err);
-    if (rc < 0) {
-        char msg[128];
-        snprintf(msg, sizeof msg, "genpc_nm_distance_ragged: %s", err);
-        set_error(msg);
-        return -1;
-    }
+    if (rc < 0) return ragged_refuse("genpc_nm_distance_ragged", err);
     if (rc == 0) return 1;
     if (!xyz || !xyz2 || !result || !result_i) {
         set_error("genpc_nm_distance_ragged: null pointer");

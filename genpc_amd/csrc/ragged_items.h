@@ -20,15 +20,7 @@ GENPC_RAGGED_HD inline int ragged_first_item_shift(const RaggedTable &t, int j, 
 inline long long ragged_items_shift(long long queries, int c, int shift) { return (queries >> shift) + c; }
 
 // the pair a work item serves: the largest j with (qoff[j] >> shift) + j <= item   (0 <= item < ragged_items_shift)
-GENPC_RAGGED_HD inline int ragged_pair_of_shift(const RaggedTable &t, int item, int shift)
-{
-    int lo = 0, hi = t.c - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if ((t.qoff[mid] >> shift) + mid <= item) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
+GENPC_RAGGED_HD inline int ragged_pair_of_shift(const RaggedTable &t, int item, int shift) { return ragged_item_owner(t.qoff, t.c, item, shift); }
 
 // the first query of a work item, counted inside its pair; at or beyond the pair's size: the item is idle
 GENPC_RAGGED_HD inline long long ragged_item_base_shift(const RaggedTable &t, int pair, int item, int shift)

@@ -9,14 +9,10 @@
 //   * its queries are dealt to workgroups of 64 lanes, the first of them numbered (qoff[j] >> 6) + j; pair j needs
 //     ceil(n_j / 64) <= (qoff[j + 1] >> 6) - (qoff[j] >> 6) + 1 of them, so the ranges do not overlap, the numbering ascends
 //     strictly (a binary search finds the pair of a workgroup) and at most one workgroup per pair finds nothing to do.
+// The check of the offsets, the padded copy and the search itself are ragged_offsets.h's.
 // Host code only, no HIP: a plain C++ program can include it (tests/ragged_table_check.cpp does, under the sanitizers).
 #pragma once
-
-#if defined(__HIPCC__)
-#define GENPC_RAGGED_HD __host__ __device__
-#else
-#define GENPC_RAGGED_HD
-#endif
+#include "ragged_offsets.h"
 
 namespace genpc {
 
@@ -53,10 +49,7 @@ inline int ragged_table_fill(int c, const int *noff, const int *moff, RaggedTabl
     if (c == 0) return 0;
     if (!noff || !moff) { *err = "null offset table"; return -1; }
     if (c > kRaggedMaxPairs) { *err = "more than 384 pairs in one call"; return -1; }
-    if (noff[0] != 0 || moff[0] != 0) { *err = "offsets must start at 0"; return -1; }
-    for (int j = 0; j < c; j++) {
-        if (noff[j + 1] < noff[j] || moff[j + 1] < moff[j]) { *err = "offsets must ascend"; return -1; }
-    }
+    if ((*err = ragged_offsets_fault(c, {noff, moff}))) return -1;
     if (noff[c] > kRaggedMaxPoints || moff[c] > kRaggedMaxPoints) { *err = "more than 2^28 points on one side"; return -1; }
     if (noff[c] == 0) return 0;
     for (int j = 0; j < c; j++) {
@@ -65,20 +58,12 @@ inline int ragged_table_fill(int c, const int *noff, const int *moff, RaggedTabl
         if (n > 0 && m > *max_targets) *max_targets = m;
     }
     t.c = c;
-    for (int j = 0; j <= c; j++) { t.qoff[j] = noff[j]; t.toff[j] = moff[j]; }
-    for (int j = c + 1; j <= kRaggedMaxPairs; j++) { t.qoff[j] = noff[c]; t.toff[j] = moff[c]; }
+    ragged_pad_copy(t.qoff, noff, c);
+    ragged_pad_copy(t.toff, moff, c);
     return 1;
 }
 
 // the pair a workgroup of the search serves: the largest j with (qoff[j] >> 6) + j <= item   (0 <= item < ragged_items)
-GENPC_RAGGED_HD inline int ragged_pair_of(const RaggedTable &t, int item)
-{
-    int lo = 0, hi = t.c - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if ((t.qoff[mid] >> 6) + mid <= item) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
+GENPC_RAGGED_HD inline int ragged_pair_of(const RaggedTable &t, int item) { return ragged_item_owner(t.qoff, t.c, item, 6); }
 
 }  // namespace genpc

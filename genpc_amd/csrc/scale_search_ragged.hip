@@ -21,6 +21,7 @@
 #include "grid.h"
 #include "cd_score.h"
 #include "scale_search_ragged_plan.h"
+#include "ragged_cand.h"
 #include "../../include/genpc_hip.h"
 
 namespace genpc {
@@ -29,12 +30,11 @@ static_assert(kSsBlock == kIBlock && kSsWaves * kWave == kIBlock, "scale_search_
 static_assert(kSsRaggedMaxPairs == GENPC_SCALE_SEARCH_RAGGED_MAX_PAIRS, "the header exports the bound");
 static_assert(kSsRaggedMaxPairs <= kRaggedMaxPairs, "the target grids are built through a RaggedTable");
 static_assert(kSsFixed % 16 == 0, "the sorted cloud is read 16 bytes at a time");
+static_assert(kSsRaggedMaxPairs == kRaggedCandMaxPairs && kSsRaggedMaxPoints == kRaggedCandMaxPoints &&
+              kSsRaggedMaxCandidates == kRaggedCandMaxCandidates, "ragged_cand.h checks and carries the table");
 
 struct ScaleSearchRaggedArgs {
-    int c;
-    int soff[kSsRaggedMaxPairs + 1];           // source of pair j: [soff[j], soff[j + 1])
-    int toff[kSsRaggedMaxPairs + 1];           // its target
-    int koff[kSsRaggedMaxPairs + 1];           // its candidates
+    RaggedCandTable t;                         // (first: the layout of the kernel arguments)
     const float *source, *target;              // packed
     const float *scales;                       // [K,3]
     const CellGridHdr *hdr;                    // [c] the targets' grids: headers,
@@ -76,13 +76,8 @@ __global__ __launch_bounds__(kIBlock) void scale_search_ragged_kernel(ScaleSearc
 {
     extern __shared__ __align__(16) unsigned char ss_lds[];
     const int cand = blockIdx.x, tid = threadIdx.x;
-    int lo = 0, hi = a.c - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (a.koff[mid] <= cand) lo = mid; else hi = mid - 1;
-    }
-    const int pair = lo, s0 = a.soff[pair], t0 = a.toff[pair];
-    const int ns = a.soff[pair + 1] - s0, nt = a.toff[pair + 1] - t0;
+    const int pair = ragged_cand_pair_of(a.t, cand), s0 = a.t.soff[pair], t0 = a.t.toff[pair];
+    const int ns = a.t.soff[pair + 1] - s0, nt = a.t.toff[pair + 1] - t0;
     const ScaleSearchPlan plan = scale_search_plan(ns);
     if (!plan.one_workgroup) return;                   // (uniform: the whole workgroup leaves; the single call scores this pair)
     const CellGridHdr HT = a.hdr[pair];
@@ -168,23 +163,6 @@ __global__ __launch_bounds__(kIBlock) void scale_search_ragged_kernel(ScaleSearc
     cd_score_reduce(s1, s2, ns, nt, a.w, red, a.scores + cand);
 }
 
-static int ss_ragged_refuse(const char *fn, const char *what)
-{
-    char msg[192];
-    snprintf(msg, sizeof msg, "%s: %s", fn, what);
-    set_error(msg);
-    return -1;
-}
-
-// one offset table of the call: null when it starts at 0 and ascends, else what is wrong with it
-static const char *ss_ragged_table_fault(int c, const int *off)
-{
-    if (off[0] != 0) return "offsets must start at 0";
-    for (int j = 0; j < c; j++)
-        if (off[j + 1] < off[j]) return "offsets must ascend";
-    return nullptr;
-}
-
 }  // namespace genpc
 
 GENPC_API int genpc_scale_search_scores_ragged(int c, const int *soff, const int *toff, const int *koff, const float *source,
@@ -192,29 +170,13 @@ GENPC_API int genpc_scale_search_scores_ragged(int c, const int *soff, const int
 {
     using namespace genpc;
     const char *fn = "genpc_scale_search_scores_ragged";
-    // every refusal is decided here, before anything touches a device
-    if (c < 0) return ss_ragged_refuse(fn, "negative number of pairs");
-    if (c == 0) return 1;
-    if (c > kSsRaggedMaxPairs) return ss_ragged_refuse(fn, "more than 256 pairs in one call");
-    static_assert(kSsRaggedMaxPairs == 256, "the message above names the bound");
-    if (!soff || !toff || !koff) return ss_ragged_refuse(fn, "null offset table");
-    for (const int *off : {soff, toff, koff}) {
-        const char *fault = ss_ragged_table_fault(c, off);
-        if (fault) return ss_ragged_refuse(fn, fault);
-    }
-    if (soff[c] > kSsRaggedMaxPoints || toff[c] > kSsRaggedMaxPoints) return ss_ragged_refuse(fn, "more than 2^28 points on one side");
-    if (koff[c] > kSsRaggedMaxCandidates) return ss_ragged_refuse(fn, "more than 2^20 candidates");
-    for (int j = 0; j < c; j++) {
-        if (koff[j + 1] == koff[j]) continue;          // a pair without candidates is skipped, whatever its clouds
-        if (soff[j + 1] == soff[j] || toff[j + 1] == toff[j]) {
-            char what[96];
-            snprintf(what, sizeof what, "pair %d has candidates and an empty %s", j, soff[j + 1] == soff[j] ? "source" : "target");
-            return ss_ragged_refuse(fn, what);
-        }
-    }
+    // every refusal is decided here, before anything touches a device: ragged_cand.h's about the table, then the payload
+    const char *what = nullptr;
+    char buf[96];
+    const int work = ragged_cand_check(c, soff, toff, koff, &what, buf);
+    if (work <= 0) return work < 0 ? ragged_refuse(fn, what) : 1;
     const int k = koff[c];
-    if (k == 0) return 1;
-    if (!source || !target || !scales || !scores) return ss_ragged_refuse(fn, "null pointer");
+    if (!source || !target || !scales || !scores) return ragged_refuse(fn, "null pointer");
     hipStream_t st = (hipStream_t)stream;
 
     // the pairs of the one launch: those with candidates whose source gets the one-workgroup plan.  Their targets' grids are
@@ -256,11 +218,7 @@ GENPC_API int genpc_scale_search_scores_ragged(int c, const int *soff, const int
             set_bytes[fma] = lds;
         }
         if (!launch_cell_grid_build_ragged(t, max_targets, target, (CellGridHdr *)a.hdr, (int *)a.start, (float4 *)a.sorted, st)) return 0;
-        a.c = c;
-        for (int j = 0; j <= kSsRaggedMaxPairs; j++) {
-            const int i = j < c ? j : c;
-            a.soff[j] = soff[i]; a.toff[j] = toff[i]; a.koff[j] = koff[i];
-        }
+        ragged_cand_fill(a.t, c, soff, toff, koff);
         a.source = source; a.target = target; a.scales = scales; a.scores = scores;
         a.w = cd_inv_weight;
         // one workgroup per candidate of the call; those of a pair of the single call leave at once
@@ -284,14 +242,13 @@ GENPC_API int genpc_scale_search_ragged_plan(int c, const int *soff, int out[3])
 {
     using namespace genpc;
     const char *fn = "genpc_scale_search_ragged_plan";
-    if (!out) return ss_ragged_refuse(fn, "null pointer");
+    if (!out) return ragged_refuse(fn, "null pointer");
     out[0] = out[1] = out[2] = 0;
-    if (c < 0) return ss_ragged_refuse(fn, "negative number of pairs");
-    if (c == 0) return 1;
-    if (c > kSsRaggedMaxPairs) return ss_ragged_refuse(fn, "more than 256 pairs in one call");
-    if (!soff) return ss_ragged_refuse(fn, "null offset table");
-    const char *fault = ss_ragged_table_fault(c, soff);
-    if (fault) return ss_ragged_refuse(fn, fault);
+    const char *what = nullptr;
+    const int some = ragged_cand_count(c, &what);
+    if (some <= 0) return some < 0 ? ragged_refuse(fn, what) : 1;
+    if (!soff) return ragged_refuse(fn, "null offset table");
+    if ((what = ragged_offsets_fault(c, soff))) return ragged_refuse(fn, what);
     const ScaleSearchRaggedPlan p = scale_search_ragged_plan(c, soff);
     out[0] = p.fused_pairs;
     out[1] = p.loop_pairs;

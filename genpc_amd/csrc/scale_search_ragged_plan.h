@@ -7,7 +7,7 @@
 //   [kSsFixed, + 16 ns)                 the scaled source in cell order: x, y, z, index
 //   [.., + 4 (cells + 1) rounded to 16) first position of every cell, one more for the end
 // Host code only, no HIP: a plain C++ program can include it (tests/scale_search_ragged_plan_check.cpp does); the kernel asks
-// the plan of its own pair on the device through ragged_table.h's GENPC_RAGGED_HD.  The library exports the split of a table
+// the plan of its own pair on the device through ragged_offsets.h's GENPC_RAGGED_HD.  The library exports the split of a table
 // as genpc_scale_search_ragged_plan.
 #pragma once
 #include <stddef.h>

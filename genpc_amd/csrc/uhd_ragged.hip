@@ -179,12 +179,7 @@ GENPC_API int genpc_uhd_ragged(int c, const int *noff, const float *xyz, const i
     int max_targets = 0;
     const char *err = nullptr;
     const int rc = ragged_table_fill(c, noff, moff, t, &max_targets, &err);
-    if (rc < 0) {
-        char msg[128];
-        snprintf(msg, sizeof msg, "genpc_uhd_ragged: %s", err);
-        set_error(msg);
-        return -1;
-    }
+    if (rc < 0) return ragged_refuse("genpc_uhd_ragged", err);
     if (c == 0) return 1;
     for (int j = 0; j < c; j++) {              // (rc == 0 with c > 0: no pair has a query)
         if (noff[j + 1] == noff[j] || moff[j + 1] == moff[j]) {

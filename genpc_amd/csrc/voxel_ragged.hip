@@ -52,17 +52,6 @@ struct VoxelRaggedArgs {
 };
 static_assert(sizeof(VoxelRaggedArgs) <= 4096, "the table must fit the kernel arguments");
 
-// the cloud that holds packed position i (0 <= i < off[c]): the largest j with off[j] <= i -- empty clouds are passed over
-__device__ __forceinline__ int voxel_ragged_cloud_of(const VoxelRaggedArgs &a, int i)
-{
-    int lo = 0, hi = a.c - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (a.off[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(kVBlock) void voxel_ragged_bounds_kernel(RaggedTable t, const float *__restrict__ xyz,
                                                                       unsigned *bmin, unsigned *bmax)
 {
@@ -109,7 +98,7 @@ __global__ __launch_bounds__(kVBlock) void voxel_ragged_key_kernel(VoxelRaggedAr
 {
     const int i = blockIdx.x * kVBlock + threadIdx.x;
     if (i >= a.off[a.c]) return;
-    const int cloud = voxel_ragged_cloud_of(a, i);
+    const int cloud = ragged_owner(a.off, a.c, i);          // (empty clouds are passed over)
     unsigned long long key;
     if (!voxel_point_key(a.xyz + (size_t)i * 3, a.voxel[cloud], a.bmin + cloud * 3, key)) a.err[cloud] = 1;
     a.keys[i] = key;
@@ -127,7 +116,7 @@ __global__ __launch_bounds__(kVBlock) void voxel_ragged_head_kernel(VoxelRaggedA
 {
     const int i = blockIdx.x * kVBlock + threadIdx.x;
     if (i >= a.off[a.c]) return;
-    const int cloud = voxel_ragged_cloud_of(a, i);
+    const int cloud = ragged_owner(a.off, a.c, i);
     a.head[i] = (i == a.off[cloud] || a.keys[a.order[i]] != a.keys[a.order[i - 1]]) ? 1 : 0;
 }
 
@@ -136,7 +125,7 @@ __global__ __launch_bounds__(kVBlock) void voxel_ragged_mean_kernel(VoxelRaggedA
 {
     const int i = blockIdx.x * kVBlock + threadIdx.x;
     if (i >= a.off[a.c]) return;
-    const int cloud = voxel_ragged_cloud_of(a, i);
+    const int cloud = ragged_owner(a.off, a.c, i);
     const int b = a.off[cloud], e = a.off[cloud + 1];
     const int first = a.rank[b];                           // (b is a head)
     if (i == e - 1) a.out_counts[cloud] = a.rank[i] - first + 1;
@@ -176,42 +165,33 @@ __global__ __launch_bounds__(kVBlock) void voxel_ragged_fold_kernel(VoxelRaggedA
     else if (a.err[j]) a.out_counts[j] = -1;
 }
 
-static int voxel_ragged_refuse(const char *what)
-{
-    char msg[160];
-    snprintf(msg, sizeof msg, "genpc_voxel_down_sample_ragged: %s", what);
-    set_error(msg);
-    return -1;
-}
-
 }  // namespace genpc
 
 GENPC_API int genpc_voxel_down_sample_ragged(int c, const int *off, const float *xyz, const float *colors, const double *voxel_sizes,
                                              float *out, float *out_colors, int *out_counts, void *stream)
 {
     using namespace genpc;
+    const char *fn = "genpc_voxel_down_sample_ragged";
     // every refusal is decided here, before anything touches a device
-    if (c < 0) return voxel_ragged_refuse("negative number of clouds");
+    if (c < 0) return ragged_refuse(fn, "negative number of clouds");
     if (c == 0) return 1;
-    if (c > kVoxelRaggedMaxClouds) return voxel_ragged_refuse("more than 256 clouds in one call");
+    if (c > kVoxelRaggedMaxClouds) return ragged_refuse(fn, "more than 256 clouds in one call");
     static_assert(kVoxelRaggedMaxClouds == 256, "the message above names the bound");
-    if (!off || !voxel_sizes) return voxel_ragged_refuse("null offset or voxel size table");
-    if (off[0] != 0) return voxel_ragged_refuse("offsets must start at 0");
-    for (int j = 0; j < c; j++)
-        if (off[j + 1] < off[j]) return voxel_ragged_refuse("offsets must ascend");
-    if (off[c] > kRaggedMaxPoints) return voxel_ragged_refuse("more than 2^28 points");
+    if (!off || !voxel_sizes) return ragged_refuse(fn, "null offset or voxel size table");
+    if (const char *fault = ragged_offsets_fault(c, off)) return ragged_refuse(fn, fault);
+    if (off[c] > kRaggedMaxPoints) return ragged_refuse(fn, "more than 2^28 points");
     for (int j = 0; j < c; j++)
         if (!(voxel_sizes[j] > 0.0)) {
             char what[96];
             snprintf(what, sizeof what, "the voxel size of cloud %d is not > 0", j);
-            return voxel_ragged_refuse(what);
+            return ragged_refuse(fn, what);
         }
-    if (!out_counts || (off[c] > 0 && (!xyz || !out))) return voxel_ragged_refuse("null pointer");
+    if (!out_counts || (off[c] > 0 && (!xyz || !out))) return ragged_refuse(fn, "null pointer");
     hipStream_t st = (hipStream_t)stream;
     const int total = off[c];
     VoxelRaggedArgs a{};
     a.c = c;
-    for (int j = 0; j <= kVoxelRaggedMaxClouds; j++) a.off[j] = off[j < c ? j : c];
+    ragged_pad_copy(a.off, off, c);
     for (int j = 0; j < kVoxelRaggedMaxClouds; j++) a.voxel[j] = voxel_sizes[j < c ? j : c - 1];
     a.xyz = xyz; a.colors = colors; a.out = out; a.out_colors = out_colors; a.out_counts = out_counts;
     if (total == 0) {          // every cloud is empty: the counts alone
@@ -220,7 +200,8 @@ GENPC_API int genpc_voxel_down_sample_ragged(int c, const int *off, const float 
     }
     RaggedTable t;
     t.c = c;
-    for (int j = 0; j <= kRaggedMaxPairs; j++) t.qoff[j] = t.toff[j] = off[j < c ? j : c];
+    ragged_pad_copy(t.qoff, off, c);
+    ragged_pad_copy(t.toff, off, c);
     unsigned cloud_bits = 0;
     while (cloud_bits < 32 && ((unsigned)(c - 1) >> cloud_bits) != 0) cloud_bits++;
     int *i0 = nullptr, *i1 = nullptr, *i2 = nullptr;

@@ -7,6 +7,7 @@ from . import _lib
 _L = _lib.lib
 _p = _lib.ptr
 MAX_K = 32
+RAGGED_MAX_PAIRS = 384          # include/genpc_hip.h: pairs per genpc_knn_query_ragged call
 
 
 def knn_query(queries, targets, k):
@@ -54,14 +55,13 @@ def knn_query_ragged(queries, targets, k):
     One library call per 384 pairs (genpc_knn_query_ragged: three launches each), nothing waits for the result.  A pair
     without queries gives empty tensors and may have no targets; a pair with queries and no targets is an error.  ``[]``
     against ``[]`` gives ``[]``."""
-    from .loss_functions.Chamfer3D.dist_chamfer_ragged import _is_offsets
-    from .reg_xyz import _ragged_chunks, _ragged_side
+    from ._ragged import chunks, host_ints, is_packed, ragged_side
     k = int(k)
     if k < 1 or k > MAX_K:
         raise ValueError("knn_query_ragged: k must be 1 .. %d, got %d" % (MAX_K, k))
-    packed = isinstance(queries, tuple) and len(queries) == 2 and torch.is_tensor(queries[0]) and _is_offsets(queries[1])
-    q, qoff = _ragged_side(queries, "knn_query_ragged", "queries")
-    t, toff = _ragged_side(targets, "knn_query_ragged", "targets")
+    packed = is_packed(queries)
+    q, qoff = ragged_side(queries, "knn_query_ragged", "queries")
+    t, toff = ragged_side(targets, "knn_query_ragged", "targets")
     if len(qoff) != len(toff):
         raise ValueError("knn_query_ragged: %d queries against %d targets" % (len(qoff) - 1, len(toff) - 1))
     s = len(qoff) - 1
@@ -75,9 +75,9 @@ def knn_query_ragged(queries, targets, k):
         raise ValueError("knn_query_ragged: queries and targets are on different devices")
     dist = torch.empty((q.shape[0], k), dtype=torch.float32, device=q.device)
     idx = torch.empty((q.shape[0], k), dtype=torch.int32, device=q.device)
-    for (a, b, narr), (_, _, marr) in zip(_ragged_chunks(qoff), _ragged_chunks(toff)):
-        rc = _lib.on_device_of(q, _L.genpc_knn_query_ragged, b - a, narr, _p(q[qoff[a]:qoff[b]]), marr, _p(t[toff[a]:toff[b]]), k,
-                               _p(dist[qoff[a]:qoff[b]]), _p(idx[qoff[a]:qoff[b]]))
+    for a, b, na, ma in chunks(RAGGED_MAX_PAIRS, qoff, toff):
+        rc = _lib.on_device_of(q, _L.genpc_knn_query_ragged, b - a, host_ints(na)[1], _p(q[qoff[a]:qoff[b]]), host_ints(ma)[1],
+                               _p(t[toff[a]:toff[b]]), k, _p(dist[qoff[a]:qoff[b]]), _p(idx[qoff[a]:qoff[b]]))
         if rc != 1:
             raise RuntimeError("genpc_knn_query_ragged failed (%d): %s" % (rc, _lib.last_error()))
     pairs = [(dist[qoff[j]:qoff[j + 1]], idx[qoff[j]:qoff[j + 1]]) for j in range(s)]

@@ -10,59 +10,16 @@ from torch import nn
 from torch.autograd import Function
 
 from ... import _lib, chamfer_3D
-
-
-def _is_offsets(x):
-    if torch.is_tensor(x):
-        return x.dim() == 1 and not x.dtype.is_floating_point and not x.dtype.is_complex
-    if isinstance(x, (list, tuple)) or type(x).__name__ == "ndarray":
-        return all(isinstance(v, int) or (hasattr(v, "dtype") and getattr(v, "ndim", 1) == 0 and "int" in str(v.dtype)) for v in x)
-    return False
-
-
-def pack_clouds(clouds, name="clouds"):
-    """A ragged batch as (points [T,3] float32 contiguous, offsets: c + 1 Python ints).  ``clouds`` is a list of [N_j,3]
-    tensors, or already packed: a tuple (points [T,3], offsets) with offsets a sequence of ints or a 1-D CPU int tensor."""
-    if isinstance(clouds, tuple) and len(clouds) == 2 and torch.is_tensor(clouds[0]) and _is_offsets(clouds[1]):
-        points, off = clouds
-        if torch.is_tensor(off):
-            if off.is_cuda:
-                raise ValueError("chamfer_ragged: the offsets of %s live on the host (a device tensor would have to be read back)" % name)
-            off = off.tolist()
-        off = [int(v) for v in off]
-        if points.dim() != 2 or points.shape[1] != 3:
-            raise ValueError("chamfer_ragged: packed %s must be [T,3], got %s" % (name, tuple(points.shape)))
-        if not off or off[0] != 0 or any(b < a for a, b in zip(off, off[1:])) or off[-1] != points.shape[0]:
-            raise ValueError("chamfer_ragged: the offsets of %s must ascend from 0 to its %d points" % (name, points.shape[0]))
-        if points.dtype != torch.float32:
-            raise TypeError("chamfer_ragged: %s must be torch.float32, got %s" % (name, points.dtype))
-        return points.contiguous(), off
-    if not isinstance(clouds, (list, tuple)):
-        raise TypeError("chamfer_ragged: %s is a list of [N,3] tensors or a tuple (points, offsets)" % name)
-    off = [0]
-    for j, t in enumerate(clouds):
-        if not torch.is_tensor(t) or t.dim() != 2 or t.shape[1] != 3:
-            raise ValueError("chamfer_ragged: %s[%d] must be an [N,3] tensor" % (name, j))
-        if t.dtype != torch.float32:
-            raise TypeError("chamfer_ragged: %s[%d] must be torch.float32, got %s" % (name, j, t.dtype))
-        if t.device != clouds[0].device:
-            raise ValueError("chamfer_ragged: %s[%d] is on %s, %s[0] on %s" % (name, j, t.device, name, clouds[0].device))
-        off.append(off[-1] + t.shape[0])
-    if len(clouds) == 0:
-        return torch.empty((0, 3), dtype=torch.float32), off
-    return torch.cat(list(clouds), dim=0).contiguous(), off
+from ..._ragged import _is_offsets, chunks, pack_clouds          # (both names are read from here too)
 
 
 def _one_way(q, qoff, t, toff):
     """Queries against targets, at most chamfer_3D.RAGGED_MAX_PAIRS pairs per library call (a longer list takes several)."""
     dist = torch.empty((q.shape[0],), dtype=torch.float32, device=q.device)
     idx = torch.empty((q.shape[0],), dtype=torch.int32, device=q.device)
-    step = chamfer_3D.RAGGED_MAX_PAIRS
-    for a in range(0, len(qoff) - 1, step):
-        b = min(a + step, len(qoff) - 1)
+    for a, b, qa, ta in chunks(chamfer_3D.RAGGED_MAX_PAIRS, qoff, toff):
         q0, q1, t0, t1 = qoff[a], qoff[b], toff[a], toff[b]
-        rc = chamfer_3D.nm_distance_ragged(q[q0:q1], [v - q0 for v in qoff[a:b + 1]], t[t0:t1], [v - t0 for v in toff[a:b + 1]],
-                                           dist[q0:q1], idx[q0:q1])
+        rc = chamfer_3D.nm_distance_ragged(q[q0:q1], qa, t[t0:t1], ta, dist[q0:q1], idx[q0:q1])
         if rc != 1:
             raise RuntimeError("chamfer_3D.nm_distance_ragged failed: " + _lib.last_error())
     return dist, idx
@@ -111,13 +68,10 @@ class chamfer_raggedFunction(Function):
         graddist2 = graddist2.contiguous()
         gradxyz1 = torch.empty_like(p1)          # every row is overwritten: nothing to zero
         gradxyz2 = torch.empty_like(p2)
-        step = chamfer_3D.RAGGED_MAX_PAIRS
-        for a in range(0, len(off1) - 1, step):
-            b = min(a + step, len(off1) - 1)
+        for a, b, na, ma in chunks(chamfer_3D.RAGGED_MAX_PAIRS, off1, off2):
             n0, n1, m0, m1 = off1[a], off1[b], off2[a], off2[b]
-            rc = chamfer_3D.backward_ragged(p1[n0:n1], [v - n0 for v in off1[a:b + 1]], p2[m0:m1], [v - m0 for v in off2[a:b + 1]],
-                                            gradxyz1[n0:n1], gradxyz2[m0:m1], graddist1[n0:n1], graddist2[m0:m1],
-                                            idx1[n0:n1], idx2[m0:m1])
+            rc = chamfer_3D.backward_ragged(p1[n0:n1], na, p2[m0:m1], ma, gradxyz1[n0:n1], gradxyz2[m0:m1], graddist1[n0:n1],
+                                            graddist2[m0:m1], idx1[n0:n1], idx2[m0:m1])
             if rc != 1:
                 raise RuntimeError("chamfer_3D.backward_ragged failed: " + _lib.last_error())
         return gradxyz1, gradxyz2, None, None

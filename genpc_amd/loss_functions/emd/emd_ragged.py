@@ -10,7 +10,7 @@ from torch import nn
 from torch.autograd import Function
 
 from ... import _lib, emd
-from ..Chamfer3D.dist_chamfer_ragged import _is_offsets, pack_clouds
+from ..._ragged import chunks, is_packed, pack_clouds
 
 
 def check_pairs(off1, off2, who="emd_ragged"):
@@ -41,11 +41,9 @@ def forward_packed(p1, p2, off, eps, iters):
     """Packed points [T,3] twice (float32, contiguous, one device) and the pairs' offsets -> the state arrays of the call(s):
     at most emd.RAGGED_MAX_PAIRS pairs per library call, a longer list takes several."""
     s = alloc_state_ragged(p1.shape[0], p1.device)
-    step = emd.RAGGED_MAX_PAIRS
-    for a in range(0, len(off) - 1, step):
-        b = min(a + step, len(off) - 1)
+    for a, b, oa in chunks(emd.RAGGED_MAX_PAIRS, off):
         t0, t1 = off[a], off[b]
-        rc = emd.forward_ragged(p1[t0:t1], p2[t0:t1], [v - t0 for v in off[a:b + 1]], s["dist"][t0:t1], s["assignment"][t0:t1],
+        rc = emd.forward_ragged(p1[t0:t1], p2[t0:t1], oa, s["dist"][t0:t1], s["assignment"][t0:t1],
                                 s["price"][t0:t1], s["assignment_inv"][t0:t1], s["bid"][t0:t1], s["bid_increments"][t0:t1],
                                 s["max_increments"][t0:t1], s["max_idx"][t0:t1], eps, iters)
         if rc == -1:
@@ -75,12 +73,9 @@ class emd_raggedFunction(Function):
         graddist = graddist.contiguous()
         gradxyz1 = torch.zeros_like(p1)
         gradxyz2 = torch.zeros_like(p2)
-        step = emd.RAGGED_MAX_PAIRS
-        for a in range(0, len(off) - 1, step):
-            b = min(a + step, len(off) - 1)
+        for a, b, oa in chunks(emd.RAGGED_MAX_PAIRS, off):
             t0, t1 = off[a], off[b]
-            rc = emd.backward_ragged(p1[t0:t1], p2[t0:t1], [v - t0 for v in off[a:b + 1]], gradxyz1[t0:t1], graddist[t0:t1],
-                                     assignment[t0:t1])
+            rc = emd.backward_ragged(p1[t0:t1], p2[t0:t1], oa, gradxyz1[t0:t1], graddist[t0:t1], assignment[t0:t1])
             if rc != 1:
                 raise RuntimeError("emd.backward_ragged failed: " + _lib.last_error())
         return gradxyz1, gradxyz2, None, None, None
@@ -96,7 +91,7 @@ class emd_raggedDist(nn.Module):
         super(emd_raggedDist, self).__init__()
 
     def forward(self, clouds1, clouds2, eps, iters):
-        packed = isinstance(clouds1, tuple) and len(clouds1) == 2 and torch.is_tensor(clouds1[0]) and _is_offsets(clouds1[1])
+        packed = is_packed(clouds1)
         p1, off1 = pack_clouds(clouds1, "clouds1")
         p2, off2 = pack_clouds(clouds2, "clouds2")
         check_pairs(off1, off2, "emd_raggedDist")

@@ -35,7 +35,6 @@ same N_j points (a multiple of 256) on both sides: ``evaluate_clouds``' two colu
 (csrc/emd_ragged.hip) for all scans.
 """
 import argparse
-import ctypes
 import os
 
 import numpy as np
@@ -225,8 +224,8 @@ UHD_RAGGED_MAX_PAIRS = 384          # include/genpc_hip.h: pairs per genpc_uhd_r
 def _uhd_ragged_side(clouds, name):
     """One side of a ragged UHD batch as (points [T,3] float32 contiguous, offsets: S + 1 Python ints): a list of [N_j,3]
     tensors or packed (points, offsets), as pack_clouds reads them, each cloud under _uhd_cloud's dtype rule."""
-    from .loss_functions.Chamfer3D.dist_chamfer_ragged import _is_offsets, pack_clouds
-    if isinstance(clouds, tuple) and len(clouds) == 2 and torch.is_tensor(clouds[0]) and _is_offsets(clouds[1]):
+    from ._ragged import is_packed, pack_clouds
+    if is_packed(clouds):
         points, off = clouds
         if points.dim() != 2 or points.shape[1] != 3:
             raise ValueError("uhd_ragged: packed %s must be [T,3], got %s" % (name, tuple(points.shape)))
@@ -246,7 +245,7 @@ def uhd_ragged(partials, completes, return_witness=False):
     the device, per pair the bits of ``uhd`` on that pair alone; return_witness=True also returns int32 [S,2], (i, j) counted
     inside the pair's own clouds.  One library call per 384 pairs (genpc_uhd_ragged; a longer list takes several), nothing
     waits for the result (a float64 input costs one synchronising check per tensor).  An empty cloud is an error."""
-    from . import chamfer_3D
+    from ._ragged import chunks, host_ints
     p, poff = _uhd_ragged_side(partials, "partials")
     c, coff = _uhd_ragged_side(completes, "completes")
     if len(poff) != len(coff):
@@ -266,13 +265,9 @@ def uhd_ragged(partials, completes, return_witness=False):
         raise ValueError("uhd_ragged: partials and completes are on different devices")
     d2 = torch.empty((s,), dtype=torch.float64, device=p.device)
     ij = torch.empty((s, 2), dtype=torch.int32, device=p.device)
-    for a in range(0, s, UHD_RAGGED_MAX_PAIRS):
-        b = min(a + UHD_RAGGED_MAX_PAIRS, s)
-        n0, m0 = poff[a], coff[a]
-        na, _ = chamfer_3D._host_offsets([v - n0 for v in poff[a:b + 1]], "noff")
-        ma, _ = chamfer_3D._host_offsets([v - m0 for v in coff[a:b + 1]], "moff")
-        rc = _lib.on_device_of(p, _lib.lib.genpc_uhd_ragged, b - a, ctypes.cast(na, ctypes.c_void_p), _lib.ptr(p[n0:poff[b]]),
-                               ctypes.cast(ma, ctypes.c_void_p), _lib.ptr(c[m0:coff[b]]), _lib.ptr(d2[a:b]), _lib.ptr(ij[a:b]))
+    for a, b, na, ma in chunks(UHD_RAGGED_MAX_PAIRS, poff, coff):
+        rc = _lib.on_device_of(p, _lib.lib.genpc_uhd_ragged, b - a, host_ints(na, "noff")[1], _lib.ptr(p[poff[a]:poff[b]]),
+                               host_ints(ma, "moff")[1], _lib.ptr(c[coff[a]:coff[b]]), _lib.ptr(d2[a:b]), _lib.ptr(ij[a:b]))
         if rc != 0:
             raise RuntimeError("genpc_uhd_ragged failed (%d): %s" % (rc, _lib.last_error()))
     hd = torch.sqrt(d2)

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._ragged import chunks, host_ints, ragged_side
 from .loss_functions import chamfer_3DDist
 
 _L = _lib.lib
@@ -61,18 +62,23 @@ def icp_with_scaling_xyz(source, target, scales, max_correspondence_distance=0.0
     return T, scaled
 
 
+def _scaled_inits(T1, scales):
+    """[K,4,4]: T1 @ diag(scale, scale, scale, 1) for every scale (reg_xyz.py:31-36)."""
+    inits = []
+    for sc in scales:
+        S = np.eye(4)
+        S[:3, :3] *= sc
+        inits.append(T1 @ S)
+    return np.stack(inits)
+
+
 def icp_with_scaling(source, target, scale, max_correspondence_distance=0.05, init_transform=None):
     """reg_xyz.py:24-38: ICP, then ICP again from result @ diag(scale).  `scale` may be
     a sequence: the first ICP is shared and the second runs as one batch."""
     init = np.eye(4) if init_transform is None else np.asarray(init_transform, np.float64)
     T1, _, _, _ = registration_icp(source, target, max_correspondence_distance, init)
     scales = np.atleast_1d(np.asarray(scale, np.float64))
-    inits = []
-    for sc in scales:
-        S = np.eye(4)
-        S[:3, :3] *= sc
-        inits.append(T1 @ S)
-    T2, fit, rmse, its = registration_icp(source, target, max_correspondence_distance, np.stack(inits))
+    T2, fit, rmse, its = registration_icp(source, target, max_correspondence_distance, _scaled_inits(T1, scales))
     if np.ndim(scale) == 0:
         return T2[0]
     return T2
@@ -99,18 +105,22 @@ def coarse_scale_sweep(source_down, target_down, cd_inv_weight=0.5, scales=None,
     return float(scales[best]), float(cd[best]), T[best]
 
 
+def _scale_candidates(ranges, steps):
+    """[steps^3,3] float64 (x, y, z) scales of the fine search, in the order z (outer), x, y (inner) (reg_xyz.py:66-75)."""
+    xs = np.linspace(ranges[0][0], ranges[0][1], steps)
+    ys = np.linspace(ranges[1][0], ranges[1][1], steps)
+    zs = np.linspace(ranges[2][0], ranges[2][1], steps)
+    gz, gx, gy = np.meshgrid(zs, xs, ys, indexing="ij")
+    return np.stack([gx.ravel(), gy.ravel(), gz.ravel()], axis=1).astype(np.float64)
+
+
 def iterative_scale_search(source_pcd, target_pcd, scale_ranges, scale_steps, init_transform=None, cd_inv_weight=0):
     """reg_xyz.py:60-96.  Returns (best_scales_transformation [4,4], best_loss,
     best_transformation [4,4]).  Candidate order z (outer), x, y (inner), strict '<'."""
     source = source_pcd.contiguous().float()
     target = target_pcd.contiguous().float()
     _lib.check_tensors((("source", source), ("target", target)))
-    xs = np.linspace(scale_ranges[0][0], scale_ranges[0][1], scale_steps)
-    ys = np.linspace(scale_ranges[1][0], scale_ranges[1][1], scale_steps)
-    zs = np.linspace(scale_ranges[2][0], scale_ranges[2][1], scale_steps)
-    # candidate order z (outer), x, y (inner)
-    gz, gx, gy = np.meshgrid(zs, xs, ys, indexing="ij")
-    cand = np.stack([gx.ravel(), gy.ravel(), gz.ravel()], axis=1).astype(np.float64)
+    cand = _scale_candidates(scale_ranges, scale_steps)
     scales_t = torch.from_numpy(cand.astype(np.float32)).to(source.device)
     scores = torch.empty(len(cand), device=source.device)
     rc = _lib.on_device_of(source, _L.genpc_scale_search_scores, len(cand), source.shape[0], _p(source),
@@ -194,6 +204,18 @@ def _is_cfg(x):
     return hasattr(x, "output_path") and not torch.is_tensor(x)
 
 
+def _check_file_form_options(who, takes, seed, kwargs):
+    """The keyword checks of the file forms (`who`: the call as its messages spell it, `takes`: how they introduce its options)."""
+    unknown = set(kwargs) - {"cd_only_pose", "rng"}
+    if unknown:          # (the file form reads these options; anything else -- a misspelt one -- used to be dropped silently: ADVICE r3)
+        raise TypeError("%s: unexpected keyword argument(s) %s (%s takes cd_only_pose, rng, seed)" % (who, sorted(unknown), takes))
+    if seed is not None:
+        if kwargs.get("rng") is not None:
+            raise TypeError("%s: seed (the device sampler) and rng (the host sampler) exclude each other" % who)
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+            raise TypeError("%s: seed must be an int or None, got %r" % (who, seed))
+
+
 def reg(cfg, flag, cd_inv_weight=0.5, diff_init=True, reg_fine_xyz=False, seed=None, **kwargs):
     """reg_xyz.py:99-223, same signature.
 
@@ -216,14 +238,7 @@ def reg(cfg, flag, cd_inv_weight=0.5, diff_init=True, reg_fine_xyz=False, seed=N
     from .optim_registration.diff_obj_pose import object_pose_optimization
     from .utils.dataUtils import read_ply, save_ply_xyzrgb
     from .utils.mesh_io import glb2point, glb2point_gpu
-    unknown = set(kwargs) - {"cd_only_pose", "rng"}
-    if unknown:          # (the file form reads these options; anything else -- a misspelt one -- used to be dropped silently: ADVICE r3)
-        raise TypeError("reg(cfg, flag, ...): unexpected keyword argument(s) %s (the file form takes cd_only_pose, rng, seed)" % sorted(unknown))
-    if seed is not None:
-        if kwargs.get("rng") is not None:
-            raise TypeError("reg(cfg, flag, ...): seed (the device sampler) and rng (the host sampler) exclude each other")
-        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
-            raise TypeError("reg(cfg, flag, ...): seed must be an int or None, got %r" % (seed,))
+    _check_file_form_options("reg(cfg, flag, ...)", "the file form", seed, kwargs)
     path = cfg.output_path
     ply = f"{path}/{flag}/color_point.ply"
     glb = f"{path}/{flag}/{flag}_{cfg.generative_model}.glb"
@@ -409,53 +424,20 @@ def remove_noise_from_point_cloud(xyz, nb_neighbors=20, std_ratio=1.5):
 OUTLIER_RAGGED_MAX_CLOUDS = 384          # include/genpc_hip.h: clouds per genpc_knn_mean_distance_ragged / genpc_outlier_filter_ragged call
 
 
-def _ragged_side(clouds, fn, name="clouds"):
-    """A ragged batch as (points [T,3] float32 contiguous, offsets: S + 1 Python ints): a list of [N_j,3] tensors or packed
-    (points, offsets), as pack_clouds of loss_functions/Chamfer3D/dist_chamfer_ragged.py reads them; errors name `fn`."""
-    from .loss_functions.Chamfer3D.dist_chamfer_ragged import _is_offsets, pack_clouds
-    if isinstance(clouds, tuple) and len(clouds) == 2 and torch.is_tensor(clouds[0]) and _is_offsets(clouds[1]):
-        points, off = clouds
-        if points.dim() != 2 or points.shape[1] != 3:
-            raise ValueError("%s: packed %s must be [T,3], got %s" % (fn, name, tuple(points.shape)))
-        if torch.is_tensor(off) and off.is_cuda:
-            raise ValueError("%s: the offsets of %s live on the host (a device tensor would have to be read back)" % (fn, name))
-        if points.dtype != torch.float32:
-            raise TypeError("%s: packed %s must be torch.float32, got %s" % (fn, name, points.dtype))
-        return pack_clouds(clouds, name)
-    if not isinstance(clouds, (list, tuple)):
-        raise TypeError("%s: %s is a list of [N,3] tensors or a tuple (points, offsets)" % (fn, name))
-    for j, t in enumerate(clouds):
-        if not torch.is_tensor(t) or t.dim() != 2 or t.shape[1] != 3:
-            raise ValueError("%s: %s[%d] must be an [N,3] tensor" % (fn, name, j))
-        if t.dtype != torch.float32:
-            raise TypeError("%s: %s[%d] must be torch.float32, got %s" % (fn, name, j, t.dtype))
-    return pack_clouds(clouds, name)
-
-
-def _ragged_chunks(off):
-    """(a, b, host offsets of clouds a..b counted from cloud a's first point) per library call."""
-    import ctypes
-    from . import chamfer_3D
-    for a in range(0, len(off) - 1, OUTLIER_RAGGED_MAX_CLOUDS):
-        b = min(a + OUTLIER_RAGGED_MAX_CLOUDS, len(off) - 1)
-        arr, _ = chamfer_3D._host_offsets([v - off[a] for v in off[a:b + 1]], "offsets")
-        yield a, b, ctypes.cast(arr, ctypes.c_void_p)
-
-
 def knn_mean_distance_ragged(clouds, k=20):
     """``knn_mean_distance`` for S clouds of any sizes: a list of [N_j,3] float32 GPU tensors, or packed as (points [T,3],
     offsets) with S + 1 host ints.  Returns a list of float32 [N_j] tensors, views of one packed result; cloud j's are the
     bits of ``knn_mean_distance(clouds[j], k)``.  One library call per 384 clouds (genpc_knn_mean_distance_ragged: two
     launches each), nothing waits for the result.  An empty cloud gives an empty tensor."""
-    pts, off = _ragged_side(clouds, "knn_mean_distance_ragged")
+    pts, off = ragged_side(clouds, "knn_mean_distance_ragged")
     if int(k) not in (8, 16, 20, 32):
         raise ValueError("knn_mean_distance_ragged: k must be 8, 16, 20 or 32")
     if len(off) == 1:
         return []
     _lib.require_gpu(pts)
     out = torch.empty(pts.shape[0], device=pts.device)
-    for a, b, arr in _ragged_chunks(off):
-        rc = _lib.on_device_of(pts, _L.genpc_knn_mean_distance_ragged, b - a, arr, _p(pts[off[a]:off[b]]), int(k), _p(out[off[a]:off[b]]))
+    for a, b, oa in chunks(OUTLIER_RAGGED_MAX_CLOUDS, off):
+        rc = _lib.on_device_of(pts, _L.genpc_knn_mean_distance_ragged, b - a, host_ints(oa)[1], _p(pts[off[a]:off[b]]), int(k), _p(out[off[a]:off[b]]))
         if rc != 1:
             raise RuntimeError("genpc_knn_mean_distance_ragged failed (%d): %s" % (rc, _lib.last_error()))
     return [out[off[j]:off[j + 1]] for j in range(len(off) - 1)]
@@ -468,9 +450,9 @@ def _outlier_filter_ragged(pts, off, nb_neighbors, std_ratio):
     # (a library call without a point enqueues nothing: its clouds are empty, and these are an empty cloud's words)
     stats = torch.full((s, 3), float("nan"), dtype=torch.float64, device=pts.device)
     kept = torch.zeros(s, dtype=torch.int32, device=pts.device)
-    for a, b, arr in _ragged_chunks(off):
-        rc = _lib.on_device_of(pts, _L.genpc_outlier_filter_ragged, b - a, arr, _p(pts[off[a]:off[b]]), int(nb_neighbors), float(std_ratio),
-                               None, _p(stats[a:b]), _p(keep[off[a]:off[b]]), _p(kept[a:b]))
+    for a, b, oa in chunks(OUTLIER_RAGGED_MAX_CLOUDS, off):
+        rc = _lib.on_device_of(pts, _L.genpc_outlier_filter_ragged, b - a, host_ints(oa)[1], _p(pts[off[a]:off[b]]), int(nb_neighbors),
+                               float(std_ratio), None, _p(stats[a:b]), _p(keep[off[a]:off[b]]), _p(kept[a:b]))
         if rc != 1:
             raise RuntimeError("genpc_outlier_filter_ragged failed (%d): %s" % (rc, _lib.last_error()))
     return keep.view(torch.bool), stats, kept
@@ -484,7 +466,7 @@ def remove_noise_from_point_clouds(clouds, nb_neighbors=20, std_ratio=1.5, retur
     include/genpc_hip.h defines -- not torch's, so a point whose mean lies within rounding of the threshold (a relative 1e-15)
     may fall on the other side than ``remove_noise_from_point_cloud`` puts it.  The host waits for the K_j, which size the
     filtered tensors, and in the boolean index over the packed points: twice, whatever S is."""
-    pts, off = _ragged_side(clouds, "remove_noise_from_point_clouds")
+    pts, off = ragged_side(clouds, "remove_noise_from_point_clouds")
     if int(nb_neighbors) not in (8, 16, 20, 32):
         raise ValueError("remove_noise_from_point_clouds: nb_neighbors must be 8, 16, 20 or 32")
     s = len(off) - 1
@@ -509,8 +491,8 @@ def fuse_scans(sources, targets, num_points=20000, distance_threshold=0.0001, st
     ``remove_noise_from_point_clouds``."""
     from .fps import fps_sampling_multi
     from .loss_functions.Chamfer3D.dist_chamfer_ragged import _one_way
-    sp, soff = _ragged_side(sources, "fuse_scans", "sources")
-    tp, toff = _ragged_side(targets, "fuse_scans", "targets")
+    sp, soff = ragged_side(sources, "fuse_scans", "sources")
+    tp, toff = ragged_side(targets, "fuse_scans", "targets")
     if len(soff) != len(toff):
         raise ValueError("fuse_scans: %d sources against %d targets" % (len(soff) - 1, len(toff) - 1))
     s = len(soff) - 1
@@ -534,8 +516,8 @@ def fuse_scans(sources, targets, num_points=20000, distance_threshold=0.0001, st
         d, _ = _one_way(tp, toff, sp, soff)
         keep_t = ~(d < distance_threshold)
     elif live:
-        q, qoff = _ragged_side([tp[toff[j]:toff[j + 1]] for j in live], "fuse_scans", "targets")
-        t, t_off = _ragged_side([sp[soff[j]:soff[j + 1]] for j in live], "fuse_scans", "sources")
+        q, qoff = ragged_side([tp[toff[j]:toff[j + 1]] for j in live], "fuse_scans", "targets")
+        t, t_off = ragged_side([sp[soff[j]:soff[j + 1]] for j in live], "fuse_scans", "sources")
         d, _ = _one_way(q, qoff, t, t_off)
         for i, j in enumerate(live):
             keep_t[toff[j]:toff[j + 1]] = ~(d[qoff[i]:qoff[i + 1]] < distance_threshold)
@@ -569,13 +551,6 @@ VOXEL_RAGGED_MAX_CLOUDS = 256            # include/genpc_hip.h: GENPC_VOXEL_RAGG
 ICP_RAGGED_MAX_PAIRS = 256               # include/genpc_hip.h: GENPC_ICP_RAGGED_MAX_PAIRS
 
 
-def _host_ints(values):
-    import ctypes
-    from . import chamfer_3D
-    arr, _ = chamfer_3D._host_offsets(values, "offsets")
-    return ctypes.cast(arr, ctypes.c_void_p), arr
-
-
 def voxel_down_sample_clouds(clouds, voxel_size, colors=None):
     """``voxel_down_sample`` for S clouds of any sizes: a list of [N_j,3] float32 GPU tensors, or packed as (points [T,3],
     offsets) with S + 1 host ints.  voxel_size: one float for all, or one per cloud (reg mixes 0.02, 0.03 and 0.04); colors,
@@ -585,7 +560,7 @@ def voxel_down_sample_clouds(clouds, voxel_size, colors=None):
     is.  A cloud with a non-finite coordinate or more than 2^21 voxels along an axis raises ValueError naming it."""
     import ctypes
     fn = "voxel_down_sample_clouds"
-    pts, off = _ragged_side(clouds, fn)
+    pts, off = ragged_side(clouds, fn)
     s = len(off) - 1
     sizes = [float(voxel_size)] * s if np.ndim(voxel_size) == 0 else [float(v) for v in voxel_size]
     if len(sizes) != s:
@@ -595,7 +570,7 @@ def voxel_down_sample_clouds(clouds, voxel_size, colors=None):
             raise ValueError("%s: the voxel size of cloud %d must be positive" % (fn, j))
     col = None
     if colors is not None:
-        col, coff = _ragged_side(colors, fn, "colors")
+        col, coff = ragged_side(colors, fn, "colors")
         if coff != off:
             raise ValueError("%s: colors must be [N_j,3] like their clouds" % fn)
     if s == 0:
@@ -608,11 +583,9 @@ def voxel_down_sample_clouds(clouds, voxel_size, colors=None):
     out = torch.empty_like(pts)
     outc = torch.empty_like(col) if col is not None else None
     counts = torch.empty(s, dtype=torch.int32, device=pts.device)
-    for a in range(0, s, VOXEL_RAGGED_MAX_CLOUDS):
-        b = min(a + VOXEL_RAGGED_MAX_CLOUDS, s)
-        arr, _keep = _host_ints([v - off[a] for v in off[a:b + 1]])
+    for a, b, oa in chunks(VOXEL_RAGGED_MAX_CLOUDS, off):
         vs = (ctypes.c_double * (b - a))(*sizes[a:b])
-        rc = _lib.on_device_of(pts, _L.genpc_voxel_down_sample_ragged, b - a, arr, _p(pts[off[a]:off[b]]),
+        rc = _lib.on_device_of(pts, _L.genpc_voxel_down_sample_ragged, b - a, host_ints(oa)[1], _p(pts[off[a]:off[b]]),
                                _p(None if col is None else col[off[a]:off[b]]), ctypes.cast(vs, ctypes.c_void_p), _p(out[off[a]:off[b]]),
                                _p(None if outc is None else outc[off[a]:off[b]]), _p(counts[a:b]))
         if rc != 1:
@@ -636,8 +609,8 @@ def registration_icp_ragged(sources, targets, max_correspondence_distance, inits
     pairs whose target fits the one-workgroup solve share ONE launch and get the bits of registration_icp on the pair alone)
     and one copy back per call of this function."""
     fn = "registration_icp_ragged"
-    sp, soff = _ragged_side(sources, fn, "sources")
-    tp, toff = _ragged_side(targets, fn, "targets")
+    sp, soff = ragged_side(sources, fn, "sources")
+    tp, toff = ragged_side(targets, fn, "targets")
     if len(soff) != len(toff):
         raise ValueError("%s: %d sources against %d targets" % (fn, len(soff) - 1, len(toff) - 1))
     s = len(soff) - 1
@@ -662,12 +635,9 @@ def registration_icp_ragged(sources, targets, max_correspondence_distance, inits
     init_t = torch.as_tensor(np.concatenate(arrs, axis=0).reshape(k, 16)).contiguous().to(dev)
     buf = torch.empty(k * 19, dtype=torch.float64, device=dev)           # transforms and statistics: one copy back
     out_T, stats = buf[:k * 16].view(k, 16), buf[k * 16:].view(k, 3)
-    for a in range(0, s, ICP_RAGGED_MAX_PAIRS):
-        b = min(a + ICP_RAGGED_MAX_PAIRS, s)
-        sa, _k1 = _host_ints([v - soff[a] for v in soff[a:b + 1]])
-        ta, _k2 = _host_ints([v - toff[a] for v in toff[a:b + 1]])
-        ka, _k3 = _host_ints([v - koff[a] for v in koff[a:b + 1]])
-        rc = _lib.on_device_of(sp, _L.genpc_icp_batch_ragged, b - a, sa, ta, ka, _p(sp[soff[a]:soff[b]]), _p(tp[toff[a]:toff[b]]),
+    for a, b, sa, ta, ka in chunks(ICP_RAGGED_MAX_PAIRS, soff, toff, koff):
+        rc = _lib.on_device_of(sp, _L.genpc_icp_batch_ragged, b - a, host_ints(sa)[1], host_ints(ta)[1], host_ints(ka)[1],
+                               _p(sp[soff[a]:soff[b]]), _p(tp[toff[a]:toff[b]]),
                                float(max_correspondence_distance), _p(init_t[koff[a]:koff[b]]), int(max_iteration),
                                float(relative_fitness), float(relative_rmse), _p(out_T[koff[a]:koff[b]]), _p(stats[koff[a]:koff[b]]))
         if rc != 1:
@@ -694,8 +664,8 @@ def coarse_scale_sweeps(sources_down, targets_down, cd_inv_weight=0.5, scales=No
     the first minimum wins, as the reference's strict '<'.  The host reads back three times whatever S is."""
     from .loss_functions.Chamfer3D.dist_chamfer_ragged import chamfer_ragged
     fn = "coarse_scale_sweeps"
-    sp, soff = _ragged_side(sources_down, fn, "sources_down")
-    tp, toff = _ragged_side(targets_down, fn, "targets_down")
+    sp, soff = ragged_side(sources_down, fn, "sources_down")
+    tp, toff = ragged_side(targets_down, fn, "targets_down")
     if len(soff) != len(toff):
         raise ValueError("%s: %d sources against %d targets" % (fn, len(soff) - 1, len(toff) - 1))
     s = len(soff) - 1
@@ -707,14 +677,7 @@ def coarse_scale_sweeps(sources_down, targets_down, cd_inv_weight=0.5, scales=No
     k = len(scales)
     md = max_correspondence_distance
     first = registration_icp_ragged((sp, soff), (tp, toff), md, [np.eye(4)] * s)
-    inits = []
-    for j in range(s):                                       # icp_with_scaling: ICP again from result @ diag(scale)
-        cand = []
-        for sc in scales:
-            S = np.eye(4)
-            S[:3, :3] *= sc
-            cand.append(first[j][0] @ S)
-        inits.append(np.stack(cand))
+    inits = [_scaled_inits(first[j][0], scales) for j in range(s)]          # icp_with_scaling: ICP again from result @ diag(scale)
     T = [r[0] for r in registration_icp_ragged((sp, soff), (tp, toff), md, inits)]          # S x [K,4,4]
     src_k, tgt_k, o1, o2 = [], [], [0], [0]
     for j in range(s):                                       # :161-162, per scan as coarse_scale_sweep writes it
@@ -748,8 +711,8 @@ SCALE_SEARCH_RAGGED_MAX_PAIRS = 256      # include/genpc_hip.h: GENPC_SCALE_SEAR
 
 def _scale_search_scores_packed(sources, targets, scales, cd_inv_weight, fn):
     """(scores [K] float32 on the device -- None without a scan --, koff: S + 1 Python ints) of scale_search_scores_ragged."""
-    sp, soff = _ragged_side(sources, fn, "sources")
-    tp, toff = _ragged_side(targets, fn, "targets")
+    sp, soff = ragged_side(sources, fn, "sources")
+    tp, toff = ragged_side(targets, fn, "targets")
     if len(soff) != len(toff):
         raise ValueError("%s: %d sources against %d targets" % (fn, len(soff) - 1, len(toff) - 1))
     s = len(soff) - 1
@@ -777,12 +740,9 @@ def _scale_search_scores_packed(sources, targets, scales, cd_inv_weight, fn):
     else:
         scales_t = torch.cat([r.to(dev) for r in rows]).contiguous()
     scores = torch.empty(koff[-1], device=dev)
-    for a in range(0, s, SCALE_SEARCH_RAGGED_MAX_PAIRS):
-        b = min(a + SCALE_SEARCH_RAGGED_MAX_PAIRS, s)
-        sa, _k1 = _host_ints([v - soff[a] for v in soff[a:b + 1]])
-        ta, _k2 = _host_ints([v - toff[a] for v in toff[a:b + 1]])
-        ka, _k3 = _host_ints([v - koff[a] for v in koff[a:b + 1]])
-        rc = _lib.on_device_of(sp, _L.genpc_scale_search_scores_ragged, b - a, sa, ta, ka, _p(sp[soff[a]:soff[b]]), _p(tp[toff[a]:toff[b]]),
+    for a, b, sa, ta, ka in chunks(SCALE_SEARCH_RAGGED_MAX_PAIRS, soff, toff, koff):
+        rc = _lib.on_device_of(sp, _L.genpc_scale_search_scores_ragged, b - a, host_ints(sa)[1], host_ints(ta)[1], host_ints(ka)[1],
+                               _p(sp[soff[a]:soff[b]]), _p(tp[toff[a]:toff[b]]),
                                _p(scales_t[koff[a]:koff[b]]), float(cd_inv_weight), _p(scores[koff[a]:koff[b]]))
         if rc != 1:
             raise RuntimeError("genpc_scale_search_scores_ragged failed (rc=%d): %s" % (rc, _lib.last_error()))
@@ -811,8 +771,8 @@ def iterative_scale_searches(sources, targets, scale_ranges, scale_steps, init_t
     y (inner); the first minimum wins.  One ``scale_search_scores_ragged``, ONE read-back of all scores and one
     ``registration_icp_ragged`` over the winners, whatever S is.  A scan whose scores hold a NaN raises ValueError naming it."""
     fn = "iterative_scale_searches"
-    sp, soff = _ragged_side(sources, fn, "sources")
-    tp, toff = _ragged_side(targets, fn, "targets")
+    sp, soff = ragged_side(sources, fn, "sources")
+    tp, toff = ragged_side(targets, fn, "targets")
     if len(soff) != len(toff):
         raise ValueError("%s: %d sources against %d targets" % (fn, len(soff) - 1, len(toff) - 1))
     s = len(soff) - 1
@@ -831,13 +791,7 @@ def iterative_scale_searches(sources, targets, scale_ranges, scale_steps, init_t
         if T.shape != (4, 4):
             raise ValueError("%s: init_transforms[%d] must be [4,4], got %s" % (fn, j, T.shape))
         inits.append(T)
-    cands = []
-    for r in ranges:
-        xs = np.linspace(r[0][0], r[0][1], scale_steps)
-        ys = np.linspace(r[1][0], r[1][1], scale_steps)
-        zs = np.linspace(r[2][0], r[2][1], scale_steps)
-        gz, gx, gy = np.meshgrid(zs, xs, ys, indexing="ij")          # candidate order z (outer), x, y (inner)
-        cands.append(np.stack([gx.ravel(), gy.ravel(), gz.ravel()], axis=1).astype(np.float64))
+    cands = [_scale_candidates(r, scale_steps) for r in ranges]
     scores, koff = _scale_search_scores_packed((sp, soff), (tp, toff), cands, cd_inv_weight, fn)
     if s == 0:
         return []
@@ -1000,14 +954,7 @@ def reg_scans(cfg, flags, cd_inv_weight=0.5, diff_init=True, reg_fine_xyz=False,
     from .optim_registration.diff_obj_pose import load_point_cloud, object_pose_optimization
     from .utils.dataUtils import read_ply, save_ply_xyzrgb
     from .utils.mesh_io import glb2point, load_glb, sample_surfaces_gpu
-    unknown = set(kwargs) - {"cd_only_pose", "rng"}
-    if unknown:
-        raise TypeError("reg_scans(cfg, flags, ...): unexpected keyword argument(s) %s (it takes cd_only_pose, rng, seed)" % sorted(unknown))
-    if seed is not None:
-        if kwargs.get("rng") is not None:
-            raise TypeError("reg_scans(cfg, flags, ...): seed (the device sampler) and rng (the host sampler) exclude each other")
-        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
-            raise TypeError("reg_scans(cfg, flags, ...): seed must be an int or None, got %r" % (seed,))
+    _check_file_form_options("reg_scans(cfg, flags, ...)", "it", seed, kwargs)
     if isinstance(flags, str) or not isinstance(flags, (list, tuple)):
         raise TypeError("reg_scans(cfg, flags, ...): flags is a list of flags")
     path = cfg.output_path

@@ -449,9 +449,9 @@ def _mesh_sample_ragged(meshes, counts, seeds, want_bary=False, device=None, fn=
     status = torch.empty(s, dtype=torch.int32, device=device)
     from .. import _lib
     L, p = _lib.lib, _lib.ptr
-    for a in range(0, s, MESH_SAMPLE_RAGGED_MAX_MESHES):
-        b = min(a + MESH_SAMPLE_RAGGED_MAX_MESHES, s)
-        tabs = [(ctypes.c_int * (b - a + 1))(*[v - off[a] for v in off[a:b + 1]]) for off in (voff, foff, soff)]
+    from .._ragged import chunks
+    for a, b, *rebased in chunks(MESH_SAMPLE_RAGGED_MAX_MESHES, voff, foff, soff):
+        tabs = [(ctypes.c_int * (b - a + 1))(*off) for off in rebased]
         sd = (ctypes.c_ulonglong * (b - a))(*seeds[a:b])
         vp = [ctypes.cast(t, ctypes.c_void_p) for t in tabs] + [ctypes.cast(sd, ctypes.c_void_p)]
         sl = slice(soff[a], soff[b])

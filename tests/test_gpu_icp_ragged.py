@@ -167,3 +167,34 @@ def test_a_call_that_also_holds_a_multi_launch_pair(rg, oracle, mode):
         np.testing.assert_allclose(T[c], oT, rtol=0, atol=bar)
         assert abs(rmse[c] - ormse) < 1e-7
         assert its[c] >= 1 and fit[c] > 0
+
+
+def many_small_pairs(seed, s=257):
+    """(sources, targets, candidates per pair) of s tiny pairs: 3 to 8 source points, 4 to 9 target points; pair 0, one in the
+    middle and the last two without candidates, every seventh of the others with two, the rest with one."""
+    rng = np.random.default_rng(seed)
+    src = [rng.uniform(-0.1, 0.1, (int(rng.integers(3, 9)), 3)).astype(np.float32) for _ in range(s)]
+    tgt = [rng.uniform(-0.1, 0.1, (int(rng.integers(4, 10)), 3)).astype(np.float32) for _ in range(s)]
+    ks = [0 if j in (0, s // 2, s - 2, s - 1) else (2 if j % 7 == 3 else 1) for j in range(s)]
+    return src, tgt, ks
+
+
+def test_more_pairs_than_one_library_call_takes(rg):
+    """257 pairs, one more than genpc_icp_batch_ragged takes: every pair's result is the bits of a one-pair call of the same
+    function (both take the one-workgroup plan), and the pairs without candidates -- the first, one in the middle, the last of
+    the first library call and the only one of the second -- come out empty."""
+    s = 257
+    assert s == rg["R"].ICP_RAGGED_MAX_PAIRS + 1
+    src, tgt, ks = many_small_pairs(41, s)
+    assert [j for j in range(s) if ks[j] == 0] == [0, 128, 255, 256] and ks.count(2) >= 3
+    inits = [np.array(R.inits(900 + j, max(k, 1))[:k]).reshape(k, 4, 4) for j, k in enumerate(ks)]
+    S_, T_ = to_dev(rg, src), to_dev(rg, tgt)
+    got = rg["R"].registration_icp_ragged(S_, T_, MD, inits, max_iteration=2)
+    assert len(got) == s
+    for j in range(s):
+        assert got[j][0].shape == (ks[j], 4, 4) and all(len(x) == ks[j] for x in got[j][1:]), j
+        if ks[j] == 0:
+            continue
+        alone = rg["R"].registration_icp_ragged([S_[j]], [T_[j]], MD, [inits[j]], max_iteration=2)
+        assert_same_bits(got[j], alone[0], "pair %d of %d" % (j, s))
+    assert sum(int((g[1] > 0).sum()) for g in got) > s // 2          # (most solves found correspondences)

@@ -271,3 +271,30 @@ def test_the_python_layer(rg):
     bad[7, 0] = float("nan")
     with pytest.raises(ValueError, match="scan 1 "):
         rg["R"].iterative_scale_searches(src, [tgt[0], bad, tgt[2]], ranges, 3, cd_inv_weight=0.5)
+
+
+def test_more_pairs_than_one_library_call_takes(rg):
+    """257 pairs, one more than genpc_scale_search_scores_ragged takes: every pair's scores are the bits of a one-pair call of
+    the same function (both take the one-workgroup plan), and the pairs without candidates -- the first, one in the middle, the
+    last of the first library call and the only one of the second -- come out empty."""
+    torch = rg["torch"]
+    s = 257
+    assert s == rg["R"].SCALE_SEARCH_RAGGED_MAX_PAIRS + 1
+    rng = np.random.default_rng(43)
+    src = [torch.from_numpy(rng.uniform(-0.1, 0.1, (int(rng.integers(3, 9)), 3)).astype(np.float32)).cuda() for _ in range(s)]
+    tgt = [torch.from_numpy(rng.uniform(-0.1, 0.1, (int(rng.integers(4, 10)), 3)).astype(np.float32)).cuda() for _ in range(s)]
+    ks = [0 if j in (0, s // 2, s - 2, s - 1) else (2 if j % 7 == 3 else 1) for j in range(s)]
+    assert [j for j in range(s) if ks[j] == 0] == [0, 128, 255, 256] and ks.count(2) >= 3
+    cands = [rng.uniform(0.8, 1.2, (k, 3)).astype(np.float32) for k in ks]
+    got = rg["R"].scale_search_scores_ragged(src, tgt, cands, cd_inv_weight=float(W))
+    assert len(got) == s
+    alone = [rg["R"].scale_search_scores_ragged([src[j]], [tgt[j]], [cands[j]], cd_inv_weight=float(W))[0] if ks[j] else None
+             for j in range(s)]
+    torch.cuda.synchronize()
+    for j in range(s):
+        g = got[j].cpu().numpy()
+        assert g.shape == (ks[j],) and g.dtype == np.float32, j
+        if ks[j]:
+            a = alone[j].cpu().numpy()
+            assert np.isfinite(a).all(), j
+            assert np.array_equal(bits(g), bits(a)), (j, g, a)
