@@ -67,6 +67,9 @@ SIGNATURES = {
     "genpc_pose_dual": (_i, [_i]),
     "genpc_render_tune": (_i, [_i]),
     "genpc_pose_optimize_batch": (_i, [_i, _i, _vp, _vp, _i, _vp, _vp, _f, _i, _i, _f, _i, _f, _vp, _vp, _vp, _vp]),
+    "genpc_pose_optimize_ragged": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _f, _i, _f, _vp, _vp, _vp, _vp]),
+    "genpc_pose_loss_grad_ragged": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i, _vp, _vp, _vp]),
+    "genpc_pose_ragged_plan": (_i, [_i, _vp, _vp, _i, _i, _i, _f, _i, _vp]),
     "genpc_pose_optimize_cd": (_i, [_i, _vp, _i, _vp, _f, _i, _i, _vp, _vp, _vp, _vp]),
     "genpc_pose_optimize_cd_batch": (_i, [_i, _i, _vp, _i, _vp, _f, _i, _i, _vp, _vp, _vp, _vp]),
     "genpc_icp_batch": (_i, [_i, _i, _vp, _i, _vp, _d, _vp, _i, _d, _d, _vp, _vp, _vp]),

@@ -76,6 +76,11 @@ enum Ws : int {
     kWsVoxelRagged = 46,      // voxel_ragged.hip genpc_voxel_down_sample_ragged: per-cloud bounds and error words | keys | clouds | orders | heads | ranks | sort / scan scratch
     kWsScaleSearchRagged = 47, // scale_search_ragged.hip genpc_scale_search_scores_ragged: the targets' grid headers | cell tables | sorted targets (nothing per candidate)
     kWsMeshSampleRagged = 48, // mesh_sample_ragged.hip genpc_mesh_sample_ragged: per-mesh headers | per-face local cumulative weights | per-chunk sums
+    kWsPoseRaggedLoop = 49,   // pose.hip genpc_pose_optimize_ragged: accumulators | states | centres | element tables | posed clouds | neighbours | mask scratch
+    kWsPoseRaggedStep = 50,   // pose.hip genpc_pose_loss_grad_ragged: accumulators | states | element tables | posed clouds | neighbours | mask scratch
+    kWsPoseRaggedReplicas = 51, // pose.hip genpc_pose_optimize_ragged: the packed clouds and colours once per start
+    kWsPoseRaggedGridPartial = 52, // pose.hip, posed -> partial: the partial clouds' grids (nn_ragged.hip), built once per call.  SHARED by the two ragged pose entry points: each builds afresh and is done with them at its last launch
+    kWsPoseRaggedGridPosed = 53,   // pose.hip, partial -> posed: the posed clouds' grids, rebuilt every step.  SHARED like 52
 };
 
 // The scratch pool: one grow-only block of device memory per (device, slot, stream); null on failure, the error recorded.

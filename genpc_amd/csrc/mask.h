@@ -248,15 +248,20 @@ int render_blend();
 // The launch pair every image of the mask term is drawn with: the b clouds of n points projected (project: unless the caller's
 // transform launch did that already; posed != 0: with center / params first, see mask_project_kernel) and splatted with their
 // colours into m.planes; accum: the sums of I and I^2 go to the images' accumulators, or null.
+// A ragged call (off: the element table of the clouds on the device, pose.h pose_span; n / np / nc then the LARGEST element's count,
+// which sizes the launches) packs pts, col, m.uvr and m.zex by that table; the images, bins and flags stay per element.
 void launch_mask_splat(int b, int n, const float *pts, const float *col, bool project, const float *center, int cstride, const float *params,
-                       int pstride, int posed, float radius, int S, const MaskScratch &m, double *accum, hipStream_t st);
+                       int pstride, int posed, float radius, int S, const MaskScratch &m, double *accum, hipStream_t st,
+                       const int *off = nullptr);
 // mask_loss.hip
 // splat of the partial clouds (with their colours) + reference soft masks / statistics (once per call)
-int mask_prepare_ref(int b, int np, const float *partial, const float *partial_col, float radius, int S, const MaskScratch &m, hipStream_t st);
+int mask_prepare_ref(int b, int np, const float *partial, const float *partial_col, float radius, int S, const MaskScratch &m, hipStream_t st,
+                     const int *off = nullptr);
 // the launches of the mask term for the current parameters: accum[0..12] += gradient, accum[15] += loss
-// (projected: the caller's transform launch projected already; ride: pose_grad's arguments, when its blocks ride in mask_grad's launch)
+// (projected: the caller's transform launch projected already; ride: pose_grad's arguments, when its blocks ride in mask_grad's launch;
+//  shape: the step's plan when the caller's own plan made it -- a ragged call's, from its totals -- otherwise mask_step_plan of b x nc)
 int mask_step(int b, int nc, const float *complete, const float *complete_col, const float *center, int cstride, const float *params,
               int pstride, float radius, int S, float mask_weight, const MaskScratch &m, double *accum, hipStream_t st,
-              bool projected = false, const PoseGradArgs *ride = nullptr);
+              bool projected = false, const PoseGradArgs *ride = nullptr, const int *off = nullptr, const MaskStepPlan *shape = nullptr);
 
 }  // namespace genpc

@@ -333,20 +333,24 @@ __global__ __launch_bounds__(kQBlock) void mask_grad_kernel(int n, const float *
                                                             int gx, int nb, const float *__restrict__ planes = nullptr,
                                                             const float *__restrict__ mref = nullptr,
                                                             const float *__restrict__ stats = nullptr, float mask_weight = 0.0f,
-                                                            PoseGradArgs pg = PoseGradArgs{})
+                                                            PoseGradArgs pg = PoseGradArgs{}, const int *__restrict__ off = nullptr)
 {
     __shared__ double red[15][kQBlock / kWave];
     // (one stream, full objective: the Chamfer half's gradient rides along as the launch's last blocks -- a launch less per step)
     if (pg.gx > 0 && (int)blockIdx.x >= gx * nb) {
         const int r = (int)blockIdx.x - gx * nb;
         pose_grad_body(r % pg.gx, pg.gx, r / pg.gx, pg.nc, pg.v, pg.center, pg.cstride, pg.params, pg.pstride, pg.np, pg.partial, pg.d1, pg.i1,
-                       pg.d2, pg.i2, pg.cd_weight, pg.accum, red);
+                       pg.d2, pg.i2, pg.cd_weight, pg.accum, red, pg.coff, pg.poff);
         return;
     }
     const XcdBlock xb = xcd_block(gx, nb);
     const int e = xb.e;
-    v += (size_t)e * n * 3;
-    if (col) col += (size_t)e * n * 3;
+    const PoseSpan sp = pose_span(off, e, n);
+    n = sp.n;
+    // a short element of a ragged call: the whole block leaves (block 0 of an element always has points, and it is the one that adds the loss)
+    if (off && xb.x * (kQBlock / kGradSub) >= n) return;
+    v += sp.base * 3;
+    if (col) col += sp.base * 3;
     const int PP = S * S;
     if (!FUSEW) {
         W1 += (size_t)e * PP;
@@ -507,22 +511,23 @@ __global__ void mask_loss_out_kernel(int P, const float4 *__restrict__ W4, doubl
     if (q == 0) *loss_out = (float)accum[15];
 }
 
-int mask_prepare_ref(int b, int np, const float *partial, const float *partial_col, float radius, int S, const MaskScratch &m, hipStream_t st)
+int mask_prepare_ref(int b, int np, const float *partial, const float *partial_col, float radius, int S, const MaskScratch &m, hipStream_t st,
+                     const int *off)
 {
-    launch_mask_splat(b, np, partial, partial_col, true, nullptr, 0, nullptr, 0, 0, radius, S, m, nullptr, st);
+    launch_mask_splat(b, np, partial, partial_col, true, nullptr, 0, nullptr, 0, 0, radius, S, m, nullptr, st, off);
     hipLaunchKernelGGL(mask_ref_kernel, dim3(b), dim3(kMLThreads), 0, st, S, (const float *)m.planes, render_blend() ? 2 : 0, m.mref, m.stats);
     return check(hipGetLastError(), "mask reference launch") ? 1 : 0;
 }
 
 int mask_step(int b, int nc, const float *complete, const float *complete_col, const float *center, int cstride, const float *params,
               int pstride, float radius, int S, float mask_weight, const MaskScratch &m, double *accum, hipStream_t st, bool projected,
-              const PoseGradArgs *ride)
+              const PoseGradArgs *ride, const int *off, const MaskStepPlan *shape)
 {
     const float rad = 1.1f * radius;      // diff_obj_pose.py:385: the posed cloud is drawn with 1.1 x the radius
-    const MaskStepPlan plan = mask_step_plan(b, nc, S, radius);      // (every size and choice below, with its reason: pose_plan.h)
+    const MaskStepPlan plan = shape ? *shape : mask_step_plan(b, nc, S, radius);      // (every size and choice below, with its reason: pose_plan.h)
     const int blend = render_blend(), mode = blend ? 2 : 0;
     // (the alignment loop projects in its transform launch)
-    launch_mask_splat(b, nc, complete, complete_col, !projected, center, cstride, params, pstride, 1, rad, S, m, accum, st);
+    launch_mask_splat(b, nc, complete, complete_col, !projected, center, cstride, params, pstride, 1, rad, S, m, accum, st, off);
     hipLaunchKernelGGL(mask_sums_kernel, dim3(plan.gs, b), dim3(kQBlock), 0, st, S, (const float *)m.planes, mode, (const float *)m.mref,
                        (const float *)m.stats, accum);
     if (!plan.fuse_w)
@@ -533,7 +538,7 @@ int mask_step(int b, int nc, const float *complete, const float *complete_col, c
     hipLaunchKernelGGL((mask_grad_kernel<SUB, BL, FW>), dim3(lin_grid((long long)nc * SUB) * b + pgx.gx * b), dim3(kQBlock), 0, st, nc, complete, \
                        complete_col, center, cstride, params, pstride, rad, S, (const float *)m.W1, (const float4 *)m.W4, accum,     \
                        lin_grid((long long)nc * SUB), b, (const float *)m.planes, (const float *)m.mref, (const float *)m.stats,      \
-                       mask_weight, pgx)
+                       mask_weight, pgx, off)
 #define GENPC_LAUNCH_MASK_GRAD2(SUB, BL) do { if (plan.fuse_w) GENPC_LAUNCH_MASK_GRAD3(SUB, BL, 1); else GENPC_LAUNCH_MASK_GRAD3(SUB, BL, 0); } while (0)
 #define GENPC_LAUNCH_MASK_GRAD(SUB) do { if (blend) GENPC_LAUNCH_MASK_GRAD2(SUB, 1); else GENPC_LAUNCH_MASK_GRAD2(SUB, 0); } while (0)
     if (plan.sub8) GENPC_LAUNCH_MASK_GRAD(8);

@@ -36,12 +36,14 @@ __global__ __launch_bounds__(kQBlock) void mask_project_kernel(int n, const floa
                                                                const float *__restrict__ center, int cstride,
                                                                const float *__restrict__ params, int pstride, int posed,
                                                                float radius, int S, float4 *__restrict__ uvr, int *__restrict__ bins,
-                                                               float *__restrict__ zex)
+                                                               float *__restrict__ zex, const int *__restrict__ off = nullptr)
 {
     const int e = blockIdx.y;
-    v += (size_t)e * n * 3;
-    uvr += (size_t)e * n;
-    if (zex) zex += (size_t)e * n;       // blend 1: the depth exponent z / gamma of every point
+    const PoseSpan sp = pose_span(off, e, n);      // (a ragged call: the element's own count, block-uniform like n)
+    n = sp.n;
+    v += sp.base * 3;
+    uvr += sp.base;
+    if (zex) zex += sp.base;             // blend 1: the depth exponent z / gamma of every point
     int *bin_cnt = bins ? bins + (size_t)e * bins_tiles(S) : nullptr;
     int *bin_idx = bins ? bins + (size_t)gridDim.y * bins_tiles(S) + (size_t)e * bins_tiles(S) * kTileCap : nullptr;
     float R[9], s = 1.0f, c[3] = {0, 0, 0}, t[3] = {0, 0, 0};
@@ -270,7 +272,8 @@ __global__ __launch_bounds__(kSplatBlock, 8) void mask_splat_kernel(int n, const
                                                                  const float *__restrict__ col, int S,
                                                                  float *__restrict__ planes, double *__restrict__ accum,
                                                                  int *__restrict__ bins, int nb,
-                                                                 const float *__restrict__ zex, int *__restrict__ clean = nullptr)
+                                                                 const float *__restrict__ zex, int *__restrict__ clean = nullptr,
+                                                                 const int *__restrict__ off = nullptr)
 {
     static_assert(kSplatBlock == 4 * kMaskTile * kMaskTile, "four threads per pixel of the tile");
     __shared__ float part[5][4][kMaskTile * kMaskTile];
@@ -288,9 +291,11 @@ __global__ __launch_bounds__(kSplatBlock, 8) void mask_splat_kernel(int n, const
     const int tiles_x = (S + kMaskTile - 1) / kMaskTile;
     const int tx0 = (tile % tiles_x) * kMaskTile, ty0 = (tile / tiles_x) * kMaskTile;
     const int tx1 = min(S, tx0 + kMaskTile) - 1, ty1 = min(S, ty0 + kMaskTile) - 1;
-    uvr += (size_t)e * n;
-    if (col) col += (size_t)e * n * 3;
-    if (BLEND) zex += (size_t)e * n;
+    const PoseSpan sp = pose_span(off, e, n);      // (list and full-scan paths alike: both see the element's own n from here on)
+    n = sp.n;
+    uvr += sp.base;
+    if (col) col += sp.base * 3;
+    if (BLEND) zex += sp.base;
     planes += (size_t)e * 5 * P;
     if (accum) accum += (size_t)e * kAcc;
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
@@ -634,20 +639,20 @@ int render_blend()
 }
 
 void launch_mask_splat(int b, int n, const float *pts, const float *col, bool project, const float *center, int cstride, const float *params,
-                       int pstride, int posed, float radius, int S, const MaskScratch &m, double *accum, hipStream_t st)
+                       int pstride, int posed, float radius, int S, const MaskScratch &m, double *accum, hipStream_t st, const int *off)
 {
     const int blend = render_blend();
     int *bins = use_bins(S) ? m.bins : (int *)nullptr;
     float *zex = blend ? m.zex : (float *)nullptr;      // blend 1: the depth exponents, written by the projection
     if (project)
         hipLaunchKernelGGL(mask_project_kernel, dim3(lin_grid(n > 0 ? n : 1), b), dim3(kQBlock), 0, st, n, pts, center, cstride, params, pstride,
-                           posed, radius, S, m.uvr, bins, zex);
+                           posed, radius, S, m.uvr, bins, zex, off);
     if (blend)
         hipLaunchKernelGGL(mask_splat_kernel<1>, dim3(mask_tiles(S) * b), dim3(kSplatBlock), 0, st, n, (const float4 *)m.uvr, col, S, m.planes,
-                           accum, bins, b, (const float *)zex, m.clean);
+                           accum, bins, b, (const float *)zex, m.clean, off);
     else
         hipLaunchKernelGGL(mask_splat_kernel<0>, dim3(mask_tiles(S) * b), dim3(kSplatBlock), 0, st, n, (const float4 *)m.uvr, col, S, m.planes,
-                           accum, bins, b, (const float *)zex, m.clean);
+                           accum, bins, b, (const float *)zex, m.clean, off);
 }
 
 }  // namespace genpc

@@ -403,4 +403,18 @@ int build_seeded_grids(int b, int nm, const float *rest_pts, int ns, const float
 int launch_nn_seeded(int b, int nm, const float *moving_pts, int ns, const float *static_pts, const SeededGrids &g, const float *center,
                      int cstride, const float *params, int pstride, float *d1, int *i1, float *d2, int *i2, int fma, hipStream_t st, int sample = 1);
 
+// ---- ragged nearest neighbours in two halves (nn_ragged.hip) ----
+// genpc_nm_distance_ragged is "build the targets' grids, search them": a caller whose targets stay where they are over many
+// searches (the ragged alignment loop: the partial clouds) builds once and searches every step.  The grids of a table: hdr [c],
+// every pair's cell table at toff[j] + 65 j of start, its targets in cell order in sorted.  The answers are the bits of
+// genpc_nm_distance on the pair alone (the head of nn_ragged.hip), in the calling thread's arithmetic mode.
+struct NnRaggedGrids {
+    const CellGridHdr *hdr;
+    const int *start;
+    const float4 *sorted;
+};
+void nn_ragged_grids_layout(WsLayout &L, NnRaggedGrids &g, const RaggedTable &t);      // the pieces behind whatever L holds (g stays put until L is bound)
+int nn_ragged_build(const RaggedTable &t, int max_targets, const float *xyz2, const NnRaggedGrids &g, hipStream_t st);
+int nn_ragged_search(const RaggedTable &t, const float *xyz, const NnRaggedGrids &g, float *result, int *result_i, hipStream_t st);
+
 }  // namespace genpc

@@ -68,22 +68,40 @@ __global__ __launch_bounds__(kRaggedLanes) void nn_ragged_kernel(NnRaggedArgs a)
     a.out_i[at] = (int)(unsigned)best;
 }
 
-static int nn_ragged(const RaggedTable &t, int max_targets, const float *xyz, const float *xyz2, float *result, int *result_i, hipStream_t st)
+// The call in its two halves (nn.h): the grids of the targets, and the search of them.
+void nn_ragged_grids_layout(WsLayout &L, NnRaggedGrids &g, const RaggedTable &t)
+{
+    const int c = t.c;
+    L.add(g.hdr, c);
+    L.add(g.start, (size_t)ragged_start_len(t.toff[c], c));
+    L.add(g.sorted, (size_t)t.toff[c]);
+}
+
+int nn_ragged_build(const RaggedTable &t, int max_targets, const float *xyz2, const NnRaggedGrids &g, hipStream_t st)
+{
+    return launch_cell_grid_build_ragged(t, max_targets, xyz2, (CellGridHdr *)g.hdr, (int *)g.start, (float4 *)g.sorted, st);
+}
+
+int nn_ragged_search(const RaggedTable &t, const float *xyz, const NnRaggedGrids &g, float *result, int *result_i, hipStream_t st)
 {
     const int fma = arith_mode() != 0;
-    const int c = t.c;
     NnRaggedArgs a{};
     a.t = t; a.q = xyz; a.out_d = result; a.out_i = result_i;
-    WsLayout L;
-    L.add(a.hdr, c);
-    L.add(a.start, (size_t)ragged_start_len(t.toff[c], c));
-    L.add(a.sorted, (size_t)t.toff[c]);
-    if (!ws_alloc(L, kWsNnRagged, st)) return 0;
-    if (!launch_cell_grid_build_ragged(t, max_targets, xyz2, (CellGridHdr *)a.hdr, (int *)a.start, (float4 *)a.sorted, st)) return 0;
-    const unsigned grid = (unsigned)ragged_items(t.qoff[c], c);
+    a.hdr = g.hdr; a.start = g.start; a.sorted = g.sorted;
+    const unsigned grid = (unsigned)ragged_items(t.qoff[t.c], t.c);
     if (fma) hipLaunchKernelGGL((nn_ragged_kernel<1>), dim3(grid), dim3(kRaggedLanes), 0, st, a);
     else hipLaunchKernelGGL((nn_ragged_kernel<0>), dim3(grid), dim3(kRaggedLanes), 0, st, a);
     return check(hipGetLastError(), "nn_ragged_kernel launch") ? 1 : 0;
+}
+
+static int nn_ragged(const RaggedTable &t, int max_targets, const float *xyz, const float *xyz2, float *result, int *result_i, hipStream_t st)
+{
+    NnRaggedGrids g{};
+    WsLayout L;
+    nn_ragged_grids_layout(L, g, t);
+    if (!ws_alloc(L, kWsNnRagged, st)) return 0;
+    if (!nn_ragged_build(t, max_targets, xyz2, g, st)) return 0;
+    return nn_ragged_search(t, xyz, g, result, result_i, st);
 }
 
 }  // namespace genpc

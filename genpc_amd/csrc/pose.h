@@ -5,6 +5,7 @@
 #pragma once
 #include "common.h"
 #include "pose_plan.h"      // kQBlock, lin_grid
+#include "ragged_table.h"   // RaggedTable: a ragged call's tables by value (pose_ragged.hip)
 
 #include <math.h>
 
@@ -66,6 +67,21 @@ __device__ __forceinline__ void pose_publish_block(unsigned *ctr, int which)
     }
 }
 
+// Where element e's points lie in an array packed element by element -- THE one statement of it for every per-point kernel of the
+// loop.  Without a table: n points at e * n, the equal-size calls' arithmetic.  With one (a ragged call; elements + 1 ints on the
+// device, csrc/pose_ragged.hip): off[e + 1] - off[e] points at off[e].  e is uniform over the block, so the two reads are scalar
+// loads, and a count taken from here is block-uniform: it may bound a loop with barriers in it.
+struct PoseSpan {
+    size_t base;
+    int n;
+};
+__device__ __forceinline__ PoseSpan pose_span(const int *__restrict__ off, int e, int n)
+{
+    if (!off) return PoseSpan{(size_t)e * n, n};
+    const int o = off[e];
+    return PoseSpan{(size_t)o, off[e + 1] - o};
+}
+
 // accum[0..8] = dL/dR (row-major), [9] = dL/ds, [10..12] = dL/dt, [13] = sum sqrt(d1),
 // [14] = sum sqrt(d2).  Thread t < nc: term of complete point t (pts -> partial);
 // nc <= t < nc+np: term of partial point t-nc (partial -> pts), attributed to the
@@ -77,6 +93,7 @@ struct PoseGradArgs {          // pose_grad_kernel's arguments, for the launch t
     float cd_weight;
     double *accum;
     int gx;                    // blocks per batch element; 0: nothing rides along
+    const int *coff, *poff;    // a ragged call's element tables (pose_span), or null
 };
 __device__ __forceinline__ void pose_grad_body(int bx, int gdx, int e, int nc, const float *__restrict__ v,
                                                const float *__restrict__ center, int cstride,
@@ -84,12 +101,16 @@ __device__ __forceinline__ void pose_grad_body(int bx, int gdx, int e, int nc, c
                                                const float *__restrict__ partial,
                                                const float *__restrict__ d1, const int *__restrict__ i1,
                                                const float *__restrict__ d2, const int *__restrict__ i2,
-                                               float cd_weight, double *__restrict__ accum, double (*red)[kQBlock / kWave])
+                                               float cd_weight, double *__restrict__ accum, double (*red)[kQBlock / kWave],
+                                               const int *__restrict__ coff = nullptr, const int *__restrict__ poff = nullptr)
 {
-    v += (size_t)e * nc * 3;
-    partial += (size_t)e * np * 3;
-    d1 += (size_t)e * nc; i1 += (size_t)e * nc;
-    d2 += (size_t)e * np; i2 += (size_t)e * np;
+    const PoseSpan sc = pose_span(coff, e, nc), sq = pose_span(poff, e, np);
+    nc = sc.n; np = sq.n;                                    // (the weights 1 / nc, 0.5 / np below are the element's own)
+    if (coff && bx * kQBlock >= nc + np) return;             // a short element of a ragged call: the whole block leaves
+    v += sc.base * 3;
+    partial += sq.base * 3;
+    d1 += sc.base; i1 += sc.base;
+    d2 += sq.base; i2 += sq.base;
     center += (size_t)e * cstride;
     params += (size_t)e * pstride;
     accum += (size_t)e * kAcc;
@@ -114,7 +135,7 @@ __device__ __forceinline__ void pose_grad_body(int bx, int gdx, int e, int nc, c
             a[14] += (double)sqrtf(d);
             w = (double)cd_weight * 0.5 / np;
         }
-        if (d == 0.0f) continue;     // torch: 0.5/sqrt(0) * 0 = NaN; no gradient here
+        if (d == 0.0f || (j | k) < 0) continue;     // torch: 0.5/sqrt(0) * 0 = NaN; no gradient here  (index -1: the ragged search's answer to a non-finite query, its distance NaN)
         w *= 1.0 / sqrt((double)d);  // d sqrt(d)/dd * 2 (from d |p-q|^2 / dp)
         const float vx = v[(size_t)j * 3 + 0], vy = v[(size_t)j * 3 + 1], vz = v[(size_t)j * 3 + 2];
         float p[3];
@@ -295,5 +316,12 @@ __device__ __forceinline__ const float *pose_fused_params(const PoseFuse &fu, in
     __syncthreads();
     return s_par;
 }
+
+// pose_ragged.hip -- the two launches of a ragged call that are not the loop's own (host functions: every file is compiled by itself).
+// The element tables (qoff: complete clouds, toff: partial clouds; c + 1 entries each) written to coff_e / poff_e on the device;
+// the scans' clouds and colours (src / dst: complete, partial, complete colours, partial colours; null = absent) copied once
+// per start, packed by the element tables.  width: blocks per scan.
+int pose_ragged_tables(const RaggedTable &elements, int *coff_e, int *poff_e, hipStream_t st);
+int pose_ragged_replicate(const RaggedTable &scans, int starts, int width, const float *const src[4], float *const dst[4], hipStream_t st);
 
 }  // namespace genpc

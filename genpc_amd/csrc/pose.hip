@@ -23,10 +23,14 @@
 //   pose_update_kernel      (one wave) orthogonality term, 6D Gram-Schmidt backward,
 //                           Adam for the three parameter groups, loss history,
 //                           best-of-starts bookkeeping
+// S scans of DIFFERENT sizes run through the same kernels in one call (genpc_pose_optimize_ragged, at the end of this file): every
+// per-point kernel takes an optional element table (pose.h pose_span), the call's shape is pose_ragged_plan.h's -- one stream, the
+// update a launch of its own, nearest neighbours from nn_ragged.hip's grid search -- and its two own kernels are pose_ragged.hip's.
 // HBM traffic per iteration is O(N): ~24 B/point for the transform, ~28 B/point for
 // the gradient pass; the NN launch dominates (VALU-bound, see chamfer.hip).
 #include "nn.h"
 #include "mask.h"
+#include "pose_ragged_plan.h"
 #include "../../include/genpc_hip.h"
 
 #include <math.h>
@@ -41,7 +45,7 @@ extern "C" int genpc_chamfer_forward(int b, int n, const float *xyz1, int m, con
 
 namespace genpc {
 
-int genpc_mean3(int b, int n, const float *v, float *out, double *accum, hipStream_t st);
+int genpc_mean3(int b, int n, const float *v, float *out, double *accum, hipStream_t st, const int *off = nullptr);
 
 // diff_obj_pose.py:419-423
 // blockIdx.y = batch element; element e reads v + e*n*3, center + e*cstride,
@@ -49,11 +53,13 @@ int genpc_mean3(int b, int n, const float *v, float *out, double *accum, hipStre
 __global__ __launch_bounds__(kQBlock) void pose_transform_kernel(int n, const float *__restrict__ v,
                                                                  const float *__restrict__ center, int cstride,
                                                                  const float *__restrict__ params, int pstride,
-                                                                 float *__restrict__ pts)
+                                                                 float *__restrict__ pts, const int *__restrict__ off = nullptr)
 {
     const int e = blockIdx.y;
-    v += (size_t)e * n * 3;
-    pts += (size_t)e * n * 3;
+    const PoseSpan sp = pose_span(off, e, n);
+    n = sp.n;
+    v += sp.base * 3;
+    pts += sp.base * 3;
     center += (size_t)e * cstride;
     params += (size_t)e * pstride;
     float R[9];
@@ -81,19 +87,24 @@ __global__ __launch_bounds__(kQBlock) void pose_grad_kernel(int nc, const float 
                                                             const float *__restrict__ partial,
                                                             const float *__restrict__ d1, const int *__restrict__ i1,
                                                             const float *__restrict__ d2, const int *__restrict__ i2,
-                                                            float cd_weight, double *__restrict__ accum, unsigned *ctr)
+                                                            float cd_weight, double *__restrict__ accum, unsigned *ctr,
+                                                            const int *__restrict__ coff = nullptr, const int *__restrict__ poff = nullptr)
 {
     __shared__ double red[15][kQBlock / kWave];
-    pose_grad_body(blockIdx.x, gridDim.x, blockIdx.y, nc, v, center, cstride, params, pstride, np, partial, d1, i1, d2, i2, cd_weight, accum, red);
+    pose_grad_body(blockIdx.x, gridDim.x, blockIdx.y, nc, v, center, cstride, params, pstride, np, partial, d1, i1, d2, i2, cd_weight, accum, red,
+                   coff, poff);
     if (ctr) pose_publish_block(ctr, 1);
 }
 
 __global__ void pose_update_kernel(int b, PoseState *__restrict__ S, double *__restrict__ accum, int nc, int np,
                                    float cd_weight, float reg_weight, float lr, int do_step,
-                                   float *__restrict__ history_slot, int history_stride)
+                                   float *__restrict__ history_slot, int history_stride,
+                                   const int *__restrict__ coff = nullptr, const int *__restrict__ poff = nullptr)
 {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= b) return;
+    nc = pose_span(coff, e, nc).n;
+    np = pose_span(poff, e, np).n;
     pose_update_one(S + e, accum + (size_t)e * kAcc, nc, np, cd_weight, reg_weight, lr, do_step,
                     history_slot ? history_slot + (size_t)e * history_stride : (float *)nullptr, true);
 }
@@ -198,14 +209,17 @@ __global__ __launch_bounds__(kQBlock) void pose_transform_project_kernel(int n, 
                                                                          const float *__restrict__ params, int pstride,
                                                                          float *__restrict__ pts, float radius, int S,
                                                                          float4 *__restrict__ uvr, int *__restrict__ bins,
-                                                                         float *__restrict__ zex, PoseFuse fu)
+                                                                         float *__restrict__ zex, PoseFuse fu,
+                                                                         const int *__restrict__ off = nullptr)
 {
     __shared__ float s_par[10];
     const int e = blockIdx.y;
-    v += (size_t)e * n * 3;
-    pts += (size_t)e * n * 3;
-    uvr += (size_t)e * n;
-    if (zex) zex += (size_t)e * n;
+    const PoseSpan sp = pose_span(off, e, n);
+    n = sp.n;
+    v += sp.base * 3;
+    pts += sp.base * 3;
+    uvr += sp.base;
+    if (zex) zex += sp.base;
     int *bin_cnt = bins ? bins + (size_t)e * bins_tiles(S) : nullptr;
     int *bin_idx = bins ? bins + (size_t)gridDim.y * bins_tiles(S) + (size_t)e * bins_tiles(S) * kTileCap : nullptr;
     center += (size_t)e * cstride;
@@ -833,15 +847,289 @@ GENPC_API int genpc_nn_seeded_step(int b, int nm, const float *rest, const float
     return check(hipGetLastError(), "nn_seeded_step launch") ? 1 : 0;
 }
 
+// ---- the ragged loop: S scans of different sizes in one call (pose_ragged_plan.h; the kernels are the ones above, given a table) ----
+namespace genpc {
+
+// What a ragged pose call is refused for before it is planned (ragged_offsets.h's check; no empty cloud: a scan without points on
+// either side has no objective).  1: go on; 0: no scan, nothing to do; -1: refused, the error recorded under fn's name.
+static int pose_ragged_admit(const char *fn, int c, const int *coff, const int *poff, int starts, int iters, bool mask, int render_size,
+                             float radius)
+{
+    if (c < 0) return ragged_refuse(fn, "negative number of scans");
+    if (c == 0) return 0;
+    if (!coff || !poff) return ragged_refuse(fn, "null offset table");
+    if (starts < 1 || iters < 0) return ragged_refuse(fn, "starts must be at least 1 and iters at least 0");
+    if (mask && (render_size <= 1 || !(radius > 0.0f))) return ragged_refuse(fn, "the full objective needs render_size > 1 and a positive radius");
+    if (const char *err = ragged_offsets_fault(c, {coff, poff})) return ragged_refuse(fn, err);
+    for (int j = 0; j < c; j++) {
+        const bool no_c = coff[j + 1] == coff[j], no_p = poff[j + 1] == poff[j];
+        if (no_c || no_p) {
+            char msg[96];
+            snprintf(msg, sizeof msg, "scan %d has an empty %s cloud", j, no_c ? "complete" : "partial");
+            return ragged_refuse(fn, msg);
+        }
+    }
+    return 1;
+}
+
+// The tables of a planned call, by value: the scans' (replication), and the elements' in the two directions of the search --
+// posed -> partial (queries by coff_e, targets by poff_e) and partial -> posed.
+struct PoseRaggedTables {
+    RaggedTable scans, fwd, bwd;
+};
+static void pose_ragged_fill(int c, const int *coff, const int *poff, int starts, PoseRaggedTables &T)
+{
+    int ce[kRaggedMaxPairs + 1], pe[kRaggedMaxPairs + 1];
+    const int elements = c * starts;
+    pose_ragged_element_offsets(c, coff, starts, ce);
+    pose_ragged_element_offsets(c, poff, starts, pe);
+    T.scans.c = c;
+    ragged_pad_copy(T.scans.qoff, coff, c);
+    ragged_pad_copy(T.scans.toff, poff, c);
+    T.fwd.c = T.bwd.c = elements;
+    ragged_pad_copy(T.fwd.qoff, ce, elements);
+    ragged_pad_copy(T.fwd.toff, pe, elements);
+    ragged_pad_copy(T.bwd.qoff, pe, elements);
+    ragged_pad_copy(T.bwd.toff, ce, elements);
+}
+
+// The pieces both entry points lay out alike, behind their accumulators and states
+struct PoseRaggedScratch {
+    int *coff_e, *poff_e;          // the element tables on the device
+    float *pts, *d1, *d2;
+    int *i1, *i2;
+    void layout(WsLayout &L, int elements, size_t total_c, size_t total_p)
+    {
+        L.add(coff_e, (size_t)elements + 1);
+        L.add(poff_e, (size_t)elements + 1);
+        L.add(pts, total_c * 3);
+        L.add(d1, total_c);
+        L.add(d2, total_p);
+        L.add(i1, total_c);
+        L.add(i2, total_p);
+    }
+};
+
+// One step's launches between the transform and the update, the same in the loop and in the single step: nearest neighbours in both
+// directions from the grid search (the partial clouds' grids are built by the caller, once; the posed clouds' here, every step),
+// the Chamfer gradient (riding or alone), the silhouette step.
+static int pose_ragged_step(const PoseRaggedPlan &plan, const PoseRaggedTables &T, const PoseRaggedScratch &x, const NnRaggedGrids &grid_partial,
+                            const NnRaggedGrids &grid_posed, const float *complete, const float *complete_col, const float *partial,
+                            const float *center, int cstride, const float *params, int pstride, float cd_weight, float mask_weight, float radius,
+                            int render_size, const MaskScratch &m, double *accum, hipStream_t st)
+{
+    const int b = plan.elements;
+    if (nn_ragged_search(T.fwd, x.pts, grid_partial, x.d1, x.i1, st) != 1) return 0;
+    if (nn_ragged_build(T.bwd, plan.nc_max, x.pts, grid_posed, st) != 1) return 0;
+    if (nn_ragged_search(T.bwd, partial, grid_posed, x.d2, x.i2, st) != 1) return 0;
+    PoseGradArgs pga{};
+    if (plan.ride) {
+        pga.nc = plan.nc_max; pga.cstride = cstride; pga.pstride = pstride; pga.np = plan.np_max;
+        pga.v = complete; pga.center = center; pga.params = params; pga.partial = partial;
+        pga.d1 = x.d1; pga.d2 = x.d2; pga.i1 = x.i1; pga.i2 = x.i2;
+        pga.cd_weight = cd_weight; pga.accum = accum; pga.gx = plan.g_g;
+        pga.coff = x.coff_e; pga.poff = x.poff_e;
+    } else {
+        hipLaunchKernelGGL(pose_grad_kernel, dim3(plan.g_g, b), dim3(kQBlock), 0, st, plan.nc_max, complete, center, cstride, params, pstride,
+                           plan.np_max, partial, (const float *)x.d1, (const int *)x.i1, (const float *)x.d2, (const int *)x.i2, cd_weight, accum,
+                           (unsigned *)nullptr, (const int *)x.coff_e, (const int *)x.poff_e);
+    }
+    if (mask_weight != 0.0f && !mask_step(b, plan.nc_max, complete, complete_col, center, cstride, params, pstride, radius, render_size, mask_weight, m,
+                                          accum, st, true, plan.ride ? &pga : nullptr, x.coff_e, &plan.step))
+        return 0;
+    return 1;
+}
+
+// the transform of a step (with the projection, for the full objective)
+static void pose_ragged_transform(const PoseRaggedPlan &plan, const PoseRaggedScratch &x, const float *complete, const float *center, int cstride,
+                                  const float *params, int pstride, bool mask, float radius, int render_size, const MaskScratch &m, hipStream_t st)
+{
+    if (mask) {
+        PoseFuse fu{};
+        hipLaunchKernelGGL(pose_transform_project_kernel, dim3(plan.g_t, plan.elements), dim3(kQBlock), 0, st, plan.nc_max, complete, center, cstride,
+                           params, pstride, x.pts, 1.1f * radius, render_size, m.uvr, use_bins(render_size) ? m.bins : (int *)nullptr,
+                           render_blend() ? m.zex : (float *)nullptr, fu, (const int *)x.coff_e);
+    } else
+        hipLaunchKernelGGL(pose_transform_kernel, dim3(plan.g_t, plan.elements), dim3(kQBlock), 0, st, plan.nc_max, complete, center, cstride, params,
+                           pstride, x.pts, (const int *)x.coff_e);
+}
+
+// both directions' grids, each in the slot of its direction
+static bool pose_ragged_grids(const PoseRaggedTables &T, NnRaggedGrids &grid_partial, NnRaggedGrids &grid_posed, hipStream_t st)
+{
+    WsLayout LP, LC;
+    nn_ragged_grids_layout(LP, grid_partial, T.fwd);
+    nn_ragged_grids_layout(LC, grid_posed, T.bwd);
+    return ws_alloc(LP, kWsPoseRaggedGridPartial, st) && ws_alloc(LC, kWsPoseRaggedGridPosed, st);
+}
+
+}  // namespace genpc
+
+GENPC_API int genpc_pose_ragged_plan(int c, const int *coff, const int *poff, int starts, int mask, int render_size, float radius, int cus,
+                                     int out[16])
+{
+    using namespace genpc;
+    const char *fn = "genpc_pose_ragged_plan";
+    if (!out) return ragged_refuse(fn, "null output");
+    for (int k = 0; k < 16; k++) out[k] = 0;
+    const int rc = pose_ragged_admit(fn, c, coff, poff, starts, 0, mask != 0, render_size, radius);
+    if (rc <= 0) return rc < 0 ? -1 : 1;
+    PoseRaggedAsk ask;
+    ask.c = c; ask.coff = coff; ask.poff = poff; ask.starts = starts; ask.mask = mask != 0; ask.render_size = render_size; ask.radius = radius;
+    ask.cus = cus;
+    const PoseRaggedPlan plan = pose_ragged_plan(ask);
+    const long long cap = 0x7fffffffll;
+    out[0] = plan.elements; out[1] = plan.nc_max; out[2] = plan.np_max; out[3] = plan.g_t; out[4] = plan.g_g; out[5] = plan.gb;
+    out[6] = plan.g_m; out[7] = plan.ride; out[8] = plan.step.fuse_w; out[9] = plan.step.sub8; out[10] = plan.step.gp; out[11] = plan.step.gs;
+    out[12] = plan.too_large ? 1 : 0;
+    out[13] = (int)std::min(plan.total_c, cap); out[14] = (int)std::min(plan.total_p, cap);
+    out[15] = plan.blocks_per_cu;
+    return 1;
+}
+
+GENPC_API int genpc_pose_loss_grad_ragged(int c, const int *coff, const int *poff, const float *v, const float *vert_col, const float *center,
+                                          const float *params, const float *partial, const float *partial_col, float cd_weight, float reg_weight,
+                                          float mask_weight, float radius, int render_size, float *loss_out, float *grad, void *stream)
+{
+    using namespace genpc;
+    const char *fn = "genpc_pose_loss_grad_ragged";
+    const bool mask = mask_weight != 0.0f;
+    const int rc = pose_ragged_admit(fn, c, coff, poff, 1, 0, mask, render_size, radius);
+    if (rc <= 0) return rc < 0 ? -1 : 1;
+    hipStream_t st = (hipStream_t)stream;
+    PoseRaggedAsk ask;
+    ask.c = c; ask.coff = coff; ask.poff = poff; ask.starts = 1; ask.mask = mask; ask.render_size = render_size; ask.radius = radius;
+    ask.cus = num_cus();
+    const PoseRaggedPlan plan = pose_ragged_plan(ask);
+    if (plan.too_large) return ragged_refuse(fn, plan.too_large);
+    if (!v || !center || !params || !partial || !loss_out || !grad) return ragged_refuse(fn, "null pointer");
+    PoseRaggedTables T;
+    pose_ragged_fill(c, coff, poff, 1, T);
+    const int b = plan.elements;
+
+    const size_t P = mask ? (size_t)render_size * render_size : 0;
+    double *accum; PoseState *S;
+    PoseRaggedScratch x{};
+    MaskScratch m = {};
+    WsLayout L;
+    L.add(accum, (size_t)b * kAcc);
+    L.add(S, (size_t)b);
+    x.layout(L, b, (size_t)plan.total_c, (size_t)plan.total_p);
+    if (mask) m.layout(L, b, P, (size_t)plan.nmax_piece);
+    if (!ws_alloc(L, kWsPoseRaggedStep, st)) return 0;
+    NnRaggedGrids grid_partial{}, grid_posed{};
+    if (!pose_ragged_grids(T, grid_partial, grid_posed, st)) return 0;
+    if (mask && !m.zero_bins(st)) return 0;
+    constexpr int kStateFloats = (int)(sizeof(PoseState) / sizeof(float));
+    if (!check(hipMemsetAsync(accum, 0, (size_t)b * kAcc * sizeof(double), st), "hipMemsetAsync(accum)")) return 0;
+    if (!check(hipMemcpy2DAsync(S->params, sizeof(PoseState), params, 10 * sizeof(float), 10 * sizeof(float), (size_t)b, hipMemcpyDeviceToDevice, st),
+               "copy params"))
+        return 0;
+    if (!pose_ragged_tables(T.fwd, x.coff_e, x.poff_e, st)) return 0;
+    // the order of genpc_pose_loss_grad_batch: reference images first (they project through the scratch the transform then fills)
+    if (mask && !mask_prepare_ref(b, plan.np_max, partial, partial_col, radius, render_size, m, st, x.poff_e)) return 0;
+    if (nn_ragged_build(T.fwd, plan.np_max, partial, grid_partial, st) != 1) return 0;
+    pose_ragged_transform(plan, x, v, center, 3, S->params, kStateFloats, mask, radius, render_size, m, st);
+    if (!pose_ragged_step(plan, T, x, grid_partial, grid_posed, v, vert_col, partial, center, 3, S->params, kStateFloats, cd_weight, mask_weight, radius,
+                          render_size, m, accum, st))
+        return 0;
+    hipLaunchKernelGGL(pose_update_kernel, dim3(plan.gb), dim3(64), 0, st, b, S, accum, plan.nc_max, plan.np_max, cd_weight, reg_weight, 0.0f, 0,
+                       (float *)nullptr, 0, (const int *)x.coff_e, (const int *)x.poff_e);
+    if (!check(hipMemcpy2DAsync(grad, 10 * sizeof(float), S->grad, sizeof(PoseState), 10 * sizeof(float), (size_t)b, hipMemcpyDeviceToDevice, st),
+               "copy grad"))
+        return 0;
+    if (!check(hipMemcpy2DAsync(loss_out, 4 * sizeof(float), S->loss, sizeof(PoseState), 4 * sizeof(float), (size_t)b, hipMemcpyDeviceToDevice, st),
+               "copy loss"))
+        return 0;
+    return check(hipGetLastError(), "pose_loss_grad_ragged launch") ? 1 : 0;
+}
+
+GENPC_API int genpc_pose_optimize_ragged(int c, const int *coff, const int *poff, const float *complete, const float *complete_col,
+                                         const float *partial, const float *partial_col, float lr, int iters, int starts, float radius,
+                                         int render_size, float mask_weight, float *transform, float *history, float *best_params, void *stream)
+{
+    using namespace genpc;
+    const char *fn = "genpc_pose_optimize_ragged";
+    const bool mask = mask_weight != 0.0f;
+    const int rc = pose_ragged_admit(fn, c, coff, poff, starts, iters, mask, render_size, radius);
+    if (rc <= 0) return rc < 0 ? -1 : 1;
+    hipStream_t st = (hipStream_t)stream;
+    PoseRaggedAsk ask;
+    ask.c = c; ask.coff = coff; ask.poff = poff; ask.starts = starts; ask.mask = mask; ask.render_size = render_size; ask.radius = radius;
+    ask.cus = num_cus();
+    const PoseRaggedPlan plan = pose_ragged_plan(ask);
+    if (plan.too_large) return ragged_refuse(fn, plan.too_large);
+    if (!complete || !partial || !transform) return ragged_refuse(fn, "null pointer");
+    PoseRaggedTables T;
+    pose_ragged_fill(c, coff, poff, starts, T);
+    const int b = plan.elements;
+
+    // every cloud once per start, packed by the element tables (as pose_replicate does for equal sizes); the pointers move there
+    if (plan.replicate) {
+        float *xs[4];
+        const size_t xc = (size_t)plan.total_c * 3, xp = (size_t)plan.total_p * 3;
+        WsLayout X;          // (the colours' pieces are reserved whether or not the call brings colours)
+        X.add(xs[0], xc);
+        X.add(xs[1], xp);
+        X.add(xs[2], xc);
+        X.add(xs[3], xp);
+        if (!ws_alloc(X, kWsPoseRaggedReplicas, st)) return 0;
+        const float *src[4] = {complete, partial, complete_col, partial_col};
+        if (!pose_ragged_replicate(T.scans, starts, plan.g_rep, src, xs, st)) return 0;
+        complete = xs[0]; partial = xs[1];
+        complete_col = complete_col ? xs[2] : nullptr; partial_col = partial_col ? xs[3] : nullptr;
+    }
+
+    const size_t P = mask ? (size_t)render_size * render_size : 0;
+    double *accum; PoseState *S; float *center;
+    PoseRaggedScratch x{};
+    MaskScratch m = {};
+    WsLayout L;
+    L.add(accum, (size_t)b * kAcc);
+    L.add(S, (size_t)b);
+    L.add(center, (size_t)b * 4);
+    x.layout(L, b, (size_t)plan.total_c, (size_t)plan.total_p);
+    if (mask) m.layout(L, b, P, (size_t)plan.nmax_piece);
+    if (!ws_alloc(L, kWsPoseRaggedLoop, st)) return 0;
+    NnRaggedGrids grid_partial{}, grid_posed{};
+    if (!pose_ragged_grids(T, grid_partial, grid_posed, st)) return 0;
+    if (mask && !m.zero_bins(st)) return 0;
+    constexpr int kStateFloats = (int)(sizeof(PoseState) / sizeof(float));
+    if (!pose_ragged_tables(T.fwd, x.coff_e, x.poff_e, st)) return 0;
+
+    // center = mean(vert_pos) per element (diff_obj_pose.py:362); the reference images; the partial clouds' grids: once per call
+    if (!genpc_mean3(b, plan.nc_max, complete, center, accum, st, x.coff_e)) return 0;
+    if (mask && !mask_prepare_ref(b, plan.np_max, partial, partial_col, radius, render_size, m, st, x.poff_e)) return 0;
+    if (nn_ragged_build(T.fwd, plan.np_max, partial, grid_partial, st) != 1) return 0;
+
+    hipLaunchKernelGGL(pose_begin_kernel, dim3(plan.gb), dim3(64), 0, st, b, S, accum, -1, 0);
+    hipLaunchKernelGGL(pose_begin_kernel, dim3(plan.gb), dim3(64), 0, st, b, S, accum, 0, starts);
+    const int hstride = iters + 1;          // history [c, starts, iters + 1]: element e's row is e
+    for (int it = 0; it <= iters; it++) {
+        pose_ragged_transform(plan, x, complete, center, 4, S->params, kStateFloats, mask, radius, render_size, m, st);
+        if (!pose_ragged_step(plan, T, x, grid_partial, grid_posed, complete, complete_col, partial, center, 4, S->params, kStateFloats, 3.0f,
+                              mask_weight, radius, render_size, m, accum, st))
+            return 0;
+        hipLaunchKernelGGL(pose_update_kernel, dim3(plan.gb), dim3(64), 0, st, b, S, accum, plan.nc_max, plan.np_max, 3.0f, 0.001f, lr, 1,
+                           history ? history + it : (float *)nullptr, hstride, (const int *)x.coff_e, (const int *)x.poff_e);
+    }
+    // the start picked per scan: pose_pick_kernel's rule, the equal-size loop's
+    hipLaunchKernelGGL(pose_pick_kernel, dim3(ceil_div(c, 64)), dim3(64), 0, st, c, starts, (const PoseState *)S, transform, best_params);
+    return check(hipGetLastError(), "pose_optimize_ragged launch") ? 1 : 0;
+}
+
 namespace genpc {
 
 // accum[e*kAcc + 0..2] += sum of v[e, :, 0..2]
 __global__ __launch_bounds__(kQBlock) void mean3_accum_kernel(int n, const float *__restrict__ v,
-                                                              double *__restrict__ accum)
+                                                              double *__restrict__ accum, const int *__restrict__ off = nullptr)
 {
     __shared__ double red[3][kQBlock / kWave];
     const int e = blockIdx.y;
-    v += (size_t)e * n * 3;
+    const PoseSpan sp = pose_span(off, e, n);
+    n = sp.n;
+    if (off && (int)blockIdx.x * kQBlock >= n) return;       // a short element of a ragged call: the whole block leaves
+    v += sp.base * 3;
     accum += (size_t)e * kAcc;
     double a[3] = {0.0, 0.0, 0.0};
     for (int j = blockIdx.x * kQBlock + threadIdx.x; j < n; j += gridDim.x * kQBlock) {
@@ -863,20 +1151,23 @@ __global__ __launch_bounds__(kQBlock) void mean3_accum_kernel(int n, const float
     }
 }
 
-__global__ void mean3_finish_kernel(int b, int n, double *__restrict__ accum, float *__restrict__ out)
+__global__ void mean3_finish_kernel(int b, int n, double *__restrict__ accum, float *__restrict__ out,
+                                    const int *__restrict__ off = nullptr)
 {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= b * 3) return;
     const int e = t / 3, k = t % 3;
+    n = pose_span(off, e, n).n;
     out[e * 4 + k] = (float)(accum[(size_t)e * kAcc + k] / n);
     accum[(size_t)e * kAcc + k] = 0.0;
 }
 
-int genpc_mean3(int b, int n, const float *v, float *out, double *accum, hipStream_t st)
+// (off: a ragged call's element table on the device, n then the largest element's count -- the launch's width)
+int genpc_mean3(int b, int n, const float *v, float *out, double *accum, hipStream_t st, const int *off)
 {
     if (!check(hipMemsetAsync(accum, 0, (size_t)b * kAcc * sizeof(double), st), "hipMemsetAsync(mean)")) return 0;
-    hipLaunchKernelGGL(mean3_accum_kernel, dim3(lin_grid(n), b), dim3(kQBlock), 0, st, n, v, accum);
-    hipLaunchKernelGGL(mean3_finish_kernel, dim3(ceil_div(b * 3, 64)), dim3(64), 0, st, b, n, accum, out);
+    hipLaunchKernelGGL(mean3_accum_kernel, dim3(lin_grid(n), b), dim3(kQBlock), 0, st, n, v, accum, off);
+    hipLaunchKernelGGL(mean3_finish_kernel, dim3(ceil_div(b * 3, 64)), dim3(64), 0, st, b, n, accum, out, off);
     return check(hipGetLastError(), "mean3 launch") ? 1 : 0;
 }
 

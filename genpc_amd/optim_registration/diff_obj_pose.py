@@ -205,6 +205,141 @@ def pose_loss_grad_batch(vert_pos, center, params, partial, radius, render_size=
     return loss, grad
 
 
+RAGGED_MAX_ELEMENTS = 384          # genpc_hip.h GENPC_POSE_RAGGED_MAX_ELEMENTS: scans x starts of one library call
+
+
+def pose_scan_chunks(scans, starts, limit=RAGGED_MAX_ELEMENTS):
+    """The library calls a list of `scans` scans at `starts` starts each is cut into: [(first, end)] scan ranges of at most
+    limit // starts scans (97 scans at 4 starts: (0, 96) and (96, 97))."""
+    if starts < 1:
+        raise ValueError("pose_scan_chunks: starts must be at least 1, got %d" % starts)
+    per = limit // starts
+    if per < 1:
+        raise ValueError("pose_scan_chunks: %d starts do not fit the %d elements of a call" % (starts, limit))
+    return [(a, min(a + per, scans)) for a in range(0, scans, per)]
+
+
+def _ragged_clouds(clouds, fn, name, what):
+    """A list of [N_j,3] GPU tensors or packed (points, offsets) -> (points [T,3], offsets); a CPU tensor and an empty cloud raise,
+    naming the scan."""
+    from .. import _ragged
+    if not _ragged.is_packed(clouds) and isinstance(clouds, (list, tuple)):
+        for j, t in enumerate(clouds):
+            if torch.is_tensor(t) and not t.is_cuda:
+                raise RuntimeError("%s: GPU tensors only (%s[%d], scan %d, is a %s tensor); the HIP path has no CPU fallback" % (fn, name, j, j, t.device))
+    points, off = _ragged.ragged_side(clouds, fn, name)
+    if len(off) > 1 and not points.is_cuda:
+        raise RuntimeError("%s: GPU tensors only (%s is a %s tensor); the HIP path has no CPU fallback" % (fn, name, points.device))
+    for j in range(len(off) - 1):
+        if off[j + 1] == off[j]:
+            raise ValueError("%s: scan %d has an empty %s cloud" % (fn, j, what))
+    return points, off
+
+
+def _ragged_colours(cols, points, off, fn, name):
+    """None, or a list with one entry per scan ([N_j,3] in [0,1], or None = white) -> packed [T,3] float32 or None."""
+    if cols is None:
+        return None
+    s = len(off) - 1
+    if not isinstance(cols, (list, tuple)) or len(cols) != s:
+        raise ValueError("%s: %s must be None or a list with one entry per scan (%d), got %s"
+                         % (fn, name, s, len(cols) if isinstance(cols, (list, tuple)) else type(cols).__name__))
+    if all(c is None for c in cols):
+        return None
+    out = torch.ones_like(points)
+    for j, c in enumerate(cols):
+        if c is None:
+            continue
+        n = off[j + 1] - off[j]
+        c = torch.as_tensor(c)
+        if tuple(c.shape) != (n, 3):
+            raise ValueError("%s: %s[%d] must have the shape of scan %d's cloud (%d, 3), got %s" % (fn, name, j, j, n, tuple(c.shape)))
+        out[off[j]:off[j + 1]] = c.to(device=points.device, dtype=torch.float32)
+    return out
+
+
+def pose_loss_grad_ragged(vert_pos, center, params, partial, radius, render_size=224, cd_weight=3.0, reg_weight=0.001,
+                          mask_weight=1.0, vert_col=None, partial_col=None):
+    """pose_loss_grad_batch for c elements of DIFFERENT sizes in one call (genpc_pose_loss_grad_ragged): vert_pos / partial are
+    lists of [N_j,3] GPU tensors or packed (points, offsets), center [c,3], params [c,10], vert_col / partial_col None or lists
+    with one entry per element -> (loss[c,4], grad[c,10]).  The launches are one step of object_pose_optimization_scans' loop;
+    no Adam step is taken.  mask_weight = 0: the Chamfer-only objective.  More than 384 elements go in several calls."""
+    from .. import _ragged
+    fn = "pose_loss_grad_ragged"
+    cpts, coff = _ragged_clouds(vert_pos, fn, "vert_pos", "complete")
+    ppts, poff = _ragged_clouds(partial, fn, "partial", "partial")
+    c = len(coff) - 1
+    if len(poff) - 1 != c:
+        raise ValueError("%s: %d complete clouds against %d partial clouds" % (fn, c, len(poff) - 1))
+    center = center.contiguous().float()
+    params = params.contiguous().float()
+    _lib.check_tensors((("center", center), ("params", params)))
+    if tuple(center.shape) != (c, 3) or tuple(params.shape) != (c, 10):
+        raise ValueError("%s: center must be [%d,3] and params [%d,10], got %s and %s" % (fn, c, c, tuple(center.shape), tuple(params.shape)))
+    vc, pc = _ragged_colours(vert_col, cpts, coff, fn, "vert_col"), _ragged_colours(partial_col, ppts, poff, fn, "partial_col")
+    loss = torch.empty(c, 4, device=center.device)
+    grad = torch.empty(c, 10, device=center.device)
+    for a, b, co, po in _ragged.chunks(RAGGED_MAX_ELEMENTS, coff, poff):
+        _, cp = _ragged.host_ints(co, "coff")
+        _, pp = _ragged.host_ints(po, "poff")
+        rc = _lib.on_device_of(cpts, _L.genpc_pose_loss_grad_ragged, b - a, cp, pp, _p(cpts[coff[a]:coff[b]]),
+                               _p(None if vc is None else vc[coff[a]:coff[b]]), _p(center[a:b]), _p(params[a:b]), _p(ppts[poff[a]:poff[b]]),
+                               _p(None if pc is None else pc[poff[a]:poff[b]]), float(cd_weight), float(reg_weight), float(mask_weight),
+                               float(radius), int(render_size), _p(loss[a:b]), _p(grad[a:b]))
+        if rc != 1:
+            raise RuntimeError("genpc_pose_loss_grad_ragged failed (rc=%d): %s" % (rc, _lib.last_error()))
+    return loss, grad
+
+
+def object_pose_optimization_scans(completes, partials, radius=0.005, lr=0.005, iters=300, render_size=224, cam_bias_num=4,
+                                   return_history=False, cd_only=False, complete_cols=None, partial_cols=None):
+    """object_pose_optimization's tensor form for S scans of DIFFERENT sizes in one call (genpc_pose_optimize_ragged): completes /
+    partials are lists of [N_j,3] GPU tensors or packed (points, offsets), complete_cols / partial_cols None or lists with one
+    entry per scan (an entry may be None = white).  Returns a list of S 4x4 numpy ``[[sR, t],[0,1]]``; with return_history
+    also a list of [cam_bias_num, iters + 1] loss histories and a list of [10] parameters.  Scan j's results are those of
+    object_pose_optimization on scan j alone up to the summation order of its gradient (tests/test_gpu_pose_ragged_loop.py).
+    The starts run side by side as batch elements; a library call holds 384 of them (96 scans at 4 starts), a longer list goes
+    in several calls (pose_scan_chunks); ONE read-back at the end.  A CPU tensor, lists of different lengths, a colour list of
+    the wrong length or shape and an empty cloud raise, naming the scan."""
+    from .. import _ragged
+    fn = "object_pose_optimization_scans"
+    cpts, coff = _ragged_clouds(completes, fn, "completes", "complete")
+    ppts, poff = _ragged_clouds(partials, fn, "partials", "partial")
+    s = len(coff) - 1
+    if len(poff) - 1 != s:
+        raise ValueError("%s: %d complete clouds against %d partial clouds" % (fn, s, len(poff) - 1))
+    cc, pc = _ragged_colours(complete_cols, cpts, coff, fn, "complete_cols"), _ragged_colours(partial_cols, ppts, poff, fn, "partial_cols")
+    starts, iters = int(cam_bias_num), int(iters)
+    ranges = pose_scan_chunks(s, starts)
+    if s == 0:
+        return ([], [], []) if return_history else []
+    if cpts.device != ppts.device:
+        raise ValueError("%s: completes are on %s, partials on %s" % (fn, cpts.device, ppts.device))
+    _lib.check_tensors((("completes", cpts), ("partials", ppts)))
+    hlen = starts * (iters + 1)
+    out = torch.empty(s, 16 + hlen + 10, device=cpts.device)          # one block: one read-back
+    T, hist, bp = out[:, :16], out[:, 16:16 + hlen], out[:, 16 + hlen:]
+    for a, b in ranges:
+        tt = torch.empty(b - a, 16, device=cpts.device)
+        hh = torch.empty(b - a, hlen, device=cpts.device)
+        pp = torch.empty(b - a, 10, device=cpts.device)
+        _, cp = _ragged.host_ints([v - coff[a] for v in coff[a:b + 1]], "coff")
+        _, pq = _ragged.host_ints([v - poff[a] for v in poff[a:b + 1]], "poff")
+        rc = _lib.on_device_of(cpts, _L.genpc_pose_optimize_ragged, b - a, cp, pq, _p(cpts[coff[a]:coff[b]]),
+                               _p(None if cc is None else cc[coff[a]:coff[b]]), _p(ppts[poff[a]:poff[b]]),
+                               _p(None if pc is None else pc[poff[a]:poff[b]]), float(lr), iters, starts, float(radius), int(render_size),
+                               0.0 if cd_only else 1.0, _p(tt), _p(hh), _p(pp))
+        if rc != 1:
+            raise RuntimeError("genpc_pose_optimize_ragged failed (rc=%d): %s" % (rc, _lib.last_error()))
+        T[a:b], hist[a:b], bp[a:b] = tt, hh, pp
+    host = out.cpu().numpy()
+    transforms = [host[j, :16].reshape(4, 4).copy() for j in range(s)]
+    if not return_history:
+        return transforms
+    return (transforms, [host[j, 16:16 + hlen].reshape(starts, iters + 1).copy() for j in range(s)],
+            [host[j, 16 + hlen:].copy() for j in range(s)])
+
+
 def load_point_cloud(point_path, device, radius=0.05, num_points=5000):
     """diff_obj_pose.py:136-164: a .ply through load_xyz, a .glb through glb2point, both voxel
     down-sampled at `radius` WITH their colours -> (vert_pos [N,3], vert_col [N,3] in [0,1]) on

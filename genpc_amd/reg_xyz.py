@@ -845,13 +845,16 @@ def _voxel_grids(clouds, voxel_size, cols=None):
 
 def reg_tensors_scans(partials, completes, generative_model="trellis", dataset="redwood", cd_inv_weight=0.5, diff_init=True,
                       reg_fine_xyz=False, pose_voxel=0.02, cd_only_pose=False, partial_cols=None, complete_cols=None,
-                      diff_transforms=None):
+                      diff_transforms=None, ragged_pose=False):
     """``reg_tensors`` for S scans at once: partials / completes are lists of [N_j,3] / [M_j,3] GPU tensors, partial_cols /
     complete_cols / diff_transforms None or lists with one entry per scan (an entry may be None); the other arguments are
     ``reg_tensors``' and hold for every scan.  Returns a list of ``reg_tensors``' dicts, same keys.  The stages:
       pose         the grids at `pose_voxel` of all clouds that need one through ``voxel_down_sample_clouds`` (with colours where
-                   given); ``object_pose_optimization`` then runs PER SCAN, unchanged -- its alignment loop is the one stage of
-                   stage 2 without a ragged form.  Entries of diff_transforms that are given are used as they are.
+                   given); ``object_pose_optimization`` then runs PER SCAN, unchanged (the default), or -- ``ragged_pose=True`` --
+                   the scans that need a pose go through ONE ``object_pose_optimization_scans`` call on the same grids (the
+                   ragged alignment loop: the same objective per scan, its gradient summed in another order, so the 200
+                   steps agree with the per-scan path in their first steps and in what they converge to, not bit for bit).
+                   Entries of diff_transforms that are given are used as they are.
       glue         ``_apply``, ``normalize_numpy`` and the instantmesh rotation are ``reg_tensors``' own statements per scan, so
                    every ragged stage receives the bits ``reg_tensors`` feeds its single-scan stage.
       instantmesh  ``remove_noise_from_point_clouds`` over all sources (its documented caveat: a point whose k-NN mean lies within
@@ -862,7 +865,7 @@ def reg_tensors_scans(partials, completes, generative_model="trellis", dataset="
     Scan j's entry is what ``reg_tensors`` returns on that scan alone, up to the caveats of the ragged stages it goes through
     (coarse_loss: ``coarse_scale_sweeps``' score, a relative few ulp; the ICP bit for bit where the down-sampled target gets
     the one-workgroup plan)."""
-    from .optim_registration.diff_obj_pose import object_pose_optimization
+    from .optim_registration.diff_obj_pose import object_pose_optimization, object_pose_optimization_scans
     fn = "reg_tensors_scans"
     if not isinstance(partials, (list, tuple)) or not isinstance(completes, (list, tuple)):
         raise TypeError("%s: partials and completes are lists of [N,3] tensors" % fn)
@@ -891,7 +894,13 @@ def reg_tensors_scans(partials, completes, generative_model="trellis", dataset="
         if need:
             down, dcol = _voxel_grids([targets[j] for j in need] + [sources[j] for j in need], pose_voxel,
                                       [tcols[j] for j in need] + [scols[j] for j in need])
-            for i, j in enumerate(need):
+            if ragged_pose:
+                n = len(need)
+                Ts = object_pose_optimization_scans(down[:n], down[n:], radius=0.02, lr=0.01, iters=200, render_size=224, cd_only=cd_only_pose,
+                                                    complete_cols=dcol[:n], partial_cols=dcol[n:])
+                for i, j in enumerate(need):
+                    diffs[j] = np.linalg.inv(Ts[i].astype(np.float64))
+            for i, j in enumerate([] if ragged_pose else need):
                 k = len(need) + i
                 # (the loop gets tensors of its own, as voxel_down_sample would hand it: the grids are views of one packed result)
                 T = object_pose_optimization(down[i].clone(), down[k].clone(), radius=0.02, lr=0.01, iters=200, render_size=224, cd_only=cd_only_pose,
@@ -939,19 +948,20 @@ def reg_tensors_scans(partials, completes, generative_model="trellis", dataset="
     return outs
 
 
-def reg_scans(cfg, flags, cd_inv_weight=0.5, diff_init=True, reg_fine_xyz=False, seed=None, **kwargs):
+def reg_scans(cfg, flags, cd_inv_weight=0.5, diff_init=True, reg_fine_xyz=False, seed=None, ragged_pose=False, **kwargs):
     """The file form of ``reg`` for a list of flags: returns a list of ``reg``'s dicts and writes every ``{flag}_fused.ply`` WITH
     COLOURS.  Every flag's two input files are checked first: a missing one raises FileNotFoundError naming it before any work.
     With an int ``seed`` ONE draw of 163 840 samples per mesh serves both of ``reg``'s samplings, all meshes in one
     ``sample_surfaces_gpu`` call: sample i does not depend on the count, so the first 120 000 samples, voxel-down-sampled at 0.02
     with their colours (one ``voxel_down_sample_clouds`` call for all meshes), ARE the cloud ``object_pose_optimization``'s file
     form builds.  The partial cloud of the pose comes through ``load_point_cloud`` and the pose runs in tensor form on those
-    tensors, per flag: its alignment loop is the one per-scan stage.  With ``seed=None`` the host sampler runs per flag, as in
+    tensors, per flag (the default), or -- ``ragged_pose=True`` -- for all flags in ONE ``object_pose_optimization_scans`` call on the
+    same clouds (the ragged alignment loop; the switch is handed on to ``reg_tensors_scans``).  With ``seed=None`` the host sampler runs per flag, as in
     ``reg`` (``rng=`` included).  Then ``reg_tensors_scans`` and ``fuse_scans`` with ``reg``'s parameters.  The pose's
     debugging files in the working directory (``partial.png``, ``partial_mask.png``, ``final_transform.npy``) are NOT written.
     kwargs: ``cd_only_pose`` and ``rng``, as in ``reg``; anything else raises."""
     import os
-    from .optim_registration.diff_obj_pose import load_point_cloud, object_pose_optimization
+    from .optim_registration.diff_obj_pose import load_point_cloud, object_pose_optimization, object_pose_optimization_scans
     from .utils.dataUtils import read_ply, save_ply_xyzrgb
     from .utils.mesh_io import glb2point, load_glb, sample_surfaces_gpu
     _check_file_form_options("reg_scans(cfg, flags, ...)", "it", seed, kwargs)
@@ -981,15 +991,24 @@ def reg_scans(cfg, flags, cd_inv_weight=0.5, diff_init=True, reg_fine_xyz=False,
     if diff_init:                                                       # :109-122
         if seed is not None:
             cxyz, ccol = voxel_down_sample_clouds([t[:120000] for t in txyz], 0.02, colors=[c[:120000] for c in tcol])
+        pose_clouds = []
         for j in range(s):
             pxyz, pcol = load_point_cloud(plys[j], dev, radius=0.02, num_points=8000)
             if seed is not None:
                 cx, cc = cxyz[j].clone(), ccol[j].clone()
             else:
                 cx, cc = load_point_cloud(glbs[j], dev, radius=0.02, num_points=120000)
+            if ragged_pose:
+                pose_clouds.append((cx, cc, pxyz, pcol))
+                continue
             T = object_pose_optimization(cx, pxyz, radius=0.02, lr=0.01, iters=200, render_size=224, vis=True,
                                          cd_only=kwargs.get("cd_only_pose", False), complete_col=cc, partial_col=pcol)
             diffs[j] = np.linalg.inv(T.astype(np.float64))
+        if ragged_pose:
+            Ts = object_pose_optimization_scans([q[0] for q in pose_clouds], [q[2] for q in pose_clouds], radius=0.02, lr=0.01, iters=200,
+                                                render_size=224, cd_only=kwargs.get("cd_only_pose", False),
+                                                complete_cols=[q[1] for q in pose_clouds], partial_cols=[q[3] for q in pose_clouds])
+            diffs = [np.linalg.inv(T.astype(np.float64)) for T in Ts]
     sxyz, scol = [], []
     for j in range(s):
         xyz, col = read_ply(plys[j])                                    # :124 o3d.io.read_point_cloud
@@ -1003,7 +1022,7 @@ def reg_scans(cfg, flags, cd_inv_weight=0.5, diff_init=True, reg_fine_xyz=False,
         scol.append(torch.as_tensor(col, dtype=torch.float32, device=dev))
     outs = reg_tensors_scans(sxyz, txyz, generative_model=cfg.generative_model, dataset=getattr(cfg, "dataset", "redwood"),
                              cd_inv_weight=cd_inv_weight, diff_init=diff_init, reg_fine_xyz=reg_fine_xyz, partial_cols=scol,
-                             complete_cols=tcol, diff_transforms=diffs if diff_init else None)
+                             complete_cols=tcol, diff_transforms=diffs if diff_init else None, ragged_pose=ragged_pose)
     fused = fuse_scans([o["source"] for o in outs], [o["target"] for o in outs], num_points=20000, distance_threshold=0.0001,
                        std_ratio=2.5, source_cols=[o["source_col"] for o in outs], target_cols=[o["target_col"] for o in outs])   # :207-217
     for j, flag in enumerate(flags):

@@ -42,6 +42,7 @@ int genpc_abi_version(void);              /* bumps when a signature or a documen
                                            * stays 27) and genpc_emd_forward_ragged / genpc_emd_backward_ragged (additive as well: still 27);
                                            * genpc_voxel_down_sample_ragged, genpc_icp_batch_ragged and genpc_icp_ragged_plan likewise: still 28;
                                            * genpc_scale_search_scores_ragged and genpc_scale_search_ragged_plan too: still 28;
+                                           * genpc_pose_optimize_ragged, genpc_pose_loss_grad_ragged and genpc_pose_ragged_plan as well: still 28;
                                            * a missing symbol is found when the binding loads. */
 const char *genpc_last_error(void);       /* last HIP error string, "" if none */
 int genpc_set_arith(int mode);            /* process default; returns the previous one */
@@ -493,6 +494,48 @@ int genpc_pose_optimize_batch(int b, int nc, const float *complete, const float 
                               int iters, int starts, float radius, int render_size,
                               float mask_weight, float *transform, float *history,
                               float *best_params, void *stream);
+
+/* The alignment loop for c scans of DIFFERENT sizes in one call (the ragged form; csrc/pose_ragged_plan.h has its shape).
+ * coff / poff [c + 1] are HOST offset tables into the packed device clouds complete[coff[c],3] and partial[poff[c],3] (colours
+ * packed alike, NULL = white); they travel by value in kernel arguments, nothing of them is read after return.
+ *   -> transform[c,16], history[c, starts*(iters+1)] or NULL (row = start, as genpc_pose_optimize_batch), best_params[c,10] or NULL.
+ * Scan j's results are those of genpc_pose_optimize_batch(1, nc_j, ...) on scan j alone wherever it stands in the batch, within
+ * the tolerances tests/test_gpu_pose_ragged_loop.py states: the same objective, renderer (genpc_render_tune), arithmetic mode,
+ * start rotations, patience rule and pick-the-best-start rule -- the same device functions, given an element table.  What differs
+ * is the simple shape of the loop: the starts side by side as batch elements (element = scan * starts + start), ONE stream,
+ * the Adam update a launch of its own, nearest neighbours from genpc_nm_distance_ragged's grid search in both directions (the
+ * bits of genpc_nm_distance per element; the partial clouds' grids are built once per call, the posed clouds' every step).
+ * A call holds at most GENPC_POSE_RAGGED_MAX_ELEMENTS = 384 elements (96 scans at 4 starts) and 2^28 points per side, starts
+ * included.  Returns 1 (also for c = 0: nothing written), 0 on a HIP error; -1 with genpc_last_error set
+ * ("genpc_pose_optimize_ragged: ...") and nothing enqueued for c < 0, a null or ill-formed table, a scan with an EMPTY cloud on
+ * either side (named by its number), more elements or points than a call holds ("more than 384 elements ..."), starts < 1,
+ * iters < 0, a null pointer, or the full objective with render_size <= 1 or a radius that is not positive.  Asynchronous on
+ * `stream`: no read-back, no synchronisation; scratch from workspace slots of its own. */
+#define GENPC_POSE_RAGGED_MAX_ELEMENTS 384
+int genpc_pose_optimize_ragged(int c, const int *coff, const int *poff, const float *complete,
+                               const float *complete_col, const float *partial, const float *partial_col,
+                               float lr, int iters, int starts, float radius, int render_size,
+                               float mask_weight, float *transform, float *history, float *best_params,
+                               void *stream);
+
+/* One step of that loop for c elements, each with its own parameters and no Adam step: genpc_pose_loss_grad_batch for clouds of
+ * different sizes.  v / vert_col / partial / partial_col packed by coff / poff as above, center [c,3], params [c,10]
+ *   -> loss_out [c,4] = loss, cd, |RR^T-I|_F, mask_loss;  grad [c,10]
+ * with the element's own 1 / nc and 0.5 / np weights.  Refusals and return values as genpc_pose_optimize_ragged (at most 384 elements). */
+int genpc_pose_loss_grad_ragged(int c, const int *coff, const int *poff, const float *v, const float *vert_col,
+                                const float *center, const float *params, const float *partial,
+                                const float *partial_col, float cd_weight, float reg_weight, float mask_weight,
+                                float radius, int render_size, float *loss_out, float *grad, void *stream);
+
+/* The plan of such a call (csrc/pose_ragged_plan.h; no GPU is touched): out[0] elements, [1] / [2] the largest complete / partial
+ * cloud, [3] blocks per element of the transform, [4] of the Chamfer gradient, [5] blocks of the one-thread-per-element kernels,
+ * [6] blocks per element of the centre's sums, [7] the Chamfer gradient rides in the silhouette gradient's launch, [8] the
+ * per-pixel weights are evaluated inside the gather, [9] eight lanes per point in the gather, [10] / [11] blocks per image of the
+ * per-pixel launches / of the sums, [12] the call is too large and would be refused, [13] / [14] points of the packed element
+ * arrays per side (starts included), [15] the transform launch's blocks per compute unit given `cus` of them.
+ * Returns 1 (c = 0: all zero); -1 with genpc_last_error set for what genpc_pose_optimize_ragged refuses before it plans. */
+int genpc_pose_ragged_plan(int c, const int *coff, const int *poff, int starts, int mask, int render_size,
+                           float radius, int cus, int out[16]);
 
 /* Voxel-grid down-sampling ---------------------------------------------------- *
  * Counterpart of open3d's PointCloud.voxel_down_sample, which reg() applies to both clouds
