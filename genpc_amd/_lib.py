@@ -91,6 +91,8 @@ SIGNATURES = {
     "genpc_grid_bound_probe": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i] + [_vp] * 9 + [_vp]),
     "genpc_grid_range_probe": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "genpc_fps_multi": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
+    "genpc_fps_large": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
+    "genpc_fps_plan": (_i, [_i, _i, _vp]),
     "genpc_fps_defer": (_i, [_i]),
     "genpc_streams_prepare": (_i, [_vp]),
     "genpc_fps_deferred_check": (_i, [_vp]),

@@ -22,11 +22,14 @@
 //     reset, no fences, no grid barrier.
 // Several clouds -- of DIFFERENT sizes and sample counts -- run side by side in one launch (grid.y):
 // the two subsamplings of the metric and the fused cloud's can share one pass (genpc_fps_multi).
+// Which of the library's three samplers a cloud takes is fps_plan.h's decision (this kernel: clouds of 24577 to 262144 points, and
+// smaller ones under genpc_fps_tune(256)); the entry points at the end of this file only carry it out.
 // All workgroups of a cloud must be co-resident; launches are sized from the device's CU count at
 // four 256-thread workgroups per CU at most (the hardware admits eight).  The polls are bounded all the same:
 // a hand-off that times out aborts the cloud's run (every workgroup leaves its step loop), raises the error
 // word and writes -1 to out[0]; genpc_amd/fps.py raises on it.
-#include "common.h"
+#include "grid.h"
+#include "fps_plan.h"
 #include "../../include/genpc_hip.h"
 #include <map>
 #include <mutex>
@@ -42,6 +45,10 @@ int emd_auction_capacity();
 bool fps_grid_takes(int n);
 int fps_grid_run(bool fma, int c, const int *sel, const int *n, const int *k, const float *const *xyz, int *const *out_idx,
                  float *const *pdist_of, float4 *spt, int *err, hipStream_t st);
+// fps_large.hip: the one-workgroup sampling with spatial pruning and its state in global memory
+int fps_large_run(bool fma, int c, const int *sel, const int *n, const int *k, const float *const *xyz, int *const *out_idx,
+                  float *const *pdist_of, float4 *spt, unsigned *dmin, unsigned *chmax, int *start, CellGridHdr *hdr, int *err,
+                  hipStream_t st);
 
 constexpr int kFThreads = 192;           // worker threads of a workgroup: three waves, the fourth wave coordinates -- one wave per SIMD
 constexpr int kFWaves = kFThreads / kWave;
@@ -703,14 +710,16 @@ GENPC_API int genpc_fps_tune(int mode)
     return prev;
 }
 
-GENPC_API int genpc_fps_multi(int c, const int *n, const int *k, const float *const *xyz, int *const *out_idx, void *stream)
+// The body of genpc_fps_multi (force_large = 0: every cloud takes the sampler fps_plan gives it) and of genpc_fps_large (1).
+static int fps_call(int c, const int *n, const int *k, const float *const *xyz, int *const *out_idx, void *stream, int force_large)
 {
     using namespace genpc;
     if (c <= 0) return 1;
     for (int j = 0; j < c; j++) {
-        static_assert(kFMaxW * kFMaxR * kFThreads >= 262144, "the documented limit");
-        if (n[j] <= 0 || k[j] <= 0 || k[j] > n[j] || n[j] > 262144) {
-            fprintf(stderr, "genpc_fps: need 0 < k <= n <= 262144\n");
+        static_assert(kFMaxW * kFMaxR * kFThreads >= kFpsMultiMaxN, "what the plan sends to fps_kernel fits its registers");
+        if (k[j] <= 0 || k[j] > n[j] || fps_plan(n[j], force_large).sampler == kFpsNone) {
+            fprintf(stderr, "genpc_fps: need 0 < k <= n <= %d\n", kFpsLargeMaxN);
+            set_error("genpc_fps: need 0 < k <= n <= 4194304 for every cloud");
             return -1;
         }
     }
@@ -737,16 +746,31 @@ GENPC_API int genpc_fps_multi(int c, const int *n, const int *k, const float *co
     // Which kernel: clouds that fit one workgroup's LDS take the pruned sampling of fps_grid.hip (no hand-off, several samples
     // per round, updates confined to the ball a sample can change), the others the multi-workgroup kernel above.  Same
     // sequences (tests/test_gpu_fps.py runs both on every case); genpc_fps_tune(256): never the former.
+    // Clouds beyond the multi-workgroup kernel's registers, and every cloud of genpc_fps_large, take the third sampler
+    // (fps_large.hip: one workgroup again, its state in global memory).  A ragged call may mix all three.
     const bool grid_on = t_fps_multi_wg == 0;
-    std::vector<int> small, big;
-    for (int j = 0; j < c; j++) (grid_on && fps_grid_takes(n[j]) ? small : big).push_back(j);
+    std::vector<int> small, big, large;
+    FpsPlan lplan = fps_plan(1, 1);
+    size_t lpts = 0, lchunks = 0;
+    for (int j = 0; j < c; j++) {
+        const FpsPlan pl = fps_plan(n[j], force_large);
+        if (pl.sampler == kFpsLarge) {
+            large.push_back(j);
+            lpts += (size_t)pl.npad;
+            lchunks += (size_t)pl.chunks;
+            lplan = pl;
+        } else (grid_on && fps_grid_takes(n[j]) ? small : big).push_back(j);
+    }
     size_t total_slots = 0, total_k = 0, spt_pts = 0;
     for (int j : big) total_slots += 2 * (size_t)fps_workgroups(n[j]);
     for (int j : small) spt_pts += ((size_t)n[j] + 63) & ~(size_t)63;
     for (int j = 0; j < c; j++) total_k += ((size_t)k[j] + 63) / 64 * 64;
+    // (the check of a cloud the large sampler takes is never cut into segments -- see verify below -- and needs no segment minima)
+    auto seg_pts = [&](int j) { return fps_plan(n[j], force_large).sampler == kFpsLarge ? (size_t)0 : (size_t)n[j]; };
     size_t total_n = 0;
-    for (int j = 0; j < c; j++) total_n += (size_t)n[j];
+    for (int j = 0; j < c; j++) total_n += seg_pts(j);
     int *err, *verr; FpsSlot *slots; float *pdist, *segmin; float4 *spt;
+    float4 *lspt; unsigned *ldmin, *lchmax; int *lstart; CellGridHdr *lhdr;
     WsLayout L;
     L.add(err, 64);          // the 256-byte status block: [0] error, [1 ..] the clouds' hand-off rounds (genpc_fps_stats reads them back)
     static_assert(sizeof(FpsSlot) == 128, "two slots per workgroup (total_slots is even) are whole 256-byte lines: add() reserves what was reserved unrounded before");
@@ -755,6 +779,12 @@ GENPC_API int genpc_fps_multi(int c, const int *n, const int *k, const float *co
     L.add(pdist, total_k);
     L.add(segmin, total_n * kFVMaxSeg);
     L.add(spt, spt_pts);
+    // the large sampler's pieces, as fps_plan counts them (none for a call without such a cloud)
+    L.add(lspt, lpts);
+    L.add(ldmin, lpts);
+    L.add(lchmax, lchunks);
+    L.add(lstart, large.size() * (size_t)lplan.starts);
+    L.add(lhdr, large.size());
     if (!ws_alloc(L, kWsFps, st)) return 0;
     if (!check(hipMemsetAsync(err, 0, (size_t)((char *)pdist - (char *)err), st), "hipMemsetAsync(fps)")) return 0;
     std::vector<float *> pd_of(c);
@@ -765,7 +795,7 @@ GENPC_API int genpc_fps_multi(int c, const int *n, const int *k, const float *co
             pd_of[j] = pdist + pd_off;
             seg_of[j] = (int)seg_off;
             pd_off += ((size_t)k[j] + 63) / 64 * 64;
-            seg_off += (size_t)n[j];
+            seg_off += seg_pts(j);
         }
     }
     // the verification of a group of clouds (fps_verify_kernel above), whichever kernel sampled them
@@ -775,6 +805,7 @@ GENPC_API int genpc_fps_multi(int c, const int *n, const int *k, const float *co
         const int gxv = ceil_div(nmax, kFVBlock);
         int nseg = (4 * cus) / (gxv * nj > 0 ? gxv * nj : 1);      // about four blocks per CU
         nseg = nseg < 1 ? 1 : (nseg > kFVMaxSeg ? kFVMaxSeg : nseg);
+        if (force_large || nmax > kFpsMultiMaxN) nseg = 1;      // (no segment minima are reserved for these clouds; their point blocks fill the chip anyway)
         const dim3 vg(gxv, nj, nseg);
         if (nseg > 1) {
             if (fma) hipLaunchKernelGGL((fps_verify_kernel<1, 0>), vg, dim3(kFVBlock), 0, st, jobs, segmin, nseg);
@@ -856,6 +887,26 @@ GENPC_API int genpc_fps_multi(int c, const int *n, const int *k, const float *co
             if (!defer || !verify_deferred(jobs, nj, defer)) verify(jobs, nj, st, segmin, nullptr);
         }
     }
+    if (!large.empty()) {
+        if (fps_large_run(fma, (int)large.size(), large.data(), n, k, xyz, out_idx, pd_of.data(), lspt, ldmin, lchmax, lstart, lhdr, err, st) != 1)
+            return 0;
+        // (always checked in line: genpc_fps_defer defers the LDS kernel's checks only)
+        for (size_t q0 = 0; q0 < large.size(); q0 += kFMaxJobs) {
+            FpsJobs jobs = {};
+            int nj = 0;
+            for (; nj < kFMaxJobs && q0 + nj < large.size(); nj++) {
+                const int j = large[q0 + nj];
+                jobs.xyz[nj] = xyz[j];
+                jobs.out[nj] = out_idx[j];
+                jobs.pdist[nj] = pd_of[j];
+                jobs.verr[nj] = verr + j;
+                jobs.segoff[nj] = seg_of[j];
+                jobs.n[nj] = n[j];
+                jobs.k[nj] = k[j];
+            }
+            verify(jobs, nj, st, segmin, nullptr);
+        }
+    }
     int slot0 = 0;
     const int cb = (int)big.size();
     for (int j0 = 0; j0 < cb;) {
@@ -901,6 +952,25 @@ GENPC_API int genpc_fps_multi(int c, const int *n, const int *k, const float *co
     }
     if (!check(hipGetLastError(), "fps launch")) return 0;
     return 1;
+}
+
+GENPC_API int genpc_fps_multi(int c, const int *n, const int *k, const float *const *xyz, int *const *out_idx, void *stream)
+{
+    return fps_call(c, n, k, xyz, out_idx, stream, 0);
+}
+
+GENPC_API int genpc_fps_large(int c, const int *n, const int *k, const float *const *xyz, int *const *out_idx, void *stream)
+{
+    return fps_call(c, n, k, xyz, out_idx, stream, 1);
+}
+
+GENPC_API int genpc_fps_plan(int n, int force_large, int out[8])
+{
+    if (!out) return -1;
+    const genpc::FpsPlan p = genpc::fps_plan(n, force_large);
+    out[0] = p.sampler; out[1] = p.cells_max; out[2] = p.cells_target; out[3] = p.npad;
+    out[4] = p.chunks; out[5] = p.starts; out[6] = p.lds_bytes; out[7] = p.build_own;
+    return p.sampler == genpc::kFpsNone ? -1 : 1;
 }
 
 namespace genpc {

@@ -19,17 +19,19 @@
 //     index among the tied points, one sample per round.
 //
 // No hand-off between workgroups: nothing has to be co-resident, nothing is admitted, nothing can time out; clouds of one
-// launch are independent blocks.  Clouds beyond kGMaxN points keep fps.hip's multi-workgroup kernel.
+// launch are independent blocks.  Clouds beyond kGMaxN points take fps.hip's multi-workgroup kernel or, beyond its limit,
+// fps_large.hip's sampler, which is this scheme with its state in global memory (fps_plan.h decides).
 // The sequence and the running minimum of every sample when drawn go to the same outputs as fps.hip's, so
 // fps_verify_kernel checks these samplings against the definition like the others.
 #include "common.h"
+#include "fps_plan.h"
 #include "../../include/genpc_hip.h"
 
 namespace genpc {
 
 constexpr int kGT = 1024;                 // threads of the workgroup (16 waves: four per SIMD)
 constexpr int kGWaves = kGT / kWave;
-constexpr int kGMaxN = 24576;             // running minima in LDS: 4 B per point (+ 0.5 per point of chunk maxima)
+constexpr int kGMaxN = kFpsGridMaxN;       // running minima in LDS: 4 B per point (+ 0.5 per point of chunk maxima)
 constexpr int kGCand = 128;               // candidates a round lists
 constexpr int kGPick = 64;                // samples a round draws at most
 constexpr int kGQueue = 4096;             // work items of an update (sample, <= 8 points of a cell) / tied points of the tie path
@@ -644,6 +646,7 @@ int fps_grid_run(bool fma, int c, const int *sel, const int *n, const int *k, co
     return check(hipGetLastError(), "fps_grid_kernel launch") ? 1 : 0;
 }
 
-bool fps_grid_takes(int n) { return n >= 1 && n <= kGMaxN; }
+static_assert(kGMaxN == kFpsGridMaxN, "the plan sends this kernel what its LDS holds");
+bool fps_grid_takes(int n) { return fps_plan(n, 0).sampler == kFpsGrid; }
 
 }  // namespace genpc

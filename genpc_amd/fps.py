@@ -14,13 +14,16 @@ _p = _lib.ptr
 # hand-off timed out (first index -1) or whose sequence failed the check -- a step's sample was not the first arg-max
 # (first index -2) -- and were sampled again
 stats = {"clouds": 0, "timed_out": 0, "failed_check": 0}
+MAX_POINTS = 4194304          # csrc/fps_plan.h: kFpsLargeMaxN
 _stats_lock = _threading.Lock()
 
 
 def fps_sampling(points, k):
-    """points: [N,3] or [C,N,3] GPU tensor -> int32 indices [k] or [C,k].  The first
+    """points: [N,3] or [C,N,3] GPU tensor -> int32 indices [k] or [C,k], N up to 4194304.  The first
     index is always 0; the kernel writes -1 there if its inter-workgroup hand-off timed
-    out (another kernel kept the cloud's workgroups from being co-resident)."""
+    out (another kernel kept the cloud's workgroups from being co-resident).  Which of the
+    library's three samplers a cloud takes follows from N alone (csrc/fps_plan.h); all return
+    the same sequence."""
     single = points.dim() == 2
     pts = (points[None] if single else points).contiguous().float()
     _lib.check_tensors((("points", pts),))
@@ -28,7 +31,7 @@ def fps_sampling(points, k):
     out = torch.empty(c, k, device=pts.device, dtype=torch.int32)
     rc = _lib.on_device_of(pts, _L.genpc_fps, c, n, _p(pts), int(k), _p(out))
     if rc == -1:
-        raise ValueError("fps_sampling: need 0 < k <= N <= 262144 (k=%d, N=%d)" % (k, n))
+        raise ValueError("fps_sampling: need 0 < k <= N <= %d (k=%d, N=%d)" % (MAX_POINTS, k, n))
     if rc != 1:
         raise RuntimeError("genpc_fps failed: " + _lib.last_error())
     # index 0 is the start point of every cloud; the kernel writes -1 there when a hand-off
@@ -46,7 +49,13 @@ def fps_sampling_multi(clouds, ks):
     return _fps_multi_direct(clouds, ks)
 
 
-def _fps_multi_direct(clouds, ks, _attempt=0):
+def fps_sampling_large(clouds, ks):
+    """fps_sampling_multi with every cloud on the sampler that clouds beyond 262144 points take (csrc/fps_large.hip: one
+    workgroup per cloud, its state in global memory, nothing that has to be co-resident), whatever its size.  Same sequences."""
+    return _fps_multi_direct(clouds, ks, _entry="genpc_fps_large")
+
+
+def _fps_multi_direct(clouds, ks, _attempt=0, _entry="genpc_fps_multi"):
     import ctypes
     pts = [c.contiguous().float() for c in clouds]
     _lib.check_tensors(tuple(("clouds[%d]" % j, p) for j, p in enumerate(pts)))
@@ -61,12 +70,12 @@ def _fps_multi_direct(clouds, ks, _attempt=0):
     k_arr = (ctypes.c_int * c)(*[int(k) for k in ks])
     x_arr = (ctypes.c_void_p * c)(*[p.data_ptr() for p in pts])
     o_arr = (ctypes.c_void_p * c)(*[o.data_ptr() for o in outs])
-    rc = _lib.on_device_of(pts[0], _L.genpc_fps_multi, c, ctypes.addressof(n_arr), ctypes.addressof(k_arr),
+    rc = _lib.on_device_of(pts[0], getattr(_L, _entry), c, ctypes.addressof(n_arr), ctypes.addressof(k_arr),
                            ctypes.addressof(x_arr), ctypes.addressof(o_arr))
     if rc == -1:
-        raise ValueError("fps_sampling_multi: need 0 < k <= N <= 262144 for every cloud")
+        raise ValueError("fps_sampling_multi: need 0 < k <= N <= %d for every cloud" % MAX_POINTS)
     if rc != 1:
-        raise RuntimeError("genpc_fps_multi failed: " + _lib.last_error())
+        raise RuntimeError(_entry + " failed: " + _lib.last_error())
     first = torch.stack([o[0] for o in outs]).tolist()          # (one host read for all clouds)
     bad = [j for j, f in enumerate(first) if f != 0]
     with _stats_lock:
@@ -79,7 +88,7 @@ def _fps_multi_direct(clouds, ks, _attempt=0):
         # seen twice for samplings running beside other streams' kernels, cause unknown.  Not an error yet: the clouds that
         # failed go again, one at a time (a launch to itself needs a fraction of the device)
         for j in bad:
-            outs[j] = _fps_multi_direct([pts[j]], [ks[j]], _attempt=_attempt + 1 if c == 1 else _attempt)[0]
+            outs[j] = _fps_multi_direct([pts[j]], [ks[j]], _attempt=_attempt + 1 if c == 1 else _attempt, _entry=_entry)[0]
         return outs
     if bad:
         raise RuntimeError("genpc_fps: no verified sampling after %d attempts (hand-off timed out or the sequence failed its "

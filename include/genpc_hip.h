@@ -711,18 +711,34 @@ int genpc_grid_range_probe(const void *hdr, int nq, const float *q, const float 
  * (main.py:21-24, reg_xyz.py:215, DepthPrompting.py:88; third-party, random start):
  * start index 0, fp32 squared distances in the library's arithmetic mode, first
  * arg-max.  xyz[C,N,3] -> out_idx[C,k] int32, C clouds side by side.  Returns -1
- * unless 0 < k <= n <= 262144.  out_idx[c][0] is 0 for a good sequence; -1: the
+ * unless 0 < k <= n <= 4194304.  Three samplers return the same sequences, and a
+ * cloud's point count decides which it takes (csrc/fps_plan.h, genpc_fps_plan):
+ * up to 24576 points one workgroup with its running minima in LDS, up to 262144
+ * the multi-workgroup kernel, beyond that one workgroup with its state in global
+ * memory (csrc/fps_large.hip).  out_idx[c][0] is 0 for a good sequence; -1: the
  * hand-off among the cloud's workgroups timed out (something kept them from running
- * together); -2: the finished sequence failed the device-side check of every step
- * against the definition -- sample that cloud again
+ * together; only the multi-workgroup kernel has one) or a one-workgroup sampler
+ * exhausted its bound of sweeps; -2: the finished sequence failed the device-side
+ * check of every step against the definition -- sample that cloud again
  * (genpc_amd/fps.py does).                                                       */
 int genpc_fps(int c, int n, const float *xyz, int k, int *out_idx, void *stream);
 
 /* The same for C clouds of DIFFERENT sizes in one pass (the metric's two subsamplings and the fused
  * cloud's run side by side: a step costs its latency, not its work): host arrays n[C], k[C],
- * xyz[C] (device pointers to [n_j,3]), out_idx[C] (device pointers to [k_j]).                    */
+ * xyz[C] (device pointers to [n_j,3]), out_idx[C] (device pointers to [k_j]).  The clouds of one
+ * call may take different samplers.                                                              */
 int genpc_fps_multi(int c, const int *n, const int *k, const float *const *xyz,
                     int *const *out_idx, void *stream);
+/* genpc_fps_multi with EVERY cloud on the sampler of csrc/fps_large.hip, for any 0 < k <= n <= 4194304 (one workgroup per
+ * cloud, no hand-off, nothing that has to be co-resident; its check is always in line).  Same contract, same sequences.  */
+int genpc_fps_large(int c, const int *n, const int *k, const float *const *xyz,
+                    int *const *out_idx, void *stream);
+/* Which sampler a cloud of n points takes, and what the large sampler needs for it (csrc/fps_plan.h; no GPU work):
+ * out[0] sampler (0 one workgroup / LDS -- genpc_fps_tune(256) sends such a cloud to 1 --, 1 multi-workgroup, 2 large; -1 refused),
+ * and for the large sampler, else 0: out[1] cells of its grid at most, out[2] cells asked for, out[3] running minima and sorted
+ * points (n padded), out[4] chunk maxima, out[5] cell table entries, out[6] LDS bytes, out[7] 0 = the grid is built by the shared
+ * multi-workgroup build.  force_large != 0: as genpc_fps_large plans it.  Returns 1, or -1 when the cloud is refused or out is null. */
+int genpc_fps_plan(int n, int force_large, int out[8]);
 /* The device-side check of finished sequences OFF the caller's critical path (calling host thread; returns the previous
  * setting).  1: samplings of clouds the one-workgroup kernel takes (<= 24576 points) return without waiting for their check --
  * the cloud, the indices and the recorded minima are copied (stream-ordered) and checked on a side stream of the library's own;
@@ -742,7 +758,8 @@ int genpc_fps_deferred_check(void *stream);
  * value returns -1 and sets genpc_last_error. */
 int genpc_fps_tune(int mode);
 /* Diagnostics: rounds[j] (host, c <= 32) = inter-workgroup exchanges cloud j of the last
- * genpc_fps_multi call on this stream took (one exchange yields several samples).  Synchronises.  */
+ * genpc_fps_multi / genpc_fps_large call on this stream took (one exchange yields several samples; for the
+ * one-workgroup samplers: the rounds of candidates).  Synchronises.  */
 int genpc_fps_stats(int c, int *rounds, void *stream);
 
 /* Statistical outlier filter ------------------------------------------------ *
