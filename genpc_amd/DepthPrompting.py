@@ -290,6 +290,146 @@ class DepthPrompting:
             self._write_stage1_files(flag, out)
         return out
 
+    def getDepths(self, clouds, flags=None, rgbs=None):
+        """``getDepth`` for S scans at once.  clouds: a list of [N_j,3] float32 GPU tensors or packed (points [T,3], host
+        offsets); flags: None or one entry per scan (a string names the scan's directory under cfg.output_path, whose stage-1
+        files are then written as getDepth writes them); rgbs: None (white, as getDepth), a list of [N_j,3] tensors or one
+        packed [T,3] tensor.  Returns a list of getDepth's dicts, same keys; scan j's products are the bits getDepth gives on
+        that scan alone, depth_sums up to the order of their summation (here float64 in a stated order, csrc/
+        depth_prompt_ragged_plan.h; there torch's float32 sum).
+          viewpoints   one ``fps_sampling_multi`` over the clouds larger than cfg.downsample_num, one
+                       ``hidden_point_removal(best_only=True)`` per scan with the counts kept on the device, ONE read-back of
+                       the S argmaxes and maxima
+          visibility   one two-eye ``genpc_hpr_visibility`` call per scan on the whole cloud, written straight into the packed
+                       visibility bytes.  Hidden-point removal stays one call per scan: 1024 views x 10000 points fill the chip
+                       already, and a ragged form would rework every kernel of csrc/hpr_*.hip
+          the rest     ONE ``genpc_depth_prompt_ragged`` call (a memset and four launches whatever S is) and ONE more read-back
+                       (the sums, the choices, the statuses).
+        Sets self.point_uvs / self.views / self.cams (lists); self.point_uv / self.view / self.cam hold the last scan's."""
+        from ._ragged import ragged_side
+        from .fps import fps_sampling_multi
+        fn = "getDepths"
+        pts, off = ragged_side(clouds, fn, "clouds")
+        s = len(off) - 1
+        if flags is not None and (not isinstance(flags, (list, tuple)) or len(flags) != s):
+            raise ValueError("%s: flags is None or a list with one entry per scan (%d scans)" % (fn, s))
+        if rgbs is not None and not torch.is_tensor(rgbs):
+            if not isinstance(rgbs, (list, tuple)) or len(rgbs) != s:
+                raise ValueError("%s: rgbs is None, a packed [T,3] tensor or a list with one entry per scan (%d scans)" % (fn, s))
+            for j, c in enumerate(rgbs):
+                if not torch.is_tensor(c) or tuple(c.shape) != (off[j + 1] - off[j], 3):
+                    raise ValueError("%s: rgbs[%d] must be [%d,3] like its cloud" % (fn, j, off[j + 1] - off[j]))
+                if c.dtype != torch.float32:
+                    raise TypeError("%s: rgbs[%d] must be torch.float32, got %s" % (fn, j, c.dtype))
+        if torch.is_tensor(rgbs):
+            if tuple(rgbs.shape) != (off[-1], 3):
+                raise ValueError("%s: packed rgbs must be [%d,3] like the packed clouds" % (fn, off[-1]))
+            if rgbs.dtype != torch.float32:
+                raise TypeError("%s: packed rgbs must be torch.float32, got %s" % (fn, rgbs.dtype))
+        if s == 0:
+            return []
+        if not pts.is_cuda:
+            raise RuntimeError("%s: GPU tensors only (got a %s tensor for clouds); the HIP path has no CPU fallback" % (fn, pts.device))
+        for j in range(s):
+            if off[j + 1] == off[j]:
+                raise ValueError("%s: clouds[%d] has no points" % (fn, j))
+        if s > 256:                     # include/genpc_hip.h: GENPC_DEPTH_PROMPT_RAGGED_MAX_SCANS
+            out = []
+            for a in range(0, s, 256):
+                b = min(s, a + 256)
+                sub = [pts[off[j]:off[j + 1]] for j in range(a, b)]
+                rg = None if rgbs is None else [(rgbs[off[j]:off[j + 1]] if torch.is_tensor(rgbs) else rgbs[j]) for j in range(a, b)]
+                out += self.getDepths(sub, None if flags is None else list(flags[a:b]), rg)
+            return out
+        dev = pts.device
+        total = off[-1]
+        if rgbs is None:
+            rgb = torch.ones(total, 3, device=dev)
+        elif torch.is_tensor(rgbs):
+            rgb = rgbs.to(dev).contiguous()
+        else:
+            rgb = torch.cat([c.to(dev) for c in rgbs], dim=0).contiguous()
+        cl = [pts[off[j]:off[j + 1]] for j in range(s)]
+        radius = getattr(self.cfg, "removal_radius", 10000)
+        # ---- the viewpoints: viewpoint_select's statements, the counts of all scans read back at once
+        if getattr(self.cfg, "view_num", 0) == 6:
+            bests = [1] * s
+        else:
+            k = int(getattr(self.cfg, "downsample_num", 10000))
+            big = [j for j in range(s) if cl[j].shape[0] > k]
+            sub = list(cl)
+            if big:
+                for j, idx in zip(big, fps_sampling_multi([cl[j] for j in big], [k] * len(big))):
+                    sub[j] = cl[j][idx.long()]
+            counts = torch.stack([self.hidden_point_removal(sub[j], self.viewpoints, radius, best_only=True)[1] for j in range(s)])
+            top, best = torch.max(counts, 1)
+            tops, bests = torch.stack([top.long(), best]).tolist()          # (the first host read)
+            for j in range(s):
+                if tops[j] < 0:
+                    raise RuntimeError("%s: genpc_hpr_best_view_counts: internal error on scan %d (the library marked its counts invalid)" % (fn, j))
+        # ---- the opposite cameras, on the host as getDepth builds them
+        if self.__dict__.get("_cameras_host") is None:
+            self._cameras_host = self.cameras.reshape(-1, 12).detach().float().cpu().numpy()      # (once per object)
+        eyes = np.empty((s, 2, 3), np.float64)
+        cams_h = np.empty((s, 2, 12), np.float32)
+        for j in range(s):
+            original = np.asarray(self.viewpoints[bests[j]], np.float64)
+            opposite = -original
+            eyes[j, 0], eyes[j, 1] = original, opposite
+            cams_h[j, 0] = self._cameras_host[bests[j]]
+            cams_h[j, 1] = look_at(opposite, np.zeros(3), calculate_up_vector(opposite, np.zeros(3)))
+        cams = torch.from_numpy(cams_h).to(dev)
+        eyes_d = torch.from_numpy(eyes).to(dev)
+        # ---- both viewpoints' visibility of the whole cloud, per scan, into the packed bytes
+        vis = torch.zeros(2 * total, device=dev, dtype=torch.uint8)
+        cnt = torch.empty(s, 2, device=dev, dtype=torch.int32)
+        budget = int(getattr(self.cfg, "hpr_workspace_bytes", 4 << 30))
+        for j in range(s):
+            n = off[j + 1] - off[j]
+            step = max(1, min(2, (2 ** 31 - 1) // n, budget // (321 * n)))
+            for v0 in range(0, 2, step):
+                rc = _lib.on_device_of(pts, _L.genpc_hpr_visibility, step, n, _p(cl[j]), _p(eyes_d[j, v0:]), float(radius),
+                                       _p(vis[2 * off[j] + v0 * n:]), _p(cnt[j, v0:]), None)
+                if rc != 1:
+                    raise RuntimeError("%s: genpc_hpr_visibility failed on scan %d (rc=%d): %s" % (fn, j, rc, _lib.last_error()))
+        # ---- everything after hidden-point removal: one call
+        res = int(self.cfg.res)
+        uv = torch.empty(total, 2, device=dev)
+        depth = torch.empty(total, device=dev)
+        pix = torch.empty(total, 2, device=dev, dtype=torch.int32)
+        visible = torch.empty(total, device=dev, dtype=torch.uint8)
+        chosen = torch.empty(s, device=dev, dtype=torch.int32)
+        sums = torch.empty(s, 2, device=dev, dtype=torch.float64)
+        images = torch.empty(s, 4, 3, res, res, device=dev)
+        status = torch.empty(s, device=dev, dtype=torch.int32)
+        harr = (ctypes.c_int * (s + 1))(*off)
+        rc = _lib.on_device_of(pts, _L.genpc_depth_prompt_ragged, s, ctypes.cast(harr, ctypes.c_void_p), _p(pts), _p(rgb), _p(cams), _p(vis),
+                               float(self.focal), 1e-2, 1e2, int(bool(self.cfg.rescale)), float(np.float32(1 - 2 * self.cfg.padding)),
+                               res, int(self.cfg.point_size), int(self.cfg.mask_pixel_rate), _p(uv), _p(depth), _p(pix), _p(visible),
+                               _p(chosen), _p(sums), _p(images), _p(status))
+        if rc != 1:
+            raise RuntimeError("genpc_depth_prompt_ragged failed (rc=%d): %s" % (rc, _lib.last_error()))
+        back = torch.cat([sums.flatten(), chosen.double(), status.double()]).tolist()          # (the second host read)
+        vis_b, pix_l = visible.bool(), pix.long()
+        outs = []
+        self.point_uvs, self.views, self.cams = [], [], []
+        for j in range(s):
+            if int(back[3 * s + j]) != 1:
+                raise RuntimeError("%s: genpc_depth_prompt_ragged refused scan %d (status %d)" % (fn, j, int(back[3 * s + j])))
+            a, b = off[j], off[j + 1]
+            opp = int(back[2 * s + j]) == 1
+            self.point_uv, self.view, self.cam = uv[a:b], eyes[j, 1 if opp else 0].copy(), cams[j, 1 if opp else 0].clone()
+            self.point_uvs.append(self.point_uv)
+            self.views.append(self.view)
+            self.cams.append(self.cam)
+            out = dict(sparse_img=images[j, 0], raw_depth=images[j, 1], hole_mask1=images[j, 2], hole_mask2=images[j, 3],
+                       view_index=int(bests[j]), used_opposite=opp, visible=vis_b[a:b], depth_sums=(back[2 * j], back[2 * j + 1]),
+                       uv=uv[a:b], depth=depth[a:b], pixels=pix_l[a:b])
+            if flags is not None and isinstance(flags[j], str) and getattr(self.cfg, "output_path", None):
+                self._write_stage1_files(flags[j], out)
+            outs.append(out)
+        return outs
+
     @staticmethod
     def _save_image(t, path):
         """torchvision.utils.save_image for one [3,H,W] image in [0,1]: mul(255).add(0.5).clamp(0,255) -> uint8 PNG."""

@@ -99,6 +99,75 @@ class ScaleAdapter:
             raise RuntimeError("colorPoint failed: " + _lib.last_error())
         return out
 
+    def colorPoints(self, uvs, imgs, scale=1024):
+        """``colorPoint``'s tensor form for S scans at once, each with its own image: uvs is a list of [N_j,2] float32 GPU
+        tensors or packed (uv [T,2], host offsets), imgs a list of [3,H,W] tensors of one size or one [S,3,H,W] tensor.  One
+        launch (``genpc_gather_colors_ragged``) makes the pixels and gathers; returns a list of colours [N_j,3], scan j's the
+        bits ``colorPoint(uvs[j], imgs[j])`` gives."""
+        fn = "colorPoints"
+        from ._ragged import is_packed
+        if is_packed(uvs):
+            uv, off = uvs
+            if torch.is_tensor(off):
+                if off.is_cuda:
+                    raise ValueError("%s: the offsets of uvs live on the host (a device tensor would have to be read back)" % fn)
+                off = off.tolist()
+            off = [int(v) for v in off]
+            if uv.dim() != 2 or uv.shape[1] != 2:
+                raise ValueError("%s: packed uvs must be [T,2], got %s" % (fn, tuple(uv.shape)))
+            if not off or off[0] != 0 or any(b < a for a, b in zip(off, off[1:])) or off[-1] != uv.shape[0]:
+                raise ValueError("%s: the offsets of uvs must ascend from 0 to its %d points" % (fn, uv.shape[0]))
+            if uv.dtype != torch.float32:
+                raise TypeError("%s: packed uvs must be torch.float32, got %s" % (fn, uv.dtype))
+        else:
+            if not isinstance(uvs, (list, tuple)):
+                raise TypeError("%s: uvs is a list of [N,2] tensors or a tuple (uv, offsets)" % fn)
+            off = [0]
+            for j, t in enumerate(uvs):
+                if not torch.is_tensor(t) or t.dim() != 2 or t.shape[1] != 2:
+                    raise ValueError("%s: uvs[%d] must be an [N,2] tensor" % (fn, j))
+                if t.dtype != torch.float32:
+                    raise TypeError("%s: uvs[%d] must be torch.float32, got %s" % (fn, j, t.dtype))
+                off.append(off[-1] + t.shape[0])
+            uv = torch.cat(list(uvs), dim=0) if uvs else torch.empty(0, 2)
+        s = len(off) - 1
+        if torch.is_tensor(imgs):
+            if imgs.dim() != 4 or imgs.shape[0] != s:
+                raise ValueError("%s: imgs must be [%d,3,H,W] (one image per scan), got %s" % (fn, s, tuple(imgs.shape)))
+            img = imgs
+        else:
+            if not isinstance(imgs, (list, tuple)) or len(imgs) != s:
+                raise ValueError("%s: one image per scan (%d scans, %d images)" % (fn, s, len(imgs) if isinstance(imgs, (list, tuple)) else -1))
+            for j, t in enumerate(imgs):
+                if not torch.is_tensor(t) or t.dim() != 3 or t.shape != imgs[0].shape:
+                    raise ValueError("%s: imgs[%d] must be [3,H,W] like imgs[0]" % (fn, j))
+                if t.dtype != torch.float32:
+                    raise TypeError("%s: imgs[%d] must be torch.float32, got %s" % (fn, j, t.dtype))
+            img = torch.stack(list(imgs)) if s else torch.empty(0, 3, scale, scale)
+        if img.dtype != torch.float32:
+            raise TypeError("%s: imgs must be torch.float32, got %s" % (fn, img.dtype))
+        if s == 0:
+            return []
+        if not uv.is_cuda or not img.is_cuda:
+            raise RuntimeError("%s: GPU tensors only (got %s for uvs, %s for imgs); the HIP path has no CPU fallback" % (fn, uv.device, img.device))
+        uv, img = uv.contiguous(), img.contiguous()
+        _, ch, h, w = img.shape
+        if h < scale or w < scale:
+            raise ValueError("%s indexes a %dx%d pixel grid (ScaleAdapter.py:59-62); the images are %dx%d" % (fn, scale, scale, h, w))
+        import ctypes
+        out = torch.empty(uv.shape[0], ch, device=img.device)
+        outs = []
+        for a in range(0, s, 256):              # include/genpc_hip.h: at most 256 scans per call
+            b = min(s, a + 256)
+            harr = (ctypes.c_int * (b - a + 1))(*[v - off[a] for v in off[a:b + 1]])
+            rc = _lib.on_device_of(img, _L.genpc_gather_colors_ragged, b - a, ctypes.cast(harr, ctypes.c_void_p), _p(uv[off[a]:]),
+                                   _p(img[a:]), ch, h, w, float(scale), int(scale) - 1, None, _p(out[off[a]:]))
+            if rc != 1:
+                raise RuntimeError("%s failed: %s" % (fn, _lib.last_error()))
+        for j in range(s):
+            outs.append(out[off[j]:off[j + 1]])
+        return outs
+
     # ------------------------------------------------------------------ scaleReg / scaleAdapter
     def scaleReg(self, flag, complete_xyz=None, **kwargs):
         """ScaleAdapter.py:74-75: ``reg(cfg, flag, cd_inv_weight=0.5, diff_init=True, reg_fine_xyz=True)``

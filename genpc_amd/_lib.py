@@ -53,6 +53,9 @@ SIGNATURES = {
     "genpc_uv_to_pixels": (_i, [_i, _vp, _f, _i, _vp, _vp]),
     "genpc_paint_pixels": (_i, [_i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "genpc_gather_colors": (_i, [_i, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "genpc_depth_prompt_ragged": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _i, _f, _i, _i, _i] + [_vp] * 8 + [_vp]),
+    "genpc_depth_prompt_ragged_plan": (_i, [_i, _vp, _i, _i, _i, _vp]),
+    "genpc_gather_colors_ragged": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _vp, _vp]),
     "genpc_hpr_visibility": (_i, [_i, _i, _vp, _vp, _d, _vp, _vp, _vp, _vp]),
     "genpc_hpr_best_view_counts": (_i, [_i, _i, _vp, _vp, _d, _vp, _vp, _vp, _vp, _vp]),
     "genpc_zbuffer_visibility": (_i, [_i, _i, _vp, _vp, _i, _i, _f, _vp, _vp, _vp]),

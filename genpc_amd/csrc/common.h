@@ -81,6 +81,7 @@ enum Ws : int {
     kWsPoseRaggedReplicas = 51, // pose.hip genpc_pose_optimize_ragged: the packed clouds and colours once per start
     kWsPoseRaggedGridPartial = 52, // pose.hip, posed -> partial: the partial clouds' grids (nn_ragged.hip), built once per call.  SHARED by the two ragged pose entry points: each builds afresh and is done with them at its last launch
     kWsPoseRaggedGridPosed = 53,   // pose.hip, partial -> posed: the posed clouds' grids, rebuilt every step.  SHARED like 52
+    kWsDepthPromptRagged = 54, // depth_prompt_ragged.hip genpc_depth_prompt_ragged: box and depth-range keys, owner planes (one memset) | chunk partial sums | per-scan records
 };
 
 // The scratch pool: one grow-only block of device memory per (device, slot, stream); null on failure, the error recorded.

@@ -15,6 +15,7 @@
 // bit; min/max are exact, so uv is bit-exact too.
 #include "common.h"
 #include "fastdiv.h"
+#include "project_math.h"
 #include "../../include/genpc_hip.h"
 
 #include <stdlib.h>
@@ -24,30 +25,6 @@
 namespace genpc {
 
 constexpr int kPBlock = 256;
-
-// float -> unsigned key with the same ordering
-__device__ __forceinline__ unsigned f2key(float f)
-{
-    unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key2f(unsigned k)
-{
-    // branch-free: the select form crashes hipcc 7.2's instruction selection inside project_write_kernel
-    return __uint_as_float(k ^ ((unsigned)((int)~k >> 31) | 0x80000000u));
-}
-
-__device__ __forceinline__ void project_point(const float *v, float focal, float A, float B, float px, float py,
-                                              float pz, float &ox, float &oy, float &oz)
-{
-    const float xc = __fadd_rn(__fmaf_rn(v[2], pz, __fmaf_rn(v[1], py, __fmul_rn(v[0], px))), v[3]);
-    const float yc = __fadd_rn(__fmaf_rn(v[6], pz, __fmaf_rn(v[5], py, __fmul_rn(v[4], px))), v[7]);
-    const float zc = __fadd_rn(__fmaf_rn(v[10], pz, __fmaf_rn(v[9], py, __fmul_rn(v[8], px))), v[11]);
-    const float w = -zc;
-    ox = __fmul_rn(focal, xc) / w;
-    oy = __fmul_rn(focal, yc) / w;
-    oz = __fmaf_rn(A, zc, B) / w;
-}
 
 // Pass 1: per-camera bounding box of the NDC xy, nothing stored per point.  Two kernels, exact result:
 //
@@ -277,10 +254,7 @@ __global__ __launch_bounds__(kPBlock) void project_write_kernel(int c, int n, in
                 float *bo = bbox + (size_t)(cam0 + threadIdx.x) * 4;
                 bo[0] = mnx; bo[1] = mny; bo[2] = mxx; bo[3] = mxy;
             }
-            cx = __fmul_rn(__fadd_rn(mnx, mxx), 0.5f);       // == / 2.0f (exact scaling; a subnormal sum halves with the same rounding)
-            cy = __fmul_rn(__fadd_rn(mny, mxy), 0.5f);
-            const float sx = __fsub_rn(mxx, mnx), sy = __fsub_rn(mxy, mny);
-            sc = sx > sy ? sx : sy;
+            project_box_centre(mnx, mny, mxx, mxy, cx, cy, sc);
         }
         *(float4 *)&rec[threadIdx.x * 16 + 12] = make_float4(cx, cy, sc, rcp_refined(sc));
     }
@@ -344,13 +318,8 @@ __global__ __launch_bounds__(kPBlock) void project_write_kernel(int c, int n, in
                 project_point(v, focal, A, B, p[t][0], p[t][1], p[t][2], ox, oy, ozt);
                 oxy[t] = (v2f){ox, oy};
                 if (t & 1) oz[t >> 1].y = ozt; else oz[t >> 1].x = ozt;
-                if (rescale) {
-                    uvv[t].x = __fadd_rn(__fmul_rn(__fsub_rn(ox, r3.x) / r3.z, padmul), 0.5f);
-                    uvv[t].y = __fadd_rn(__fmul_rn(__fsub_rn(oy, r3.y) / r3.z, padmul), 0.5f);
-                } else {
-                    uvv[t].x = __fmul_rn(__fadd_rn(ox, 1.0f), 0.5f);
-                    uvv[t].y = __fmul_rn(__fadd_rn(oy, 1.0f), 0.5f);
-                }
+                uvv[t].x = project_rescale(ox, r3.x, r3.z, padmul, rescale);
+                uvv[t].y = project_rescale(oy, r3.y, r3.z, padmul, rescale);
             }
         }
         const size_t q = (size_t)(cam0 + k) * n + j0;
@@ -391,12 +360,8 @@ __global__ __launch_bounds__(kPBlock) void uv_to_pixels_kernel(int n, const floa
 {
     const int j = blockIdx.x * kPBlock + threadIdx.x;
     if (j >= n) return;
-    long long pu = (long long)__fmul_rn(uv[(size_t)j * 2 + 0], res);
-    long long pv = (long long)__fmul_rn(uv[(size_t)j * 2 + 1], res);
-    pu = pu < 0 ? 0 : (pu > clip_max ? clip_max : pu);
-    pv = pv < 0 ? 0 : (pv > clip_max ? clip_max : pv);
-    pix[(size_t)j * 2 + 0] = (int)pv;
-    pix[(size_t)j * 2 + 1] = (int)pu;
+    pix[(size_t)j * 2 + 0] = uv_pixel(uv[(size_t)j * 2 + 1], res, clip_max);
+    pix[(size_t)j * 2 + 1] = uv_pixel(uv[(size_t)j * 2 + 0], res, clip_max);
 }
 
 // paintPixels pass 1: highest point index covering a pixel owns it (the reference's
@@ -684,8 +649,8 @@ GENPC_API int genpc_get_uvs(int c, int n, const float *view, float focal, float 
     L.add(part, (size_t)c * kBoxSlices * 4);
     L.add_tail(keys, (size_t)c * 4);
     if (!ws_alloc(L, kWsGetUvs, st)) return 0;
-    const float A = (zfar + znear) / (znear - zfar);
-    const float B = (2.0f * zfar * znear) / (znear - zfar);
+    float A, B;
+    project_depth_constants(znear, zfar, A, B);
     const int have_box = (rescale || bbox) ? 1 : 0;
     // Pass 1 is arithmetic only (see above), pass 2 is bound by its stores and five divisions per pair.
     // (Running pass 1 of one camera group on a side stream under pass 2 of the previous one was measured in

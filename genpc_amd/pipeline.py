@@ -315,3 +315,61 @@ def complete_scans(jobs, lanes=2, cfg=None, dps=None, **kw):
         return complete_scan(*job, cfg=cfg, dp=own[li], **kw)
 
     return run_in_lanes(one, jobs, lanes, dev)
+
+
+def complete_scans_batched(jobs, cfg=None, dp=None, metric_points=16384, fused_points=20000, cd_only_pose=False, ragged_pose=False):
+    """``complete_scan`` for S scans with several scans per library call in every stage, on the caller's stream, no lanes:
+      stage 1   ``DepthPrompting.getDepths`` and ``ScaleAdapter.colorPoints`` (hidden-point removal stays one call per scan:
+                1024 views x 10000 points fill the chip already; everything after it is one call for all scans)
+      stage 2   ``reg_xyz.reg_tensors_scans`` with complete_scan's arguments (``ragged_pose=True``: the alignment loop of all
+                scans in one call too, with that function's caveat)
+      tail      ``reg_xyz.fuse_scans``, ONE ``fps_sampling_multi`` for all predictions and ground truths that reach
+                metric_points, one batched ``evaluate_scans``.
+    jobs: the tuples ``complete_scans`` takes, (partial_xyz, generated_xyz, generated_img[, gt_xyz]) -> a list of
+    complete_scan's dicts, in order.  Scan j's stage-1 products and point colours are the bits complete_scan gives; the rest
+    holds up to the caveats of the ragged stages (reg_tensors_scans, fuse_scans)."""
+    from .fps import fps_sampling_multi
+    jobs = [tuple(j) for j in jobs]
+    if not jobs:
+        return []
+    for k, job in enumerate(jobs):
+        if len(job) not in (3, 4):
+            raise ValueError("complete_scans_batched: jobs[%d] must be (partial_xyz, generated_xyz, generated_img[, gt_xyz])" % k)
+    s = len(jobs)
+    partials = [j[0] for j in jobs]
+    gts = [j[3] if len(j) == 4 else None for j in jobs]
+    cfg = cfg or default_cfg(partials[0].device)
+    dp = dp or DepthPrompting(cfg)
+    sa = ScaleAdapter(cfg)
+    gs = dp.getDepths([p.contiguous().float() for p in partials])
+    colors = sa.colorPoints([g["uv"] for g in gs], [j[2].contiguous().float() for j in jobs])
+    regs = reg_xyz.reg_tensors_scans(partials, [j[1] for j in jobs], generative_model=cfg.generative_model, dataset=cfg.dataset,
+                                     cd_inv_weight=0.5, diff_init=True, reg_fine_xyz=True, cd_only_pose=cd_only_pose,
+                                     ragged_pose=ragged_pose)
+    fused = reg_xyz.fuse_scans([r["source"] for r in regs], [r["target"] for r in regs], num_points=fused_points)
+    # ---- metric: main.metric (main.py:11-36) for the scans that bring a ground truth
+    with_gt = [j for j in range(s) if gts[j] is not None]
+    clouds = [fused[j] for j in with_gt] + [gts[j] for j in with_gt]
+    sampled = list(clouds)
+    big = [i for i, c in enumerate(clouds) if c.shape[0] >= metric_points]
+    if big:
+        for i, idx in zip(big, fps_sampling_multi([clouds[i] for i in big], [metric_points] * len(big))):
+            sampled[i] = clouds[i][idx.long()]
+    for i, c in enumerate(clouds):
+        if c.shape[0] < metric_points:
+            sampled[i] = fps_to(c, metric_points)              # (pad-repeat: no sampling)
+    metric = None
+    if with_gt:
+        m = len(with_gt)
+        metric = evaluate_scans(torch.stack(sampled[:m]).contiguous(), torch.stack(sampled[m:]).contiguous())
+    outs = []
+    for j in range(s):
+        g = gs[j]
+        out = dict(view=g["view_index"], used_opposite=g["used_opposite"], visible=g["visible"], uv=g["uv"], depth=g["depth"],
+                   pixels=g["pixels"], sparse_img=g["sparse_img"], sparse_depth=g["raw_depth"], hole_mask1=g["hole_mask1"],
+                   hole_mask2=g["hole_mask2"], point_colors=colors[j], reg=regs[j], fused=fused[j])
+        if gts[j] is not None:
+            i = with_gt.index(j)
+            out.update(pred_metric_points=sampled[i], gt_metric_points=sampled[len(with_gt) + i], metric=metric[i])
+        outs.append(out)
+    return outs

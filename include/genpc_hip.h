@@ -291,6 +291,46 @@ int genpc_paint_pixels(int res, int n, const int *pix, const float *colors, int 
 int genpc_gather_colors(int n, const int *pix, const float *img, int ch, int h,
                         int w, float *out, void *stream);
 
+/* Everything of DepthPrompting.getDepth (DepthPrompting.py:100-237) after hidden-point removal, for c scans of different sizes
+ * in one call (csrc/depth_prompt_ragged.hip).  off[c + 1]: HOST offsets, scan j owns the packed rows [off[j], off[j + 1]) of
+ * xyz[T,3] and rgb[T,3] (device).  cams[c,2,12]: per scan the chosen view matrix and the opposite one.  vis: bytes, scan j's
+ * block starts at 2 off[j] and is [2, n_j] -- what genpc_hpr_visibility writes for two eyes.  focal, znear, zfar, rescale and
+ * padmul as genpc_get_uvs takes them; res the image side, point_size and mask_pixel_rate as getRawDepth takes them.
+ * Per scan j: uv and depth through both cameras with the bits of genpc_get_uvs(2, n_j, ...) on that scan alone;
+ * sums[j][r] (double) = the sum of (double) depth over the points visible in row r, in the order written down in
+ * csrc/depth_prompt_ragged_plan.h, which depends on n_j alone (the same bits alone, anywhere in a batch, on every run; no
+ * floating-point atomics); chosen[j] = sums[j][0] >= sums[j][1] ? 0 : 1; uv[T,2], depth[T], pix[T,2] (genpc_uv_to_pixels with
+ * res and res - 1) and visible[T] (bytes) of the chosen row; images[c,4,3,res,res] = sparse_img, raw_depth, hole_mask1,
+ * hole_mask2 of getRawDepth over the chosen row's visible points, in the vertically flipped form paintPixels returns (on a
+ * pixel the highest point index wins; grey level 0.1 + 0.8 (1 - (d - dmin) / (dmax - dmin)) in float, every operation rounded
+ * on its own, dmin / dmax the exact extremes of the visible depths; masks per channel).  status[j] = 1, or -1 for a scan
+ * without points: nothing else of that scan is written and no other scan notices.
+ * Asynchronous on `stream`: ONE memset and FOUR launches whatever c is, the table in the kernel arguments, scratch from the
+ * library's workspace, integer atomics only, no copy, no read-back.  Returns 1 (c == 0 too); -1 with genpc_last_error set
+ * ("genpc_depth_prompt_ragged: ...") and nothing enqueued for c < 0, c > GENPC_DEPTH_PROMPT_RAGGED_MAX_SCANS, res outside
+ * [1, 4096], point_size or mask_pixel_rate < 1, point_size * mask_pixel_rate > 32, a null or ill-formed table, more than
+ * 2^28 points, 2 c res^2 > 2^28, or a null required pointer.                                                             */
+#define GENPC_DEPTH_PROMPT_RAGGED_MAX_SCANS 256
+int genpc_depth_prompt_ragged(int c, const int *off, const float *xyz, const float *rgb, const float *cams,
+                              const unsigned char *vis, float focal, float znear, float zfar, int rescale,
+                              float padmul, int res, int point_size, int mask_pixel_rate, float *uv, float *depth,
+                              int *pix, unsigned char *visible, int *chosen, double *sums, float *images,
+                              int *status, void *stream);
+
+/* What a genpc_depth_prompt_ragged call with this table and these settings does (csrc/depth_prompt_ragged_plan.h; no GPU is
+ * touched): out[0] = workgroups of the per-point launches, out[1] = kernels, out[2] = memsets, out[3] = scans refused for
+ * having no points, out[4] = the lowest of them (-1: none), out[5] = 32-bit words the memset fills, out[6] = scratch bytes.
+ * Returns 1; -1 with genpc_last_error set for out == NULL or a call genpc_depth_prompt_ragged refuses.                    */
+int genpc_depth_prompt_ragged_plan(int c, const int *off, int res, int point_size, int mask_pixel_rate,
+                                   long long out[7]);
+
+/* ScaleAdapter.colorPoint for c scans, each with its own image: imgs[c,ch,h,w]; uv[T,2] packed by the HOST table off[c + 1].
+ * One launch: per scan, pix (optional, [T,2]) has the bits of genpc_uv_to_pixels(res, clip_max) and out[T,ch] those of
+ * genpc_gather_colors on that scan and its image.  Returns 1; -1 with genpc_last_error set for c < 0, c > 256, a null or
+ * ill-formed table, more than 2^28 points, clip_max outside [0, min(h, w)), or a null required pointer.                  */
+int genpc_gather_colors_ragged(int c, const int *off, const float *uv, const float *imgs, int ch, int h, int w,
+                               float res, int clip_max, int *pix, float *out, void *stream);
+
 /* Replaces DepthPrompting.getVisiblePoints (DepthPrompting.py:273-290): open3d's
  * PointCloud.hidden_point_removal(camera, radius) for every viewpoint -- Katz' operator:
  * spherical flipping p' = v + 2 (radius - |v|) v / |v|, v = p - eye, then the vertices of

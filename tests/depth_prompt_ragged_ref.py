@@ -1,0 +1,73 @@
+"""The definition of genpc_depth_prompt_ragged on the CPU: per scan, DepthPrompting.getDepth after hidden-point removal, composed
+from the oracle's get_uvs, uv_to_pixels and get_raw_depth, with the visibility masks as arguments and the two sums taken with
+math.fsum (the correctly rounded sum: whatever order the library states, it lies within n 2^-53 relative of this one).
+gather_ref is ScaleAdapter.colorPoint's tensor form per scan.  Shared by the CPU definition test and the GPU tests."""
+import math
+
+import numpy as np
+
+# the batch of the GPU test: sizes, and which row each scan's masks favour (None: both rows random)
+SIZES = (1, 2, 257, 300, 5000)
+RES, RATE = 64, 3
+PADDING = 0.0            # the box fills the image: the stamps of 2 * 3 clip at the border
+
+
+def images_ref(O, uv, depth, rgb, vis, res, point_size, rate):
+    """One row's uv [n,2], depth [n], colours [n,3], visibility [n] -> pix [n,2] and the four images [4,3,res,res]."""
+    pix = O.uv_to_pixels(uv, res)
+    keep = np.asarray(vis) != 0
+    with np.errstate(all="ignore"):          # (one visible depth: 0 / 0, the NaN the per-scan path paints too)
+        imgs = O.get_raw_depth(pix[keep], depth[keep], np.ascontiguousarray(rgb[keep]), res, point_size, rate)
+    return pix, np.stack(imgs)
+
+
+def scan_ref(O, xyz, rgb, cams, masks, focal, rescale, padding, res, point_size, rate):
+    """cams [2,12], masks [2,n] bytes -> dict(uv, depth, pix, visible, chosen, sums, images) of one scan."""
+    uv2, d2, _, _ = O.get_uvs(np.asarray(cams, np.float32).reshape(2, 12), focal, xyz, rescale=rescale, padding=padding)
+    masks = np.asarray(masks).reshape(2, -1)
+    sums = tuple(math.fsum(float(x) for x in d2[r][masks[r] != 0]) for r in range(2))
+    ch = 0 if sums[0] >= sums[1] else 1
+    pix, imgs = images_ref(O, uv2[ch], d2[ch], rgb, masks[ch], res, point_size, rate)
+    return dict(uv=uv2[ch], depth=d2[ch], pix=pix, visible=(masks[ch] != 0).astype(np.uint8), chosen=ch, sums=sums, images=imgs,
+                depth_rows=d2)
+
+
+def batch_ref(O, clouds, rgbs, cams, masks, focal, rescale, padding, res, point_size, rate):
+    return [scan_ref(O, clouds[j], rgbs[j], cams[j], masks[j], focal, rescale, padding, res, point_size, rate) for j in range(len(clouds))]
+
+
+def gather_ref(O, uv, img, scale):
+    return O.gather_colors(O.uv_to_pixels(uv, scale), img)
+
+
+def margin_ok(sums, n):
+    """The decision margin: the two sums lie further apart than any summation order of n float32-or-better terms can move them."""
+    return abs(sums[0] - sums[1]) > n * 2.0 ** -22 * max(abs(sums[0]), abs(sums[1]))
+
+
+def make_batch(seed=11, sizes=SIZES, views=8):
+    """The GPU test's batch: seeded clouds inside the unit ball, colours with exact zeros in some channels, cameras from
+    create_cameras(num_views=8) (view j and its opposite), masks of seeded random bytes with point 0 visible in both rows.
+    Scan 2 has row 1 all ones and row 0 sparse, scan 3 the other way round, so both decisions occur."""
+    from genpc_amd.DepthPrompting import calculate_up_vector, fibonacci_sphere, look_at
+    rng = np.random.default_rng(seed)
+    eyes = fibonacci_sphere(views, 1.6)
+    clouds, rgbs, cams, masks = [], [], [], []
+    for j, n in enumerate(sizes):
+        p = rng.normal(size=(n, 3))
+        p = (p / np.maximum(np.linalg.norm(p, axis=1, keepdims=True), 1e-9) * rng.random((n, 1)) ** (1 / 3) * 0.5).astype(np.float32)
+        c = rng.random((n, 3), dtype=np.float32)
+        c[rng.random((n, 3)) < 0.1] = 0.0                       # a channel that is exactly 0 is background in that channel
+        e = eyes[(1 + 2 * j) % views]
+        cam = np.stack([look_at(e, np.zeros(3), calculate_up_vector(e, np.zeros(3))),
+                        look_at(-e, np.zeros(3), calculate_up_vector(-e, np.zeros(3)))]).astype(np.float32)
+        m = (rng.integers(0, 256, size=(2, n)) < 128).astype(np.uint8) * rng.integers(1, 256, size=(2, n)).astype(np.uint8)
+        if j == 2:
+            m[1] = 1
+            m[0] = (rng.random(n) < 0.05).astype(np.uint8)
+        if j == 3:
+            m[0] = 255
+            m[1] = (rng.random(n) < 0.05).astype(np.uint8)
+        m[:, 0] = 1
+        clouds.append(p); rgbs.append(c); cams.append(cam); masks.append(m)
+    return clouds, rgbs, cams, masks
