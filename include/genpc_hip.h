@@ -304,7 +304,10 @@ int genpc_gather_colors(int n, const int *pix, const float *img, int ch, int h,
  * hole_mask2 of getRawDepth over the chosen row's visible points, in the vertically flipped form paintPixels returns (on a
  * pixel the highest point index wins; grey level 0.1 + 0.8 (1 - (d - dmin) / (dmax - dmin)) in float, every operation rounded
  * on its own, dmin / dmax the exact extremes of the visible depths; masks per channel).  status[j] = 1, or -1 for a scan
- * without points: nothing else of that scan is written and no other scan notices.
+ * without points: nothing else of that scan is written and no other scan notices.  A scan that has points but none visible in a
+ * row has that row's sum 0.0 exactly; with none visible in either row chosen[j] = 0 (by >=), status[j] = 1, uv, depth and pix of
+ * row 0 are written as always, visible is all zero and the images are the paint of nothing: sparse_img = raw_depth =
+ * hole_mask1 = 0 and hole_mask2 = 1 in every channel (this library's definition: the reference's getDepth raises there).
  * Asynchronous on `stream`: ONE memset and FOUR launches whatever c is, the table in the kernel arguments, scratch from the
  * library's workspace, integer atomics only, no copy, no read-back.  Returns 1 (c == 0 too); -1 with genpc_last_error set
  * ("genpc_depth_prompt_ragged: ...") and nothing enqueued for c < 0, c > GENPC_DEPTH_PROMPT_RAGGED_MAX_SCANS, res outside

@@ -16,7 +16,14 @@ def images_ref(O, uv, depth, rgb, vis, res, point_size, rate):
     """One row's uv [n,2], depth [n], colours [n,3], visibility [n] -> pix [n,2] and the four images [4,3,res,res]."""
     pix = O.uv_to_pixels(uv, res)
     keep = np.asarray(vis) != 0
-    with np.errstate(all="ignore"):          # (one visible depth: 0 / 0, the NaN the per-scan path paints too)
+    if not keep.any():
+        # The paint of nothing.  This is THIS LIBRARY'S definition (include/genpc_hip.h): the reference's getDepth raises on a
+        # scan without a visible point (the extremes of no depths), and so does the oracle's get_raw_depth.  No owner on any
+        # pixel: the paints stay 0, so all_front = 0, all_back = back = 1, hole_mask1 = 255 ^ 255 = 0, hole_mask2 = 0 ^ 255 = 1.
+        imgs = np.zeros((4, 3, res, res), np.float32)
+        imgs[3] = 1.0
+        return pix, imgs
+    with np.errstate(all="ignore"):        # (one visible depth: 0 / 0, the NaN the per-scan path paints too)
         imgs = O.get_raw_depth(pix[keep], depth[keep], np.ascontiguousarray(rgb[keep]), res, point_size, rate)
     return pix, np.stack(imgs)
 
