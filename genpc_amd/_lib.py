@@ -37,7 +37,9 @@ SIGNATURES = {
     "genpc_chamfer_forward": (_i, [_i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "genpc_nm_distance": (_i, [_i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "genpc_nm_distance_ragged": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "genpc_nm_distance_within": (_i, [_i, _i, _vp, _i, _vp, _f, _vp, _vp, _vp]),
+    "genpc_nn_ragged_tune": (_i, [_i]),
+    "genpc_nn_ragged_dense_plan": (_i, [_i, _vp, _vp, _vp]),
+    "genpc_nm_distance_within":(_i, [_i, _i, _vp, _i, _vp, _f, _vp, _vp, _vp]),
     "genpc_chamfer_backward": (_i, [_i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "genpc_chamfer_backward_ragged": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "genpc_emd_forward": (_i, [_i, _i, _i] + [_vp] * 14 + [_f, _i, _vp]),
@@ -207,6 +209,37 @@ def require(t, dtype, name):
         raise TypeError("genpc_amd: %s must be %s, got %s" % (name, dtype, t.dtype))
     if not t.is_contiguous():
         raise ValueError("genpc_amd: %s must be contiguous" % name)
+
+
+NN_RAGGED_SEARCHES = {"grid": 0, "dense": 1}          # genpc_nn_ragged_tune's values
+
+
+def check_nn_ragged_search(kind, what="search"):
+    """None, "grid" or "dense"; anything else raises ValueError naming the two words (before any library call)."""
+    if kind is not None and (not isinstance(kind, str) or kind not in NN_RAGGED_SEARCHES):
+        raise ValueError('genpc_amd: %s must be None, "grid" or "dense", got %r' % (what, kind))
+    return kind
+
+
+class nn_ragged_search:
+    """Context manager over genpc_nn_ragged_tune: the calling thread's ragged nearest-neighbour search is `kind` ("grid": the
+    grid search, the library's default; "dense": all pairs, csrc/nn_ragged_dense.hip) inside the block and what it was behind
+    it, on an exception too.  None leaves the thread's mode alone."""
+
+    def __init__(self, kind, what="search"):
+        self.kind = check_nn_ragged_search(kind, what)
+        self.prev = None
+
+    def __enter__(self):
+        if self.kind is not None:
+            self.prev = lib.genpc_nn_ragged_tune(NN_RAGGED_SEARCHES[self.kind])
+        return self
+
+    def __exit__(self, *exc):
+        if self.prev is not None:
+            lib.genpc_nn_ragged_tune(self.prev)
+            self.prev = None
+        return False
 
 
 def thread_state():

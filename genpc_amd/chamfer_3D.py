@@ -68,10 +68,13 @@ def _host_offsets(off, name):
     return (ctypes.c_int * len(off))(*off), off
 
 
-def nm_distance_ragged(xyz, noff, xyz2, moff, result, result_i):
+def nm_distance_ragged(xyz, noff, xyz2, moff, result, result_i, search=None):
     """nm_distance over a ragged batch (genpc_nm_distance_ragged): pair j has the queries xyz[noff[j]:noff[j+1]] and the
     targets xyz2[moff[j]:moff[j+1]]; xyz [N,3], xyz2 [M,3], result [N], result_i [N] packed in pair order, result_i
-    counted inside the pair's own targets.  noff, moff: c + 1 ints each, Python sequences or CPU int tensors."""
+    counted inside the pair's own targets.  noff, moff: c + 1 ints each, Python sequences or CPU int tensors.
+    search: None leaves the calling thread's ragged search alone (the grid search unless genpc_nn_ragged_tune was called);
+    "grid" or "dense" (all pairs, csrc/nn_ragged_dense.hip: the same bits) holds for this call and is restored behind it."""
+    _lib.check_nn_ragged_search(search)
     _lib.check_tensors((("xyz", xyz), ("xyz2", xyz2), ("result", result)), (("result_i", result_i),))
     na, nl = _host_offsets(noff, "noff")
     ma, ml = _host_offsets(moff, "moff")
@@ -83,8 +86,9 @@ def nm_distance_ragged(xyz, noff, xyz2, moff, result, result_i):
             raise ValueError("genpc_amd: %s must be [%d,3] (the last offset), got %s" % (name, rows, tuple(t.shape)))
     if result.numel() != nl[-1] or result_i.numel() != nl[-1]:
         raise ValueError("genpc_amd: result and result_i must hold noff[-1] = %d elements" % nl[-1])
-    return _lib.on_device_of(xyz, _L.genpc_nm_distance_ragged, len(nl) - 1, ctypes.cast(na, ctypes.c_void_p), _p(xyz),
-                             ctypes.cast(ma, ctypes.c_void_p), _p(xyz2), _p(result), _p(result_i))
+    with _lib.nn_ragged_search(search):
+        return _lib.on_device_of(xyz, _L.genpc_nm_distance_ragged, len(nl) - 1, ctypes.cast(na, ctypes.c_void_p), _p(xyz),
+                                 ctypes.cast(ma, ctypes.c_void_p), _p(xyz2), _p(result), _p(result_i))
 
 
 def backward_ragged(xyz1, noff, xyz2, moff, gradxyz1, gradxyz2, graddist1, graddist2, idx1, idx2):

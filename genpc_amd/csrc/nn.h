@@ -6,6 +6,7 @@
 #include "grid.h"
 #include "nn_plan.h"      // kChunk, kBlock, kMaxLists, kHTile, kFQ; NNPlan
 #include "nn_decode.h"    // NNDiv; which (query block, batch element, slice) a block is
+#include "nn_ragged_dense_plan.h"      // the all-pairs ragged search: its constants and NnRaggedDensePlan
 
 namespace genpc {
 
@@ -416,5 +417,11 @@ struct NnRaggedGrids {
 void nn_ragged_grids_layout(WsLayout &L, NnRaggedGrids &g, const RaggedTable &t);      // the pieces behind whatever L holds (g stays put until L is bound)
 int nn_ragged_build(const RaggedTable &t, int max_targets, const float *xyz2, const NnRaggedGrids &g, hipStream_t st);
 int nn_ragged_search(const RaggedTable &t, const float *xyz, const NnRaggedGrids &g, float *result, int *result_i, hipStream_t st);
+// The same answers by all pairs (nn_ragged_dense.hip): one launch on the packed, unsorted targets, no grid and no workspace; its
+// cost is n_j m_j wherever the points lie.  The caller has asked nn_ragged_dense_plan and refused what it refuses (0, with the
+// error recorded, for a table it refuses all the same).  t_nn_ragged_dense: the calling thread's choice between the two for
+// every ragged nearest-neighbour search (genpc_nn_ragged_tune; 0 the grid, the default).
+int nn_ragged_dense(const RaggedTable &t, const float *queries, const float *targets, float *d, int *i, hipStream_t st);
+extern thread_local int t_nn_ragged_dense;
 
 }  // namespace genpc

@@ -120,5 +120,9 @@ GENPC_API int genpc_nm_distance_ragged(int c, const int *noff, const float *xyz,
         set_error("genpc_nm_distance_ragged: null pointer");
         return -1;
     }
+    if (t_nn_ragged_dense) {          // the thread's choice (genpc_nn_ragged_tune): all pairs, one launch, no workspace (nn_ragged_dense.hip)
+        if (const char *why = nn_ragged_dense_plan(t).too_large) return ragged_refuse("genpc_nm_distance_ragged", why);
+        return nn_ragged_dense(t, xyz, xyz2, result, result_i, (hipStream_t)stream);
+    }
     return nn_ragged(t, max_targets, xyz, xyz2, result, result_i, (hipStream_t)stream);
 }

@@ -25,7 +25,8 @@
 //                           best-of-starts bookkeeping
 // S scans of DIFFERENT sizes run through the same kernels in one call (genpc_pose_optimize_ragged, at the end of this file): every
 // per-point kernel takes an optional element table (pose.h pose_span), the call's shape is pose_ragged_plan.h's -- one stream, the
-// update a launch of its own, nearest neighbours from nn_ragged.hip's grid search -- and its two own kernels are pose_ragged.hip's.
+// update a launch of its own, nearest neighbours from nn_ragged.hip's grid search or, on request, nn_ragged_dense.hip's all-pairs
+// search -- and its two own kernels are pose_ragged.hip's.
 // HBM traffic per iteration is O(N): ~24 B/point for the transform, ~28 B/point for
 // the gradient pass; the NN launch dominates (VALU-bound, see chamfer.hip).
 #include "nn.h"
@@ -919,9 +920,14 @@ static int pose_ragged_step(const PoseRaggedPlan &plan, const PoseRaggedTables &
                             int render_size, const MaskScratch &m, double *accum, hipStream_t st)
 {
     const int b = plan.elements;
-    if (nn_ragged_search(T.fwd, x.pts, grid_partial, x.d1, x.i1, st) != 1) return 0;
-    if (nn_ragged_build(T.bwd, plan.nc_max, x.pts, grid_posed, st) != 1) return 0;
-    if (nn_ragged_search(T.bwd, partial, grid_posed, x.d2, x.i2, st) != 1) return 0;
+    if (plan.nn_dense) {              // all pairs: two launches on the clouds as they lie, no grid (the same bits)
+        if (nn_ragged_dense(T.fwd, x.pts, partial, x.d1, x.i1, st) != 1) return 0;
+        if (nn_ragged_dense(T.bwd, partial, x.pts, x.d2, x.i2, st) != 1) return 0;
+    } else {
+        if (nn_ragged_search(T.fwd, x.pts, grid_partial, x.d1, x.i1, st) != 1) return 0;
+        if (nn_ragged_build(T.bwd, plan.nc_max, x.pts, grid_posed, st) != 1) return 0;
+        if (nn_ragged_search(T.bwd, partial, grid_posed, x.d2, x.i2, st) != 1) return 0;
+    }
     PoseGradArgs pga{};
     if (plan.ride) {
         pga.nc = plan.nc_max; pga.cstride = cstride; pga.pstride = pstride; pga.np = plan.np_max;
@@ -963,6 +969,14 @@ static bool pose_ragged_grids(const PoseRaggedTables &T, NnRaggedGrids &grid_par
     return ws_alloc(LP, kWsPoseRaggedGridPartial, st) && ws_alloc(LC, kWsPoseRaggedGridPosed, st);
 }
 
+// What the all-pairs search refuses of a planned call (nn_ragged_dense_plan.h: both directions count the same pair evaluations,
+// and each side is the other's targets), by the entry point's name; null when it takes the call.
+static const char *pose_ragged_dense_refusal(const PoseRaggedTables &T)
+{
+    if (const char *why = nn_ragged_dense_plan(T.fwd).too_large) return why;
+    return nn_ragged_dense_plan(T.bwd).too_large;
+}
+
 }  // namespace genpc
 
 GENPC_API int genpc_pose_ragged_plan(int c, const int *coff, const int *poff, int starts, int mask, int render_size, float radius, int cus,
@@ -1000,11 +1014,14 @@ GENPC_API int genpc_pose_loss_grad_ragged(int c, const int *coff, const int *pof
     PoseRaggedAsk ask;
     ask.c = c; ask.coff = coff; ask.poff = poff; ask.starts = 1; ask.mask = mask; ask.render_size = render_size; ask.radius = radius;
     ask.cus = num_cus();
+    ask.nn_dense = t_nn_ragged_dense;
     const PoseRaggedPlan plan = pose_ragged_plan(ask);
     if (plan.too_large) return ragged_refuse(fn, plan.too_large);
     if (!v || !center || !params || !partial || !loss_out || !grad) return ragged_refuse(fn, "null pointer");
     PoseRaggedTables T;
     pose_ragged_fill(c, coff, poff, 1, T);
+    if (plan.nn_dense)
+        if (const char *why = pose_ragged_dense_refusal(T)) return ragged_refuse(fn, why);
     const int b = plan.elements;
 
     const size_t P = mask ? (size_t)render_size * render_size : 0;
@@ -1018,7 +1035,7 @@ GENPC_API int genpc_pose_loss_grad_ragged(int c, const int *coff, const int *pof
     if (mask) m.layout(L, b, P, (size_t)plan.nmax_piece);
     if (!ws_alloc(L, kWsPoseRaggedStep, st)) return 0;
     NnRaggedGrids grid_partial{}, grid_posed{};
-    if (!pose_ragged_grids(T, grid_partial, grid_posed, st)) return 0;
+    if (!plan.nn_dense && !pose_ragged_grids(T, grid_partial, grid_posed, st)) return 0;          // (all pairs: neither slot is taken)
     if (mask && !m.zero_bins(st)) return 0;
     constexpr int kStateFloats = (int)(sizeof(PoseState) / sizeof(float));
     if (!check(hipMemsetAsync(accum, 0, (size_t)b * kAcc * sizeof(double), st), "hipMemsetAsync(accum)")) return 0;
@@ -1028,7 +1045,7 @@ GENPC_API int genpc_pose_loss_grad_ragged(int c, const int *coff, const int *pof
     if (!pose_ragged_tables(T.fwd, x.coff_e, x.poff_e, st)) return 0;
     // the order of genpc_pose_loss_grad_batch: reference images first (they project through the scratch the transform then fills)
     if (mask && !mask_prepare_ref(b, plan.np_max, partial, partial_col, radius, render_size, m, st, x.poff_e)) return 0;
-    if (nn_ragged_build(T.fwd, plan.np_max, partial, grid_partial, st) != 1) return 0;
+    if (!plan.nn_dense && nn_ragged_build(T.fwd, plan.np_max, partial, grid_partial, st) != 1) return 0;
     pose_ragged_transform(plan, x, v, center, 3, S->params, kStateFloats, mask, radius, render_size, m, st);
     if (!pose_ragged_step(plan, T, x, grid_partial, grid_posed, v, vert_col, partial, center, 3, S->params, kStateFloats, cd_weight, mask_weight, radius,
                           render_size, m, accum, st))
@@ -1057,11 +1074,14 @@ GENPC_API int genpc_pose_optimize_ragged(int c, const int *coff, const int *poff
     PoseRaggedAsk ask;
     ask.c = c; ask.coff = coff; ask.poff = poff; ask.starts = starts; ask.mask = mask; ask.render_size = render_size; ask.radius = radius;
     ask.cus = num_cus();
+    ask.nn_dense = t_nn_ragged_dense;
     const PoseRaggedPlan plan = pose_ragged_plan(ask);
     if (plan.too_large) return ragged_refuse(fn, plan.too_large);
     if (!complete || !partial || !transform) return ragged_refuse(fn, "null pointer");
     PoseRaggedTables T;
     pose_ragged_fill(c, coff, poff, starts, T);
+    if (plan.nn_dense)
+        if (const char *why = pose_ragged_dense_refusal(T)) return ragged_refuse(fn, why);
     const int b = plan.elements;
 
     // every cloud once per start, packed by the element tables (as pose_replicate does for equal sizes); the pointers move there
@@ -1092,7 +1112,7 @@ GENPC_API int genpc_pose_optimize_ragged(int c, const int *coff, const int *poff
     if (mask) m.layout(L, b, P, (size_t)plan.nmax_piece);
     if (!ws_alloc(L, kWsPoseRaggedLoop, st)) return 0;
     NnRaggedGrids grid_partial{}, grid_posed{};
-    if (!pose_ragged_grids(T, grid_partial, grid_posed, st)) return 0;
+    if (!plan.nn_dense && !pose_ragged_grids(T, grid_partial, grid_posed, st)) return 0;          // (all pairs: neither slot is taken)
     if (mask && !m.zero_bins(st)) return 0;
     constexpr int kStateFloats = (int)(sizeof(PoseState) / sizeof(float));
     if (!pose_ragged_tables(T.fwd, x.coff_e, x.poff_e, st)) return 0;
@@ -1100,7 +1120,7 @@ GENPC_API int genpc_pose_optimize_ragged(int c, const int *coff, const int *poff
     // center = mean(vert_pos) per element (diff_obj_pose.py:362); the reference images; the partial clouds' grids: once per call
     if (!genpc_mean3(b, plan.nc_max, complete, center, accum, st, x.coff_e)) return 0;
     if (mask && !mask_prepare_ref(b, plan.np_max, partial, partial_col, radius, render_size, m, st, x.poff_e)) return 0;
-    if (nn_ragged_build(T.fwd, plan.np_max, partial, grid_partial, st) != 1) return 0;
+    if (!plan.nn_dense && nn_ragged_build(T.fwd, plan.np_max, partial, grid_partial, st) != 1) return 0;
 
     hipLaunchKernelGGL(pose_begin_kernel, dim3(plan.gb), dim3(64), 0, st, b, S, accum, -1, 0);
     hipLaunchKernelGGL(pose_begin_kernel, dim3(plan.gb), dim3(64), 0, st, b, S, accum, 0, starts);

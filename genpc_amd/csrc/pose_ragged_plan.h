@@ -5,7 +5,7 @@
 // The ragged loop is the SIMPLE form of pose_plan.h's loop: one stream (no side stream, no device-counter hand-over: no kernel
 // of the call waits for another), the Adam update a launch of its own (the fused form is for <= 8 elements), nearest neighbours
 // from nn_ragged.hip's grid search in both directions (the MFMA filter, the seeded search and the duplicate masks need equal
-// sizes).  What it shares with pose_loop_plan -- pose_grad riding in the silhouette gradient's launch, pose_grad's block cap,
+// sizes) or, where the calling thread asks for it, from nn_ragged_dense.hip's all-pairs search (nn_dense: the same bits).  What it shares with pose_loop_plan -- pose_grad riding in the silhouette gradient's launch, pose_grad's block cap,
 // the widths of the one-thread-per-element kernels -- it asks of pose_loop_plan, for `elements` clouds of the largest sizes.
 // Element e = scan * starts + start owns starts-fold replicated points: its complete cloud lies at starts * coff[scan] +
 // start * nc_scan of the packed element arrays (partial alike), so the element tables ascend and are valid RaggedTables.
@@ -27,6 +27,7 @@ struct PoseRaggedAsk {
     int render_size = 0;
     float radius = 0.0f;
     int cus = 256;                    // compute units of the device (reported only: no width depends on it)
+    int nn_dense = 0;                 // the calling thread's ragged search (genpc_nn_ragged_tune): 0 the grid search, 1 all pairs
 };
 
 struct PoseRaggedPlan {
@@ -44,6 +45,7 @@ struct PoseRaggedPlan {
     MaskStepPlan step;                // gp, gs as mask_step_plan has them; fuse_w and sub8 from the totals (the mean element)
     int nmax_piece;                   // per-element count that sizes MaskScratch's uvr / zex: elements x this >= both totals
     int blocks_per_cu;                // the transform launch's blocks per compute unit, rounded up (a figure, not a decision)
+    int nn_dense;                     // nearest neighbours by all pairs (nn_ragged_dense.hip): two launches a step, no grid built or kept
 };
 
 // element tables of a call: e = scan * starts + start
@@ -76,6 +78,7 @@ inline PoseRaggedPlan pose_ragged_plan(const PoseRaggedAsk &a)
         return p;
     }
     p.replicate = a.starts > 1;
+    p.nn_dense = a.nn_dense != 0;
     if (p.elements == 0) return p;
 
     // what the equal-size loop decides for `elements` clouds on one stream: taken over, not restated

@@ -13,25 +13,27 @@ from ... import _lib, chamfer_3D
 from ..._ragged import _is_offsets, chunks, pack_clouds          # (both names are read from here too)
 
 
-def _one_way(q, qoff, t, toff):
+def _one_way(q, qoff, t, toff, search=None):
     """Queries against targets, at most chamfer_3D.RAGGED_MAX_PAIRS pairs per library call (a longer list takes several)."""
     dist = torch.empty((q.shape[0],), dtype=torch.float32, device=q.device)
     idx = torch.empty((q.shape[0],), dtype=torch.int32, device=q.device)
     for a, b, qa, ta in chunks(chamfer_3D.RAGGED_MAX_PAIRS, qoff, toff):
         q0, q1, t0, t1 = qoff[a], qoff[b], toff[a], toff[b]
-        rc = chamfer_3D.nm_distance_ragged(q[q0:q1], qa, t[t0:t1], ta, dist[q0:q1], idx[q0:q1])
+        rc = chamfer_3D.nm_distance_ragged(q[q0:q1], qa, t[t0:t1], ta, dist[q0:q1], idx[q0:q1], search=search)
         if rc != 1:
             raise RuntimeError("chamfer_3D.nm_distance_ragged failed: " + _lib.last_error())
     return dist, idx
 
 
-def chamfer_ragged(clouds1, clouds2):
+def chamfer_ragged(clouds1, clouds2, search=None):
     """Pair j: clouds1[j] [N_j,3] against clouds2[j] [M_j,3], float32 GPU tensors; each side a list, or packed as
     (points, offsets).  Returns (dist1, dist2, idx1, idx2, offsets1, offsets2): dist1 / idx1 packed like clouds1 -- the
     squared distance from each of its points to the nearest point of the pair's clouds2[j] and that point's index INSIDE
     clouds2[j] -- dist2 / idx2 the converse; offsets as int64 CPU tensors of c + 1 entries.  Per pair the bits of
     chamfer_3DDist on that pair alone, for finite clouds; a pair with an empty cloud on one side only is an error.
-    Forward only."""
+    Forward only.  search: None (the calling thread's ragged search, the grid search by default), "grid" or "dense" (all
+    pairs, the same bits) for both directions of this call."""
+    _lib.check_nn_ragged_search(search)
     p1, off1 = pack_clouds(clouds1, "clouds1")
     p2, off2 = pack_clouds(clouds2, "clouds2")
     if len(off1) != len(off2):
@@ -42,8 +44,8 @@ def chamfer_ragged(clouds1, clouds2):
     _lib.require_gpu(p1, p2)
     if p1.device != p2.device:
         raise ValueError("chamfer_ragged: clouds1 and clouds2 are on different devices")
-    dist1, idx1 = _one_way(p1, off1, p2, off2)
-    dist2, idx2 = _one_way(p2, off2, p1, off1)
+    dist1, idx1 = _one_way(p1, off1, p2, off2, search)
+    dist2, idx2 = _one_way(p2, off2, p1, off1, search)
     return dist1, dist2, idx1, idx2, torch.tensor(off1, dtype=torch.int64), torch.tensor(off2, dtype=torch.int64)
 
 

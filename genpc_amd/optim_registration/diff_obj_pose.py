@@ -259,13 +259,16 @@ def _ragged_colours(cols, points, off, fn, name):
 
 
 def pose_loss_grad_ragged(vert_pos, center, params, partial, radius, render_size=224, cd_weight=3.0, reg_weight=0.001,
-                          mask_weight=1.0, vert_col=None, partial_col=None):
+                          mask_weight=1.0, vert_col=None, partial_col=None, nn_search=None):
     """pose_loss_grad_batch for c elements of DIFFERENT sizes in one call (genpc_pose_loss_grad_ragged): vert_pos / partial are
     lists of [N_j,3] GPU tensors or packed (points, offsets), center [c,3], params [c,10], vert_col / partial_col None or lists
     with one entry per element -> (loss[c,4], grad[c,10]).  The launches are one step of object_pose_optimization_scans' loop;
-    no Adam step is taken.  mask_weight = 0: the Chamfer-only objective.  More than 384 elements go in several calls."""
+    no Adam step is taken.  mask_weight = 0: the Chamfer-only objective.  More than 384 elements go in several calls.
+    nn_search: None (the calling thread's ragged search, the grid search by default), "grid" or "dense" (all pairs: the same
+    bits) for the step's two nearest-neighbour searches."""
     from .. import _ragged
     fn = "pose_loss_grad_ragged"
+    _lib.check_nn_ragged_search(nn_search, "nn_search")
     cpts, coff = _ragged_clouds(vert_pos, fn, "vert_pos", "complete")
     ppts, poff = _ragged_clouds(partial, fn, "partial", "partial")
     c = len(coff) - 1
@@ -282,17 +285,18 @@ def pose_loss_grad_ragged(vert_pos, center, params, partial, radius, render_size
     for a, b, co, po in _ragged.chunks(RAGGED_MAX_ELEMENTS, coff, poff):
         _, cp = _ragged.host_ints(co, "coff")
         _, pp = _ragged.host_ints(po, "poff")
-        rc = _lib.on_device_of(cpts, _L.genpc_pose_loss_grad_ragged, b - a, cp, pp, _p(cpts[coff[a]:coff[b]]),
-                               _p(None if vc is None else vc[coff[a]:coff[b]]), _p(center[a:b]), _p(params[a:b]), _p(ppts[poff[a]:poff[b]]),
-                               _p(None if pc is None else pc[poff[a]:poff[b]]), float(cd_weight), float(reg_weight), float(mask_weight),
-                               float(radius), int(render_size), _p(loss[a:b]), _p(grad[a:b]))
+        with _lib.nn_ragged_search(nn_search, "nn_search"):
+            rc = _lib.on_device_of(cpts, _L.genpc_pose_loss_grad_ragged, b - a, cp, pp, _p(cpts[coff[a]:coff[b]]),
+                                   _p(None if vc is None else vc[coff[a]:coff[b]]), _p(center[a:b]), _p(params[a:b]), _p(ppts[poff[a]:poff[b]]),
+                                   _p(None if pc is None else pc[poff[a]:poff[b]]), float(cd_weight), float(reg_weight), float(mask_weight),
+                                   float(radius), int(render_size), _p(loss[a:b]), _p(grad[a:b]))
         if rc != 1:
             raise RuntimeError("genpc_pose_loss_grad_ragged failed (rc=%d): %s" % (rc, _lib.last_error()))
     return loss, grad
 
 
 def object_pose_optimization_scans(completes, partials, radius=0.005, lr=0.005, iters=300, render_size=224, cam_bias_num=4,
-                                   return_history=False, cd_only=False, complete_cols=None, partial_cols=None):
+                                   return_history=False, cd_only=False, complete_cols=None, partial_cols=None, nn_search=None):
     """object_pose_optimization's tensor form for S scans of DIFFERENT sizes in one call (genpc_pose_optimize_ragged): completes /
     partials are lists of [N_j,3] GPU tensors or packed (points, offsets), complete_cols / partial_cols None or lists with one
     entry per scan (an entry may be None = white).  Returns a list of S 4x4 numpy ``[[sR, t],[0,1]]``; with return_history
@@ -300,9 +304,13 @@ def object_pose_optimization_scans(completes, partials, radius=0.005, lr=0.005, 
     object_pose_optimization on scan j alone up to the summation order of its gradient (tests/test_gpu_pose_ragged_loop.py).
     The starts run side by side as batch elements; a library call holds 384 of them (96 scans at 4 starts), a longer list goes
     in several calls (pose_scan_chunks); ONE read-back at the end.  A CPU tensor, lists of different lengths, a colour list of
-    the wrong length or shape and an empty cloud raise, naming the scan."""
+    the wrong length or shape and an empty cloud raise, naming the scan.
+    nn_search: None (the calling thread's ragged search, the grid search by default), "grid" or "dense" -- every step's two
+    nearest-neighbour searches by all pairs (csrc/nn_ragged_dense.hip): the same bits, at a cost that does not depend on how
+    well a start is aligned, and no grid is built."""
     from .. import _ragged
     fn = "object_pose_optimization_scans"
+    _lib.check_nn_ragged_search(nn_search, "nn_search")
     cpts, coff = _ragged_clouds(completes, fn, "completes", "complete")
     ppts, poff = _ragged_clouds(partials, fn, "partials", "partial")
     s = len(coff) - 1
@@ -325,10 +333,11 @@ def object_pose_optimization_scans(completes, partials, radius=0.005, lr=0.005, 
         pp = torch.empty(b - a, 10, device=cpts.device)
         _, cp = _ragged.host_ints([v - coff[a] for v in coff[a:b + 1]], "coff")
         _, pq = _ragged.host_ints([v - poff[a] for v in poff[a:b + 1]], "poff")
-        rc = _lib.on_device_of(cpts, _L.genpc_pose_optimize_ragged, b - a, cp, pq, _p(cpts[coff[a]:coff[b]]),
-                               _p(None if cc is None else cc[coff[a]:coff[b]]), _p(ppts[poff[a]:poff[b]]),
-                               _p(None if pc is None else pc[poff[a]:poff[b]]), float(lr), iters, starts, float(radius), int(render_size),
-                               0.0 if cd_only else 1.0, _p(tt), _p(hh), _p(pp))
+        with _lib.nn_ragged_search(nn_search, "nn_search"):
+            rc = _lib.on_device_of(cpts, _L.genpc_pose_optimize_ragged, b - a, cp, pq, _p(cpts[coff[a]:coff[b]]),
+                                   _p(None if cc is None else cc[coff[a]:coff[b]]), _p(ppts[poff[a]:poff[b]]),
+                                   _p(None if pc is None else pc[poff[a]:poff[b]]), float(lr), iters, starts, float(radius), int(render_size),
+                                   0.0 if cd_only else 1.0, _p(tt), _p(hh), _p(pp))
         if rc != 1:
             raise RuntimeError("genpc_pose_optimize_ragged failed (rc=%d): %s" % (rc, _lib.last_error()))
         T[a:b], hist[a:b], bp[a:b] = tt, hh, pp

@@ -845,7 +845,7 @@ def _voxel_grids(clouds, voxel_size, cols=None):
 
 def reg_tensors_scans(partials, completes, generative_model="trellis", dataset="redwood", cd_inv_weight=0.5, diff_init=True,
                       reg_fine_xyz=False, pose_voxel=0.02, cd_only_pose=False, partial_cols=None, complete_cols=None,
-                      diff_transforms=None, ragged_pose=False):
+                      diff_transforms=None, ragged_pose=False, nn_search=None):
     """``reg_tensors`` for S scans at once: partials / completes are lists of [N_j,3] / [M_j,3] GPU tensors, partial_cols /
     complete_cols / diff_transforms None or lists with one entry per scan (an entry may be None); the other arguments are
     ``reg_tensors``' and hold for every scan.  Returns a list of ``reg_tensors``' dicts, same keys.  The stages:
@@ -853,7 +853,8 @@ def reg_tensors_scans(partials, completes, generative_model="trellis", dataset="
                    given); ``object_pose_optimization`` then runs PER SCAN, unchanged (the default), or -- ``ragged_pose=True`` --
                    the scans that need a pose go through ONE ``object_pose_optimization_scans`` call on the same grids (the
                    ragged alignment loop: the same objective per scan, its gradient summed in another order, so the 200
-                   steps agree with the per-scan path in their first steps and in what they converge to, not bit for bit).
+                   steps agree with the per-scan path in their first steps and in what they converge to, not bit for bit);
+                   ``nn_search`` (None, "grid" or "dense") is handed to that call and means nothing without ``ragged_pose``.
                    Entries of diff_transforms that are given are used as they are.
       glue         ``_apply``, ``normalize_numpy`` and the instantmesh rotation are ``reg_tensors``' own statements per scan, so
                    every ragged stage receives the bits ``reg_tensors`` feeds its single-scan stage.
@@ -867,6 +868,7 @@ def reg_tensors_scans(partials, completes, generative_model="trellis", dataset="
     the one-workgroup plan)."""
     from .optim_registration.diff_obj_pose import object_pose_optimization, object_pose_optimization_scans
     fn = "reg_tensors_scans"
+    _lib.check_nn_ragged_search(nn_search, "nn_search")
     if not isinstance(partials, (list, tuple)) or not isinstance(completes, (list, tuple)):
         raise TypeError("%s: partials and completes are lists of [N,3] tensors" % fn)
     s = len(partials)
@@ -897,7 +899,7 @@ def reg_tensors_scans(partials, completes, generative_model="trellis", dataset="
             if ragged_pose:
                 n = len(need)
                 Ts = object_pose_optimization_scans(down[:n], down[n:], radius=0.02, lr=0.01, iters=200, render_size=224, cd_only=cd_only_pose,
-                                                    complete_cols=dcol[:n], partial_cols=dcol[n:])
+                                                    complete_cols=dcol[:n], partial_cols=dcol[n:], nn_search=nn_search)
                 for i, j in enumerate(need):
                     diffs[j] = np.linalg.inv(Ts[i].astype(np.float64))
             for i, j in enumerate([] if ragged_pose else need):
@@ -948,7 +950,7 @@ def reg_tensors_scans(partials, completes, generative_model="trellis", dataset="
     return outs
 
 
-def reg_scans(cfg, flags, cd_inv_weight=0.5, diff_init=True, reg_fine_xyz=False, seed=None, ragged_pose=False, **kwargs):
+def reg_scans(cfg, flags, cd_inv_weight=0.5, diff_init=True, reg_fine_xyz=False, seed=None, ragged_pose=False, nn_search=None, **kwargs):
     """The file form of ``reg`` for a list of flags: returns a list of ``reg``'s dicts and writes every ``{flag}_fused.ply`` WITH
     COLOURS.  Every flag's two input files are checked first: a missing one raises FileNotFoundError naming it before any work.
     With an int ``seed`` ONE draw of 163 840 samples per mesh serves both of ``reg``'s samplings, all meshes in one
@@ -956,7 +958,8 @@ def reg_scans(cfg, flags, cd_inv_weight=0.5, diff_init=True, reg_fine_xyz=False,
     with their colours (one ``voxel_down_sample_clouds`` call for all meshes), ARE the cloud ``object_pose_optimization``'s file
     form builds.  The partial cloud of the pose comes through ``load_point_cloud`` and the pose runs in tensor form on those
     tensors, per flag (the default), or -- ``ragged_pose=True`` -- for all flags in ONE ``object_pose_optimization_scans`` call on the
-    same clouds (the ragged alignment loop; the switch is handed on to ``reg_tensors_scans``).  With ``seed=None`` the host sampler runs per flag, as in
+    same clouds (the ragged alignment loop; the switch is handed on to ``reg_tensors_scans``, and so is ``nn_search`` -- None, "grid" or
+    "dense": that call's nearest-neighbour search).  With ``seed=None`` the host sampler runs per flag, as in
     ``reg`` (``rng=`` included).  Then ``reg_tensors_scans`` and ``fuse_scans`` with ``reg``'s parameters.  The pose's
     debugging files in the working directory (``partial.png``, ``partial_mask.png``, ``final_transform.npy``) are NOT written.
     kwargs: ``cd_only_pose`` and ``rng``, as in ``reg``; anything else raises."""
@@ -965,6 +968,7 @@ def reg_scans(cfg, flags, cd_inv_weight=0.5, diff_init=True, reg_fine_xyz=False,
     from .utils.dataUtils import read_ply, save_ply_xyzrgb
     from .utils.mesh_io import glb2point, load_glb, sample_surfaces_gpu
     _check_file_form_options("reg_scans(cfg, flags, ...)", "it", seed, kwargs)
+    _lib.check_nn_ragged_search(nn_search, "nn_search")
     if isinstance(flags, str) or not isinstance(flags, (list, tuple)):
         raise TypeError("reg_scans(cfg, flags, ...): flags is a list of flags")
     path = cfg.output_path
@@ -1007,7 +1011,8 @@ def reg_scans(cfg, flags, cd_inv_weight=0.5, diff_init=True, reg_fine_xyz=False,
         if ragged_pose:
             Ts = object_pose_optimization_scans([q[0] for q in pose_clouds], [q[2] for q in pose_clouds], radius=0.02, lr=0.01, iters=200,
                                                 render_size=224, cd_only=kwargs.get("cd_only_pose", False),
-                                                complete_cols=[q[1] for q in pose_clouds], partial_cols=[q[3] for q in pose_clouds])
+                                                complete_cols=[q[1] for q in pose_clouds], partial_cols=[q[3] for q in pose_clouds],
+                                                nn_search=nn_search)
             diffs = [np.linalg.inv(T.astype(np.float64)) for T in Ts]
     sxyz, scol = [], []
     for j in range(s):
@@ -1022,7 +1027,7 @@ def reg_scans(cfg, flags, cd_inv_weight=0.5, diff_init=True, reg_fine_xyz=False,
         scol.append(torch.as_tensor(col, dtype=torch.float32, device=dev))
     outs = reg_tensors_scans(sxyz, txyz, generative_model=cfg.generative_model, dataset=getattr(cfg, "dataset", "redwood"),
                              cd_inv_weight=cd_inv_weight, diff_init=diff_init, reg_fine_xyz=reg_fine_xyz, partial_cols=scol,
-                             complete_cols=tcol, diff_transforms=diffs if diff_init else None, ragged_pose=ragged_pose)
+                             complete_cols=tcol, diff_transforms=diffs if diff_init else None, ragged_pose=ragged_pose, nn_search=nn_search)
     fused = fuse_scans([o["source"] for o in outs], [o["target"] for o in outs], num_points=20000, distance_threshold=0.0001,
                        std_ratio=2.5, source_cols=[o["source_col"] for o in outs], target_cols=[o["target_col"] for o in outs])   # :207-217
     for j, flag in enumerate(flags):

@@ -43,6 +43,7 @@ int genpc_abi_version(void);              /* bumps when a signature or a documen
                                            * genpc_voxel_down_sample_ragged, genpc_icp_batch_ragged and genpc_icp_ragged_plan likewise: still 28;
                                            * genpc_scale_search_scores_ragged and genpc_scale_search_ragged_plan too: still 28;
                                            * genpc_pose_optimize_ragged, genpc_pose_loss_grad_ragged and genpc_pose_ragged_plan as well: still 28;
+                                           * genpc_nn_ragged_tune and genpc_nn_ragged_dense_plan (the default search is unchanged): still 28;
                                            * a missing symbol is found when the binding loads. */
 const char *genpc_last_error(void);       /* last HIP error string, "" if none */
 int genpc_set_arith(int mode);            /* process default; returns the previous one */
@@ -147,6 +148,25 @@ int genpc_nm_distance_within(int b, int n, const float *xyz, int m, const float 
  * no synchronisation (csrc/nn_ragged.hip).                                                                              */
 int genpc_nm_distance_ragged(int c, const int *noff, const float *xyz, const int *moff, const float *xyz2,
                              float *result, int *result_i, void *stream);
+
+/* The calling host thread's choice for EVERY ragged nearest-neighbour search -- genpc_nm_distance_ragged and the two searches of
+ * a step of genpc_pose_optimize_ragged / genpc_pose_loss_grad_ragged: 0 the grid search (the default), 1 the dense search
+ * (csrc/nn_ragged_dense.hip): every query of a pair against every target of it, one launch on the targets as they are packed,
+ * no grid and no workspace at all.  The same bits, non-finite contract included; what differs is the cost, n_j m_j wherever the
+ * points lie, where the grid search's depends on how far a query is from its nearest target.  Returns the previous value; any
+ * other value returns -1 with genpc_last_error set and leaves the choice as it was.  A per-thread mode like genpc_pose_tune, with
+ * no environment variable.  It is NOT part of genpc_thread_state_export: the eight ints are taken, and the lanes of
+ * genpc_amd/pipeline.py make no ragged call -- a thread that wants the dense search sets it itself.
+ * In dense mode a call is refused (-1, genpc_last_error names the limit, nothing enqueued, no pointer looked at beyond the null
+ * check) for more than 2^36 pair evaluations, sum of N_j M_j, in one call, and for a pair with queries and more than 2^20
+ * targets: one workgroup walks all targets of its pair.                                                                       */
+int genpc_nn_ragged_tune(int search);
+/* The plan of a dense call with these HOST offset tables (csrc/nn_ragged_dense_plan.h; no GPU is touched): out[0] work items
+ * (workgroups), [1] threads per workgroup, [2] queries per item, [3] targets per LDS tile, [4] targets per wave's share of a
+ * tile, [5] LDS bytes per workgroup, [6] / [7] the low / high 32 bits of the 64-bit count of pair evaluations.  [1] .. [5] are
+ * constants and are filled whatever the table is.  Returns 1; -1 with genpc_last_error set for out == NULL, for what
+ * genpc_nm_distance_ragged refuses of a table, and -- out filled all the same -- for a call the dense search refuses.        */
+int genpc_nn_ragged_dense_plan(int c, const int *noff, const int *moff, int out[8]);
 
 /* Replaces chamfer_cuda_backward (chamfer3D.cu:176-195, chamfer_3D.backward in
  * chamfer_cuda.cpp:22-26,32).  gradxyz1[B,N,3] / gradxyz2[B,M,3] must be zeroed

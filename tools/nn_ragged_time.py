@@ -9,7 +9,16 @@ Inputs are packed and outputs allocated before the clock starts, for both ways a
 alternate; each repetition is bracketed by HIP events on the stream.  Median, 10th / 90th percentile and minimum of
 each, and the ratio of the medians, go to profiles/nn_ragged_time.json.  Needs a GPU.
 
-    python tools/nn_ragged_time.py [--reps 40] [--warmup 5] [--out profiles/nn_ragged_time.json]
+--which dense times the ragged call's two searches against each other instead, search="grid" against search="dense" (all pairs,
+csrc/nn_ragged_dense.hip), same protocol, into --dense-out.  Its batches are the ragged alignment loop's: 64
+pairs of about 900 against 4 500 points, both directions --
+  * pose64_aligned: the queries drawn on the targets' surface (every query has a near target: the grid search's best case);
+  * pose64_turned: three of every four pairs with the queries turned by 90 / 180 / 270 degrees about the cloud's centre, as the
+    loop's starts are (the grid search's lanes walk many cells);
+  * pose64_far: the queries turned by 180 degrees and pushed four diameters away (no query has a near target);
+  * big16_aligned: 16 pairs of 4 096 against 65 536 points, aligned -- larger targets, where all pairs cost the most.
+
+    python tools/nn_ragged_time.py [--reps 40] [--warmup 5] [--which ragged|dense|both] [--out profiles/nn_ragged_time.json]
 """
 import argparse
 import json
@@ -38,6 +47,85 @@ def batches():
     return {"waymo59": waymo, "mix64": mix}
 
 
+def surface(rng, n):
+    u = rng.standard_normal((n, 3))
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    return (u * np.array([0.5, 0.3, 0.2])).astype(np.float32)
+
+
+def dense_batches():
+    """(queries, targets) pairs for the dense-against-grid comparison (the head of this file)."""
+    rng = np.random.default_rng(45)
+    out = {"pose64_aligned": [], "pose64_turned": [], "pose64_far": [], "big16_aligned": []}
+    for j in range(64):
+        n, m = 886 + 11 * (j % 6) - 17 * (j % 4), 4493 + 37 * (j % 7) - 53 * (j % 5)
+        t = surface(rng, m)
+        q = surface(rng, 4 * n)
+        q = q[q[:, 2] > -0.05][:n]
+        c = t.astype(np.float64).mean(0)
+        th = np.radians(90.0 * (j % 4))
+        R = np.array([[np.cos(th), -np.sin(th), 0], [np.sin(th), np.cos(th), 0], [0, 0, 1]])
+        out["pose64_aligned"].append((q, t))
+        out["pose64_turned"].append(((c + (q - c) @ R.T).astype(np.float32), t))
+        out["pose64_far"].append(((c - (q - c) * np.array([1, 1, -1]) + np.array([4.0, 0, 0])).astype(np.float32), t))
+    for j in range(16):
+        out["big16_aligned"].append((surface(rng, 4096), surface(rng, 65536)))
+    return out
+
+
+def time_dense(args, dev, _lib, chamfer_3D):
+    result = {"device": torch.cuda.get_device_name(dev), "arith_mode": _lib.lib.genpc_get_arith(),
+              "protocol": "one process; after %d warm-ups the grid and the dense call alternate, %d repetitions, each bracketed by HIP "
+                          "events on the stream; q_to_t = the queries against the targets, t_to_q the converse" % (args.warmup, args.reps),
+              "batches": {}}
+    for name, pairs in dense_batches().items():
+        PA = torch.from_numpy(np.concatenate([a for a, _ in pairs])).to(dev)
+        PB = torch.from_numpy(np.concatenate([b for _, b in pairs])).to(dev)
+        offa = [0] + list(np.cumsum([len(a) for a, _ in pairs]))
+        offb = [0] + list(np.cumsum([len(b) for _, b in pairs]))
+        outs = {s: [torch.empty(PA.shape[0], device=dev), torch.empty(PA.shape[0], device=dev, dtype=torch.int32),
+                    torch.empty(PB.shape[0], device=dev), torch.empty(PB.shape[0], device=dev, dtype=torch.int32)] for s in ("grid", "dense")}
+
+        def call(search, way):
+            o = outs[search]
+            if way == 0:
+                assert chamfer_3D.nm_distance_ragged(PA, offa, PB, offb, o[0], o[1], search=search) == 1, _lib.last_error()
+            else:
+                assert chamfer_3D.nm_distance_ragged(PB, offb, PA, offa, o[2], o[3], search=search) == 1, _lib.last_error()
+
+        def timed(search, way):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            call(search, way)
+            e1.record()
+            e1.synchronize()
+            return e0.elapsed_time(e1)
+
+        for _ in range(args.warmup):
+            for s in ("grid", "dense"):
+                call(s, 0)
+                call(s, 1)
+        torch.cuda.synchronize()
+        same = all(torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(outs["grid"], outs["dense"]))
+        ts = {(s, w): [] for s in ("grid", "dense") for w in (0, 1)}
+        for _ in range(args.reps):
+            for key in ts:
+                ts[key].append(timed(*key))
+        entry = {"pairs": len(pairs), "queries": int(offa[-1]), "targets": int(offb[-1]), "same_bits": bool(same),
+                 "pair_evaluations_per_direction": int(sum(len(a) * len(b) for a, b in pairs))}
+        for s in ("grid", "dense"):
+            entry[s] = {"q_to_t": stats(ts[(s, 0)]), "t_to_q": stats(ts[(s, 1)])}
+        for w, way in ((0, "q_to_t"), (1, "t_to_q")):
+            entry["grid_over_dense_" + way] = entry["grid"][way]["median_ms"] / entry["dense"][way]["median_ms"]
+        result["batches"][name] = entry
+        print(name, json.dumps(entry), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(args.dense_out)), exist_ok=True)
+    with open(args.dense_out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    print(json.dumps({"out": args.dense_out}))
+
+
 def stats(ms):
     a = np.sort(np.asarray(ms))
     return {"median_ms": float(np.median(a)), "p10_ms": float(np.percentile(a, 10)), "p90_ms": float(np.percentile(a, 90)),
@@ -49,11 +137,17 @@ def main():
     ap.add_argument("--reps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "nn_ragged_time.json"))
+    ap.add_argument("--which", default="ragged", choices=("ragged", "dense", "both"))
+    ap.add_argument("--dense-out", default=os.path.join(ROOT, "profiles", "nn_ragged_dense_time.json"))
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("nn_ragged_time: needs a GPU (a time taken elsewhere says nothing)")
     from genpc_amd import _lib, chamfer_3D
     dev = torch.device("cuda", torch.cuda.current_device())
+    if args.which in ("dense", "both"):
+        time_dense(args, dev, _lib, chamfer_3D)
+    if args.which == "dense":
+        return
     result = {"device": torch.cuda.get_device_name(dev), "arith_mode": _lib.lib.genpc_get_arith(), "batches": {}}
     for name, pairs in batches().items():
         A = [torch.from_numpy(a).to(dev) for a, _ in pairs]

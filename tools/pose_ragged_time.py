@@ -3,15 +3,17 @@
   (a) loop      S object_pose_optimization calls, one scan after the other (runs on any commit: check out the parent, build it,
                 run this file there with --only a for the parent's figure);
   (b) ragged    ONE object_pose_optimization_scans call on the same S scans;
+  (d) dense     the same one call with nn_search="dense": every step's two searches by all pairs (csrc/nn_ragged_dense.hip);
   (1) S = 1     one scan through either;
-  (c) reg       reg_xyz.reg_scans over S flags of a stage-2 directory (tools/reg_scans_time.py's), ragged_pose False and True.
+  (c) reg       reg_xyz.reg_scans over S flags of a stage-2 directory (tools/reg_scans_time.py's), ragged_pose False, True with
+                the grid search and True with the dense search.
 
 The scans are reg()'s post-voxel sizes -- about 4.5 k complete against 0.9 k partial points, every scan a different size, with
 colours -- and the call is reg()'s: full objective, radius 0.02, lr 0.01, iters 200, 4 starts.  Each figure is the median of
 --repeats runs after --warmup, a host clock around work that ends in a read-back; where several sides are timed they alternate.
---profile runs (b) alone, --profile times after one warm-up, and nothing else: the run to trace.
+--profile runs (b) alone -- with --search dense: (d) alone --, --profile times after one warm-up, and nothing else: the run to trace.
 
-    python tools/pose_ragged_time.py [--scans 16] [--repeats 5] [--only a|b|1|c] [--profile N] [--json OUT]
+    python tools/pose_ragged_time.py [--scans 16] [--repeats 5] [--only a|b|d|1|c] [--profile N] [--search grid|dense] [--json OUT]
 """
 import argparse
 import json
@@ -70,7 +72,8 @@ def main():
     ap.add_argument("--scans", type=int, default=16)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--only", default="ab1c")
+    ap.add_argument("--only", default="abd1c")
+    ap.add_argument("--search", default="grid", choices=("grid", "dense"))
     ap.add_argument("--profile", type=int, default=0)
     ap.add_argument("--dir", default=None)
     ap.add_argument("--json", default=None)
@@ -86,6 +89,8 @@ def main():
     kw = dict(radius=0.02, lr=0.01, iters=200, render_size=224)
     res = {"scans": s, "sizes": sizes, "device": torch.cuda.get_device_name(0), "call": dict(kw, starts=4)}
     has_ragged = hasattr(POSE, "object_pose_optimization_scans")
+    import inspect
+    has_dense = has_ragged and "nn_search" in inspect.signature(POSE.object_pose_optimization_scans).parameters
 
     def loop():
         return [POSE.object_pose_optimization(C[j], P[j], complete_col=CC[j], partial_col=PC[j], **kw) for j in range(s)]
@@ -93,10 +98,14 @@ def main():
     def ragged():
         return POSE.object_pose_optimization_scans(C, P, complete_cols=CC, partial_cols=PC, **kw)
 
+    def dense():
+        return POSE.object_pose_optimization_scans(C, P, complete_cols=CC, partial_cols=PC, nn_search="dense", **kw)
+
     if args.profile:
-        ragged()
+        traced = dense if args.search == "dense" else ragged
+        traced()
         for _ in range(args.profile):
-            ragged()
+            traced()
         return
     if has_ragged:
         import ctypes
@@ -108,20 +117,25 @@ def main():
         res["plan"] = list(out)
         # transform | search, build, search | splat, sums, [weights], gradient (pose_grad rides or is a launch of its own) | update
         res["launches_per_step"] = 3 + 3 + (0 if out[8] else 1) + (0 if out[7] else 1) + 1 + 1
-    if "a" in args.only and "b" in args.only and has_ragged:
-        res["loop_ms"], res["ragged_ms"] = alternate([loop, ragged], args.warmup, args.repeats)
-    elif "a" in args.only:
-        res["loop_ms"], = alternate([loop], args.warmup, args.repeats)
-    elif "b" in args.only and has_ragged:
-        res["ragged_ms"], = alternate([ragged], args.warmup, args.repeats)
+        if has_dense:
+            res["launches_per_step_dense"] = res["launches_per_step"] - 1          # two searches and no build
+    sides = [(k, n, f) for k, n, f, ok in (("a", "loop_ms", loop, True), ("b", "ragged_ms", ragged, has_ragged), ("d", "ragged_dense_ms", dense, has_dense))
+             if k in args.only and ok]
+    if sides:          # the sides that are asked for alternate in one process
+        for (_, name, _), t in zip(sides, alternate([f for _, _, f in sides], args.warmup, args.repeats)):
+            res[name] = t
     if "1" in args.only:
         one = [lambda: POSE.object_pose_optimization(C[0], P[0], complete_col=CC[0], partial_col=PC[0], **kw)]
         if has_ragged:
             one.append(lambda: POSE.object_pose_optimization_scans(C[:1], P[:1], complete_cols=CC[:1], partial_cols=PC[:1], **kw))
+        if has_dense:
+            one.append(lambda: POSE.object_pose_optimization_scans(C[:1], P[:1], complete_cols=CC[:1], partial_cols=PC[:1], nn_search="dense", **kw))
         t = alternate(one, args.warmup, args.repeats)
         res["single_1_ms"] = t[0]
         if has_ragged:
             res["ragged_1_ms"] = t[1]
+        if has_dense:
+            res["ragged_dense_1_ms"] = t[2]
     if "c" in args.only and has_ragged:
         from conftest import write_glb
         from reg_scans_time import ellipsoid
@@ -145,7 +159,12 @@ def main():
         os.chdir(root)
         try:
             fns = [lambda: R.reg_scans(cfg, flags, seed=7), lambda: R.reg_scans(cfg, flags, seed=7, ragged_pose=True)]
-            res["reg_scans_per_scan_pose_ms"], res["reg_scans_ragged_pose_ms"] = alternate(fns, 1, args.repeats)
+            if has_dense:
+                fns.append(lambda: R.reg_scans(cfg, flags, seed=7, ragged_pose=True, nn_search="dense"))
+            t = alternate(fns, 1, args.repeats)
+            res["reg_scans_per_scan_pose_ms"], res["reg_scans_ragged_pose_ms"] = t[0], t[1]
+            if has_dense:
+                res["reg_scans_ragged_dense_pose_ms"] = t[2]
         finally:
             os.chdir(cwd)
     for k in sorted(res):
