@@ -75,6 +75,18 @@ struct NNArgs {
 #define NN_HELD(name) "+s"(name##_0), "+s"(name##_1)
 #define NN_OF_DIR(name) (d ? name##_1 : name##_0)
 
+// A point's three coordinates in ONE 12-byte load whose address is a block-uniform base (a pair of SGPRs) plus a 32-bit byte
+// offset of the lane: no 64-bit vector arithmetic per address.  `base` must be uniform and `bytes` below 2^32; a point is
+// 4-byte aligned, which is all a global load needs.  (Not a 3-vector: the compiler widens a 3-vector's load to 16 bytes, four
+// bytes past the end of the cloud for its last point.)
+struct NNPoint { float x, y, z; };
+__device__ __forceinline__ NNPoint nn_load_point(NN_GLOBAL(const char) base, unsigned bytes)
+{
+    NNPoint p;
+    __builtin_memcpy(&p, (const char *)(base + bytes), sizeof(NNPoint));
+    return p;
+}
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct Top3 {

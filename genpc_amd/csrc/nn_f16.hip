@@ -110,7 +110,7 @@ __global__ __launch_bounds__(WV * kWave, W) void nn_f16_kernel(NNArgs a)
                  NN_HELD(q), NN_HELD(t), NN_HELD(dup), NN_HELD(tmaxp), NN_HELD(part));
     const int d = (ndir > 1 && (int)blockIdx.x >= begin_1) ? 1 : 0;
     const int qblocks = NN_OF_DIR(qblocks), nq = NN_OF_DIR(nq), nt = NN_OF_DIR(nt), slices = NN_OF_DIR(slices), dup_shared = NN_OF_DIR(dupsh);
-    const float *const q_dir = (const float *)NN_OF_DIR(q), *const t_dir = (const float *)NN_OF_DIR(t);
+    const float *const t_dir = (const float *)NN_OF_DIR(t);
     const float *const t_dir0 = (const float *)t_0;
     const int nt_dir0 = nt_0;
     const unsigned *const dup_dir = (const unsigned *)NN_OF_DIR(dup);
@@ -119,7 +119,6 @@ __global__ __launch_bounds__(WV * kWave, W) void nn_f16_kernel(NNArgs a)
     const NNBlockId id = nn_decode_block((int)blockIdx.x - NN_OF_DIR(begin), qblocks, NNDiv{NN_OF_DIR(by_q).mul, NN_OF_DIR(by_q).shift}, nbatch, by_b);
     const int qb = id.qb, batch = id.batch, slice = id.slice;
 
-    const float *__restrict__ Qp = q_dir + (size_t)batch * nq * 3;
     const float *__restrict__ T = t_dir + (size_t)batch * nt * 3;
     // both clouds are centred on the first point of the direction-0 target cloud
     const auto cptr = NN_CONST(t_dir0 + (size_t)batch * nt_dir0 * 3);
@@ -133,17 +132,22 @@ __global__ __launch_bounds__(WV * kWave, W) void nn_f16_kernel(NNArgs a)
     // requested back to back, before any of the values is used: one memory round trip behind the kernel boundary
     // (with the loads where each value was first needed, the Q query tiles and the slice made Q + 1 round trips in a
     // row, and every word of the duplicate mask one more -- DESIGN_NOTEBOOK.md, "prologue loads").
-    // raw coordinates of this lane's queries: lanes < 32 carry x and y, lanes >= 32 z (their y is loaded and dropped:
-    // a load that every lane issues needs no branch, and a branch would hold its own wait)
+    // raw coordinates of this lane's queries: lanes < 32 carry x and y, lanes >= 32 z (every lane loads the whole point and
+    // drops what it does not carry: a load that every lane issues needs no branch, and a branch would hold its own wait)
+    // Addresses: batch element, query block and slice are the block's, so each cloud has a scalar base and a lane adds a
+    // 32-bit offset to it (nn_load_point); a query tile is one 12-byte load per lane.
     float raw0[Q], raw1[Q];
-    const int q0 = (qb * WV + wave) * (32 * Q) + col;
+    const int qfirst = qb * (WV * 32 * Q);         // the block's first query: below nq
+    const int q0 = qfirst + wave * (32 * Q) + col;
+    const auto q_base = (NN_GLOBAL(const char))NN_OF_DIR(q) + ((size_t)batch * nq + qfirst) * sizeof(NNPoint);
     GENPC_TL(8);
 #pragma unroll
     for (int r = 0; r < Q; r++) {
         int j = q0 + r * 32;
         if (j >= nq) j = nq - 1;
-        raw0[r] = Qp[(size_t)j * 3 + (half ? 2 : 0)];
-        raw1[r] = Qp[(size_t)j * 3 + 1];
+        const NNPoint p = nn_load_point(q_base, (unsigned)(j - qfirst) * (unsigned)sizeof(NNPoint));
+        raw0[r] = half ? p.z : p.x;
+        raw1[r] = p.y;
     }
     // (A per-launch pre-pass that hands every block its batch element's scale -- so that a slice longer than an LDS tile is
     // not read twice -- was measured: 13 x 16384^2 280.5 -> 278.9 us, 4 x 16384 x 8192 54.0 -> 58.2: the pre-scan of a
@@ -159,6 +163,7 @@ __global__ __launch_bounds__(WV * kWave, W) void nn_f16_kernel(NNArgs a)
     // padding: the first copy answers for them, and three equal minima in one list would send the query to the exhaustive pass
     const unsigned *__restrict__ dupm = dup_dir ? dup_dir + (dup_shared ? (size_t)0 : (size_t)batch * ((nt + 31) >> 5)) : nullptr;
     unsigned predup = 0u;
+    const auto t_base = (NN_GLOBAL(const char))NN_OF_DIR(t) + (size_t)batch * nt * sizeof(NNPoint);
     auto prefetch = [&](int t0) {
         predup = 0u;
         int tc[kPer];
@@ -166,8 +171,11 @@ __global__ __launch_bounds__(WV * kWave, W) void nn_f16_kernel(NNArgs a)
         for (int i = 0; i < kPer; i++) {
             const int t = t0 + i * kThreads + threadIdx.x;
             tc[i] = t < nt ? t : nt - 1;
-#pragma unroll
-            for (int k = 0; k < 3; k++) pre[i][k] = T[(size_t)tc[i] * 3 + k];
+            // (12 tc below 2^32: the plan keeps clouds of 2^25 targets and more away from this kernel)
+            const NNPoint p = nn_load_point(t_base, (unsigned)tc[i] * (unsigned)sizeof(NNPoint));
+            pre[i][0] = p.x;
+            pre[i][1] = p.y;
+            pre[i][2] = p.z;
         }
         if (dupm) {
             // all mask words first, then their bits: no wait per target
@@ -179,6 +187,17 @@ __global__ __launch_bounds__(WV * kWave, W) void nn_f16_kernel(NNArgs a)
         }
     };
     const bool resident = k_end - k_begin <= HT;        // block-uniform
+    // A resident slice that fills the LDS tile and has no duplicate mask -- every slice of a call whose clouds are multiples
+    // of the slice length, 1 x 16384^2 among them -- is reduced and staged in a straight line: no padding rows, no mask
+    // bits, no predicate per target (block-uniform, as are `resident` and `publishes`).
+    // (The loads are the same on both paths, clamp included: a second set of loads behind a branch made the compiler wait for
+    // the query loads at the point where the two met.)
+    // (the three-wave form with two lists per lane is held to 168 VGPRs with 128 B of scratch; the second staging path cost
+    // it 4 B more, so it keeps the general one)
+    constexpr bool kStraight = !(W == 3 && NL == 2);
+    const bool full = kStraight && k_end - k_begin == HT && !dupm;
+    // every query block of a slice sees the same targets: the first one alone works out and publishes their max |t'|^2
+    const bool publishes = qb == 0;
     if (resident && k_begin < k_end) prefetch(k_begin);
     // centred queries of this lane; the block's largest |coordinate| over queries and slice
     float qc0[Q], qc1[Q];
@@ -191,7 +210,11 @@ __global__ __launch_bounds__(WV * kWave, W) void nn_f16_kernel(NNArgs a)
         const float m0 = fabsf(qc0[r]), m1 = fabsf(qc1[r]);
         mx = fmaxf(mx, fmaxf(m0 < __builtin_inff() ? m0 : 0.0f, m1 < __builtin_inff() ? m1 : 0.0f));
     }
-    if (resident) {
+    if (full) {
+#pragma unroll
+        for (int i = 0; i < kPer; i++)
+            mx = fmaxf(mx, fmaxf(fmaxf(fabsf(pre[i][0] - cx), fabsf(pre[i][1] - cy)), fabsf(pre[i][2] - cz)));
+    } else if (resident) {
 #pragma unroll
         for (int i = 0; i < kPer; i++)
             if (k_begin + i * kThreads + (int)threadIdx.x < k_end)
@@ -265,33 +288,58 @@ __global__ __launch_bounds__(WV * kWave, W) void nn_f16_kernel(NNArgs a)
         const int tn = min(HT, k_end - t0);
         const int tn_pad = (tn + kC - 1) / kC * kC;
         __syncthreads();                 // every wave is done reading the previous tile
+        // the two rows of target i of this thread: centre, scale, two f16 pieces of -2s x', -2s y', -2s z', s^2 |t'|^2 2^-8
+        auto rows_of = [&](int i, uint4 &V0, uint4 &V1) {
+            const float x = pre[i][0] - cx, y = pre[i][1] - cy, z = pre[i][2] - cz;
+            const float xs = x * sc, ys = y * sc, zs = z * sc;
+            const float tts = __fmaf_rn(zs, zs, __fmaf_rn(ys, ys, __fmul_rn(xs, xs)));
+            const unsigned px = split2(x * tsc), py = split2(y * tsc), pz = split2(z * tsc);
+            const unsigned pt = split2(tts * 0.00390625f);
+            V0 = make_uint4(dup_lo(px), dup_hi(px), dup_lo(py), dup_hi(py));
+            V1 = make_uint4(dup_lo(pz), dup_hi(pz), pt, 0u);
+        };
+        // ... and what it adds to max |t'|^2 and the non-finite flag (unscaled, centred: the finish step's threshold is made of it)
+        auto measure = [&](int i) {
+            const float x = pre[i][0] - cx, y = pre[i][1] - cy, z = pre[i][2] - cz;
+            const float tt = __fmaf_rn(z, z, __fmaf_rn(y, y, __fmul_rn(x, x)));
+            tmax2 = fmaxf(tmax2, tt);
+            nf = __fmaf_rn(tt, 0.0f, nf);        // inf x 0 = NaN, NaN sticks (v_max drops NaNs)
+        };
+        if (full) {
 #pragma unroll
-        for (int i = 0; i < kPer; i++) {
-            const int t = i * kThreads + threadIdx.x;
-            if (t < tn_pad) {
-                // centre, scale, two f16 pieces of -2s x', -2s y', -2s z', s^2 |t'|^2 2^-8
-                const float x = pre[i][0] - cx, y = pre[i][1] - cy, z = pre[i][2] - cz;
-                const float xs = x * sc, ys = y * sc, zs = z * sc;
-                const float tts = __fmaf_rn(zs, zs, __fmaf_rn(ys, ys, __fmul_rn(xs, xs)));
-                const unsigned px = split2(x * tsc), py = split2(y * tsc), pz = split2(z * tsc);
-                const unsigned pt = split2(tts * 0.00390625f);
-                uint4 V0 = make_uint4(dup_lo(px), dup_hi(px), dup_lo(py), dup_hi(py));
-                uint4 V1 = make_uint4(dup_lo(pz), dup_hi(pz), pt, 0u);
-                if (t >= tn || ((predup >> i) & 1u)) {
-                    // padding: |t'|^2 = +inf (f16 0x7c00) x 2^8 never wins, the other terms are 0
-                    V0 = make_uint4(0u, 0u, 0u, 0u);
-                    V1 = make_uint4(0u, 0u, 0x7c00u, 0u);
-                } else {
-                    const float tt = __fmaf_rn(z, z, __fmaf_rn(y, y, __fmul_rn(x, x)));
-                    tmax2 = fmaxf(tmax2, tt);
-                    nf = __fmaf_rn(tt, 0.0f, nf);        // inf x 0 = NaN, NaN sticks (v_max drops NaNs)
-                }
+            for (int i = 0; i < kPer; i++) {
+                const int t = i * kThreads + threadIdx.x;
+                uint4 V0, V1;
+                rows_of(i, V0, V1);
                 const int row = (t & ~31) | tile_row(t & 31);
                 plane[0][row] = V0;
                 plane[1][row] = V1;
             }
+            if (publishes) {
+#pragma unroll
+                for (int i = 0; i < kPer; i++) measure(i);
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < kPer; i++) {
+                const int t = i * kThreads + threadIdx.x;
+                if (t < tn_pad) {
+                    uint4 V0, V1;
+                    rows_of(i, V0, V1);
+                    if (t >= tn || ((predup >> i) & 1u)) {
+                        // padding: |t'|^2 = +inf (f16 0x7c00) x 2^8 never wins, the other terms are 0
+                        V0 = make_uint4(0u, 0u, 0u, 0u);
+                        V1 = make_uint4(0u, 0u, 0x7c00u, 0u);
+                    } else if (publishes) {
+                        measure(i);
+                    }
+                    const int row = (t & ~31) | tile_row(t & 31);
+                    plane[0][row] = V0;
+                    plane[1][row] = V1;
+                }
+            }
+            if (t0 + HT < k_end) prefetch(t0 + HT);
         }
-        if (t0 + HT < k_end) prefetch(t0 + HT);
         __syncthreads();
         if (t0 == k_begin) { GENPC_TL(2); GENPC_TL_PARTNER(9); } else GENPC_TL(3);
         // prologue of the LDS tile: target tile 0, rows of tiles 0 and 1
@@ -332,7 +380,7 @@ __global__ __launch_bounds__(WV * kWave, W) void nn_f16_kernel(NNArgs a)
     GENPC_TL_PARTNER(10);
     // max |t'|^2 of the slice, for the bound of the finish step: every query block sees the same targets, the
     // first one publishes
-    if (qb == 0) {
+    if (publishes) {
         // non-finite targets: +inf tells the finish step to answer every query of this cloud
         // exhaustively (the reference's tile semantics for NaNs, nn_exhaustive in nn.h)
         if (nf != nf) tmax2 = __builtin_inff();
@@ -350,36 +398,63 @@ __global__ __launch_bounds__(WV * kWave, W) void nn_f16_kernel(NNArgs a)
     // Publish the lists: the two lane halves folded, NL lists of one 16-byte record per query and slice
     // (a1, c1) (codes of a2 and a3, c2): list_enc and ListRec in nn.h.  One 16-byte store per list: the 32 lanes that store
     // write 512 contiguous bytes.
+    // The halves share the work: of the wave's Q query tiles, lanes 0-31 merge, encode and store the first Q / 2, lanes 32-63 the
+    // others, tile r beside tile r + Q / 2 in one pass -- all 64 lanes store, and each tile's instructions run once per pair.
     const size_t bnq = (size_t)nbatch * nq;
+    constexpr int QH = Q / 2;
+    static_assert(Q % 2 == 0, "the lane halves take half of the query tiles each");
+    // v_permlane32_swap: lanes 32-63 of a <-> lanes 0-31 of b (the compiler supplies the instruction's wait states).
+    // The two results go into scalars before they are cast: __builtin_bit_cast applied to an ELEMENT of the result vector,
+    // __builtin_bit_cast(float, v[1]), reads element 0 whichever is named -- half of all nearest neighbours were wrong that way.
+    auto swap_word = [](auto &a, auto &b) {
+        const auto v = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), false, false);
+        const unsigned va = v[0], vb = v[1];
+        a = __builtin_bit_cast(std::remove_reference_t<decltype(a)>, va);
+        b = __builtin_bit_cast(std::remove_reference_t<decltype(b)>, vb);
+    };
+    auto swap_halves = [&](Top3 &a, Top3 &b) {
+        swap_word(a.a1, b.a1);
+        swap_word(a.a2, b.a2);
+        swap_word(a.a3, b.a3);
+        swap_word(a.c1, b.c1);
+        swap_word(a.c2, b.c2);
+    };
 #pragma unroll
-    for (int r = 0; r < Q; r++) {
+    for (int r = 0; r < QH; r++) {
 #pragma unroll
         for (int n = 0; n < NL; n++) {
-            Top3 &f = lst[r][n];
+            Top3 &f = lst[r][n], &o = lst[r + QH][n];
             // unscale (the block's scale is one power of two, so the order was not affected):
             // s^2 (|t'|^2 - 2 q'.t') -> |t'|^2 - 2 q'.t', two exact multiplications
             f.a1 = (f.a1 * isc) * isc;
             f.a2 = (f.a2 * isc) * isc;
             f.a3 = (f.a3 * isc) * isc;
-            const float o1 = __shfl_xor(f.a1, 32), o2 = __shfl_xor(f.a2, 32), o3 = __shfl_xor(f.a3, 32);
-            const int oc1 = __shfl_xor(f.c1, 32), oc2 = __shfl_xor(f.c2, 32);
-            top3_insert(f, o1, oc1);
-            top3_insert(f, o2, oc2);
-            top3_insert(f, o3, -1);
-            const int j = q0 + r * 32;
-            if (!half && j < nq) {
+            o.a1 = (o.a1 * isc) * isc;
+            o.a2 = (o.a2 * isc) * isc;
+            o.a3 = (o.a3 * isc) * isc;
+            // f held tile r and o tile r + QH, each lane its own half's rows.  Swapped, f is in every lane what lanes 0-31
+            // found for the lane's tile of the pair and o what lanes 32-63 found for it: the merge below is, in both halves,
+            // the one lanes 0-31 alone used to run for each tile -- their list first, the other half's entries inserted in order.
+            swap_halves(f, o);
+            top3_insert(f, o.a1, o.c1);
+            top3_insert(f, o.a2, o.c2);
+            top3_insert(f, o.a3, -1);
+            const int j = q0 + (r + QH * half) * 32;
+            if (j < nq) {
                 const unsigned code2 = list_enc(f.a1, f.a2);
                 const unsigned code3 = list_enc(list_dec(f.a1, code2), f.a3);
                 ListRec rec;
                 rec.x = ((unsigned long long)__float_as_uint(f.a1) << 32) | (unsigned)f.c1;
                 rec.y = ((unsigned long long)((code2 << 16) | code3) << 32) | (unsigned)f.c2;
-                ListRec *p = list_rec(part_dir, slice * NL + n, bnq, batch, nq, j);
+                // the block's first record of this list: a scalar base, the lane adds 16 (j - qfirst) to it
+                ListRec *p = list_rec(part_dir, slice * NL + n, bnq, batch, nq, qfirst);
                 // written through (sc1): a block's 16 KB of lists are on their way to memory when they are stored, not when the
                 // kernel's end finds them dirty in the L2 -- and the finish blocks read them from other XCDs in any case.
                 // (The filter's trace duration minus its last block's end, 1 x 16384^2: plain 3.0 us, non-temporal 2.8,
                 // written through 2.2, the finish kernel unchanged; DESIGN_NOTEBOOK.md, "list records".)  Written as the
                 // instruction: a plain 16-byte store cannot carry the bit; the s_nop keeps the next instruction off the data registers.
-                asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"((NN_GLOBAL(ListRec))p), "v"(rec) : "memory");
+                asm volatile("global_store_dwordx4 %0, %1, %2 sc1\n\ts_nop 1"
+                             : : "v"((unsigned)(j - qfirst) * (unsigned)sizeof(ListRec)), "v"(rec), "s"((NN_GLOBAL(ListRec))p) : "memory");
             }
         }
     }
