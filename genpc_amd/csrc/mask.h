@@ -263,5 +263,11 @@ int mask_prepare_ref(int b, int np, const float *partial, const float *partial_c
 int mask_step(int b, int nc, const float *complete, const float *complete_col, const float *center, int cstride, const float *params,
               int pstride, float radius, int S, float mask_weight, const MaskScratch &m, double *accum, hipStream_t st,
               bool projected = false, const PoseGradArgs *ride = nullptr, const int *off = nullptr, const MaskStepPlan *shape = nullptr);
+// mask_step without its splat: the launches that follow it (mask_sums_kernel, mask_w_kernel unless plan.fuse_w, mask_grad_kernel) on
+// the image that stands in m.planes, read as `blend` says, with its sums in accum[16..21]; rad: the radius that image was drawn with
+// (genpc_mask_backward_probe calls this on caller-built planes)
+int mask_step_backward(const MaskStepPlan &plan, int blend, int b, int nc, const float *complete, const float *complete_col,
+                       const float *center, int cstride, const float *params, int pstride, float rad, int S, float mask_weight,
+                       const MaskScratch &m, double *accum, hipStream_t st, const PoseGradArgs *ride = nullptr, const int *off = nullptr);
 
 }  // namespace genpc

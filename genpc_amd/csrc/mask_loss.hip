@@ -10,6 +10,8 @@
 //   mask_grad_kernel     one thread per point: gathers the weights over the pixels it covers, chains
 //                        through (u, v, rho) to the point and on to (R, s, t): same 13 accumulators as
 //                        the Chamfer gradient
+// mask_step = the splat + mask_step_backward (sums, weights, gather); genpc_mask_backward_probe runs the latter on a caller's planes
+// (tests/test_gpu_mask_backward_probe.py: weights per pixel and sums per point against tests/mask_loss_ref.py).
 #include "mask.h"
 #include "../../include/genpc_hip.h"
 
@@ -147,8 +149,8 @@ __device__ __forceinline__ MaskPx mask_pixel(const float *I, float mr, const Mas
     return o;
 }
 
-// grid (blocks, b): accum[16..21] += sum I_ch, sum I_ch^2 of a direct image (the splat does this for its own)
-__global__ __launch_bounds__(kQBlock) void mask_image_sums_kernel(int P, const float *__restrict__ planes,
+// grid (blocks, b): accum[16..21] += sum I_ch, sum I_ch^2 of a five-plane image read as `direct` says (the splat does this for its own)
+__global__ __launch_bounds__(kQBlock) void mask_image_sums_kernel(int P, const float *__restrict__ planes, int direct,
                                                                   double *__restrict__ accum)
 {
     __shared__ double red[6][kQBlock / kWave];
@@ -157,9 +159,10 @@ __global__ __launch_bounds__(kQBlock) void mask_image_sums_kernel(int P, const f
     accum += (size_t)e * kAcc;
     double a[6] = {0, 0, 0, 0, 0, 0};
     for (int q = blockIdx.x * kQBlock + threadIdx.x; q < P; q += gridDim.x * kQBlock) {
+        const PxImg px = load_pixel(planes, P, q, direct);
 #pragma unroll
         for (int ch = 0; ch < 3; ch++) {
-            const double I = (double)planes[(size_t)ch * P + q];
+            const double I = (double)px.I[ch];
             a[ch] += I;
             a[3 + ch] += I * I;
         }
@@ -519,15 +522,13 @@ int mask_prepare_ref(int b, int np, const float *partial, const float *partial_c
     return check(hipGetLastError(), "mask reference launch") ? 1 : 0;
 }
 
-int mask_step(int b, int nc, const float *complete, const float *complete_col, const float *center, int cstride, const float *params,
-              int pstride, float radius, int S, float mask_weight, const MaskScratch &m, double *accum, hipStream_t st, bool projected,
-              const PoseGradArgs *ride, const int *off, const MaskStepPlan *shape)
+// What a silhouette step does once the image of the posed clouds stands in m.planes with its sums in accum[16..21]: the loss's sums,
+// the per-pixel weights (unless the gather evaluates them) and the gather.  rad: the radius the image was drawn with.
+int mask_step_backward(const MaskStepPlan &plan, int blend, int b, int nc, const float *complete, const float *complete_col,
+                       const float *center, int cstride, const float *params, int pstride, float rad, int S, float mask_weight,
+                       const MaskScratch &m, double *accum, hipStream_t st, const PoseGradArgs *ride, const int *off)
 {
-    const float rad = 1.1f * radius;      // diff_obj_pose.py:385: the posed cloud is drawn with 1.1 x the radius
-    const MaskStepPlan plan = shape ? *shape : mask_step_plan(b, nc, S, radius);      // (every size and choice below, with its reason: pose_plan.h)
-    const int blend = render_blend(), mode = blend ? 2 : 0;
-    // (the alignment loop projects in its transform launch)
-    launch_mask_splat(b, nc, complete, complete_col, !projected, center, cstride, params, pstride, 1, rad, S, m, accum, st, off);
+    const int mode = blend ? 2 : 0;
     hipLaunchKernelGGL(mask_sums_kernel, dim3(plan.gs, b), dim3(kQBlock), 0, st, S, (const float *)m.planes, mode, (const float *)m.mref,
                        (const float *)m.stats, accum);
     if (!plan.fuse_w)
@@ -547,6 +548,18 @@ int mask_step(int b, int nc, const float *complete, const float *complete_col, c
 #undef GENPC_LAUNCH_MASK_GRAD2
 #undef GENPC_LAUNCH_MASK_GRAD
     return check(hipGetLastError(), "mask step launch") ? 1 : 0;
+}
+
+int mask_step(int b, int nc, const float *complete, const float *complete_col, const float *center, int cstride, const float *params,
+              int pstride, float radius, int S, float mask_weight, const MaskScratch &m, double *accum, hipStream_t st, bool projected,
+              const PoseGradArgs *ride, const int *off, const MaskStepPlan *shape)
+{
+    const float rad = 1.1f * radius;      // diff_obj_pose.py:385: the posed cloud is drawn with 1.1 x the radius
+    const MaskStepPlan plan = shape ? *shape : mask_step_plan(b, nc, S, radius);      // (every size and choice below, with its reason: pose_plan.h)
+    // (the alignment loop projects in its transform launch)
+    launch_mask_splat(b, nc, complete, complete_col, !projected, center, cstride, params, pstride, 1, rad, S, m, accum, st, off);
+    return mask_step_backward(plan, render_blend(), b, nc, complete, complete_col, center, cstride, params, pstride, rad, S, mask_weight, m,
+                              accum, st, ride, off);
 }
 
 }  // namespace genpc
@@ -569,11 +582,45 @@ GENPC_API int genpc_mask_loss(int size, const float *img, const float *ref, floa
     hipLaunchKernelGGL(mask_to_planes_kernel, dim3(g256), dim3(256), 0, st, P, img, pl_img);
     hipLaunchKernelGGL(mask_to_planes_kernel, dim3(g256), dim3(256), 0, st, P, ref, pl_ref);
     hipLaunchKernelGGL(mask_ref_kernel, dim3(1), dim3(kMLThreads), 0, st, size, (const float *)pl_ref, 1, m.mref, m.stats);
-    hipLaunchKernelGGL(mask_image_sums_kernel, dim3(gp, 1), dim3(kQBlock), 0, st, P, (const float *)pl_img, accum);
+    hipLaunchKernelGGL(mask_image_sums_kernel, dim3(gp, 1), dim3(kQBlock), 0, st, P, (const float *)pl_img, 1, accum);
     hipLaunchKernelGGL(mask_sums_kernel, dim3(gp, 1), dim3(kQBlock), 0, st, size, (const float *)pl_img, 1, (const float *)m.mref,
                        (const float *)m.stats, accum);
     hipLaunchKernelGGL(mask_w_kernel, dim3(gp, 1), dim3(kQBlock), 0, st, size, (const float *)pl_img, 1, (const float *)m.mref,
                        (const float *)m.stats, 1.0f, m.W1, m.W4, accum);
     hipLaunchKernelGGL(mask_loss_out_kernel, dim3(g256), dim3(256), 0, st, P, (const float4 *)m.W4, accum, loss_out, grad);
     return check(hipGetLastError(), "mask_loss launch") ? 1 : 0;
+}
+
+GENPC_API int genpc_mask_backward_probe(int S, int blend, int sub8, int fuse_w, const float *planes, const float *ref_img, int n,
+                                        const float *pts, const float *col, const float *center, const float *params, float radius,
+                                        float mask_weight, double *accum_out, float *W1_out, float *W4_out, void *stream)
+{
+    using namespace genpc;
+    if (S <= 1 || n < 1 || !planes || !ref_img || !pts || !center || !params || !accum_out) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    const int P = S * S;
+    double *accum;
+    MaskScratch m;
+    WsLayout L;
+    L.add(accum, 64);          // (genpc_mask_loss's layout: image 0 the posed cloud's planes, image 1 the reference's)
+    m.layout(L, 2, (size_t)P, 1);
+    if (!ws_alloc(L, kWsMaskLoss, st)) return 0;
+    float *pl_ref = m.planes + (size_t)5 * P;
+    if (!check(hipMemsetAsync(accum, 0, kAcc * sizeof(double), st), "hipMemsetAsync(accum)")) return 0;
+    if (!check(hipMemcpyAsync(m.planes, planes, (size_t)5 * P * sizeof(float), hipMemcpyDeviceToDevice, st), "hipMemcpyAsync(planes)")) return 0;
+    MaskStepPlan plan{};
+    plan.gp = lin_grid(P);
+    plan.gs = std::min(plan.gp, 48);
+    plan.fuse_w = fuse_w != 0;
+    plan.sub8 = sub8 != 0;
+    hipLaunchKernelGGL(mask_to_planes_kernel, dim3(ceil_div(P, 256)), dim3(256), 0, st, P, ref_img, pl_ref);
+    hipLaunchKernelGGL(mask_ref_kernel, dim3(1), dim3(kMLThreads), 0, st, S, (const float *)pl_ref, 1, m.mref, m.stats);
+    hipLaunchKernelGGL(mask_image_sums_kernel, dim3(plan.gp, 1), dim3(kQBlock), 0, st, P, (const float *)m.planes, blend ? 2 : 0, accum);
+    if (!mask_step_backward(plan, blend, 1, n, pts, col, center, 0, params, 0, radius, S, mask_weight, m, accum, st, nullptr, nullptr)) return 0;
+    if (!check(hipMemcpyAsync(accum_out, accum, 16 * sizeof(double), hipMemcpyDeviceToDevice, st), "hipMemcpyAsync(accum_out)")) return 0;
+    if (!plan.fuse_w) {
+        if (W1_out && !check(hipMemcpyAsync(W1_out, m.W1, (size_t)P * sizeof(float), hipMemcpyDeviceToDevice, st), "hipMemcpyAsync(W1)")) return 0;
+        if (W4_out && !check(hipMemcpyAsync(W4_out, m.W4, (size_t)P * sizeof(float4), hipMemcpyDeviceToDevice, st), "hipMemcpyAsync(W4)")) return 0;
+    }
+    return 1;
 }

@@ -769,6 +769,18 @@ int genpc_grid_bound_probe(const void *hdr, int nq, const float *q, int n, const
 int genpc_grid_range_probe(const void *hdr, int nq, const float *q, const float *radius, const int *clip, int *range,
                            void *stream);
 
+/* Silhouette backward probe: everything mask_step does after its splat, on the caller's image (tests/test_gpu_mask_backward_probe.py).
+ * planes[5, P], P = S * S: the five planes as the splat leaves them for `blend` (0: T, D, N_r, N_g, N_b; 1: m, D', N'_r, N'_g, N'_b);
+ * ref_img[P, 3] the reference image; pts[n, 3] with colours col[n, 3] (null: white), center[3], params[10]; radius is the
+ * radius the planes were drawn with and is used as given (no factor 1.1).  Runs mask_ref_kernel on ref_img, the image sums of the
+ * planes, then mask_sums_kernel, mask_w_kernel (fuse_w == 0) and mask_grad_kernel<sub8 ? 8 : 1, blend, fuse_w> as one image with
+ * genpc_mask_loss's grids.  accum_out[16] (double): 0..12 the gradient sums of mask_grad_kernel (d / d R row-major, d / d log-scale
+ * at 9 without its factor s, d / d t at 10..12), 15 mask_weight * loss.  fuse_w == 0: W1_out[P], W4_out[P, 4] (either may be null)
+ * receive the per-pixel weights.  Device memory.  Returns 1 / 0 / -1 (S < 2, n < 1, a null input).                      */
+int genpc_mask_backward_probe(int S, int blend, int sub8, int fuse_w, const float *planes, const float *ref_img, int n,
+                              const float *pts, const float *col, const float *center, const float *params, float radius,
+                              float mask_weight, double *accum_out, float *W1_out, float *W4_out, void *stream);
+
 /* Farthest point sampling --------------------------------------------------- *
  * Deterministic counterpart of fpsample.fps_sampling as the reference uses it
  * (main.py:21-24, reg_xyz.py:215, DepthPrompting.py:88; third-party, random start):
