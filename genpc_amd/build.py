@@ -23,7 +23,7 @@ FLAGS = [
     "-Wall", "-Wno-unused-function",
 ]
 # No packed fp32 instructions (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32) anywhere in the library: in the farthest-point
-# sampling they were what drew wrong samples beside other streams' matrix instructions (csrc/fps.hip; the low half
+# sampling they were what drew wrong samples beside other streams' matrix instructions (csrc/fps.hip: fps_body; the low half
 # of a register pair, lanes 48-63); scalar fp32 instructions give the same bits.
 # (The feature is the device compiler's: the host pass prints one "not a recognized feature" line per file, dropped below.)
 FLAGS += ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]

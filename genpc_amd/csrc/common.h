@@ -40,7 +40,7 @@ enum Ws : int {
     kWsPoseLoop = 4,          // pose.hip genpc_pose_optimize_batch: accumulators | states | posed cloud | neighbours | mask scratch
     kWsIcp = 5,               // icp.hip genpc_icp_batch (launch-per-pass path): sums | states | clouds | neighbours
     kWsScaleSearch = 6,       // icp.hip genpc_scale_search_scores: scaled copies | neighbours
-    kWsFps = 7,               // fps.hip genpc_fps_multi: status block | hand-off slots | check scratch.  SHARED: genpc_fps_stats reads the status block of the stream's last call back
+    kWsFps = 7,               // fps_call.hip fps_call (genpc_fps_multi, genpc_fps_large): status block | hand-off slots | check scratch.  SHARED: genpc_fps_stats reads the status block of the stream's last call back
     kWsZbuffer = 8,           // project.hip genpc_zbuffer_visibility: the z-buffers of a camera group
     kWsNnTmax = 9,            // nn_f16.hip launch_nn_f16: partial maxima of the split targets
     kWsNnStats = 12,          // chamfer.hip: hook counters, one block per DEVICE (null stream).  SHARED: nn_forward hands it to the kernels, genpc_nn_stats reads it back

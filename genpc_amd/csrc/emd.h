@@ -163,8 +163,11 @@ struct EmdGridBid {
 int launch_emd_auction(int b, int n, const float *xyz1, const float *xyz2, float *dist, int *assignment, float *price, int *assignment_inv,
                        int *bid, float *bid_increments, float *max_increments, int *max_idx, float eps, int iters, int fma, hipStream_t st, bool forced);
 int *emd_feedback_slot(int b, int n, bool device);
+// admission of launches whose workgroups wait for each other (emd_auction.hip; the multi-workgroup sampling of fps.hip takes its
+// share from the same budget): quarter-CU units
 bool persist_reserve(int wgs, int capacity, hipStream_t st);
 void persist_commit(int wgs, hipStream_t st);
+int emd_auction_capacity();
 int launch_emd_bid_grid(const EmdGridBid &a, int fma, hipStream_t st);
 int launch_emd_cell_pmin(int b, int cells_max, const CellGridHdr *hdr, const int *start, const float4 *sorted, int n, float *pmin, hipStream_t st);
 

@@ -22,53 +22,21 @@
 //     reset, no fences, no grid barrier.
 // Several clouds -- of DIFFERENT sizes and sample counts -- run side by side in one launch (grid.y):
 // the two subsamplings of the metric and the fused cloud's can share one pass (genpc_fps_multi).
-// Which of the library's three samplers a cloud takes is fps_plan.h's decision (this kernel: clouds of 24577 to 262144 points, and
-// smaller ones under genpc_fps_tune(256)); the entry points at the end of this file only carry it out.
-// All workgroups of a cloud must be co-resident; launches are sized from the device's CU count at
-// four 256-thread workgroups per CU at most (the hardware admits eight).  The polls are bounded all the same:
+// This file is the multi-workgroup sampler alone: the kernel, the one table of its instantiations and fps_multi_run, which carries
+// out the launches fps_plan.h planned.  Which of the library's three samplers a cloud takes (this one: clouds of 24577 to 262144
+// points, and smaller ones under genpc_fps_tune(256)), a cloud's workgroups and points per thread, and which clouds share a launch
+// are fps_plan.h's decisions; fps_call.hip holds the entry points, fps_verify.hip the check every finished sequence gets.
+// All workgroups of a launch must be co-resident: launches are sized from what the device holds of the instantiation they take
+// (fps_device) and admitted through the budget the one-launch auction shares.  The polls are bounded all the same:
 // a hand-off that times out aborts the cloud's run (every workgroup leaves its step loop), raises the error
 // word and writes -1 to out[0]; genpc_amd/fps.py raises on it.
-#include "grid.h"
-#include "fps_plan.h"
+#include "fps.h"
 #include "../../include/genpc_hip.h"
-#include <map>
-#include <mutex>
-#include <vector>
 
 namespace genpc {
 
-// admission of launches whose workgroups wait for each other (csrc/emd_auction.hip): quarter-CU units
-bool persist_reserve(int wgs, int capacity, hipStream_t st);
-void persist_commit(int wgs, hipStream_t st);
-int emd_auction_capacity();
-// fps_grid.hip: the one-workgroup sampling with spatial pruning
-bool fps_grid_takes(int n);
-int fps_grid_run(bool fma, int c, const int *sel, const int *n, const int *k, const float *const *xyz, int *const *out_idx,
-                 float *const *pdist_of, float4 *spt, int *err, hipStream_t st);
-// fps_large.hip: the one-workgroup sampling with spatial pruning and its state in global memory
-int fps_large_run(bool fma, int c, const int *sel, const int *n, const int *k, const float *const *xyz, int *const *out_idx,
-                  float *const *pdist_of, float4 *spt, unsigned *dmin, unsigned *chmax, int *start, CellGridHdr *hdr, int *err,
-                  hipStream_t st);
-
-constexpr int kFThreads = 192;           // worker threads of a workgroup: three waves, the fourth wave coordinates -- one wave per SIMD
 constexpr int kFWaves = kFThreads / kWave;
-constexpr int kFMaxR = 24;
-constexpr int kFMaxW = 64;
-constexpr int kFMaxJobs = 8;
-constexpr int kFPointsPerWg = 192;       // target: one point per worker thread.  What a round yields grows with the NUMBER of lists
-                                         // (64 lists x 4 candidates: ~45 samples per exchange; 8 lists: 13), so small clouds are spread
-                                         // over many workgroups too; the cap of 64 workgroups raises the share for clouds beyond 16384 points
-
-struct FpsJobs {
-    const float *xyz[kFMaxJobs];
-    int *out[kFMaxJobs];
-    int n[kFMaxJobs], k[kFMaxJobs], W[kFMaxJobs];
-    int slot0[kFMaxJobs];        // first slot of the job in the slot array (slots are per (job, parity, workgroup))
-    int stat0;                   // index of the launch's first cloud in the call (statistics)
-    float *pdist[kFMaxJobs];     // the running minimum of every sample when it was drawn (fps_verify_kernel)
-    int *verr[kFMaxJobs];        // != 0: the verification found a step whose sample is not the first arg-max
-    int segoff[kFMaxJobs];       // first point of the job in the verification's per-(point, segment) minima
-};
+static_assert(kFMaxW * kFMaxR * kFThreads >= kFpsMultiMaxN, "what the plan sends to fps_kernel fits its registers");
 
 // Wave-wide integer max / min, uniform result, in seven instructions: four row rotations (each one v_max_i32 with a
 // DPP operand -- written in assembly: the compiler emits v_mov_b32 + v_mov_b32_dpp + v_max_i32 per step) leave every
@@ -487,551 +455,64 @@ __global__ __launch_bounds__(kFBlock) void fps_kernel(FpsJobs jobs, FpsSlot *slo
     fps_body<FMA, R>(jobs, slots, err);
 }
 
-// Verification of a sampling, on the device, against the DEFINITION (round 5).  The k steps of a sampling are sequential, but
-// checking a finished sequence is not: sample j (drawn with running minimum M_j, as the sampling itself recorded it) is right
-// iff, after the first j samples have been applied, every point i has running minimum D_i < M_j, or D_i == M_j and i > s_j,
-// and the sample itself has D == M_j exactly -- "s_j is the FIRST arg-max" -- with the sampling's own arithmetic.  One thread
-// per point walks the sample list once (n k distance evaluations, all independent across points: ~0.4 ms for 16384 of 24000,
-// beside the sampling's 7).  Why: twice now (round 4 next to another stream's f16 MFMAs, round 5 again with the pivot taken
-// through scalar registers and with self-tagged pivot granules) a sampling running BESIDE other kernels drew a sample a step
-// early -- silently, mechanism not established.  A violation poisons out[0] with -1, which genpc_amd/fps.py
-// already treats as "this cloud again": a wrong sequence can no longer leave the library unnoticed, whatever causes it.
-constexpr int kFVBlock = 128, kFVTile = 1024, kFVMaxSeg = 16;
-// The sample list is cut into `nseg` segments (grid.z) so that the whole chip takes part (one thread per point alone
-// leaves a 24000-point cloud on 188 two-wave blocks: 1.8 ms beside a 10 ms sampling).  CHECK = 0: the minimum over the
-// segment's samples of the point's distances -> segmin[point][segment]; CHECK = 1: the running minimum enters the segment
-// with the minimum of the earlier segments' results and the segment's steps are checked.  Twice the distance
-// evaluations, nseg times the threads.
-template <int FMA, int CHECK>
-__global__ __launch_bounds__(kFVBlock) void fps_verify_kernel(FpsJobs jobs, float *__restrict__ segmin, int nseg)
-{
-    __shared__ float4 s_s[kFVTile];          // x, y, z of sample l; M of sample l + 1
-    __shared__ int s_i[kFVTile];             // index of sample l + 1
-    __shared__ unsigned s_hit[kFVTile / 256];      // per trip of eight samples: one of them is a point of this block
-    const int job = blockIdx.y, seg = blockIdx.z;
-    const int n = jobs.n[job], k = jobs.k[job];
-    const float *__restrict__ X = jobs.xyz[job];
-    const int *__restrict__ out = jobs.out[job];
-    const float *__restrict__ pd = jobs.pdist[job];
-    float *__restrict__ sm = segmin + (size_t)jobs.segoff[job] * nseg;
-    // samples l = 0 .. k - 2 are applied (sample l decides step l + 1); the segment's share, a multiple of 8 long
-    const int per = (((k - 1) + nseg - 1) / nseg + 7) & ~7;
-    const int l_lo = min(seg * per, k - 1), l_hi = min(l_lo + per, k - 1);
-    bool bad = false;
-    for (int i0 = blockIdx.x * kFVBlock; i0 < n; i0 += gridDim.x * kFVBlock) {      // (block-uniform: the tiles are staged together)
-        const int i = min(i0 + (int)threadIdx.x, n - 1);      // (lanes past the end repeat the last point)
-        const float px = X[(size_t)i * 3 + 0], py = X[(size_t)i * 3 + 1], pz = X[(size_t)i * 3 + 2];
-        float D = __builtin_inff();
-        if (CHECK) {
-            for (int g = 0; g < seg; g++) D = fminf(D, sm[(size_t)i * nseg + g]);
-            if (i == 0 && seg == 0 && out[0] != 0) bad = true;      // (-1: the hand-off gave up; anything else: not the start point)
-        }
-        for (int l0 = l_lo; l0 < l_hi; l0 += kFVTile) {
-            __syncthreads();
-            if (CHECK && threadIdx.x < kFVTile / 256) s_hit[threadIdx.x] = 0u;
-            if (CHECK) __syncthreads();
-            for (int t = threadIdx.x; t < kFVTile && l0 + t < l_hi; t += kFVBlock) {
-                int sl = out[l0 + t];
-                if (CHECK && ((unsigned)sl >= (unsigned)n || (unsigned)out[l0 + t + 1] >= (unsigned)n)) bad = true;      // (not an index of the cloud)
-                sl = (unsigned)sl < (unsigned)n ? sl : 0;
-                s_s[t] = make_float4(X[(size_t)sl * 3 + 0], X[(size_t)sl * 3 + 1], X[(size_t)sl * 3 + 2], pd[l0 + t + 1]);
-                const int sn = out[l0 + t + 1];
-                s_i[t] = sn;
-                if (CHECK && (unsigned)(sn - i0) < (unsigned)kFVBlock) atomicOr(&s_hit[t >> 8], 1u << ((t >> 3) & 31));
-            }
-            __syncthreads();
-            const int cnt = min(kFVTile, l_hi - l0);
-            // eight samples per trip: the LDS reads (broadcasts) and the eight independent distances first, then the
-            // running minimum's short dependent chain
-            int t = 0;
-            for (; t + 8 <= cnt; t += 8) {
-                float4 q[8];
-                float dd[8];
-#pragma unroll
-                for (int u = 0; u < 8; u++) q[u] = s_s[t + u];
-#pragma unroll
-                for (int u = 0; u < 8; u++) dd[u] = sqdist<FMA>(px - q[u].x, py - q[u].y, pz - q[u].z);
-                if (!CHECK) {
-#pragma unroll
-                    for (int u = 0; u < 8; u++) D = D < dd[u] ? D : dd[u];
-                    continue;
-                }
-                // the common case costs one comparison per step: D < M.  A step with D >= M -- the sample itself (D == M), an exact
-                // tie, or a violation -- is rare and looked at again below with the index rule
-                const float D0 = D;
-                bool ge = false;
-#pragma unroll
-                for (int u = 0; u < 8; u++) {
-                    D = D < dd[u] ? D : dd[u];
-                    ge |= D >= q[u].w;
-                }
-                // (a sample whose recorded minimum is too HIGH has D < M at its own step: the trips in which a point of THIS block
-                // is sampled are marked while the tile is staged and take the full rule whatever the comparison says)
-                const bool hit = CHECK && ((s_hit[t >> 8] >> ((t >> 3) & 31)) & 1u) != 0u;
-                if (hit || __any(ge)) {
-                    float E = D0;
-#pragma unroll
-                    for (int u = 0; u < 8; u++) {
-                        E = E < dd[u] ? E : dd[u];
-                        const int sj = s_i[t + u];
-                        // E < M, or the tie goes to the lower index s_j; and s_j itself has exactly its recorded minimum
-                        bad |= !(E < q[u].w || (E == q[u].w && i >= sj)) || (i == sj && E != q[u].w);
-                    }
-                }
-            }
-            for (; t < cnt; t++) {
-                const float4 q = s_s[t];
-                const float dd = sqdist<FMA>(px - q.x, py - q.y, pz - q.z);
-                D = D < dd ? D : dd;
-                const int sj = s_i[t];
-                if (CHECK) bad |= !(D < q.w || (D == q.w && i >= sj)) || (i == sj && D != q.w);
-            }
-        }
-        if (!CHECK && i0 + (int)threadIdx.x < n) sm[(size_t)i * nseg + seg] = D;
-    }
-    if (CHECK && __any(bad) && (threadIdx.x & (kWave - 1)) == 0) atomicOr(jobs.verr[job], 1);      // (padding lanes repeat point n - 1: same verdict)
-}
-
-__global__ void fps_poison_kernel(FpsJobs jobs, int nj)
-{
-    const int j = threadIdx.x;
-    // (-2: the sequence failed the check; a sampling whose hand-off timed out has written -1 itself, and fails the check too)
-    if (j < nj && *jobs.verr[j] != 0) { if (jobs.out[j][0] != -1) jobs.out[j][0] = -2; *jobs.verr[j] = 0; }
-}
-
-// deferred verification (below): a failed check is counted instead of poisoning a result that has left already
-__global__ void fps_count_kernel(FpsJobs jobs, int nj, int *__restrict__ violations)
-{
-    const int j = threadIdx.x;
-    if (j < nj && *jobs.verr[j] != 0) { atomicAdd(violations, 1); *jobs.verr[j] = 0; }
-}
-
+// THE dispatch over the register classes (fps_plan.h: kFpsClassPoints, fps_class): the instantiation of class cls, for the launch
+// and for the occupancy query alike -- a launch is sized from the occupancy of the very kernel it takes.
+typedef void (*FpsKernel)(FpsJobs, FpsSlot *, int *);
 template <int FMA>
-static void launch_fps(int R, dim3 grid, hipStream_t st, const FpsJobs &jobs, FpsSlot *slots, int *err)
+static FpsKernel fps_kernel_of(int cls)
 {
-    switch (R) {
-    case 1: case 2: hipLaunchKernelGGL((fps_kernel<FMA, 2>), grid, dim3(kFBlock), 0, st, jobs, slots, err); break;
-    case 3: case 4: hipLaunchKernelGGL((fps_kernel<FMA, 4>), grid, dim3(kFBlock), 0, st, jobs, slots, err); break;
-    case 5: case 6: case 7: case 8: hipLaunchKernelGGL((fps_kernel<FMA, 8>), grid, dim3(kFBlock), 0, st, jobs, slots, err); break;
-    case 9: case 10: case 11: case 12: hipLaunchKernelGGL((fps_kernel<FMA, 12>), grid, dim3(kFBlock), 0, st, jobs, slots, err); break;
-    case 13: case 14: case 15: case 16: hipLaunchKernelGGL((fps_kernel<FMA, 16>), grid, dim3(kFBlock), 0, st, jobs, slots, err); break;
-    default: hipLaunchKernelGGL((fps_kernel<FMA, 24>), grid, dim3(kFBlock), 0, st, jobs, slots, err); break;
-    }
+    static_assert(kFpsClasses == 6, "an entry per class");
+    static const FpsKernel table[kFpsClasses] = {fps_kernel<FMA, kFpsClassPoints[0]>, fps_kernel<FMA, kFpsClassPoints[1]>,
+                                                 fps_kernel<FMA, kFpsClassPoints[2]>, fps_kernel<FMA, kFpsClassPoints[3]>,
+                                                 fps_kernel<FMA, kFpsClassPoints[4]>, fps_kernel<FMA, kFpsClassPoints[5]>};
+    return table[cls];
 }
-
-static int fps_workgroups(int n)
-{
-    int W = ceil_div(n, kFPointsPerWg);
-    if (W > kFMaxW) W = kFMaxW;
-    return W < 1 ? 1 : W;
-}
-
-// the instantiation launch_fps takes for R points per thread, as an index; its points per thread
-static int fps_class(int R) { return R <= 2 ? 0 : (R <= 4 ? 1 : (R <= 8 ? 2 : (R <= 12 ? 3 : (R <= 16 ? 4 : 5)))); }
 
 // Workgroups of an instantiation one CU holds at a time, as the runtime reports it (registers: fps_kernel<*, 16> is 152
-// VGPRs = 3 per CU, <*, 24> 224 VGPRs = 2; the smaller ones 4+).  The hand-off between a cloud's workgroups needs ALL of
-// the launch resident together, so launches are sized from this, not from a constant (a budget of four per CU
-// admitted grids of the two large instantiations that an idle full chip just holds and a busy or partitioned one does not).
-template <int FMA>
-static int fps_blocks_per_cu(int cls)
+// VGPRs = 3 per CU, <*, 24> 224 VGPRs = 2; the smaller ones 4+), asked once per arithmetic mode.  The hand-off between a cloud's
+// workgroups needs ALL of the launch resident together, so launches are sized from this, not from a constant (a budget
+// of four per CU admitted grids of the two large instantiations that an idle full chip just holds and a busy or partitioned one
+// does not).
+bool fps_device(bool fma, FpsDevice &dev)
 {
-    static int cache[6] = {0, 0, 0, 0, 0, 0};
-    if (cache[cls] > 0) return cache[cls];
-    int nb = 0;
-    hipError_t e = hipSuccess;
-    switch (cls) {
-    case 0: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fps_kernel<FMA, 2>, kFBlock, 0); break;
-    case 1: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fps_kernel<FMA, 4>, kFBlock, 0); break;
-    case 2: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fps_kernel<FMA, 8>, kFBlock, 0); break;
-    case 3: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fps_kernel<FMA, 12>, kFBlock, 0); break;
-    case 4: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fps_kernel<FMA, 16>, kFBlock, 0); break;
-    default: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fps_kernel<FMA, 24>, kFBlock, 0); break;
+    static int cache[2][kFpsClasses] = {{0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0}};
+    int id = 0;
+    if (!check(hipGetDevice(&id), "hipGetDevice")) return false;
+    if (!check(hipDeviceGetAttribute(&dev.cus, hipDeviceAttributeMultiprocessorCount, id), "hipDeviceGetAttribute")) return false;
+    if (dev.cus < 1) dev.cus = 1;
+    int *nb = cache[fma ? 1 : 0];
+    for (int cls = 0; cls < kFpsClasses; cls++) {
+        if (nb[cls] < 1) {
+            const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb[cls], fma ? fps_kernel_of<1>(cls) : fps_kernel_of<0>(cls), kFBlock, 0);
+            if (e != hipSuccess || nb[cls] < 1) nb[cls] = 1;
+        }
+        dev.blocks_per_cu[cls] = nb[cls];
     }
-    if (e != hipSuccess || nb < 1) nb = 1;
-    cache[cls] = nb;
-    return nb;
+    return true;
 }
 
-thread_local int t_fps_multi_wg = 0;
+static_assert(sizeof(FpsSlot) == kFpsSlotBytes, "what fps_call reserves per slot");
 
-// Verification OFF the caller's critical path (round 6; genpc_fps_defer).  The check of a finished sequence reads the cloud, the
-// samples and their recorded minima: ~1 ms of chip-wide kernels behind a 4-5 ms sampling, twice per completed scan.  Deferred,
-// the three arrays are copied (stream-ordered, ~0.5 MB) into a buffer of the library's own and the check runs on a side stream
-// of the lowest priority class beside whatever the caller enqueues next; a failed check is COUNTED (the indices have left by
-// then) and genpc_fps_deferred_check() hands the count to the caller, who samples again with the check in line
-// (genpc_amd/pipeline.py does, per completed scan).  Only samplings of the one-workgroup kernel (csrc/fps_grid.hip) are
-// deferred: the failures that made the check necessary were hand-offs between workgroups, which it does not have.
-thread_local int t_fps_defer = 0;
-struct FpsDeferred {
-    hipStream_t side = nullptr;
-    hipEvent_t fork[4] = {nullptr, nullptr, nullptr, nullptr}, done[4] = {nullptr, nullptr, nullptr, nullptr};
-    char *buf[4] = {nullptr, nullptr, nullptr, nullptr};
-    size_t cap[4] = {0, 0, 0, 0};
-    bool used[4] = {false, false, false, false};
-    int *violations = nullptr;      // device word
-    unsigned next = 0;
-    bool ok = false;
-};
-static std::mutex g_fps_def_mu;
-static std::map<std::pair<int, hipStream_t>, FpsDeferred *> g_fps_def;
-static FpsDeferred *fps_deferred_of(hipStream_t st, bool create)
+// Clouds `sel[0 .. )` (indices into the call's arrays) through the multi-workgroup kernel, in the launches the plan made of them
+// (shape and slot0 per selected cloud): admission, launch, and the check of the launch's clouds in line.
+int fps_multi_run(const FpsCall &c, const int *sel, const FpsShape *shape, int nl, const FpsLaunch *launches, const int *slot0, void *slots)
 {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    std::lock_guard<std::mutex> g(g_fps_def_mu);
-    auto it = g_fps_def.find({dev, st});
-    if (it != g_fps_def.end()) return it->second->ok ? it->second : nullptr;
-    if (!create) return nullptr;
-    FpsDeferred *p = new FpsDeferred();
-    int prio_lo = 0, prio_hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    p->ok = hipStreamCreateWithPriority(&p->side, hipStreamNonBlocking, prio_lo) == hipSuccess;
-    for (int i = 0; i < 4 && p->ok; i++)
-        p->ok = hipEventCreateWithFlags(&p->fork[i], hipEventDisableTiming) == hipSuccess &&
-                hipEventCreateWithFlags(&p->done[i], hipEventDisableTiming) == hipSuccess;
-    p->ok = p->ok && hipMalloc((void **)&p->violations, sizeof(int)) == hipSuccess && hipMemset(p->violations, 0, sizeof(int)) == hipSuccess;
-    g_fps_def[{dev, st}] = p;
-    return p->ok ? p : nullptr;
-}
-
-}  // namespace genpc
-
-/* Test hook (applies to the calling host thread; returns the previous setting): 256 = every cloud takes the multi-workgroup
- * kernel (never the one-workgroup kernel of fps_grid.hip), 0 = the default choice; any other value is refused (-1). */
-GENPC_API int genpc_fps_tune(int mode)
-{
-    if (mode != 0 && mode != 256) {
-        genpc::set_error("genpc_fps_tune: the mode is 0 or 256");
-        return -1;
-    }
-    const int prev = genpc::t_fps_multi_wg;
-    genpc::t_fps_multi_wg = mode;
-    return prev;
-}
-
-// The body of genpc_fps_multi (force_large = 0: every cloud takes the sampler fps_plan gives it) and of genpc_fps_large (1).
-static int fps_call(int c, const int *n, const int *k, const float *const *xyz, int *const *out_idx, void *stream, int force_large)
-{
-    using namespace genpc;
-    if (c <= 0) return 1;
-    for (int j = 0; j < c; j++) {
-        static_assert(kFMaxW * kFMaxR * kFThreads >= kFpsMultiMaxN, "what the plan sends to fps_kernel fits its registers");
-        if (k[j] <= 0 || k[j] > n[j] || fps_plan(n[j], force_large).sampler == kFpsNone) {
-            fprintf(stderr, "genpc_fps: need 0 < k <= n <= %d\n", kFpsLargeMaxN);
-            set_error("genpc_fps: need 0 < k <= n <= 4194304 for every cloud");
-            return -1;
-        }
-    }
-    hipStream_t st = (hipStream_t)stream;
-    // co-residency budget: what THIS device holds of the instantiation a launch takes (a partitioned or smaller part
-    // has fewer than the 256 CUs of a full MI355X; another stream's kernels are not counted -- a hand-off that times
-    // out because of them is retried one cloud at a time by genpc_amd/fps.py)
-    int dev = 0, cus = 0;
-    if (!check(hipGetDevice(&dev), "hipGetDevice")) return 0;
-    if (!check(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev), "hipDeviceGetAttribute")) return 0;
-    if (cus < 1) cus = 1;
-    const bool fma = arith_mode() != 0;
-    auto budget_of = [&](int R) { return (fma ? fps_blocks_per_cu<1>(fps_class(R)) : fps_blocks_per_cu<0>(fps_class(R))) * cus; };
-    // a cloud's workgroups: as many as its size asks for, fewer (more points per thread) if the device does not hold them
-    auto plan = [&](int npts, int &W, int &R) {
-        W = fps_workgroups(npts);
-        for (;;) {
-            R = ceil_div(ceil_div(npts, W), kFThreads);
-            if (R > kFMaxR) return false;
-            if (W <= budget_of(R) || W == 1) return W <= budget_of(R);
-            W = W > 2 * budget_of(R) ? budget_of(R) : W - 1;
-        }
-    };
-    // Which kernel: clouds that fit one workgroup's LDS take the pruned sampling of fps_grid.hip (no hand-off, several samples
-    // per round, updates confined to the ball a sample can change), the others the multi-workgroup kernel above.  Same
-    // sequences (tests/test_gpu_fps.py runs both on every case); genpc_fps_tune(256): never the former.
-    // Clouds beyond the multi-workgroup kernel's registers, and every cloud of genpc_fps_large, take the third sampler
-    // (fps_large.hip: one workgroup again, its state in global memory).  A ragged call may mix all three.
-    const bool grid_on = t_fps_multi_wg == 0;
-    std::vector<int> small, big, large;
-    FpsPlan lplan = fps_plan(1, 1);
-    size_t lpts = 0, lchunks = 0;
-    for (int j = 0; j < c; j++) {
-        const FpsPlan pl = fps_plan(n[j], force_large);
-        if (pl.sampler == kFpsLarge) {
-            large.push_back(j);
-            lpts += (size_t)pl.npad;
-            lchunks += (size_t)pl.chunks;
-            lplan = pl;
-        } else (grid_on && fps_grid_takes(n[j]) ? small : big).push_back(j);
-    }
-    size_t total_slots = 0, total_k = 0, spt_pts = 0;
-    for (int j : big) total_slots += 2 * (size_t)fps_workgroups(n[j]);
-    for (int j : small) spt_pts += ((size_t)n[j] + 63) & ~(size_t)63;
-    for (int j = 0; j < c; j++) total_k += ((size_t)k[j] + 63) / 64 * 64;
-    // (the check of a cloud the large sampler takes is never cut into segments -- see verify below -- and needs no segment minima)
-    auto seg_pts = [&](int j) { return fps_plan(n[j], force_large).sampler == kFpsLarge ? (size_t)0 : (size_t)n[j]; };
-    size_t total_n = 0;
-    for (int j = 0; j < c; j++) total_n += seg_pts(j);
-    int *err, *verr; FpsSlot *slots; float *pdist, *segmin; float4 *spt;
-    float4 *lspt; unsigned *ldmin, *lchmax; int *lstart; CellGridHdr *lhdr;
-    WsLayout L;
-    L.add(err, 64);          // the 256-byte status block: [0] error, [1 ..] the clouds' hand-off rounds (genpc_fps_stats reads them back)
-    static_assert(sizeof(FpsSlot) == 128, "two slots per workgroup (total_slots is even) are whole 256-byte lines: add() reserves what was reserved unrounded before");
-    L.add(slots, total_slots);
-    L.add(verr, c);
-    L.add(pdist, total_k);
-    L.add(segmin, total_n * kFVMaxSeg);
-    L.add(spt, spt_pts);
-    // the large sampler's pieces, as fps_plan counts them (none for a call without such a cloud)
-    L.add(lspt, lpts);
-    L.add(ldmin, lpts);
-    L.add(lchmax, lchunks);
-    L.add(lstart, large.size() * (size_t)lplan.starts);
-    L.add(lhdr, large.size());
-    if (!ws_alloc(L, kWsFps, st)) return 0;
-    if (!check(hipMemsetAsync(err, 0, (size_t)((char *)pdist - (char *)err), st), "hipMemsetAsync(fps)")) return 0;
-    std::vector<float *> pd_of(c);
-    std::vector<int> seg_of(c);
-    {
-        size_t pd_off = 0, seg_off = 0;
-        for (int j = 0; j < c; j++) {
-            pd_of[j] = pdist + pd_off;
-            seg_of[j] = (int)seg_off;
-            pd_off += ((size_t)k[j] + 63) / 64 * 64;
-            seg_off += seg_pts(j);
-        }
-    }
-    // the verification of a group of clouds (fps_verify_kernel above), whichever kernel sampled them
-    auto verify = [&](const FpsJobs &jobs, int nj, hipStream_t st, float *segmin, int *violations) {
-        int nmax = 1;
-        for (int q = 0; q < nj; q++) nmax = jobs.n[q] > nmax ? jobs.n[q] : nmax;
-        const int gxv = ceil_div(nmax, kFVBlock);
-        int nseg = (4 * cus) / (gxv * nj > 0 ? gxv * nj : 1);      // about four blocks per CU
-        nseg = nseg < 1 ? 1 : (nseg > kFVMaxSeg ? kFVMaxSeg : nseg);
-        if (force_large || nmax > kFpsMultiMaxN) nseg = 1;      // (no segment minima are reserved for these clouds; their point blocks fill the chip anyway)
-        const dim3 vg(gxv, nj, nseg);
-        if (nseg > 1) {
-            if (fma) hipLaunchKernelGGL((fps_verify_kernel<1, 0>), vg, dim3(kFVBlock), 0, st, jobs, segmin, nseg);
-            else hipLaunchKernelGGL((fps_verify_kernel<0, 0>), vg, dim3(kFVBlock), 0, st, jobs, segmin, nseg);
-        }
-        if (fma) hipLaunchKernelGGL((fps_verify_kernel<1, 1>), vg, dim3(kFVBlock), 0, st, jobs, segmin, nseg);
-        else hipLaunchKernelGGL((fps_verify_kernel<0, 1>), vg, dim3(kFVBlock), 0, st, jobs, segmin, nseg);
-        if (violations) hipLaunchKernelGGL(fps_count_kernel, dim3(1), dim3(kFMaxJobs), 0, st, jobs, nj, violations);
-        else hipLaunchKernelGGL(fps_poison_kernel, dim3(1), dim3(kFMaxJobs), 0, st, jobs, nj);
-    };
-    // deferred form: the group's arrays copied behind the sampling, the check on the side stream
-    auto verify_deferred = [&](const FpsJobs &jobs, int nj, FpsDeferred *d) -> bool {
-        // (buffers of the check's own, not the pool's; three pieces per cloud: the layout is a loop, rounded by the one rule)
-        constexpr auto up = WsLayout::up;
-        size_t bytes = 256, pts = 0;
-        for (int q = 0; q < nj; q++) {
-            bytes += up((size_t)jobs.n[q] * 12) + 2 * up((size_t)jobs.k[q] * 4);
-            pts += (size_t)jobs.n[q];
-        }
-        bytes += up(pts * kFVMaxSeg * sizeof(float));
-        const int sl = (int)(d->next++ & 3u);
-        if (d->used[sl] && hipStreamWaitEvent(st, d->done[sl], 0) != hipSuccess) return false;       // (the slot's previous check: long finished)
-        if (d->cap[sl] == 0 && !d->used[0] && !d->used[1] && !d->used[2] && !d->used[3]) {
-            // first use: all four buffers at once (an allocation synchronises the device: not inside the caller's second and third call)
-            for (int q = 0; q < 4; q++) {
-                if (hipMalloc((void **)&d->buf[q], bytes + bytes / 4) != hipSuccess) return false;
-                d->cap[q] = bytes + bytes / 4;
-            }
-        }
-        if (d->cap[sl] < bytes) {
-            if (d->buf[sl]) {
-                if (hipStreamSynchronize(d->side) != hipSuccess || hipFree(d->buf[sl]) != hipSuccess) return false;
-                d->buf[sl] = nullptr;
-                d->cap[sl] = 0;
-            }
-            if (hipMalloc((void **)&d->buf[sl], bytes + bytes / 4) != hipSuccess) return false;
-            d->cap[sl] = bytes + bytes / 4;
-        }
-        char *b = d->buf[sl];
-        FpsJobs cp = jobs;
-        size_t off = 256, seg = 0;
-        if (hipMemsetAsync(b, 0, 256, st) != hipSuccess) return false;
-        for (int q = 0; q < nj; q++) {
-            const size_t xb = (size_t)jobs.n[q] * 12, kb = (size_t)jobs.k[q] * 4;
-            if (hipMemcpyAsync(b + off, jobs.xyz[q], xb, hipMemcpyDeviceToDevice, st) != hipSuccess) return false;
-            cp.xyz[q] = (const float *)(b + off); off += up(xb);
-            if (hipMemcpyAsync(b + off, jobs.out[q], kb, hipMemcpyDeviceToDevice, st) != hipSuccess) return false;
-            cp.out[q] = (int *)(b + off); off += up(kb);
-            if (hipMemcpyAsync(b + off, jobs.pdist[q], kb, hipMemcpyDeviceToDevice, st) != hipSuccess) return false;
-            cp.pdist[q] = (float *)(b + off); off += up(kb);
-            // (test hook, genpc_fps_defer(2): the check's copy of one recorded minimum is zeroed -- the check must fail)
-            if (t_fps_defer == 2 && jobs.k[q] > 8 && hipMemsetAsync(cp.pdist[q] + 8, 0, sizeof(float), st) != hipSuccess) return false;
-            cp.verr[q] = (int *)b + q;
-            cp.segoff[q] = (int)seg;
-            seg += (size_t)jobs.n[q];
-        }
-        if (hipEventRecord(d->fork[sl], st) != hipSuccess || hipStreamWaitEvent(d->side, d->fork[sl], 0) != hipSuccess) return false;
-        verify(cp, nj, d->side, (float *)(b + off), d->violations);
-        if (hipEventRecord(d->done[sl], d->side) != hipSuccess) return false;
-        d->used[sl] = true;
-        return true;
-    };
-    FpsDeferred *defer = t_fps_defer ? fps_deferred_of(st, true) : nullptr;
-    if (!small.empty()) {
-        if (fps_grid_run(fma, (int)small.size(), small.data(), n, k, xyz, out_idx, pd_of.data(), spt, err, st) != 1) return 0;
-        for (size_t q0 = 0; q0 < small.size(); q0 += kFMaxJobs) {
-            FpsJobs jobs = {};
-            int nj = 0;
-            for (; nj < kFMaxJobs && q0 + nj < small.size(); nj++) {
-                const int j = small[q0 + nj];
-                jobs.xyz[nj] = xyz[j];
-                jobs.out[nj] = out_idx[j];
-                jobs.pdist[nj] = pd_of[j];
-                jobs.verr[nj] = verr + j;
-                jobs.segoff[nj] = seg_of[j];
-                jobs.n[nj] = n[j];
-                jobs.k[nj] = k[j];
-            }
-            if (!defer || !verify_deferred(jobs, nj, defer)) verify(jobs, nj, st, segmin, nullptr);
-        }
-    }
-    if (!large.empty()) {
-        if (fps_large_run(fma, (int)large.size(), large.data(), n, k, xyz, out_idx, pd_of.data(), lspt, ldmin, lchmax, lstart, lhdr, err, st) != 1)
-            return 0;
-        // (always checked in line: genpc_fps_defer defers the LDS kernel's checks only)
-        for (size_t q0 = 0; q0 < large.size(); q0 += kFMaxJobs) {
-            FpsJobs jobs = {};
-            int nj = 0;
-            for (; nj < kFMaxJobs && q0 + nj < large.size(); nj++) {
-                const int j = large[q0 + nj];
-                jobs.xyz[nj] = xyz[j];
-                jobs.out[nj] = out_idx[j];
-                jobs.pdist[nj] = pd_of[j];
-                jobs.verr[nj] = verr + j;
-                jobs.segoff[nj] = seg_of[j];
-                jobs.n[nj] = n[j];
-                jobs.k[nj] = k[j];
-            }
-            verify(jobs, nj, st, segmin, nullptr);
-        }
-    }
-    int slot0 = 0;
-    const int cb = (int)big.size();
-    for (int j0 = 0; j0 < cb;) {
-        // a launch takes up to kFMaxJobs clouds; its grid is (largest W) x (clouds), all of it resident together
+    for (int l = 0; l < nl; l++) {
+        const FpsLaunch &la = launches[l];
         FpsJobs jobs = {};
-        jobs.stat0 = big[j0] < 32 ? big[j0] : 32;
-        int nj = 0, wmax = 0, rmax = 1;
-        while (j0 + nj < cb && nj < kFMaxJobs) {
-            const int j = big[j0 + nj];
-            int W = 0, R = 0;
-            if (!plan(n[j], W, R)) {
-                set_error("genpc_fps: the cloud needs more co-resident workgroups than the device admits");
-                return 0;
-            }
-            const int wm = W > wmax ? W : wmax, rm = R > rmax ? R : rmax;
-            if (nj > 0 && (long long)wm * (nj + 1) > budget_of(rm)) break;
-            jobs.xyz[nj] = xyz[j];
-            jobs.out[nj] = out_idx[j];
-            jobs.pdist[nj] = pd_of[j];
-            jobs.verr[nj] = verr + j;
-            jobs.segoff[nj] = seg_of[j];
-            jobs.n[nj] = n[j];
-            jobs.k[nj] = k[j];
-            jobs.W[nj] = W;
-            jobs.slot0[nj] = slot0;
-            slot0 += 2 * W;
-            wmax = wm;
-            rmax = rm;
-            nj++;
+        jobs.stat0 = sel[la.first] < 32 ? sel[la.first] : 32;
+        for (int q = 0; q < la.count; q++) {
+            fps_fill_job(jobs, q, c, sel[la.first + q]);
+            jobs.W[q] = shape[la.first + q].W;
+            jobs.slot0[q] = slot0[la.first + q];
         }
-        // The hand-off needs the launch resident as a whole, like the one-launch auction: both take their share of the chip
-        // from one budget (quarter-CU units; a workgroup of an instantiation the CU holds k of costs ceil(4 / k)), so two such
-        // launches of different streams never sit half-resident waiting for workgroups the other one keeps out (ADVICE r4:
-        // two samplings of different lanes could spin against each other until the timeout).
-        const int per_cu = fma ? fps_blocks_per_cu<1>(fps_class(rmax)) : fps_blocks_per_cu<0>(fps_class(rmax));
-        const int units = wmax * nj * ((4 + per_cu - 1) / per_cu);
-        const bool admitted = persist_reserve(units, emd_auction_capacity(), st);
-        if (fma) launch_fps<1>(rmax, dim3(wmax, nj), st, jobs, slots, err);
-        else launch_fps<0>(rmax, dim3(wmax, nj), st, jobs, slots, err);
-        if (admitted) persist_commit(units, st);
-        verify(jobs, nj, st, segmin, nullptr);
-        j0 += nj;
+        const FpsKernel kernel = c.fma ? fps_kernel_of<1>(fps_class(la.rmax)) : fps_kernel_of<0>(fps_class(la.rmax));
+        const bool admitted = persist_reserve(la.units, emd_auction_capacity(), c.st);
+        hipLaunchKernelGGL(kernel, dim3(la.wmax, la.count), dim3(kFBlock), 0, c.st, jobs, (FpsSlot *)slots, c.err);
+        if (admitted) persist_commit(la.units, c.st);
+        fps_verify(c, jobs, la.count, false);
     }
-    if (!check(hipGetLastError(), "fps launch")) return 0;
-    return 1;
+    return check(hipGetLastError(), "fps_kernel launch") ? 1 : 0;
 }
 
-GENPC_API int genpc_fps_multi(int c, const int *n, const int *k, const float *const *xyz, int *const *out_idx, void *stream)
-{
-    return fps_call(c, n, k, xyz, out_idx, stream, 0);
-}
-
-GENPC_API int genpc_fps_large(int c, const int *n, const int *k, const float *const *xyz, int *const *out_idx, void *stream)
-{
-    return fps_call(c, n, k, xyz, out_idx, stream, 1);
-}
-
-GENPC_API int genpc_fps_plan(int n, int force_large, int out[8])
-{
-    if (!out) return -1;
-    const genpc::FpsPlan p = genpc::fps_plan(n, force_large);
-    out[0] = p.sampler; out[1] = p.cells_max; out[2] = p.cells_target; out[3] = p.npad;
-    out[4] = p.chunks; out[5] = p.starts; out[6] = p.lds_bytes; out[7] = p.build_own;
-    return p.sampler == genpc::kFpsNone ? -1 : 1;
-}
-
-namespace genpc {
-void fps_deferred_prepare(hipStream_t st)
-{
-    FpsDeferred *d = fps_deferred_of(st, true);
-    if (d) {
-        (void)hipEventRecord(d->fork[0], d->side);
-        (void)hipStreamSynchronize(d->side);
-    }
-}
 }  // namespace genpc
-
-GENPC_API int genpc_fps_defer(int on)
-{
-    const int prev = genpc::t_fps_defer;
-    genpc::t_fps_defer = on == 2 ? 2 : (on ? 1 : 0);
-    return prev;
-}
-
-GENPC_API int genpc_fps_deferred_check(void *stream)
-{
-    using namespace genpc;
-    FpsDeferred *d = fps_deferred_of((hipStream_t)stream, false);
-    if (!d) return 0;
-    int v = 0;
-    if (!check(hipStreamSynchronize(d->side), "hipStreamSynchronize(fps check)")) return -1;
-    if (!check(hipMemcpy(&v, d->violations, sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy(fps check)")) return -1;
-    if (v != 0 && !check(hipMemset(d->violations, 0, sizeof(int)), "hipMemset(fps check)")) return -1;
-    return v;
-}
-
-GENPC_API int genpc_fps_stats(int c, int *rounds, void *stream)
-{
-    // exchanges (hand-off rounds) each of the first c <= 32 clouds of the last genpc_fps_multi call on this
-    // stream took; synchronises the stream
-    using namespace genpc;
-    if (c < 0 || c > 60) return -1;
-    hipStream_t st = (hipStream_t)stream;
-    char *ws = (char *)workspace(kWsFps, 256, st);
-    if (!ws) return 0;
-    if (!check(hipMemcpyAsync(rounds, ws + 4, (size_t)c * sizeof(int), hipMemcpyDeviceToHost, st), "fps stats copy")) return 0;
-    return check(hipStreamSynchronize(st), "fps stats sync") ? 1 : 0;
-}
-
-GENPC_API int genpc_fps(int c, int n, const float *xyz, int k, int *out_idx, void *stream)
-{
-    if (c <= 0 || k <= 0) return 1;
-    // C clouds of one size: chunks of kFMaxJobs through the ragged entry
-    for (int c0 = 0; c0 < c; c0 += genpc::kFMaxJobs) {
-        const int cc = c - c0 < genpc::kFMaxJobs ? c - c0 : genpc::kFMaxJobs;
-        int ns[genpc::kFMaxJobs], ks[genpc::kFMaxJobs];
-        const float *xs[genpc::kFMaxJobs];
-        int *os[genpc::kFMaxJobs];
-        for (int j = 0; j < cc; j++) {
-            ns[j] = n; ks[j] = k;
-            xs[j] = xyz + (size_t)(c0 + j) * n * 3;
-            os[j] = out_idx + (size_t)(c0 + j) * k;
-        }
-        const int rc = genpc_fps_multi(cc, ns, ks, xs, os, stream);
-        if (rc != 1) return rc;
-    }
-    return 1;
-}

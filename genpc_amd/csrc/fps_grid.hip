@@ -20,11 +20,10 @@
 //
 // No hand-off between workgroups: nothing has to be co-resident, nothing is admitted, nothing can time out; clouds of one
 // launch are independent blocks.  Clouds beyond kGMaxN points take fps.hip's multi-workgroup kernel or, beyond its limit,
-// fps_large.hip's sampler, which is this scheme with its state in global memory (fps_plan.h decides).
+// fps_large.hip's sampler, which is this scheme with its state in global memory (fps_plan.h decides; fps_call.hip carries it out).
 // The sequence and the running minimum of every sample when drawn go to the same outputs as fps.hip's, so
-// fps_verify_kernel checks these samplings against the definition like the others.
-#include "common.h"
-#include "fps_plan.h"
+// fps_verify_kernel (fps_verify.hip) checks these samplings against the definition like the others.
+#include "fps.h"
 #include "../../include/genpc_hip.h"
 
 namespace genpc {
@@ -614,7 +613,7 @@ static int fps_grid_launch_one(bool fma, int nj, size_t lds, hipStream_t st, con
 }
 
 // Clouds `sel[0..c)` (indices into the call's arrays) through the one-workgroup kernel.  `spt`: 16 bytes per point of scratch,
-// `pdist_of[j]`: where cloud j's running minima go (fps.hip's verification reads them), err: the call's error / statistics words.
+// `pdist_of[j]`: where cloud j's running minima go (fps_verify.hip reads them), err: the call's error / statistics words.
 int fps_grid_run(bool fma, int c, const int *sel, const int *n, const int *k, const float *const *xyz, int *const *out_idx,
                  float *const *pdist_of, float4 *spt, int *err, hipStream_t st)
 {
@@ -630,7 +629,7 @@ int fps_grid_run(bool fma, int c, const int *sel, const int *n, const int *k, co
             jobs.out[q] = out_idx[j];
             jobs.pdist[q] = pdist_of[j];
             jobs.spt[q] = spt + off;
-            off += ((size_t)n[j] + 63) & ~(size_t)63;
+            off += fps_grid_points(n[j]);
             jobs.n[q] = n[j];
             jobs.k[q] = k[j];
             const size_t b = fps_grid_lds(n[j]);
@@ -639,8 +638,8 @@ int fps_grid_run(bool fma, int c, const int *sel, const int *n, const int *k, co
         // statistics slot of the launch's first cloud (genpc_fps_stats reads the first 32 clouds of a call)
         jobs.stat0 = sel[j0] < 32 ? sel[j0] : 32;
         // (the kernel writes err[1 + stat0 + job]: consecutive slots -- exact when the selected clouds are consecutive, as they are
-        //  for calls of one size; a ragged call's statistics may land in a neighbour's slot, never outside the 64 words)
-        if (jobs.stat0 + nj > 40) jobs.stat0 = 40 - nj;
+        //  for calls of one size; a ragged call's statistics may land in a neighbour's slot)
+        static_assert(1 + 32 + kGMaxJobs <= 64, "the launch's slots lie within the 64 words of the status block");
         if (!fps_grid_launch_one(fma, nj, lds, st, jobs, err)) return 0;
     }
     return check(hipGetLastError(), "fps_grid_kernel launch") ? 1 : 0;

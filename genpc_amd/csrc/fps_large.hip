@@ -38,9 +38,8 @@
 // No workgroup waits on another: no spin loop, no polled counter, no admission.  Every loop is bounded (max_attempts sweeps; a
 // round draws at least one sample); a sampling that exhausts a bound writes out[0] = -1, raises the error word and returns, as
 // fps_grid_kernel does.  The sequence and the running minimum of every sample when drawn go to the same outputs as the other two
-// samplers', and fps_verify_kernel (fps.hip) checks every finished sequence against the definition, in line.
-#include "grid.h"
-#include "fps_plan.h"
+// samplers', and fps_verify_kernel (fps_verify.hip) checks every finished sequence against the definition, in line.
+#include "fps.h"
 #include "../../include/genpc_hip.h"
 
 namespace genpc {
@@ -540,7 +539,7 @@ __global__ __launch_bounds__(kLT) void fps_large_kernel(FpsLargeJobs jobs, int *
 
 // Clouds `sel[0..c)` (indices into the call's arrays) through the large sampler.  The scratch pieces hold what fps_plan counts, for
 // the selected clouds in order: spt / dmin (npad each), chmax (chunks each), start (starts each), hdr (one each).  `pdist_of[j]`:
-// where cloud j's running minima go (fps.hip's verification reads them), err: the call's error / statistics words.
+// where cloud j's running minima go (fps_verify.hip reads them), err: the call's error / statistics words.
 int fps_large_run(bool fma, int c, const int *sel, const int *n, const int *k, const float *const *xyz, int *const *out_idx,
                   float *const *pdist_of, float4 *spt, unsigned *dmin, unsigned *chmax, int *start, CellGridHdr *hdr, int *err,
                   hipStream_t st)

@@ -31,6 +31,7 @@
 // the gradient pass; the NN launch dominates (VALU-bound, see chamfer.hip).
 #include "nn.h"
 #include "mask.h"
+#include "fps.h"
 #include "pose_ragged_plan.h"
 #include "../../include/genpc_hip.h"
 
@@ -532,8 +533,6 @@ static bool pose_replicate(int scans, int rep, int nc, int np, const float *&com
     return true;
 }
 }  // namespace genpc
-
-namespace genpc { void fps_deferred_prepare(hipStream_t st); }
 
 /* The side streams the library pairs with `stream` (the alignment loop's second stream, the sampling check's), made NOW and
  * each given a first command, so that they get their hardware queues before the caller makes other streams: which queue

@@ -84,7 +84,7 @@ def _fps_multi_direct(clouds, ks, _attempt=0, _entry="genpc_fps_multi"):
         stats["failed_check"] += sum(1 for j in bad if first[j] == -2)
     if bad and (c > 1 or _attempt < 3):
         # out[0] == -1: a hand-off timed out (something else on the GPU kept a cloud's workgroups from running together), or
-        # the device-side verification (csrc/fps.hip: fps_verify_kernel) found a step whose sample is not the first arg-max --
+        # the device-side verification (csrc/fps_verify.hip: fps_verify_kernel) found a step whose sample is not the first arg-max --
         # seen twice for samplings running beside other streams' kernels, cause unknown.  Not an error yet: the clouds that
         # failed go again, one at a time (a launch to itself needs a fraction of the device)
         for j in bad:

@@ -154,7 +154,7 @@ def complete_scan(partial_xyz, generated_xyz, generated_img, gt_xyz=None, cfg=No
     tail_inline = tail
 
     def tail(res):          # noqa: F811
-        # The samplings' device-side check runs BESIDE what follows them (csrc/fps.hip, genpc_fps_defer: ~1 ms of chip-wide kernels
+        # The samplings' device-side check runs BESIDE what follows them (csrc/fps_verify.hip, genpc_fps_defer: ~1 ms of chip-wide kernels
         # behind each of the tail's two samplings otherwise); its verdict is collected here, before anything is returned, and a
         # failed check means the tail again with the check in line.
         # (with several scans in flight the chip is shared already and the check's side stream only adds to the queues: six lanes

@@ -47,14 +47,20 @@ def _code(text):
 def test_the_entry_points_and_the_kernels_read_the_plan():
     """genpc_fps_multi and genpc_fps_large are one body that asks fps_plan for every cloud and holds no size of its own;
     fps_grid_takes is the plan's answer; the large sampler's launcher takes its sizes from the plan."""
-    fps = open(os.path.join(CSRC, "fps.hip")).read()
+    fps = open(os.path.join(CSRC, "fps_call.hip")).read()
     assert "fps_call(c, n, k, xyz, out_idx, stream, 0)" in _body(fps, "GENPC_API int genpc_fps_multi(")
     assert "fps_call(c, n, k, xyz, out_idx, stream, 1)" in _body(fps, "GENPC_API int genpc_fps_large(")
     call = _code(_body(fps, "static int fps_call("))
-    assert len(re.findall(r"fps_plan\(n\[j\], force_large\)", call)) >= 3
+    # the admission and the choice of sampler in fps_call, the sizes in the workspace function it calls: all ask fps_plan
+    header = _code(open(os.path.join(CSRC, "fps_plan.h")).read())
+    assert len(re.findall(r"fps_plan\(n\[j\], force_large\)", call)) >= 2
+    assert "fps_workspace(c, n, k, sampler.data()" in call and "fps_plan(n[j], 1)" in _body(header, "inline FpsWorkspace fps_workspace(")
     for word in ("262144", "24576", "kGMaxN", "15360"):
         assert word not in call, word
     assert not re.search(r"n\[j\]\s*[<>]=?\s*\d", call)                  # no comparison of a point count with a number
+    assert not re.search(r"\[[&=]?\]\s*\(", call)                         # no lambda: every decision is a function of fps_plan.h
+    for name in ("fps_multi_shape(", "fps_multi_launches(", "fps_workspace(", "fps_k_pad(", "fps_seg_points("):
+        assert name in call, name
     assert "genpc::fps_plan(n, force_large)" in _body(fps, "GENPC_API int genpc_fps_plan(")
     grid = _code(open(os.path.join(CSRC, "fps_grid.hip")).read())
     assert re.search(r"bool fps_grid_takes\(int n\)\s*\{\s*return fps_plan\(n, 0\)\.sampler == kFpsGrid;\s*\}", grid)
@@ -70,6 +76,41 @@ def test_the_entry_points_and_the_kernels_read_the_plan():
     for name in ("kFpsLargeCellBits", "kFpsLargePosBits", "kFpsLargeIndexBits", "kFpsLargeSampleBits"):
         assert re.search(r"static_assert\([^;]*%s" % name, plan), name
         assert name in large or name == "kFpsLargeSampleBits", name
+
+
+def test_the_register_classes_are_stated_once():
+    """The boundaries 2 / 4 / 8 / 12 / 16 / 24 of fps_kernel's instantiations stand in fps_plan.h alone; fps.hip builds ONE table of
+    instantiations from them, and both the launch and the occupancy query go through it -- no file launches fps_kernel by name."""
+    literal = re.compile(r"2\s*,\s*4\s*,\s*8\s*,\s*12\s*,\s*16\s*,\s*24")
+    holders = [f for f in sorted(os.listdir(CSRC)) if literal.search(_code(open(os.path.join(CSRC, f)).read()))]
+    assert holders == ["fps_plan.h"], holders
+    plan = _code(open(os.path.join(CSRC, "fps_plan.h")).read())
+    assert len(literal.findall(plan)) == 1 and re.search(r"kFpsClassPoints\[kFpsClasses\]\s*=\s*\{2, 4, 8, 12, 16, 24\}", plan)
+    assert "kFpsClassPoints[cls]" in _body(plan, "inline int fps_class(")
+    fps = _code(open(os.path.join(CSRC, "fps.hip")).read())
+    table = _body(fps, "static FpsKernel fps_kernel_of(")
+    assert [int(i) for i in re.findall(r"fps_kernel<FMA, kFpsClassPoints\[(\d)\]>", table)] == [0, 1, 2, 3, 4, 5]
+    # an instantiation is named in the table and nowhere else; switch statements over R or the class are gone
+    for name in ("fps.hip", "fps_call.hip", "fps_verify.hip"):
+        text = _code(open(os.path.join(CSRC, name)).read())
+        outside = text.replace(table, "") if name == "fps.hip" else text
+        assert "hipLaunchKernelGGL((fps_kernel<" not in outside, name
+        assert not re.search(r"fps_kernel<\s*(FMA|[01])\s*,", outside), name
+        assert not re.search(r"case 1[0-9]:|R <= \d", outside), name
+    assert re.search(r"hipOccupancyMaxActiveBlocksPerMultiprocessor\([^;]*fps_kernel_of<1>\(cls\)[^;]*fps_kernel_of<0>\(cls\)", _body(fps, "bool fps_device("))
+    run = _body(fps, "int fps_multi_run(")
+    assert re.search(r"fps_kernel_of<1>\(fps_class\(la\.rmax\)\)\s*:\s*fps_kernel_of<0>\(fps_class\(la\.rmax\)\)", run)
+    assert "hipLaunchKernelGGL(kernel, dim3(la.wmax, la.count), dim3(kFBlock)" in run
+    # one fill of a job-table entry, in the shared header
+    shared = _code(open(os.path.join(CSRC, "fps.h")).read())
+    fills = sum(len(re.findall(r"jobs\.pdist\[\w+\]\s*=", _code(open(os.path.join(CSRC, f)).read())))
+                for f in ("fps.h", "fps.hip", "fps_call.hip", "fps_verify.hip"))
+    assert fills == 1 and "jobs.pdist[q] = c.pdist[j];" in _body(shared, "inline void fps_fill_job(")
+    # nothing is declared by hand any more
+    for name in ("fps.hip", "fps_call.hip", "fps_verify.hip", "fps_grid.hip", "fps_large.hip", "pose.hip"):
+        text = _code(open(os.path.join(CSRC, name)).read())
+        assert '#include "fps.h"' in text, name
+        assert not re.search(r"^\s*(bool|void|int)\s+(persist_reserve|persist_commit|emd_auction_capacity|fps_deferred_prepare)\([^)]*\);", text, re.M), name
 
 
 def test_exported_plan_is_the_header_s(program):

@@ -1,8 +1,8 @@
 """Entry points called from several host threads, each on a stream of its own, give the single-threaded results.
 
 Round 4 found a farthest-point sampling that ran next to the f16 nearest-neighbour filter (another stream, another thread)
-drawing a sample one step early, silently -- not once in the suite's single-stream tests (csrc/fps.hip: the workers' pivot
-reads).  The library keys its scratch by stream and its entry points take the stream as an argument, so this is supported
+drawing a sample one step early, silently -- not once in the suite's single-stream tests (csrc/fps.hip, fps_body: the workers' pivot
+reads; csrc/fps_verify.hip now checks every sequence on the device).  The library keys its scratch by stream and its entry points take the stream as an argument, so this is supported
 use; this is the test that was missing.
 """
 import os

@@ -214,6 +214,38 @@ def test_fps_multi_ragged(fg, oracle):
     assert sorted(got[1].cpu().numpy().tolist()) == list(range(16384))      # k == n: a permutation
 
 
+@pytest.mark.parametrize("mode", [0, 1])
+def test_fps_multi_two_launches_of_the_multi_workgroup_kernel(fg, oracle, mode):
+    """Ten small clouds in ONE call, all on the multi-workgroup kernel (genpc_fps_tune(256)): more than a launch takes
+    (csrc/fps_plan.h: kFMaxJobs = 8), so the plan makes two launches of 8 and 2 clouds -- the second one's hand-off slots and
+    statistics words carry on behind the first one's.  Every sequence equals the oracle's, and every cloud's word of the status
+    block holds its exchanges."""
+    import ctypes
+    torch = fg["torch"]
+    from genpc_amd.fps import fps_sampling_multi
+    L = fg["lib"].lib
+    rng = np.random.default_rng(256)
+    shapes = [(193, 64), (3000, 64), (385, 17), (1000, 64), (2049, 33), (577, 64), (1500, 1), (2500, 50), (769, 64), (2999, 40)]
+    clouds = [(rng.random((n, 3), dtype=np.float32) - 0.5).astype(np.float32) for n, _ in shapes]
+    clouds[9][50:90] = clouds[9][0:40]                       # duplicates, in the second launch: ties
+    dev = [torch.from_numpy(c).cuda() for c in clouds]
+    rounds = (ctypes.c_int * len(shapes))(*([-7] * len(shapes)))
+    prev_a = L.genpc_set_arith(mode)
+    try:
+        prev = L.genpc_fps_tune(256)
+        try:
+            got = [g.cpu().numpy() for g in fps_sampling_multi(dev, [k for _, k in shapes])]
+            assert fg["lib"].on_device_of(dev[0], L.genpc_fps_stats, len(shapes), ctypes.addressof(rounds)) == 1
+        finally:
+            L.genpc_fps_tune(prev)
+    finally:
+        L.genpc_set_arith(prev_a)
+    for j, ((n, k), c, g) in enumerate(zip(shapes, clouds, got)):
+        np.testing.assert_array_equal(g, oracle.fps(c, k, mode), err_msg="cloud %d: n %d k %d" % (j, n, k))
+        # a cloud draws at most 64 samples per exchange and at least one: 0 exchanges for k = 1
+        assert (k - 1 + 63) // 64 <= rounds[j] <= k - 1, (j, rounds[j])
+
+
 def test_fps_threads_on_their_own_streams_get_their_own_sequences(fg):
     """Samplings of several host threads at once (a stream each): every thread gets the sequences a call of its own gives."""
     import threading
