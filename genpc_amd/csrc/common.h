@@ -82,6 +82,8 @@ enum Ws : int {
     kWsPoseRaggedGridPartial = 52, // pose.hip, posed -> partial: the partial clouds' grids (nn_ragged.hip), built once per call.  SHARED by the two ragged pose entry points: each builds afresh and is done with them at its last launch
     kWsPoseRaggedGridPosed = 53,   // pose.hip, partial -> posed: the posed clouds' grids, rebuilt every step.  SHARED like 52
     kWsDepthPromptRagged = 54, // depth_prompt_ragged.hip genpc_depth_prompt_ragged: box and depth-range keys, owner planes (one memset) | chunk partial sums | per-scan records
+    kWsRenderPoints = 55,     // render_grad.hip genpc_render_points: mask scratch of the b images
+    kWsRenderPointsGrad = 56, // render_grad.hip genpc_render_points_backward: the per-pixel weights W1 | W4 of the b images
 };
 
 // The scratch pool: one grow-only block of device memory per (device, slot, stream); null on failure, the error recorded.

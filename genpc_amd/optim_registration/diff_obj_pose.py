@@ -18,8 +18,18 @@ splat of rounds 2-4 (occupancy times the coverage-weighted mean colour: order-in
 front and back surfaces averaged).  The whole multi-start loop
 runs on the device without host synchronisation (7 launches per Adam step; 4 with
 ``cd_only=True``).
+
+That loop is ONE fixed objective with an analytic gradient.  The reference's stage is a torch program, and the second half of
+this file is that program on the library's renderer: ``render_points`` (a ``torch.autograd.Function`` over genpc_render_points /
+genpc_render_points_backward, csrc/render_grad.hip), the reference's ``ObjectPoseOptim``, ``render_reference_image``,
+``compute_loss_function`` (with ``weights=``), ``normalize_images``, ``compute_soft_mask``, ``dice_loss``, ``soft_iou_loss``,
+``edge_loss``, ``get_init_rot``, ``build_transform`` restated from their formulas, and ``object_pose_optimization_torch``, its
+Adam loop with an objective the caller may replace (``loss_fn=``).  DESIGN.md 4.5d.
 """
+import math
+
 import torch
+from torch import nn
 
 from .. import _lib
 
@@ -449,4 +459,388 @@ def object_pose_optimization(glb_path, point_path, radius=0.005, lr=0.005, iters
         np.save("final_transform.npy", final_transform)      # :591
     if return_history:
         return final_transform, h, bpn
+    return final_transform
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The customisable path: the renderer as a torch.autograd.Function, the reference's torch helpers restated from their formulas,
+# its nn.Module and its Adam loop in torch.  object_pose_optimization above stays the fast path (one fused analytic-gradient
+# loop of ONE objective); what follows lets a caller change the objective, optimise points or colours, or put the rendered
+# image into an autograd graph of their own.
+
+def _thread_blend():
+    """the calling thread's render_tune mode as 0 / 1 (read by setting the default and putting back what was there)"""
+    prev = int(_L.genpc_render_tune(-1))
+    _L.genpc_render_tune(prev)
+    return 0 if prev == 0 else 1
+
+
+def render_points_forward(pts, col, radius, render_size, blend):
+    """genpc_render_points on [B,N,3] float32 GPU tensors (col None: white) -> (img [B,S,S,3], planes [B,5,S*S])."""
+    b, n, s = pts.shape[0], pts.shape[1], int(render_size)
+    img = torch.empty(b, s, s, 3, device=pts.device)
+    planes = torch.empty(b, 5, s * s, device=pts.device)
+    rc = _lib.on_device_of(pts, _L.genpc_render_points, b, n, _p(pts), _p(col), float(radius), s, int(blend), _p(img), _p(planes))
+    if rc != 1:
+        raise RuntimeError("genpc_render_points failed (rc=%d): %s" % (rc, _lib.last_error()))
+    return img, planes
+
+
+def render_points_backward(pts, col, radius, render_size, blend, planes, grad_img, want_col=True):
+    """genpc_render_points_backward: planes as render_points_forward returned them for the same arguments, grad_img [B,S,S,3]
+    -> (grad_pts [B,N,3], grad_col [B,N,3] or None)."""
+    b, n = pts.shape[0], pts.shape[1]
+    grad_pts = torch.zeros_like(pts) if n == 0 else torch.empty_like(pts)
+    grad_col = (torch.zeros_like(pts) if n == 0 else torch.empty_like(pts)) if want_col else None
+    rc = _lib.on_device_of(pts, _L.genpc_render_points_backward, b, n, _p(pts), _p(col), float(radius), int(render_size), int(blend),
+                           _p(planes), _p(grad_img), _p(grad_pts), _p(grad_col))
+    if rc != 1:
+        raise RuntimeError("genpc_render_points_backward failed (rc=%d): %s" % (rc, _lib.last_error()))
+    return grad_pts, grad_col
+
+
+class _RenderPoints(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pts, col, radius, render_size, blend):
+        img, planes = render_points_forward(pts, col, radius, render_size, blend)
+        if col is None:
+            ctx.save_for_backward(pts, planes)
+        else:
+            ctx.save_for_backward(pts, planes, col)
+        ctx.args = (float(radius), int(render_size), int(blend))      # (the blend of the FORWARD: the backward's thread has a mode of its own)
+        return img
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_img):
+        saved = ctx.saved_tensors
+        pts, planes, col = saved[0], saved[1], saved[2] if len(saved) > 2 else None
+        radius, render_size, blend = ctx.args
+        want_col = col is not None and ctx.needs_input_grad[1]
+        g = grad_img.contiguous().float()
+        grad_pts, grad_col = render_points_backward(pts, col, radius, render_size, blend, planes, g, want_col)
+        return grad_pts, grad_col, None, None, None
+
+
+def render_points(points, colors=None, radius=0.005, render_size=224, blend=None):
+    """The library's renderer as a differentiable torch operation (genpc_render_points / genpc_render_points_backward,
+    csrc/render_grad.hip): points [N,3] -> image [S,S,3], or [B,N,3] -> [B,S,S,3] (B clouds of equal size, one call); colors of
+    the points' shape in [0,1], None = white.  The camera is the library's one (eye (0,0,3) looking at the origin, focal 4);
+    radius is used as given (ObjectPoseOptim applies the reference's factor 1.1).
+    blend: 1 Pulsar's blending function, 0 the coverage splat, None the calling thread's render_tune mode AT FORWARD TIME -- the
+    backward uses the forward's blend whatever thread it runs on and whatever mode is set by then.
+    Gradients go to `points`, and to `colors` when it requires grad (otherwise the colour gradient is not computed); none to
+    the radius.  once_differentiable: no double backward.  The backward sums in a fixed order: the same bits in every run.
+    GPU tensors only."""
+    if not torch.is_tensor(points):
+        raise TypeError("render_points: points must be a tensor")
+    _lib.require_gpu(points)
+    if points.dim() not in (2, 3) or points.shape[-1] != 3:
+        raise ValueError("render_points: points must be [N,3] or [B,N,3], got %s" % (tuple(points.shape),))
+    if colors is not None:
+        if not torch.is_tensor(colors):
+            colors = torch.as_tensor(colors, device=points.device)
+        _lib.require_gpu(colors)
+        if colors.shape != points.shape:
+            raise ValueError("render_points: colors must have the shape of points %s, got %s" % (tuple(points.shape), tuple(colors.shape)))
+    if blend is None:
+        blend = _thread_blend()
+    elif blend not in (0, 1):
+        raise ValueError("render_points: blend must be None, 0 or 1, got %r" % (blend,))
+    single = points.dim() == 2
+    pts = (points[None] if single else points).float().contiguous()
+    col = None if colors is None else (colors[None] if single else colors).float().contiguous()
+    img = _RenderPoints.apply(pts, col, float(radius), int(render_size), int(blend))
+    return img[0] if single else img
+
+
+def rotation_6d_to_matrix(d6):
+    """Zhou et al.'s 6-D rotation (CVPR 2019), pytorch3d's convention: Gram-Schmidt of the two 3-vectors, the three results as
+    ROWS.  [...,6] -> [...,3,3]."""
+    a1, a2 = d6[..., :3], d6[..., 3:]
+    b1 = torch.nn.functional.normalize(a1, dim=-1)
+    b2 = a2 - (b1 * a2).sum(-1, keepdim=True) * b1
+    b2 = torch.nn.functional.normalize(b2, dim=-1)
+    b3 = torch.cross(b1, b2, dim=-1)
+    return torch.stack((b1, b2, b3), dim=-2)
+
+
+def matrix_to_rotation_6d(matrix):
+    """the first two rows of [...,3,3] as [...,6] (the inverse of rotation_6d_to_matrix on rotations)"""
+    return matrix[..., :2, :].clone().reshape(matrix.shape[:-2] + (6,))
+
+
+def get_init_rot(axis, angle_deg, device):
+    """diff_obj_pose.py:470-493: the 6-D form of the rotation by angle_deg degrees about `axis` ('x', 'y', 'z' or a 3-vector,
+    normalised here) -> [6] float32 on device.  Rodrigues' formula R = I + sin t K + (1 - cos t) K^2."""
+    if isinstance(axis, str):
+        names = {"x": (1.0, 0.0, 0.0), "y": (0.0, 1.0, 0.0), "z": (0.0, 0.0, 1.0)}
+        if axis.lower() not in names:
+            raise ValueError("unknown axis %r: 'x', 'y', 'z' or a 3-vector" % (axis,))
+        k = torch.tensor(names[axis.lower()], dtype=torch.float32)
+    else:
+        k = torch.as_tensor(axis, dtype=torch.float32).reshape(-1).cpu()
+        if k.numel() != 3:
+            raise ValueError("a custom axis must have 3 entries")
+        k = k / (k.norm() + 1e-8)
+    t = math.radians(angle_deg)
+    K = torch.tensor([[0.0, -float(k[2]), float(k[1])], [float(k[2]), 0.0, -float(k[0])], [-float(k[1]), float(k[0]), 0.0]], dtype=torch.float64)
+    R = torch.eye(3, dtype=torch.float64) + math.sin(t) * K + (1.0 - math.cos(t)) * (K @ K)
+    return matrix_to_rotation_6d(R.float()[None])[0].to(device)
+
+
+def build_transform(R_obj, t, scale):
+    """diff_obj_pose.py:464-468: [[s R, t], [0, 1]]"""
+    T = torch.eye(4, device=R_obj.device)
+    T[:3, :3] = R_obj * scale
+    T[:3, 3] = t
+    return T
+
+
+def _luminance(img):
+    return 0.299 * img[:, :, 0] + 0.587 * img[:, :, 1] + 0.114 * img[:, :, 2]
+
+
+def normalize_images(ref_img, result_img, method="statistical"):
+    """diff_obj_pose.py:201-236: result_img's per-channel mean and (unbiased) std moved onto ref_img's, clamped to [0,1];
+    'histogram': the same with the luminances' scalar statistics; anything else: unchanged.  -> (ref_img, result_normalized)"""
+    if method == "statistical":
+        ref_mean = torch.mean(ref_img, dim=(0, 1), keepdim=True)
+        ref_std = torch.std(ref_img, dim=(0, 1), keepdim=True) + 1e-6
+        res_mean = torch.mean(result_img, dim=(0, 1), keepdim=True)
+        res_std = torch.std(result_img, dim=(0, 1), keepdim=True) + 1e-6
+    elif method == "histogram":
+        rg, sg = _luminance(ref_img), _luminance(result_img)
+        ref_mean, ref_std = torch.mean(rg), torch.std(rg) + 1e-6
+        res_mean, res_std = torch.mean(sg), torch.std(sg) + 1e-6
+    else:
+        return ref_img, result_img
+    return ref_img, torch.clamp((result_img - res_mean) / res_std * ref_std + ref_mean, 0.0, 1.0)
+
+
+def compute_soft_mask(rendered_img, threshold=0.1, tau=0.05, method="luminance"):
+    """diff_obj_pose.py:258-275: sigmoid((occupancy - threshold) / tau), occupancy the luminance or ('occupancy') the channel sum"""
+    occ = rendered_img.sum(-1) if method == "occupancy" else _luminance(rendered_img)
+    return torch.sigmoid((occ - threshold) / tau)
+
+
+def dice_loss(pred_mask, target_mask, smooth=1e-6):
+    """diff_obj_pose.py:239-256: 1 - (2 sum(p t) + smooth) / (sum p + sum t + smooth)"""
+    p, t = pred_mask.reshape(-1), target_mask.reshape(-1)
+    return 1 - (2.0 * (p * t).sum() + smooth) / (p.sum() + t.sum() + smooth)
+
+
+def soft_iou_loss(result_img, ref_mask, threshold=0.1, tau=0.05, method="luminance", smooth=1e-6):
+    """diff_obj_pose.py:181-199 -> (1 - iou, iou, the soft mask of result_img)"""
+    pred = compute_soft_mask(result_img, threshold, tau, method)
+    inter = (pred * ref_mask).sum()
+    union = pred.sum() + ref_mask.sum() - inter
+    iou = (inter + smooth) / (union + smooth)
+    return 1.0 - iou, iou, pred
+
+
+def edge_loss(ref_img, result):
+    """diff_obj_pose.py:277-284: MSE between the absolute differences of neighbouring pixels, along both image axes"""
+    mse = torch.nn.functional.mse_loss
+    eh = lambda x: torch.abs(x[:, :-1, :] - x[:, 1:, :])
+    ev = lambda x: torch.abs(x[:-1, :, :] - x[1:, :, :])
+    return mse(eh(ref_img), eh(result)) + mse(ev(ref_img), ev(result))
+
+
+LOSS_WEIGHTS = dict(mse=0.0, edge=0.0, mask=1.0, iou=0.0, cd=3.0)      # diff_obj_pose.py:329-334
+
+
+def _loss_weights(weights):
+    w = dict(LOSS_WEIGHTS)
+    if weights is None:
+        return w
+    if isinstance(weights, dict):
+        unknown = set(weights) - set(w)
+        if unknown:
+            raise ValueError("compute_loss_function: unknown weights %s (known: %s)" % (sorted(unknown), sorted(w)))
+        w.update({k: float(v) for k, v in weights.items()})
+        return w
+    vals = [float(v) for v in weights]
+    if len(vals) != 5:
+        raise ValueError("compute_loss_function: weights is a dict or the five numbers (mse, edge, mask, iou, cd)")
+    return dict(zip(("mse", "edge", "mask", "iou", "cd"), vals))
+
+
+def compute_loss_function(ref_img, result, ref_mask=None, ref_points=None, result_points=None, cdloss=None, weights=None):
+    """diff_obj_pose.py:286-336 -> (total_loss, mse_loss, edge_loss_value, iou_loss_value, iou_value, cd_loss_value, mask_loss):
+    the images statistically normalised, their soft masks, mask_loss = 30 MSE + BCE + 10 Dice of the masks, the soft IoU against
+    ref_mask (when given), cd = partial_l1(result_points, ref_points) + 0.5 partial_l1(ref_points, result_points) (when both are
+    given; cdloss: a Completionloss, made here when None).
+    weights: None = the reference's (mse 0, edge 0, mask 1, iou 0, cd 3); a dict over those names or the five numbers in that
+    order -- the reference's comment invites the edit.  A term whose weight is 0 is still returned, as in the reference; the
+    edge term, which the reference leaves commented out and returns as 0, is evaluated when its weight is not 0."""
+    F = torch.nn.functional
+    w = _loss_weights(weights)
+    ref_n, res_n = normalize_images(ref_img, result)
+    mask_result, mask_ref = compute_soft_mask(res_n, 0.1, 0.05), compute_soft_mask(ref_n, 0.1, 0.05)
+    mse_loss = F.mse_loss(ref_n, res_n)
+    mask_loss = F.mse_loss(mask_result, mask_ref) * 30 + F.binary_cross_entropy(mask_result, mask_ref)
+    mask_loss = mask_loss * 1 + dice_loss(mask_result, mask_ref) * 10
+    zero = lambda v=0.0: torch.tensor(v, device=result.device)
+    edge_loss_value = edge_loss(ref_n, res_n) if w["edge"] != 0.0 else zero()
+    iou_loss_value, iou_value = zero(), zero(1.0)
+    if ref_mask is not None:
+        iou_loss_value, iou_value, _ = soft_iou_loss(res_n, ref_mask, threshold=0.1, tau=0.05)
+    cd_loss_value = zero()
+    if ref_points is not None and result_points is not None:
+        if cdloss is None:
+            from ..utils.loss_util import Completionloss
+            cdloss = Completionloss(loss_func="cd_l1")
+        cd_loss_value = cdloss.chamfer_partial_l1(result_points.unsqueeze(0), ref_points.unsqueeze(0)) + \
+            0.5 * cdloss.chamfer_partial_l1(ref_points.unsqueeze(0), result_points.unsqueeze(0))
+    total_loss = mse_loss * w["mse"] + edge_loss_value * w["edge"] + mask_loss * w["mask"] + iou_loss_value * w["iou"] + cd_loss_value * w["cd"]
+    return total_loss, mse_loss, edge_loss_value, iou_loss_value, iou_value, cd_loss_value, mask_loss
+
+
+# the library's one camera in pytorch3d's look_at_view_transform form (eye (0,0,3), at the origin, up +y): X_view = X_world R + T
+_CAMERA_R = ((-1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, -1.0))
+_CAMERA_T = (0.0, 0.0, 3.0)
+_CAMERA_FOCAL = 4.0
+_CAMERA_WORDS = "the library has one camera: eye (0,0,3) looking at the origin, up +y (R = diag(-1, 1, -1), T = (0, 0, 3)), focal 4.0"
+
+
+def render_reference_image(vert_pos, vert_col, radius, render_size, device):
+    """diff_obj_pose.py:108-134: the partial cloud's image under the fixed camera -> (ref_img [S,S,3], ref_mask [S,S],
+    R_cam [1,3,3], T_cam [1,3]); vert_col None = white.  No gradient is recorded."""
+    with torch.no_grad():
+        pts = torch.as_tensor(vert_pos, dtype=torch.float32, device=device)
+        col = None if vert_col is None else torch.as_tensor(vert_col, dtype=torch.float32, device=device)
+        result = render_points(pts, col, radius, render_size)
+    R = torch.tensor([_CAMERA_R], dtype=torch.float32, device=device)
+    T = torch.tensor([_CAMERA_T], dtype=torch.float32, device=device)
+    return result, compute_mask_from_rendering(result), R, T
+
+
+class ObjectPoseOptim(nn.Module):
+    """diff_obj_pose.py:339-436: the 7-DoF pose (6-D rotation, translation, log scale) of a cloud as an nn.Module whose forward
+    poses the cloud in plain torch and renders it with render_points at 1.1 x radius.  Parameters rot_6d [6], trans [3],
+    log_scale [1] (log 0.75); buffer center (the cloud's mean).  vert_col None = white.  R_cam / T_cam / focal must describe the
+    library's one camera (what render_reference_image returns); another camera or focal raises ValueError.
+    project_every > 0: every that many forwards rot_6d is replaced by the 6-D form of the nearest rotation."""
+
+    def __init__(self, vert_pos, vert_col, radius, render_size, device, R_cam, T_cam, init_rot, focal=4.0, project_every=0):
+        super().__init__()
+        Rc = torch.as_tensor(R_cam, dtype=torch.float32).reshape(-1).cpu()
+        Tc = torch.as_tensor(T_cam, dtype=torch.float32).reshape(-1).cpu()
+        if Rc.numel() != 9 or Tc.numel() != 3 or not torch.allclose(Rc, torch.tensor(_CAMERA_R).reshape(-1), atol=1e-6) \
+                or not torch.allclose(Tc, torch.tensor(_CAMERA_T), atol=1e-6):
+            raise ValueError("ObjectPoseOptim: unsupported camera R_cam / T_cam; " + _CAMERA_WORDS)
+        if float(focal) != _CAMERA_FOCAL:
+            raise ValueError("ObjectPoseOptim: unsupported focal %r; %s" % (focal, _CAMERA_WORDS))
+        self.device = device
+        self.render_size = int(render_size)
+        self.radius = float(radius)
+        self.gamma = 1e-2
+        self.project_every = project_every
+        vert_pos = torch.as_tensor(vert_pos, dtype=torch.float32, device=device)
+        self.register_parameter("vert_pos", nn.Parameter(vert_pos, requires_grad=False))
+        if vert_col is None:
+            self.vert_col = None
+        else:
+            self.register_parameter("vert_col", nn.Parameter(torch.as_tensor(vert_col, dtype=torch.float32, device=device), requires_grad=False))
+        self.register_buffer("center", vert_pos.mean(0))
+        self.rot_6d = nn.Parameter(torch.as_tensor(init_rot, dtype=torch.float32, device=device).clone())
+        self.trans = nn.Parameter(torch.zeros(3, dtype=torch.float32, device=device))
+        self.log_scale = nn.Parameter(torch.tensor([math.log(0.75)], dtype=torch.float32, device=device))
+        self.register_buffer("R_cam", torch.as_tensor(R_cam, dtype=torch.float32, device=device))
+        self.register_buffer("T_cam", torch.as_tensor(T_cam, dtype=torch.float32, device=device))
+        self.register_buffer("focal_length", torch.tensor([float(focal)], dtype=torch.float32, device=device))
+        self._step = 0
+
+    def get_current_RT(self):
+        R = rotation_6d_to_matrix(self.rot_6d[None])[0].detach()
+        return R, self.trans.detach(), torch.exp(self.log_scale.detach())[0]
+
+    def get_transform(self):
+        R, t, s = self.get_current_RT()
+        return build_transform(R, t, s)
+
+    @staticmethod
+    def _project_to_rotation(R):
+        U, _, Vh = torch.linalg.svd(R.double())
+        d = torch.sign(torch.linalg.det(U @ Vh))
+        D = torch.diag(torch.stack([torch.ones_like(d), torch.ones_like(d), d]))
+        return (U @ D @ Vh).to(R.dtype)
+
+    def forward(self, return_pts=False, project_now=False):
+        if project_now or (self.project_every > 0 and self._step % self.project_every == 0 and self._step > 0):
+            with torch.no_grad():
+                R_proj = self._project_to_rotation(rotation_6d_to_matrix(self.rot_6d[None])[0])
+                self.rot_6d.data = matrix_to_rotation_6d(R_proj[None])[0].data
+        self._step += 1
+        R_obj = rotation_6d_to_matrix(self.rot_6d[None])[0]
+        scale = torch.exp(self.log_scale)[0]
+        local = (self.vert_pos - self.center) * scale
+        local = (R_obj @ local.T).T
+        pts = local + self.center + self.trans
+        img = render_points(pts, self.vert_col, 1.1 * self.radius, self.render_size)
+        if return_pts:
+            return img, R_obj, scale, pts
+        return img, R_obj, scale
+
+
+def object_pose_optimization_torch(complete_xyz, partial_xyz, radius=0.005, lr=0.005, iters=300, render_size=224, cam_bias_num=4,
+                                   complete_col=None, partial_col=None, weights=None, loss_fn=None, return_history=False):
+    """The reference's loop (diff_obj_pose.py:496-594) in torch on render_points -- the customisable path; object_pose_optimization
+    is the fast one (a fused loop of the one default objective) and gives the same histories to the rounding of their sums.
+    complete_xyz [Nc,3], partial_xyz [Np,3] GPU tensors with colours complete_col / partial_col (None = white).  Per start
+    (rotated by 90 degrees about y each): ObjectPoseOptim under torch.optim.Adam with the groups rot_6d lr, trans 0.2 lr,
+    log_scale 0.1 lr; iters + 1 steps of
+        loss = compute_loss_function(ref_img, result, ref_mask, partial_xyz, pts, cdloss, weights)[0] + 0.001 |R R^T - I|_F
+    or, with loss_fn, loss = loss_fn(ref_img, result, ref_mask, partial_xyz, pts, R_obj) (a scalar tensor: the whole objective).
+    A start stops after 300 steps without a new best loss; the start with the lowest best loss gives the result, with the
+    parameters it ENDED on (as in the reference).  Returns the 4x4 numpy [[sR, t], [0, 1]]; return_history: also the
+    [cam_bias_num, iters + 1] losses (a start that stopped early repeats its last loss) and the [10] parameters."""
+    import numpy as np
+    from ..utils.loss_util import Completionloss
+    complete_xyz = complete_xyz.contiguous().float()
+    partial_xyz = partial_xyz.contiguous().float()
+    _lib.check_tensors((("complete_xyz", complete_xyz), ("partial_xyz", partial_xyz)))
+    if complete_xyz.dim() != 2 or partial_xyz.dim() != 2:
+        raise ValueError("object_pose_optimization_torch: clouds must be [N,3], got %s and %s" % (tuple(complete_xyz.shape), tuple(partial_xyz.shape)))
+    device = complete_xyz.device
+    cc, pc = _col(complete_col, complete_xyz, "complete_col"), _col(partial_col, partial_xyz, "partial_col")
+    cdloss = Completionloss(loss_func="cd_l1")
+    ref_img, ref_mask, R_cam, T_cam = render_reference_image(partial_xyz, pc, radius, render_size, device)
+    eye = torch.eye(3, device=device)
+    hist = np.zeros((int(cam_bias_num), int(iters) + 1), np.float32)
+    best_loss, best_state = float("inf"), None
+    for start in range(int(cam_bias_num)):
+        model = ObjectPoseOptim(complete_xyz, cc, radius, render_size, device, R_cam, T_cam, get_init_rot("y", start * 90, device))
+        optimizer = torch.optim.Adam([{"params": [model.rot_6d], "lr": lr}, {"params": [model.trans], "lr": lr * 0.2},
+                                      {"params": [model.log_scale], "lr": lr * 0.1}])
+        patience, patience_counter, local_best, cur_loss = 300, 0, float("inf"), float("nan")
+        for i in range(int(iters) + 1):
+            optimizer.zero_grad()
+            result, R_obj, scale, pts = model(return_pts=True)
+            if loss_fn is not None:
+                loss = loss_fn(ref_img, result, ref_mask, partial_xyz, pts, R_obj)
+            else:
+                total = compute_loss_function(ref_img, result, ref_mask, partial_xyz, pts, cdloss, weights)[0]
+                loss = total + 0.001 * torch.norm(R_obj @ R_obj.T - eye)
+            loss.backward()
+            optimizer.step()
+            cur_loss = loss.item()
+            hist[start, i:] = cur_loss
+            if cur_loss < local_best:
+                local_best, patience_counter = cur_loss, 0
+            else:
+                patience_counter += 1
+            if patience_counter > patience:
+                break
+        if local_best < best_loss:
+            best_loss = local_best
+            best_state = (model.rot_6d.detach().clone(), model.trans.detach().clone(), model.log_scale.detach().clone())
+    if best_state is None:
+        raise RuntimeError("object_pose_optimization_torch: no start gave a finite loss")
+    rot_6d, trans, log_scale = best_state
+    T_final = build_transform(rotation_6d_to_matrix(rot_6d[None])[0], trans, torch.exp(log_scale)[0])
+    final_transform = T_final.detach().cpu().numpy()
+    if return_history:
+        return final_transform, hist, torch.cat([rot_6d, trans, log_scale]).cpu().numpy()
     return final_transform

@@ -516,6 +516,40 @@ int genpc_pose_loss_grad_batch(int b, int nc, const float *v, const float *vert_
  * < 0 = back to the default.  Returns the previous setting (-1 = default). */
 int genpc_render_tune(int blend);
 
+/* The renderer as a differentiable operation of its own: b clouds of n points drawn in one call, and the backward of those images
+ * for a caller's d L / d img, per point (csrc/render_grad.hip; genpc_amd.optim_registration.diff_obj_pose.render_points is the
+ * torch.autograd.Function over the pair).  The camera is the one above; radius is used as given (a caller who draws the posed
+ * cloud applies the reference's factor 1.1 itself, like genpc_splat_image's).
+ *   pts [b,n,3], col [b,n,3] or NULL (white), img / grad_img [b,size,size,3], planes [b,5,size*size],
+ *   grad_pts [b,n,3], grad_col [b,n,3] or NULL (not computed; it may be asked for with col == NULL).
+ * blend (0 or 1) is an ARGUMENT, not the calling thread's genpc_render_tune mode: torch runs a backward on an autograd engine
+ * thread, where a mode the forward's thread set is not visible.  (Inside, the thread's mode is saved, set and restored around the
+ * launches; genpc_splat_image and every other call keep reading the thread's mode.)
+ * genpc_render_points: element e of img is bit for bit genpc_splat_image of element e alone under that blend.  planes_out (NULL to
+ *   skip) receives the five planes the images were made from -- blend 0: T, D, N_r, N_g, N_b; blend 1: m, D', N'_r, N'_g, N'_b
+ *   (csrc/mask.h).  n == 0 draws the background.
+ * genpc_render_points_backward: two launches, no atomics, no workgroup that waits for another; the same bits in every run, on every
+ *   stream and in every batch.  Per pixel, with G = grad_img:
+ *     blend 1:  W1 = m,  W4 = (G, G . I) / D';      blend 0:  W1 = T (G . A),  W4 = (O / D) (G, G . A),  1 / D := 0 where D = 0.
+ *   Per point, over the pixel centres of its disc's box in a fixed order (eight lanes a point, rows interleaved, columns ascending,
+ *   a fixed tree over the eight), gu, gv, grho, gz as the silhouette loss's own gather forms them, then
+ *     grad_pts = (gu f4 / Zv, -gv f4 / Zv, -gZv),   f4 = 4 size / 2,
+ *     grad_col[ch] = sum over the pixels with a > 0 of W4.ch min(a, 0.999) exp(ze - W1)  (blend 1),  W4.ch min(a, 0.999)  (blend 0).
+ *   Pixels where the coverage is clamped (a >= 0.999) count for the colour and for the depth term gz, not for gu, gv, grho.
+ *   A point the camera does not see, or one with a coordinate that is not finite, gets +0 rows.  n == 0: nothing is written.
+ *   THE PLANES CONTRACT: `planes` must be what genpc_render_points returned in planes_out for the same pts, col, radius, size and
+ *   blend.  Blend 1 evaluates exp(ze - m) with m the pixel's largest exponent; it is <= 1 only for the planes of these very points
+ *   and overflows for others.  No gradient with respect to the radius or the camera; no double backward.
+ * Both return 1, 0 (a runtime error, genpc_last_error) or -1 with genpc_last_error set and NOTHING enqueued: b <= 0, n < 0,
+ * size <= 0 (or > 8192), a radius that is not positive, blend outside {0, 1}, b * n or b * size * size beyond 2^28, or a null pts, img,
+ * planes, grad_img or grad_pts with work to do.
+ * Asynchronous on `stream`; scratch from workspace slots of their own. */
+int genpc_render_points(int b, int n, const float *pts, const float *col, float radius, int size, int blend,
+                        float *img, float *planes_out, void *stream);
+int genpc_render_points_backward(int b, int n, const float *pts, const float *col, float radius, int size, int blend,
+                                 const float *planes, const float *grad_img,
+                                 float *grad_pts, float *grad_col, void *stream);
+
 /* Nearest-neighbour path of genpc_pose_optimize_batch, for tests and A/B (applies to the calling host thread): 1 the
  * seeded cell search from the second Adam step on (csrc/nn_seeded.hip: every query starts from last step's answer and
  * searches only the ball it leaves; grids built once per call, the moving cloud's in its rest frame), 0 the brute-force
