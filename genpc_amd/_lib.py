@@ -73,6 +73,9 @@ SIGNATURES = {
     "genpc_render_tune": (_i, [_i]),
     "genpc_render_points": (_i, [_i, _i, _vp, _vp, _f, _i, _i, _vp, _vp, _vp]),
     "genpc_render_points_backward": (_i, [_i, _i, _vp, _vp, _f, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "genpc_render_points_ragged": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "genpc_render_points_ragged_backward": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "genpc_render_ragged_plan": (_i, [_i, _vp, _vp, _i, _i, _vp]),
     "genpc_pose_optimize_batch": (_i, [_i, _i, _vp, _vp, _i, _vp, _vp, _f, _i, _i, _f, _i, _f, _vp, _vp, _vp, _vp]),
     "genpc_pose_optimize_ragged": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _f, _i, _f, _vp, _vp, _vp, _vp]),
     "genpc_pose_loss_grad_ragged": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i, _vp, _vp, _vp]),

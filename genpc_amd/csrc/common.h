@@ -84,6 +84,8 @@ enum Ws : int {
     kWsDepthPromptRagged = 54, // depth_prompt_ragged.hip genpc_depth_prompt_ragged: box and depth-range keys, owner planes (one memset) | chunk partial sums | per-scan records
     kWsRenderPoints = 55,     // render_grad.hip genpc_render_points: mask scratch of the b images
     kWsRenderPointsGrad = 56, // render_grad.hip genpc_render_points_backward: the per-pixel weights W1 | W4 of the b images
+    kWsRenderPointsRagged = 57,     // render_grad.hip genpc_render_points_ragged: element table | radii | mask scratch of the s images
+    kWsRenderPointsRaggedGrad = 58, // render_grad.hip genpc_render_points_ragged_backward: element table | radii | W1 | W4 of the s images
 };
 
 // The scratch pool: one grow-only block of device memory per (device, slot, stream); null on failure, the error recorded.

@@ -25,7 +25,14 @@ genpc_render_points_backward, csrc/render_grad.hip), the reference's ``ObjectPos
 ``compute_loss_function`` (with ``weights=``), ``normalize_images``, ``compute_soft_mask``, ``dice_loss``, ``soft_iou_loss``,
 ``edge_loss``, ``get_init_rot``, ``build_transform`` restated from their formulas, and ``object_pose_optimization_torch``, its
 Adam loop with an objective the caller may replace (``loss_fn=``).  DESIGN.md 4.5d.
+
+``render_points_ragged`` is that operation for S clouds of different sizes in one call, each with a radius of its own
+(genpc_render_points_ragged / genpc_render_points_ragged_backward), and with ``cameras=(R, T, focal)`` for other pinhole cameras
+than the library's one: ``camera_points`` maps the points into the library's camera frame in plain torch (so R and T get
+gradients from autograd) and the radius is scaled by focal / 4.  ``look_at_view_transform``, ``render_reference_images`` and
+``ObjectPoseOptimViews`` (one posed cloud under V cameras) stand on it.  DESIGN.md 4.5e.
 """
+import ctypes
 import math
 
 import torch
@@ -554,6 +561,187 @@ def render_points(points, colors=None, radius=0.005, render_size=224, blend=None
     return img[0] if single else img
 
 
+RENDER_RAGGED_MAX_ELEMENTS = 384          # genpc_hip.h GENPC_RENDER_RAGGED_MAX_ELEMENTS: clouds of one library call
+
+
+def _host_floats(values):
+    """(a ctypes float array of the values, its void pointer -- which keeps the array alive)"""
+    arr = (ctypes.c_float * max(1, len(values)))(*[float(v) for v in values])
+    return arr, ctypes.cast(arr, ctypes.c_void_p)
+
+
+def render_points_ragged_forward(pts, off, col, radii, render_size, blend):
+    """genpc_render_points_ragged on packed clouds: pts [T,3] float32 GPU, off S + 1 host ints, col None (white) or [T,3], radii S
+    host floats -> (img [S,size,size,3], planes [S,5,size*size]).  More than 384 clouds go in several library calls."""
+    from .. import _ragged
+    s, size = len(off) - 1, int(render_size)
+    img = torch.empty(s, size, size, 3, device=pts.device)
+    planes = torch.empty(s, 5, size * size, device=pts.device)
+    for a, b, o in _ragged.chunks(RENDER_RAGGED_MAX_ELEMENTS, off):
+        _, op = _ragged.host_ints(o, "offsets")
+        _, rp = _host_floats(radii[a:b])
+        rc = _lib.on_device_of(pts, _L.genpc_render_points_ragged, b - a, op, _p(pts[off[a]:off[b]]),
+                               _p(None if col is None else col[off[a]:off[b]]), rp, size, int(blend), _p(img[a:b]), _p(planes[a:b]))
+        if rc != 1:
+            raise RuntimeError("genpc_render_points_ragged failed (rc=%d): %s" % (rc, _lib.last_error()))
+    return img, planes
+
+
+def render_points_ragged_backward(pts, off, col, radii, render_size, blend, planes, grad_img, want_col=True):
+    """genpc_render_points_ragged_backward: planes as render_points_ragged_forward returned them for the same arguments, grad_img
+    [S,size,size,3] -> (grad_pts [T,3], grad_col [T,3] or None)."""
+    from .. import _ragged
+    empty = pts.shape[0] == 0
+    grad_pts = torch.zeros_like(pts) if empty else torch.empty_like(pts)
+    grad_col = (torch.zeros_like(pts) if empty else torch.empty_like(pts)) if want_col else None
+    for a, b, o in _ragged.chunks(RENDER_RAGGED_MAX_ELEMENTS, off):
+        _, op = _ragged.host_ints(o, "offsets")
+        _, rp = _host_floats(radii[a:b])
+        rc = _lib.on_device_of(pts, _L.genpc_render_points_ragged_backward, b - a, op, _p(pts[off[a]:off[b]]),
+                               _p(None if col is None else col[off[a]:off[b]]), rp, int(render_size), int(blend), _p(planes[a:b]),
+                               _p(grad_img[a:b]), _p(grad_pts[off[a]:off[b]]), _p(None if grad_col is None else grad_col[off[a]:off[b]]))
+        if rc != 1:
+            raise RuntimeError("genpc_render_points_ragged_backward failed (rc=%d): %s" % (rc, _lib.last_error()))
+    return grad_pts, grad_col
+
+
+class _RenderPointsRagged(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pts, col, off, radii, render_size, blend):
+        img, planes = render_points_ragged_forward(pts, off, col, radii, render_size, blend)
+        if col is None:
+            ctx.save_for_backward(pts, planes)
+        else:
+            ctx.save_for_backward(pts, planes, col)
+        ctx.args = (tuple(off), tuple(radii), int(render_size), int(blend))      # (the blend of the FORWARD, as in _RenderPoints)
+        return img
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_img):
+        saved = ctx.saved_tensors
+        pts, planes, col = saved[0], saved[1], saved[2] if len(saved) > 2 else None
+        off, radii, render_size, blend = ctx.args
+        want_col = col is not None and ctx.needs_input_grad[1]
+        g = grad_img.contiguous().float()
+        grad_pts, grad_col = render_points_ragged_backward(pts, list(off), col, list(radii), render_size, blend, planes, g, want_col)
+        return grad_pts, grad_col, None, None, None, None
+
+
+def _per_element(value, s, fn, name):
+    """a float, or S host floats -> a list of S Python floats"""
+    if torch.is_tensor(value):
+        value = value.detach().cpu().tolist()
+    if hasattr(value, "tolist"):          # a numpy array or scalar
+        value = value.tolist()
+    if not isinstance(value, (str, bytes)) and hasattr(value, "__iter__"):
+        vals = [float(v) for v in value]
+        if len(vals) != s:
+            raise ValueError("%s: %s must be a float or one float per cloud (%d), got %d" % (fn, name, s, len(vals)))
+        return vals
+    return [float(value)] * s
+
+
+def camera_points(points, R, T, focal=4.0):
+    """The affine map that takes world points seen by a pinhole camera (R [3,3], T [3], focal) in pytorch3d's convention --
+    X_view = X R + T, +X left, +Y up, +Z into the scene -- into the library's camera frame, where the library's own camera draws
+    what that camera sees once the radius is scaled by focal / 4:  with D = diag(-f/4, f/4, -1),
+        p = X (R D) + (T D + (0, 0, 3)).
+    R D and T D + (0,0,3) are formed first, then one affine map is applied as sums of products in a fixed order (no matrix
+    kernel): the library's own camera (R = diag(-1, 1, -1), T = (0, 0, 3), f = 4) is the identity exactly, a signed-permutation R
+    with T = (0, 0, 3) and a power-of-two focal maps without rounding.  points [...,3]; plain torch: gradients to points, R and T
+    are autograd's; focal is a host float (it also enters through the radius, which has no gradient)."""
+    if not torch.is_tensor(points) or points.shape[-1] != 3:
+        raise ValueError("camera_points: points must be a [...,3] tensor")
+    R = torch.as_tensor(R, dtype=points.dtype if not torch.is_tensor(R) else None).to(device=points.device, dtype=points.dtype)
+    T = torch.as_tensor(T, dtype=points.dtype if not torch.is_tensor(T) else None).to(device=points.device, dtype=points.dtype)
+    if tuple(R.shape) != (3, 3) or tuple(T.shape) != (3,):
+        raise ValueError("camera_points: R must be [3,3] and T [3], got %s and %s" % (tuple(R.shape), tuple(T.shape)))
+    f = float(focal)
+    if not f > 0.0:
+        raise ValueError("camera_points: focal must be positive, got %r" % (focal,))
+    d = torch.tensor([-f / 4.0, f / 4.0, -1.0], dtype=points.dtype, device=points.device)
+    M = R * d
+    t = T * d + torch.tensor([0.0, 0.0, 3.0], dtype=points.dtype, device=points.device)
+    return points[..., 0:1] * M[0] + points[..., 1:2] * M[1] + points[..., 2:3] * M[2] + t
+
+
+def look_at_view_transform(eye, at=(0.0, 0.0, 0.0), up=(0.0, 1.0, 0.0)):
+    """pytorch3d's look_at_view_transform for V eyes: eye [V,3] or [3] (at, up alike, or one for all) -> (R [V,3,3], T [V,3]),
+    float32 on the CPU, with X_view = X R + T:  z = normalize(at - eye), x = normalize(up x z), y = z x x, R has x, y, z as
+    COLUMNS and T = -eye R.  Formed in float64.  Eye (0,0,3) gives the library's camera: R = diag(-1, 1, -1), T = (0, 0, 3)."""
+    e = torch.as_tensor(eye, dtype=torch.float64).reshape(-1, 3)
+    a = torch.as_tensor(at, dtype=torch.float64).reshape(-1, 3).expand_as(e)
+    u = torch.as_tensor(up, dtype=torch.float64).reshape(-1, 3).expand_as(e)
+    z = torch.nn.functional.normalize(a - e, dim=-1)
+    x = torch.nn.functional.normalize(torch.cross(u, z, dim=-1), dim=-1)
+    y = torch.cross(z, x, dim=-1)
+    if not bool(torch.isfinite(x).all()) or bool((x.norm(dim=-1) < 0.5).any()):
+        raise ValueError("look_at_view_transform: up is parallel to the viewing direction (or eye == at)")
+    R = torch.stack((x, y, z), dim=-1)
+    T = -(e[:, None, :] @ R)[:, 0, :]
+    return (R + 0.0).float(), (T + 0.0).float()          # (+ 0: no negative zeros)
+
+
+def _camera_list(cameras, s, fn):
+    """(R, T, focal) -> S triples (R_j [3,3], T_j [3], f_j)"""
+    if not isinstance(cameras, (list, tuple)) or len(cameras) != 3:
+        raise ValueError("%s: cameras must be None or (R, T, focal)" % fn)
+    R, T, focal = cameras
+    R, T = torch.as_tensor(R), torch.as_tensor(T)
+    if tuple(R.shape) == (3, 3):
+        R = R[None].expand(s, 3, 3)
+    if tuple(T.shape) == (3,):
+        T = T[None].expand(s, 3)
+    if tuple(R.shape) != (s, 3, 3) or tuple(T.shape) != (s, 3):
+        raise ValueError("%s: cameras' R must be [%d,3,3] or [3,3] and T [%d,3] or [3], got %s and %s" % (fn, s, s, tuple(R.shape), tuple(T.shape)))
+    f = _per_element(focal, s, fn, "focal")
+    for j, v in enumerate(f):
+        if not v > 0.0:
+            raise ValueError("%s: the focal of camera %d must be positive, got %r" % (fn, j, v))
+    return [(R[j], T[j], f[j]) for j in range(s)]
+
+
+def render_points_ragged(clouds, colors=None, radius=0.005, render_size=224, blend=None, cameras=None):
+    """render_points for S clouds of DIFFERENT sizes in one call, each with its own radius and, if asked, its own camera
+    (genpc_render_points_ragged / genpc_render_points_ragged_backward) -> [S,size,size,3].
+    clouds: a list of [N_j,3] float32 GPU tensors or packed (points [T,3], offsets); a cloud may be empty (its image is the
+    background).  colors: None (white) or the same form with the same sizes.  radius: a float or S host floats, used as given.
+    blend: as in render_points -- None is the calling thread's render_tune mode AT FORWARD TIME, kept for the backward.
+    cameras: None -- the library's camera, no map at all -- or (R, T, focal): R [S,3,3] or [3,3], T [S,3] or [3], focal a float
+    or S host floats, pytorch3d's convention (camera_points).  Cloud j is mapped by camera_points in plain torch and drawn with
+    radius_j focal_j / 4; znear, zfar and gamma stay the library's.
+    Image j is bit for bit render_points of cloud j alone (mapped, with its radius).  Gradients go to every list element (or to
+    the packed points), to the colours when they require grad (otherwise the colour gradient is not computed), through the map
+    to R and T; none to the radius or the focal.  once_differentiable.  More than 384 clouds go in several library calls."""
+    from .. import _ragged
+    fn = "render_points_ragged"
+    pts, off = _ragged.ragged_side(clouds, fn, "clouds")
+    s = len(off) - 1
+    if s == 0:
+        raise ValueError("%s: clouds is empty" % fn)
+    _lib.require_gpu(pts)
+    col = None
+    if colors is not None:
+        col, coff = _ragged.ragged_side(colors, fn, "colors")
+        if coff != off:
+            raise ValueError("%s: colors must have the sizes of clouds" % fn)
+        _lib.require_gpu(col)
+    if blend is None:
+        blend = _thread_blend()
+    elif blend not in (0, 1):
+        raise ValueError("%s: blend must be None, 0 or 1, got %r" % (fn, blend))
+    radii = _per_element(radius, s, fn, "radius")
+    if cameras is not None:
+        cams = _camera_list(cameras, s, fn)
+        pts = torch.cat([camera_points(pts[off[j]:off[j + 1]], *cams[j]) for j in range(s)], dim=0).contiguous()
+        radii = [radii[j] * (cams[j][2] / 4.0) for j in range(s)]
+    for j, r in enumerate(radii):
+        if not r > 0.0:
+            raise ValueError("%s: the radius of cloud %d must be positive, got %r" % (fn, j, r))
+    return _RenderPointsRagged.apply(pts, col, off, radii, int(render_size), int(blend))
+
+
 def rotation_6d_to_matrix(d6):
     """Zhou et al.'s 6-D rotation (CVPR 2019), pytorch3d's convention: Gram-Schmidt of the two 3-vectors, the three results as
     ROWS.  [...,6] -> [...,3,3]."""
@@ -778,10 +966,52 @@ class ObjectPoseOptim(nn.Module):
         local = (self.vert_pos - self.center) * scale
         local = (R_obj @ local.T).T
         pts = local + self.center + self.trans
-        img = render_points(pts, self.vert_col, 1.1 * self.radius, self.render_size)
+        img = self._render(pts)
         if return_pts:
             return img, R_obj, scale, pts
         return img, R_obj, scale
+
+    def _render(self, pts):
+        return render_points(pts, self.vert_col, 1.1 * self.radius, self.render_size)
+
+
+def render_reference_images(vert_pos, vert_col, radius, render_size, R_cams, T_cams, focal=4.0):
+    """render_reference_image under V cameras: vert_pos [N,3] (a float32 GPU tensor), vert_col None = white, R_cams [V,3,3],
+    T_cams [V,3] (look_at_view_transform's form), focal a float or V floats -> (ref_imgs [V,S,S,3], ref_masks [V,S,S]).  One ragged
+    call of V mapped copies; no gradient is recorded.  With the library's camera view v is render_reference_image's image."""
+    with torch.no_grad():
+        pts = torch.as_tensor(vert_pos).float()
+        _lib.require_gpu(pts)
+        col = None if vert_col is None else torch.as_tensor(vert_col, dtype=torch.float32, device=pts.device)
+        v = int(torch.as_tensor(R_cams).reshape(-1, 3, 3).shape[0])
+        imgs = render_points_ragged([pts] * v, None if col is None else [col] * v, radius, render_size,
+                                    cameras=(torch.as_tensor(R_cams).reshape(-1, 3, 3), torch.as_tensor(T_cams).reshape(-1, 3), focal))
+        masks = torch.stack([compute_mask_from_rendering(imgs[k]) for k in range(v)])
+    return imgs, masks
+
+
+class ObjectPoseOptimViews(ObjectPoseOptim):
+    """ObjectPoseOptim under V cameras: the same parameters (rot_6d, trans, log_scale), buffers and pose statements; R_cams
+    [V,3,3], T_cams [V,3] (look_at_view_transform's form), focal a float or V floats.  forward() returns (imgs [V,S,S,3], R_obj,
+    scale[, pts]): the ONE posed cloud through render_points_ragged with V mapped copies at 1.1 x radius.  With the single
+    library camera its image is ObjectPoseOptim's, bit for bit."""
+
+    def __init__(self, vert_pos, vert_col, radius, render_size, device, R_cams, T_cams, init_rot, focal=4.0, project_every=0):
+        super().__init__(vert_pos, vert_col, radius, render_size, device, [_CAMERA_R], [_CAMERA_T], init_rot, _CAMERA_FOCAL, project_every)
+        R = torch.as_tensor(R_cams, dtype=torch.float32).reshape(-1, 3, 3)
+        T = torch.as_tensor(T_cams, dtype=torch.float32).reshape(-1, 3)
+        if R.shape[0] < 1 or T.shape[0] != R.shape[0]:
+            raise ValueError("ObjectPoseOptimViews: R_cams must be [V,3,3] and T_cams [V,3], got %s and %s" % (tuple(R.shape), tuple(T.shape)))
+        self.views = int(R.shape[0])
+        self.focals = _per_element(focal, self.views, "ObjectPoseOptimViews", "focal")
+        self.R_cam = R.to(device)
+        self.T_cam = T.to(device)
+        self.focal_length = torch.tensor(self.focals, dtype=torch.float32, device=device)
+
+    def _render(self, pts):
+        v = self.views
+        return render_points_ragged([pts] * v, None if self.vert_col is None else [self.vert_col] * v, 1.1 * self.radius, self.render_size,
+                                    cameras=(self.R_cam, self.T_cam, self.focals))
 
 
 def object_pose_optimization_torch(complete_xyz, partial_xyz, radius=0.005, lr=0.005, iters=300, render_size=224, cam_bias_num=4,

@@ -44,6 +44,7 @@ int genpc_abi_version(void);              /* bumps when a signature or a documen
                                            * genpc_scale_search_scores_ragged and genpc_scale_search_ragged_plan too: still 28;
                                            * genpc_pose_optimize_ragged, genpc_pose_loss_grad_ragged and genpc_pose_ragged_plan as well: still 28;
                                            * genpc_nn_ragged_tune and genpc_nn_ragged_dense_plan (the default search is unchanged): still 28;
+                                           * genpc_render_points_ragged, genpc_render_points_ragged_backward and genpc_render_ragged_plan: still 28;
                                            * a missing symbol is found when the binding loads. */
 const char *genpc_last_error(void);       /* last HIP error string, "" if none */
 int genpc_set_arith(int mode);            /* process default; returns the previous one */
@@ -549,6 +550,35 @@ int genpc_render_points(int b, int n, const float *pts, const float *col, float 
 int genpc_render_points_backward(int b, int n, const float *pts, const float *col, float radius, int size, int blend,
                                  const float *planes, const float *grad_img,
                                  float *grad_pts, float *grad_col, void *stream);
+
+/* The same pair for s clouds of DIFFERENT sizes, each drawn with a radius of its own, in one call (csrc/render_grad.hip, shape:
+ * csrc/render_ragged_plan.h; genpc_amd.optim_registration.diff_obj_pose.render_points_ragged is the torch.autograd.Function over it,
+ * and maps other pinhole cameras onto the library's one by an affine map of the points and a scaling of the radius).
+ *   off: HOST, s + 1 ints from 0, ascending (element j owns points [off[j], off[j + 1]); an element may be empty);
+ *   radius: HOST, s floats; pts [off[s],3], col [off[s],3] or NULL (white), img / grad_img [s,size,size,3], planes [s,5,size*size],
+ *   grad_pts [off[s],3], grad_col [off[s],3] or NULL (not computed).
+ * Element j of img, planes_out, grad_pts and grad_col is BIT FOR BIT what genpc_render_points / genpc_render_points_backward give for
+ * b = 1 on element j alone with radius[j] -- the same bytes in every run, on every stream, wherever the element stands in the list and
+ * whatever its neighbours are.  An empty element's image is the background (b = 1, n = 0) and it has no gradient rows.  The planes
+ * contract above holds per element.  The backward uses no atomics and no workgroup waits for another.
+ * Neither host table is read after the call returns: both travel by value in a kernel's arguments, which bounds a call at
+ * GENPC_RENDER_RAGGED_MAX_ELEMENTS = 384 elements (a longer list goes in several calls).  Per-element limits are
+ * genpc_render_points' own.
+ * Both return 1, 0 (a runtime error) or -1 with genpc_last_error set, NOTHING enqueued and nothing written: s <= 0 or s > 384, a null
+ * off or radius, size outside 1 .. 8192, blend outside {0, 1}, a table that does not start at 0 or descends, a radius that is not
+ * positive (named by its element), off[s] or s * size * size beyond 2^28, or a null pts, img, planes, grad_img or grad_pts with work
+ * to do.  A backward of a list without points returns 1 and writes nothing.
+ * genpc_render_ragged_plan: the plan both read (no GPU is touched), out = { the bound on s, the element a refusal names or -1, s, the
+ *   largest element, off[s], size * size, the projection's blocks per element, the per-pixel kernels' blocks per image, the gather's
+ *   blocks per element, the gather's blocks, the per-element count that sizes the projected points' scratch, s * size * size };
+ *   -1 with the refusal recorded as the forward would. */
+#define GENPC_RENDER_RAGGED_MAX_ELEMENTS 384
+int genpc_render_points_ragged(int s, const int *off, const float *pts, const float *col, const float *radius, int size, int blend,
+                               float *img, float *planes_out, void *stream);
+int genpc_render_points_ragged_backward(int s, const int *off, const float *pts, const float *col, const float *radius, int size,
+                                        int blend, const float *planes, const float *grad_img,
+                                        float *grad_pts, float *grad_col, void *stream);
+int genpc_render_ragged_plan(int s, const int *off, const float *radius, int size, int blend, int out[12]);
 
 /* Nearest-neighbour path of genpc_pose_optimize_batch, for tests and A/B (applies to the calling host thread): 1 the
  * seeded cell search from the second Adam step on (csrc/nn_seeded.hip: every query starts from last step's answer and
