@@ -101,6 +101,7 @@ SIGNATURES = {
     "genpc_grid_bound_probe": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i] + [_vp] * 9 + [_vp]),
     "genpc_grid_range_probe": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "genpc_mask_backward_probe": (_i, [_i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp]),
+    "genpc_fps_verify_probe": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "genpc_fps_multi": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
     "genpc_fps_large": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
     "genpc_fps_plan": (_i, [_i, _i, _vp]),

@@ -86,6 +86,7 @@ enum Ws : int {
     kWsRenderPointsGrad = 56, // render_grad.hip genpc_render_points_backward: the per-pixel weights W1 | W4 of the b images
     kWsRenderPointsRagged = 57,     // render_grad.hip genpc_render_points_ragged: element table | radii | mask scratch of the s images
     kWsRenderPointsRaggedGrad = 58, // render_grad.hip genpc_render_points_ragged_backward: element table | radii | W1 | W4 of the s images
+    kWsFpsVerifyProbe = 59,   // fps_verify.hip genpc_fps_verify_probe: a verdict word per cloud | segment minima (not kWsFps: genpc_fps_stats reads that one back)
 };
 
 // The scratch pool: one grow-only block of device memory per (device, slot, stream); null on failure, the error recorded.

@@ -128,12 +128,14 @@ __global__ void fps_count_kernel(FpsJobs jobs, int nj, int *__restrict__ violati
     if (j < nj && *jobs.verr[j] != 0) { atomicAdd(violations, 1); *jobs.verr[j] = 0; }
 }
 
-// the check of a group of clouds on `st`; violations: the deferred form's counter, null in line (a failed check poisons out[0])
-static void launch_verify(const FpsJobs &jobs, int nj, bool single, bool fma, int cus, hipStream_t st, float *segmin, int *violations)
+// the check of a group of clouds on `st`; violations: the deferred form's counter, null in line (a failed check poisons out[0]);
+// force_nseg: 0, or the number of segments to cut into whatever fps_verify_segments says (genpc_fps_verify_probe)
+static void launch_verify(const FpsJobs &jobs, int nj, bool single, bool fma, int cus, hipStream_t st, float *segmin, int *violations,
+                          int force_nseg)
 {
     int nmax = 1;
     for (int q = 0; q < nj; q++) nmax = jobs.n[q] > nmax ? jobs.n[q] : nmax;
-    const int nseg = fps_verify_segments(nmax, nj, cus, single);
+    const int nseg = force_nseg > 0 ? force_nseg : fps_verify_segments(nmax, nj, cus, single);
     const dim3 vg(ceil_div(nmax, kFVBlock), nj, nseg);
     if (nseg > 1) {
         if (fma) hipLaunchKernelGGL((fps_verify_kernel<1, 0>), vg, dim3(kFVBlock), 0, st, jobs, segmin, nseg);
@@ -147,7 +149,7 @@ static void launch_verify(const FpsJobs &jobs, int nj, bool single, bool fma, in
 
 void fps_verify(const FpsCall &c, const FpsJobs &jobs, int nj, bool single)
 {
-    launch_verify(jobs, nj, single, c.fma, c.cus, c.st, c.segmin, nullptr);
+    launch_verify(jobs, nj, single, c.fma, c.cus, c.st, c.segmin, nullptr, 0);
 }
 
 // Verification OFF the caller's critical path (round 6; genpc_fps_defer).  The check of a finished sequence reads the cloud, the
@@ -232,7 +234,7 @@ bool fps_verify_deferred(const FpsCall &c, const FpsJobs &jobs, int nj, FpsDefer
         cp.segoff[q] = lay.segoff[q];
     }
     if (hipEventRecord(d->fork[sl], st) != hipSuccess || hipStreamWaitEvent(d->side, d->fork[sl], 0) != hipSuccess) return false;
-    launch_verify(cp, nj, false, c.fma, c.cus, d->side, (float *)(b + lay.segmin), d->violations);
+    launch_verify(cp, nj, false, c.fma, c.cus, d->side, (float *)(b + lay.segmin), d->violations, 0);
     if (hipEventRecord(d->done[sl], d->side) != hipSuccess) return false;
     d->used[sl] = true;
     return true;
@@ -266,4 +268,44 @@ GENPC_API int genpc_fps_deferred_check(void *stream)
     if (!check(hipMemcpy(&v, d->violations, sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy(fps check)")) return -1;
     if (v != 0 && !check(hipMemset(d->violations, 0, sizeof(int)), "hipMemset(fps check)")) return -1;
     return v;
+}
+
+// The check on the caller's arrays (tests/test_gpu_fps_check.py): a job table of nj clouds through launch_verify in its in-line
+// form, as fps_call.hip's verify_clouds hands it one -- verdict words and segment minima from the scratch pool, a cloud's rows
+// of segment minima behind the earlier clouds', the poisoning kernel behind the check.
+GENPC_API int genpc_fps_verify_probe(int nj, const int *n, const int *k, const float *const *xyz, int *const *out,
+                                     const float *const *pdist, int nseg, int single, void *stream)
+{
+    using namespace genpc;
+    if (nj < 1 || nj > kFMaxJobs) return ragged_refuse("genpc_fps_verify_probe", "need 1 <= nj <= 8 clouds");
+    if (!n || !k || !xyz || !out || !pdist) return ragged_refuse("genpc_fps_verify_probe", "a null table");
+    if (nseg < 0 || nseg > kFVMaxSeg) return ragged_refuse("genpc_fps_verify_probe", "need 0 <= nseg <= 16");
+    size_t points = 0;
+    for (int q = 0; q < nj; q++) {
+        if (!xyz[q] || !out[q] || !pdist[q]) return ragged_refuse("genpc_fps_verify_probe", "a null array");
+        if (k[q] < 1 || k[q] > n[q]) return ragged_refuse("genpc_fps_verify_probe", "need 1 <= k <= n for every cloud");
+        points += (size_t)n[q];
+    }
+    if (points > (size_t)kFpsLargeMaxN) return ragged_refuse("genpc_fps_verify_probe", "more than 4194304 points");
+    hipStream_t st = (hipStream_t)stream;
+    int *verr; float *segmin;
+    WsLayout L;
+    L.add(verr, kFMaxJobs);
+    L.add(segmin, points * kFVMaxSeg);
+    if (!ws_alloc(L, kWsFpsVerifyProbe, st)) return 0;
+    if (!check(hipMemsetAsync(verr, 0, kFMaxJobs * sizeof(int), st), "hipMemsetAsync(fps verify probe)")) return 0;
+    // the call as fps_call would describe it (the check reads the recorded minima only), and its one job table
+    float *pd_of[kFMaxJobs];
+    int seg_of[kFMaxJobs];
+    size_t seg_off = 0;
+    for (int q = 0; q < nj; q++) {
+        pd_of[q] = const_cast<float *>(pdist[q]);
+        seg_of[q] = (int)seg_off;
+        seg_off += (size_t)n[q];
+    }
+    const FpsCall call = {arith_mode() != 0, num_cus(), st, n, k, xyz, out, pd_of, seg_of, nullptr, verr, segmin};
+    FpsJobs jobs = {};
+    for (int q = 0; q < nj; q++) fps_fill_job(jobs, q, call, q);
+    launch_verify(jobs, nj, single != 0, call.fma, call.cus, call.st, call.segmin, nullptr, nseg);
+    return check(hipGetLastError(), "fps verify probe launch") ? 1 : 0;
 }

@@ -36,7 +36,13 @@ def fps_sampling(points, k):
         raise RuntimeError("genpc_fps failed: " + _lib.last_error())
     # index 0 is the start point of every cloud; the kernel writes -1 there when a hand-off
     # between its workgroups timed out (the samples after it would be garbage): those clouds go again, one at a time
-    bad = torch.nonzero(out[:, 0] != 0).flatten().tolist()
+    first = out[:, 0].tolist()
+    bad = [j for j, f in enumerate(first) if f != 0]
+    if bad:
+        # (counted as _fps_multi_direct counts them: a failed check is visible whichever form was called)
+        with _stats_lock:
+            stats["timed_out"] += sum(1 for j in bad if first[j] != -2)
+            stats["failed_check"] += sum(1 for j in bad if first[j] == -2)
     for j in bad:
         out[j] = _fps_multi_direct([pts[j]], [k])[0]
     return out[0] if single else out

@@ -845,6 +845,17 @@ int genpc_mask_backward_probe(int S, int blend, int sub8, int fuse_w, const floa
                               const float *pts, const float *col, const float *center, const float *params, float radius,
                               float mask_weight, double *accum_out, float *W1_out, float *W4_out, void *stream);
 
+/* Sampling-check probe: the device-side check every farthest point sampling gets (csrc/fps_verify.hip: fps_verify_kernel and the
+ * poisoning kernel behind it, in line, in the call's arithmetic mode) run on the caller's arrays (tests/test_gpu_fps_check.py).
+ * 1 <= nj <= 8 clouds in one job table; n, k and the three pointer tables are HOST arrays, xyz[q][n_q][3], out[q][k_q] (the
+ * sequence) and pdist[q][k_q] (the running minimum of every sample when it was drawn; [0] is not read) device memory.  The verdict
+ * is what a caller of genpc_fps sees: out[q][0] stays 0, becomes -2 (a step is wrong), or stays -1 if it was -1.  nseg == 0: the
+ * sample lists are cut into as many segments as in production (csrc/fps_plan.h: fps_verify_segments); 1 <= nseg <= 16 forces
+ * that number.  single != 0: as for the large sampler's clouds (never cut, unless nseg forces it).  Returns 1 / 0; -1 with
+ * genpc_last_error set for nj outside 1..8, a null pointer, k_q < 1, k_q > n_q, nseg outside 0..16, more than 4194304 points in all. */
+int genpc_fps_verify_probe(int nj, const int *n, const int *k, const float *const *xyz, int *const *out,
+                           const float *const *pdist, int nseg, int single, void *stream);
+
 /* Farthest point sampling --------------------------------------------------- *
  * Deterministic counterpart of fpsample.fps_sampling as the reference uses it
  * (main.py:21-24, reg_xyz.py:215, DepthPrompting.py:88; third-party, random start):

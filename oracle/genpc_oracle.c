@@ -401,3 +401,68 @@ ORACLE_API void oracle_fps_mode(int n, const float *xyz, int k, int fma_mode, in
     }
     free(d);
 }
+
+/* oracle_fps_mode that also returns, per sample, the running minimum it had when it
+ * was drawn (minima[0] = +inf: the start point is not drawn from anything).  This is
+ * what the samplers record for the device-side check (csrc/fps_verify.hip). */
+ORACLE_API void oracle_fps_minima(int n, const float *xyz, int k, int fma_mode, int *out_idx, float *minima)
+{
+    float *d = (float *)malloc(sizeof(float) * (size_t)n);
+    for (int i = 0; i < n; i++) d[i] = INFINITY;
+    int cur = 0;
+    float curv = INFINITY;
+    for (int s = 0; s < k; s++) {
+        out_idx[s] = cur;
+        minima[s] = curv;
+        float cx = xyz[cur * 3 + 0], cy = xyz[cur * 3 + 1], cz = xyz[cur * 3 + 2];
+        float bestv = -1.0f;
+        int besti = 0;
+        for (int i = 0; i < n; i++) {
+            float dd = sqdist(xyz[i * 3 + 0] - cx, xyz[i * 3 + 1] - cy,
+                              xyz[i * 3 + 2] - cz, fma_mode);
+            float v = d[i] < dd ? d[i] : dd;
+            d[i] = v;
+            if (v > bestv) {
+                bestv = v;
+                besti = i;
+            }
+        }
+        cur = besti;
+        curv = bestv;
+    }
+    free(d);
+}
+
+/* The DEFINITION of a right sampling, checked step by step with no shortcuts
+ * (n k distance evaluations): the first wrong step of (idx, minima), or -1.
+ * Step 0: idx[0] is the start point 0.  Step j >= 1: idx[j] is a point of the
+ * cloud, and after samples idx[0 .. j-1] have been applied to the running minima D
+ * every point i has D_i < M_j, or D_i == M_j and i >= idx[j] (the FIRST arg-max),
+ * and the sample itself has D == M_j exactly.  minima[0] is not read. */
+ORACLE_API int oracle_fps_check(int n, const float *xyz, int k, int fma_mode, const int *idx, const float *minima)
+{
+    if (idx[0] != 0) return 0;
+    float *d = (float *)malloc(sizeof(float) * (size_t)n);
+    for (int i = 0; i < n; i++) d[i] = INFINITY;
+    int wrong = -1;
+    for (int j = 1; j < k && wrong < 0; j++) {
+        const int prev = idx[j - 1];          /* (in the cloud: step j - 1 passed) */
+        const float cx = xyz[prev * 3 + 0], cy = xyz[prev * 3 + 1], cz = xyz[prev * 3 + 2];
+        for (int i = 0; i < n; i++) {
+            float dd = sqdist(xyz[i * 3 + 0] - cx, xyz[i * 3 + 1] - cy,
+                              xyz[i * 3 + 2] - cz, fma_mode);
+            d[i] = d[i] < dd ? d[i] : dd;
+        }
+        const int s = idx[j];
+        const float m = minima[j];
+        if (s < 0 || s >= n) {
+            wrong = j;
+            break;
+        }
+        for (int i = 0; i < n; i++)
+            if (!(d[i] < m || (d[i] == m && i >= s))) wrong = j;
+        if (d[s] != m) wrong = j;
+    }
+    free(d);
+    return wrong;
+}

@@ -329,6 +329,29 @@ def fps(xyz, k, fma_mode=0):
     return out
 
 
+def fps_minima(xyz, k, fma_mode=0):
+    """fps() that also returns the running minimum of every sample when it was drawn -> idx[k], minima[k]
+    (minima[0] = +inf), as the samplers record them for the device-side check."""
+    xyz, p = _f(xyz)
+    out = np.zeros(k, np.int32)
+    minima = np.zeros(k, np.float32)
+    lib().oracle_fps_minima(xyz.shape[0], p, int(k), int(fma_mode), out.ctypes.data_as(_i32p),
+                            minima.ctypes.data_as(_f32p))
+    return out, minima
+
+
+def fps_check(xyz, idx, minima, fma_mode=0):
+    """The definition of a right sampling, step by step without shortcuts: the first wrong step of (idx[k], minima[k]) on
+    the cloud, or -1 (start point 0, every index in the cloud, every sample the first arg-max with exactly its minimum)."""
+    xyz, p = _f(xyz)
+    idx, pi = _i(idx)
+    minima, pm = _f(minima)
+    assert idx.ndim == 1 and idx.shape == minima.shape and 1 <= idx.shape[0]
+    L = lib()
+    L.oracle_fps_check.restype = ctypes.c_int
+    return int(L.oracle_fps_check(xyz.shape[0], p, int(idx.shape[0]), int(fma_mode), pi, pm))
+
+
 def read_ply_xyz(path):
     """Binary-little-endian PLY with double/float x,y,z vertex properties (the
     layout Open3D wrote for the reference's data/*.ply) -> float64 [N,3]."""

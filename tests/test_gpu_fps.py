@@ -17,6 +17,23 @@ def fg():
     return dict(torch=torch, lib=_lib, fps=fps_sampling, sub=fps_subsample)
 
 
+@pytest.fixture(autouse=True)
+def fps_counters_stand_still(request):
+    """genpc_amd/fps.py samples a cloud again when its sequence failed the device-side check (or its hand-off timed out) and only
+    counts it: a check that fails on a right sequence would leave every comparison here green.  The counters are recorded around
+    each test and any movement is printed; failed_check must not move, except in the test that provokes a failed check and in
+    the threaded one.  (timed_out is not asserted: beside another process's kernels a hand-off can time out honestly.)"""
+    from genpc_amd import fps as F
+    before = dict(F.stats)
+    yield
+    moved = {key: F.stats[key] - before[key] for key in before if F.stats[key] != before[key]}
+    if moved:
+        print("fps.stats moved in %s: %s" % (request.node.name, moved))
+    if request.node.originalname not in ("test_fps_check_beside_the_callers_stream",
+                                         "test_fps_threads_on_their_own_streams_get_their_own_sequences"):
+        assert F.stats["failed_check"] == before["failed_check"], (request.node.name, moved)
+
+
 @pytest.mark.parametrize("n,k,c", [(1000, 100, 1), (5000, 2048, 3), (40000, 4096, 2), (165546, 2000, 1)])
 @pytest.mark.parametrize("mode", [0, 1])
 def test_fps_matches_oracle(fg, oracle, n, k, c, mode):
